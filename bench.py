@@ -7,8 +7,14 @@ route/reorg, region head, box decode, per-class NMS and compaction of the detect
 ending with the small D2H copy of the compact detection records
 (y2_forward_device + y2_detect_enqueue/fetch of libsr_yolo2.so).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step and the roofline / per-kernel
+figures of the HIP events inside the timed region).  --full adds everything else the line can carry: the host-fed loops,
+the CPU baseline, the detection equivalence with the CPU path, the batch-1 latency block, the clock probe and, at N > 1,
+the bit-for-bit check of every rank's last batch.  --dump-outputs DIR writes what the last timed step returned
+(see dump_outputs).
 
 Multi-GPU: one process per GPU.  Under torchrun the ranks exist already; a bare
 `python bench.py --gpus N` starts them itself (sr_object_detection_amd/launch.py: the parent
@@ -21,9 +27,9 @@ every rank then runs its own frame batches (weak scaling, no per-step collective
 Timing = K steps between barriers, MAX over ranks.
 
 Rank 0 prints one JSON line: value, roofline of the dominant kernel
-from HIP-event timings taken inside the timed region, the same loop fed from pinned host
-memory (PCIe-inclusive, never `value`), the CPU baseline (the reference's own CPU path
-compiled into oracle/_ref when present, otherwise the oracle port) and the
+from HIP-event timings taken inside the timed region and, with --full, the same loop fed from
+pinned host memory (PCIe-inclusive, never `value`), the CPU baseline (the reference's own CPU
+path compiled into oracle/_ref when present, otherwise the oracle port) and the
 detection-equivalence of the GPU and CPU paths on frames of the timed batch.
 """
 from __future__ import annotations
@@ -32,6 +38,7 @@ import gc
 import argparse
 import json
 import os
+import shutil
 import subprocess
 import sys
 import tempfile
@@ -69,15 +76,21 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=50)      # >= 50 timed batches (the driver passes its own K / W)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="yolo608_b32", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: host-fed loops, CPU baseline, equivalence with the CPU path, batch-1 latency "
+                         "block, clock probe and (N>1) the shard check; off: set up, warm up, time --steps, print the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (rank 0) as DIR/<name>.npy, float32 / float64")
     ap.add_argument("--cpu-iters", type=int, default=3,
-                    help="timed CPU-baseline forwards per leg, median reported (0 disables the CPU legs)")
+                    help="timed CPU-baseline forwards per leg, median reported (0 disables the CPU legs; --full only)")
     ap.add_argument("--cpu-legs", default="all", choices=["all", "headline"],
                     help="all: tiny@416 / yolo@416 / yolo@608 at 1 thread and all cores (SURVEY 8d); headline: the workload's net, all cores")
-    ap.add_argument("--equiv-frames", type=int, default=8, help="frames of the timed batch compared with the CPU reference")
+    ap.add_argument("--equiv-frames", type=int, default=8, help="frames of the timed batch compared with the CPU reference (--full only)")
     ap.add_argument("--seed", type=int, default=31)
-    ap.add_argument("--host-input", default="also", choices=["also", "only", "off"],
+    ap.add_argument("--host-input", default=None, choices=["also", "only", "off"],
                     help="also: after the resident loop, time the same steps fed from pinned host memory (reported as "
-                         "host_input, never as value); only: time just that; off: skip it")
+                         "host_input, never as value); only: time just that; off: skip it (default: also with --full, "
+                         "else off)")
     ap.add_argument("--bcast", default=os.environ.get("Y2_BENCH_BCAST", "torch"), choices=["torch", "c-abi"],
                     help="transport of the one weight broadcast at N>1")
     ap.add_argument("--detect-overlap", type=int, default=-1,
@@ -88,11 +101,17 @@ def parse_args():
                     help="1: the plan measures the conv tile shapes once instead of modelling them (y2_set_autotune)")
     ap.add_argument("--latency-iters", type=int, default=200,
                     help="calls per entry of the batch-1 latency block (test_detector_img / Detector::detect on tiny-yolo-voc and "
-                         "yolo at 416; N=1 only; 0 disables)")
+                         "yolo at 416; N=1 and --full only; 0 disables)")
     ap.add_argument("--clock-probe", type=int, default=1,
-                    help="0: skip the 0.6 s clock probe behind the timed region (profiling runs: its launches would fill the kernel trace)")
+                    help="0: skip the 0.6 s clock probe behind the timed region (profiling runs: its launches would fill the kernel trace); "
+                         "--full only")
     ap.add_argument("--dump-dets", default=None, help="write each rank's last-batch detections to PATH.rank<r>.npz")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.host_input is None:
+        args.host_input = "also" if args.full else "off"
+    return args
 
 
 def write_cfg(tmp: str, name: str, size: int, batch: int, fname: str = "net.cfg") -> str:
@@ -369,6 +388,36 @@ def latency_block(tmp, seed, iters=200):
         det.free()
         net.free()
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, is_detector: bool, dets, counts, batch: int):
+    """What the last timed step returned to its caller, as DIR/<name>.npy (inputs and weights are seeded, so two builds
+    given the same arguments can be compared array for array):
+      detector:   detections.npy float64 [n, 7] = frame, x, y, w, h, prob, obj_id per record, frames in order and each
+                  frame's records in the order y2_detect_fetch returns them; counts.npy float64 [batch]
+      classifier: class_scores.npy float32 [batch, outputs]
+    An array that would take the total over DUMP_LIMIT_BYTES is cut to a fixed, seeded sample of its rows (ascending
+    order), whose row indices go to <name>_rows.npy."""
+    import numpy as np
+    if is_detector:
+        rows = [np.column_stack([np.full(len(d), b), d["x"], d["y"], d["w"], d["h"], d["prob"], d["obj_id"]])
+                for b, d in enumerate(dets)]
+        arrays = {"detections": np.concatenate(rows).astype(np.float64) if rows else np.zeros((0, 7)),
+                  "counts": np.asarray(counts, dtype=np.float64)}
+    else:
+        arrays = {"class_scores": np.asarray(dets, dtype=np.float32).reshape(batch, -1)}
+    os.makedirs(out_dir, exist_ok=True)
+    budget = (DUMP_LIMIT_BYTES - 4096) // len(arrays)           # (room for the .npy headers)
+    for key, a in arrays.items():
+        if a.nbytes > budget:
+            keep = max(1, budget // (a[0].nbytes + 8))      # the rows plus their float64 indices
+            idx = np.sort(np.random.default_rng(0).choice(len(a), size=keep, replace=False))
+            np.save(os.path.join(out_dir, key + "_rows.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(out_dir, key + ".npy"), a)
 
 
 def main():
@@ -663,12 +712,14 @@ def main():
     if args.dump_dets and is_detector:
         np.savez(args.dump_dets + ".rank%d.npz" % rank, counts=np.asarray(counts),
                  **{"dets_%d" % b: dets[b] for b in range(len(dets))})
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, is_detector, dets, counts, batch)
 
     # N > 1, outside the timed region: every rank's last batch is recomputed on rank 0 (same frames: seed 0xC0FFEE + r * batch,
     # same arena bytes, same kernels) and must come out bit for bit -- a rank whose replica, frames or device misbehaved
-    # shows here, not in a throughput number.  Also what each rank ran on.
+    # shows here, not in a throughput number.  Also what each rank ran on.  (--full only)
     shards_verified, rank_devices, shards_mismatched = None, None, []
-    if world > 1:
+    if world > 1 and args.full:
         def digest(d_, c_):
             if is_detector:
                 return [np.asarray(c_).tobytes()] + [np.ascontiguousarray(d_[b]).tobytes() for b in range(len(d_))]
@@ -707,11 +758,11 @@ def main():
         conv_ms = sum(per_kernel_ms.values()) / max(args.steps, 1)
         conv_flops_step = sum(per_kernel_flops.values()) / max(args.steps, 1)
         # the CPU legs are timed at N=1 only (rank 0 would otherwise hold the other ranks at the final barrier)
-        cpu = cpu_baseline(tmp, wl, wts, args.cpu_iters, args.cpu_legs, args.seed) if world == 1 else None
+        cpu = cpu_baseline(tmp, wl, wts, args.cpu_iters, args.cpu_legs, args.seed) if (world == 1 and args.full) else None
         equiv = None
-        if world == 1 and args.cpu_iters > 0 and is_detector and args.equiv_frames > 0:
+        if world == 1 and args.full and args.cpu_iters > 0 and is_detector and args.equiv_frames > 0:
             equiv = equivalence_vs_cpu(tmp, name, size, wts, x, dets, args.equiv_frames)
-        latency = latency_block(tmp, args.seed, args.latency_iters) if (world == 1 and args.latency_iters > 0) else None
+        latency = latency_block(tmp, args.seed, args.latency_iters) if (world == 1 and args.full and args.latency_iters > 0) else None
         what = ("forward + region decode + NMS(%.1f) + collect + fetch of the detections" % NMS) if is_detector else \
                "forward (conv trunk, avgpool, softmax) + fetch of the class scores"
         line = {
@@ -738,11 +789,12 @@ def main():
             "device": darknet.device_name(),
             # what this box's silicon does: the clock it holds under a full-chip fp32 matrix load (in-kernel stamps, measured
             # right after the timed region); lines of different boxes differ by this much before any code does
-            "mfma_f32_clock_ghz": round(darknet.clock_probe(), 3) if args.clock_probe else None,
+            "mfma_f32_clock_ghz": round(darknet.clock_probe(), 3) if (args.full and args.clock_probe) else None,
         }
         print(json.dumps(line))
         sys.stdout.flush()
     net.free()
+    shutil.rmtree(tmp, ignore_errors=True)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

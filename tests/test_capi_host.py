@@ -1,7 +1,7 @@
 """CPU-only checks of the product library's host side: it loads, exports every
 symbol the public headers declare, lays its structs out as the Python mirror
 expects, parses cfgs to the same layer table as the oracle (and as the
-reference's own cfg files), reads/writes .weights, and fails loudly -- never
+reference's own cfg files, kept verbatim under tests/golden/ref_cfg/), reads/writes .weights, and fails loudly -- never
 falls back -- when no GPU is present.  No compute entry point is called."""
 import ctypes as C
 import os
@@ -11,10 +11,11 @@ import numpy as np
 import pytest
 
 from sr_object_detection_amd import darknet, zoo
-from tests.conftest import REFERENCE_ROOT, has_gpu
+from tests.conftest import GOLDEN, has_gpu
 from tests.helpers import load_golden, materialize
 
 INCLUDE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
+REF_CFG_DIR = os.path.join(GOLDEN, "ref_cfg")      # the reference's cfg/ files these tests read, byte for byte
 
 
 def declared_functions(header):
@@ -97,13 +98,12 @@ REF_CFGS = {"yolo": ("yolo.cfg", 416), "tiny-yolo-voc": ("tiny-yolo-voc.cfg", 41
             "tiny-yolo-v1": ("yolov1/tiny-yolo.cfg", 448)}
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE_ROOT), reason="reference checkout not present (GPU box)")
 @pytest.mark.parametrize("name", sorted(REF_CFGS))
 def test_reference_cfg_files_parse_to_the_zoo_tables(workdir, name):
     """The reference's own cfg text (training keys, comments, blanks, batch/subdivisions) is accepted
     verbatim and yields the same layers as the cfg this repo emits for that network."""
     fname, size = REF_CFGS[name]
-    ref_net = darknet.Network.parse_network_cfg(os.path.join(REFERENCE_ROOT, "cfg", fname))
+    ref_net = darknet.Network.parse_network_cfg(os.path.join(REF_CFG_DIR, fname))
     ours = os.path.join(workdir, name + "_ours.cfg")
     open(ours, "w").write(zoo.cfg_text(name, size, size, ref_net.batch))
     our_net = darknet.Network.parse_network_cfg(ours)
@@ -222,10 +222,9 @@ def test_denormalize_net_writes_the_reference_weight_file(workdir):
     net.free()
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE_ROOT), reason="reference checkout not present (GPU box)")
 def test_reference_resnet50_cfg_parses(oracle):
     """cfg/resnet50.cfg ([shortcut] + strided convolutions) is accepted verbatim; shapes agree with the oracle"""
-    path = os.path.join(REFERENCE_ROOT, "cfg", "resnet50.cfg")
+    path = os.path.join(REF_CFG_DIR, "resnet50.cfg")
     net = darknet.Network.parse_network_cfg(path)
     on = oracle.OracleNet(path)
     assert net.n == on.n == 70 and net.output_size == 1000
