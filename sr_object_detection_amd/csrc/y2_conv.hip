@@ -1276,16 +1276,7 @@ static int c32_f32_launch(const y2h_conv *d, ConvK &a, y2h_stream s)
     void (*fn)(ConvK) = a.pool ? (fast ? conv_c32_f32_kernel<true, true> : conv_c32_f32_kernel<true, false>)
                                : (fast ? conv_c32_f32_kernel<false, true> : conv_c32_f32_kernel<false, false>);
     const size_t lds = (size_t)2 * 18 * 2688 + 8 * 32 * 144;
-    {
-        static bool attr_set[16][4] = {{false}};
-        const int which = (a.pool ? 2 : 0) + (fast ? 1 : 0);
-        int dev = 0;
-        Y2H_CHECK(hipGetDevice(&dev));
-        if (dev < 0 || dev >= 16 || !attr_set[dev][which]) {
-            Y2H_CHECK(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            if (dev >= 0 && dev < 16) attr_set[dev][which] = true;
-        }
-    }
+    Y2H_CHECK(y2h_lds_limit((const void *)fn, lds));
     long tiles = (long)d->batch * (d->h >> 4) * (d->w >> 4);
     long grid = tiles < 256 ? tiles : 256;
     if (const char *g = getenv("Y2_CONV_GRID")) { if (atol(g) > 0 && atol(g) < grid) grid = atol(g); }
@@ -1342,26 +1333,22 @@ struct Variant {
     void (*fn)(ConvK);
     size_t lds;
     int threads;
-    bool attr_set[16];     // per device
     void (*fn_xo)(ConvK);  // the same tile with the XCD-grouped tile order (ConvK.xcd_order), where instantiated
-    bool attr_set_xo[16];
     void (*fn_sk)(ConvK);  // the same tile with stream-K work items (ConvK.sk_tiles / sk_wgs), where instantiated
-    bool attr_set_sk[16];
     void (*fn_skh)(ConvK); // the same tile, hybrid: whole tiles + the last partial round as stream-K pieces finished in the launch
-    bool attr_set_skh[16];
 };
 
 #define VAR(BM, BN, BK, KS, WM, WN)                                                             \
     { "conv_mfma_f32_" #BM "x" #BN "x" #BK "_k" #KS, BM, BN, BK, KS, conv_mfma_kernel<BM, BN, BK, KS, WM, WN, Y2_PIPE>, \
-      (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float) + (WM * WN == 8 ? (size_t)8 * 16 * 36 * sizeof(float) : 0), WM * WN * 64, {false}, nullptr, {false}, nullptr, {false}, nullptr, {false} }
+      (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float) + (WM * WN == 8 ? (size_t)8 * 16 * 36 * sizeof(float) : 0), WM * WN * 64, nullptr, nullptr, nullptr }
 #define VARSK(BM, BN, BK, KS, WM, WN)                                                           \
     { "conv_mfma_f32_" #BM "x" #BN "x" #BK "_k" #KS, BM, BN, BK, KS, conv_mfma_kernel<BM, BN, BK, KS, WM, WN, Y2_PIPE>, \
-      (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float) + (WM * WN == 8 ? (size_t)8 * 16 * 36 * sizeof(float) : 0), WM * WN * 64, {false}, \
-      nullptr, {false}, conv_mfma_kernel<BM, BN, BK, KS, WM, WN, Y2_PIPE, false, 1>, {false}, conv_mfma_kernel<BM, BN, BK, KS, WM, WN, Y2_PIPE, false, 2>, {false} }
+      (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float) + (WM * WN == 8 ? (size_t)8 * 16 * 36 * sizeof(float) : 0), WM * WN * 64, \
+      nullptr, conv_mfma_kernel<BM, BN, BK, KS, WM, WN, Y2_PIPE, false, 1>, conv_mfma_kernel<BM, BN, BK, KS, WM, WN, Y2_PIPE, false, 2> }
 #define VARXO(BM, BN, BK, KS, WM, WN)                                                           \
     { "conv_mfma_f32_" #BM "x" #BN "x" #BK "_k" #KS, BM, BN, BK, KS, conv_mfma_kernel<BM, BN, BK, KS, WM, WN, Y2_PIPE>, \
-      (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float) + (WM * WN == 8 ? (size_t)8 * 16 * 36 * sizeof(float) : 0), WM * WN * 64, {false}, \
-      conv_mfma_kernel<BM, BN, BK, KS, WM, WN, Y2_PIPE, true>, {false}, nullptr, {false}, nullptr, {false} }
+      (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float) + (WM * WN == 8 ? (size_t)8 * 16 * 36 * sizeof(float) : 0), WM * WN * 64, \
+      conv_mfma_kernel<BM, BN, BK, KS, WM, WN, Y2_PIPE, true>, nullptr, nullptr }
 
 #ifndef Y2_PIPE
 #define Y2_PIPE true
@@ -1491,7 +1478,9 @@ static size_t skh_ws_bytes(const Variant &v)
     return wgs * v.bm * v.bn * sizeof(float) + wgs * sizeof(int);
 }
 
-static Variant *pick_variant(const y2h_conv *d, int *ksplit_out = nullptr, int *sk_wgs_out = nullptr, int *skh_tiles_out = nullptr)
+// Fills p.v / p.ksplit (the choice among whole-tile launches), p.sk_v / p.sk_wgs (stream-K), p.tile / p.tile_ksplit and
+// p.skh_tiles.  Env: Y2_SKF=0 no stream-K; Y2_SKF_WGS=n forces stream-K on n workgroups for the (forced) tile.
+static bool pick_variant(const y2h_conv *d, ConvPlan &p)
 {
     const int bk = (d->c % 32 == 0) ? 32 : 16;
     const long npix = (long)d->batch * d->out_h * d->out_w;
@@ -1500,9 +1489,9 @@ static Variant *pick_variant(const y2h_conv *d, int *ksplit_out = nullptr, int *
     int force_bm = d->tile_bm, force_bn = d->tile_bn, force_split = d->ksplit;      // a tuned descriptor (y2_set_autotune)
     if (const char *f = getenv("Y2_CONV_TILE")) sscanf(f, "%dx%d", &force_bm, &force_bn);
     if (const char *f = getenv("Y2_CONV_KSPLIT")) force_split = atoi(f);
-    Variant *best = nullptr;
-    double best_cost = 0;
-    int best_split = 1, best_sk = 0;
+    Variant *best = nullptr, *plain = nullptr;          // best of all candidates; best of the whole-tile ones
+    double best_cost = 0, plain_cost = 0;
+    int best_split = 1, best_sk = 0, plain_split = 1;
     bool sk_on = true;
     long sk_force = 0;
     if (const char *f = getenv("Y2_SKF")) sk_on = atoi(f) != 0;
@@ -1518,7 +1507,7 @@ static Variant *pick_variant(const y2h_conv *d, int *ksplit_out = nullptr, int *
             ksplit = (int)((long)CUS * bpc / tiles);
             // (>= 8 K-steps per range; 1x1 layers >= 4: their ranges are short anyway -- K = 512-1024 is 16-32 steps -- and the
             // batch-1 autotune logs preferred twice the split on every one of them: yolo 416 b1 device part 0.656 -> 0.648 ms)
-            { const int per = (d->size == 1 && !getenv("Y2_MODEL_R1")) ? 4 : 8; if (ksplit > nk / per) ksplit = nk / per; }
+            { const int per = d->size == 1 ? 4 : 8; if (ksplit > nk / per) ksplit = nk / per; }
             if (ksplit > 32) ksplit = 32;
             if (ksplit < 1) ksplit = 1;
         }
@@ -1529,11 +1518,7 @@ static Variant *pick_variant(const y2h_conv *d, int *ksplit_out = nullptr, int *
         // whatever bpc is.  (Round 1's non-persistent grids refilled a CU bpc workgroups at a time, and the model counted the
         // tail in whole groups of bpc: that over-charged the small tiles on grids of 1.3-2.6 rounds -- autotune logs of yolo 416
         // b8 / yolo9000 544 b8, profiles/r03_notes.md section 11.)
-        long per_cu = (blocks + CUS - 1) / CUS;
-        if (getenv("Y2_MODEL_R1")) {
-            if (blocks <= (long)CUS * bpc) per_cu = (blocks + CUS - 1) / CUS;
-            else per_cu = (long)bpc * ((blocks + (long)CUS * bpc - 1) / ((long)CUS * bpc));
-        }
+        const long per_cu = (blocks + CUS - 1) / CUS;
         // measured in-tile efficiency relative to the 192x256 tile (yolo.cfg 608x608 b32 sweep,
         // profiles/r01_tile_sweep.txt): bigger wave tiles re-read less LDS per MFMA; the small
         // 64x64 tile wins on short-K 1x1 layers, where prologue/epilogue dominate and four
@@ -1543,13 +1528,18 @@ static Variant *pick_variant(const y2h_conv *d, int *ksplit_out = nullptr, int *
         else if (v.bm == 128 && v.bn == 128) eff = 0.96;
         else if (v.bm == 256 && v.bn == 128) eff = 0.945;
         else if (v.bm == 64 && v.bn == 64) eff = (d->size == 1) ? 1.0 : 0.90;
-        else if (v.bm == 128 && v.bn == 64) eff = (d->size == 3 && !getenv("Y2_MODEL_R1")) ? 0.92 : 0.86;     // r3: 0.94-0.95 against the 64x64 tile's 0.90 on grids of 3-5 tiles per CU (52x52 / 68x68 128->256 at batch 8)
+        else if (v.bm == 128 && v.bn == 64) eff = d->size == 3 ? 0.92 : 0.86;     // r3: 0.94-0.95 against the 64x64 tile's 0.90 on grids of 3-5 tiles per CU (52x52 / 68x68 128->256 at batch 8)
         else if (v.bm == 256 && v.bn == 64) eff = 0.82;
         else if (v.bm == 128 && v.bn == 32) eff = (d->size == 1) ? 0.95 : 0.7;
         // in CU cycles: one K-step of a tile = bm*bn*bk*2 flop at 256 flop/clk; ~5 K-steps of fixed cost
         // per work item (measured); a split pays the workspace round trip (~4 TB/s) and a launch
         double cost = (double)per_cu * v.bm * v.bn * v.bk / 128.0 * ((double)nk / ksplit + 5.0) / eff;
         if (ksplit > 1) cost += (double)npix * d->n * 4.0 * (ksplit + 1) * 5.75e-4 + 5000.0;
+        if (!plain || cost < plain_cost * 0.999 || (cost <= plain_cost * 1.001 && v.bm * v.bn > plain->bm * plain->bn)) {
+            plain = &v;
+            plain_cost = cost;
+            plain_split = ksplit;
+        }
         if (!best || cost < best_cost * 0.999 || (cost <= best_cost * 1.001 && v.bm * v.bn > best->bm * best->bn)) {
             best = &v;
             best_cost = cost;
@@ -1560,7 +1550,7 @@ static Variant *pick_variant(const y2h_conv *d, int *ksplit_out = nullptr, int *
         // whatever the tile count -- the integer split above leaves CUs idle whenever tiles * ksplit is not a multiple of the
         // slots (113 tiles x 2 = 226 of 256) and cannot cut a tile into 2.5.  Costs: up to two work items per workgroup (their
         // fixed cost once and a half), pieces = wgs + tiles slots of bm x bn floats written and read once, one more launch.
-        if (sk_wgs_out && v.fn_sk && d->n % 4 == 0 && d->ldy % 4 == 0 && force_split <= 0 && d->tile_bm == 0 && nk >= 16 && sk_on) {
+        if (v.fn_sk && d->n % 4 == 0 && d->ldy % 4 == 0 && force_split <= 0 && d->tile_bm == 0 && nk >= 16 && sk_on) {
             long wgs = (long)CUS * bpc;
             if (wgs > tiles * nk / 8) wgs = tiles * nk / 8;             // shares of >= 8 K-steps
             if (sk_force > 0) wgs = sk_force;
@@ -1578,18 +1568,48 @@ static Variant *pick_variant(const y2h_conv *d, int *ksplit_out = nullptr, int *
             }
         }
     }
-    if (ksplit_out) *ksplit_out = best_split;
-    if (sk_wgs_out) *sk_wgs_out = best_sk;
-    if (skh_tiles_out) {
-        *skh_tiles_out = 0;
-        if (best && best->fn_skh && best_sk == 0 && best_split == 1 && !getenv("Y2_CONV_GRID")) {
-            const long tiles = ((npix + best->bm - 1) / best->bm) * ((d->n + best->bn - 1) / best->bn);
-            const int bpc = variant_bpc(*best);
-            *skh_tiles_out = skh_plan(tiles, nk, skh_slots(*best), best->bm, best->bn, best->bk, bpc);
-        }
+    if (!best) return false;
+    p.v = plain;
+    p.ksplit = plain_split;
+    p.sk_v = best_sk ? best : nullptr;
+    p.sk_wgs = best_sk;
+    p.tile = best_sk ? plain : best;
+    p.tile_ksplit = best_sk ? plain_split : best_split;
+    if (best->fn_skh && best_sk == 0 && best_split == 1 && !getenv("Y2_CONV_GRID")) {
+        const long tiles = ((npix + best->bm - 1) / best->bm) * ((d->n + best->bn - 1) / best->bn);
+        p.skh_tiles = skh_plan(tiles, nk, skh_slots(*best), best->bm, best->bn, best->bk, variant_bpc(*best));
     }
-    return best;
+    return true;
 }
+
+// The whole-tile launch of p.tile: a persistent grid of at most what is co-resident, and on wide heads the XCD-grouped order.
+static void tile_shape(const y2h_conv *d, ConvPlan &p)
+{
+    const Variant &v = *p.tile;
+    const long npix = (long)d->batch * d->out_h * d->out_w;
+    const long tiles_n = (d->n + v.bn - 1) / v.bn, ntiles = ((npix + v.bm - 1) / v.bm) * tiles_n * p.tile_ksplit;
+    p.tiles_m = (int)((npix + v.bm - 1) / v.bm);
+    p.grid = 256L * variant_bpc(v);
+    if (const char *g = getenv("Y2_CONV_GRID")) { if (atol(g) > 0 && atol(g) < p.grid) p.grid = atol(g); }   // tests: many tiles per workgroup on small shapes
+    if (p.grid > ntiles) p.grid = ntiles;
+    // Wide heads: when the weights are the large operand and there are many filter tiles, filter-tile-fastest numbering
+    // makes every round of workgroups stream the whole weight matrix again (yolo9000 544 b8, final 1x1: 4.3 GB fetched
+    // for 125 MB of operands, profiles/r02_9k544b8_pmc_summary.txt).  See ConvK.xcd_order.  Y2_XCD_ORDER=0/1 forces.
+    const double wb = (double)d->n * d->size * d->size * d->c * 4.0, xb = (double)npix * d->c * 4.0;
+    bool on = v.fn_xo && p.tile_ksplit == 1 && p.grid >= 8 && tiles_n >= 16 && wb > 2.0 * xb && wb > 16e6;
+    if (const char *f = getenv("Y2_XCD_ORDER")) on = v.fn_xo && atoi(f) != 0 && p.tile_ksplit == 1 && p.grid >= 8;
+    if (!on) return;
+    p.xcd_order = 1;
+    const double tile_b = (double)v.bm * d->c * d->size * d->size * 4.0;      // input bytes one pixel tile touches (upper bound)
+    long pb = (long)(3.0e6 / tile_b);
+    if (const char *f = getenv("Y2_XCD_PBLK")) pb = atol(f);
+    if (pb < 1) pb = 1;
+    if (pb > p.tiles_m) pb = p.tiles_m;
+    p.pblk = (int)pb;
+    p.grid -= p.grid % 8;
+}
+
+static ConvPlan conv_plan(const y2h_conv *d, int strict);
 
 // ---------------------------------------------------------------------------
 // Tile autotuning: the cost model above ranks tile shapes from grid arithmetic; on small grids (batch 1..8) its
@@ -1601,20 +1621,21 @@ static Variant *pick_variant(const y2h_conv *d, int *ksplit_out = nullptr, int *
 extern "C" int y2h_conv_candidates(const y2h_conv *d, int *bm, int *bn, int *ks, int max)
 {
     if (!d || !bm || !bn || !ks || max < 1) return Y2H_EINVAL;
-    if (d->x_f16 || d->x_halo != 0 || !mfma_ok(d)) return 0;
     const int bk = (d->c % 32 == 0) ? 32 : 16;
     const int nk = d->size * d->size * (d->c / bk);
     y2h_conv t = *d;
     t.tile_bm = t.tile_bn = t.ksplit = 0;
-    int model_split = 1, n = 0;
-    Variant *mv = pick_variant(&t, &model_split);
-    if (!mv) return 0;
-    bm[n] = mv->bm; bn[n] = mv->bn; ks[n] = model_split; ++n;
+    const ConvPlan mp = conv_plan(&t, 0);
+    if (!mp.v) return 0;
+    const int model_split = mp.ksplit;
+    int n = 0;
+    bm[n] = mp.v->bm; bn[n] = mp.v->bn; ks[n] = model_split; ++n;
     for (Variant &v : g_variants) {
         if (v.bk != bk || v.ks != d->size) continue;
         y2h_conv q = t; q.tile_bm = v.bm; q.tile_bn = v.bn;
-        int own = 1;
-        if (!pick_variant(&q, &own)) continue;
+        const ConvPlan qp = conv_plan(&q, 0);
+        if (!qp.v) continue;
+        const int own = qp.ksplit;
         const int splits[5] = {1, model_split, model_split * 2, model_split / 2, own};
         for (int a = 0; a < 5; ++a) {
             const int k = splits[a];
@@ -1628,19 +1649,7 @@ extern "C" int y2h_conv_candidates(const y2h_conv *d, int *bm, int *bn, int *ks,
     return n;
 }
 
-extern "C" size_t y2h_conv_workspace_bytes(const y2h_conv *d)
-{
-    int ksplit = 1;
-    if (d->x_f16 && !d->x_halo) return y2_f16_conv_workspace_bytes(d);      // stream-K piece slots of the fp16 256x256 kernel
-    if (c32_f32_ok(d)) return 0;
-    int sk_wgs = 0, skh_tiles = 0;
-    Variant *v = (d->x_halo || d->x_f16 || !mfma_ok(d)) ? nullptr : pick_variant(d, &ksplit, &sk_wgs, &skh_tiles);
-    if (!v) return 0;
-    if (sk_wgs > 0) return (size_t)2 * sk_wgs * v->bm * v->bn * sizeof(float);          // stream-K piece slots
-    if (skh_tiles > 0) return skh_ws_bytes(*v);                                          // one slot and one flag per workgroup
-    if (ksplit <= 1) return 0;
-    return (size_t)ksplit * d->batch * d->out_h * d->out_w * d->n * sizeof(float);
-}
+extern "C" size_t y2h_conv_workspace_bytes(const y2h_conv *d) { return conv_plan(d, 0).ws; }
 
 // first-layer kernel: 3 channels, 3x3/1 pad 1, <= 64 filters, input stored with a 1-pixel zero halo
 static bool first_ok(const y2h_conv *d)
@@ -1681,6 +1690,56 @@ static bool stem_ok(const y2h_conv *d)
     return xbytes < 4294967000.0 && d->w_packed != nullptr;
 }
 
+// The one place that decides which kernel runs a descriptor and how it is launched (see ConvPlan).  Honours the
+// environment switches on every call: tests set them between calls.
+static ConvPlan conv_plan(const y2h_conv *d, int strict)
+{
+    ConvPlan p;
+    memset(&p, 0, sizeof p);
+    p.kind = CK_DIRECT;
+    const bool n32 = d->n <= 32;
+    if (d->x_nchw) {                   // the network input itself (fp32 planes): only the first-layer kernels read that layout
+        p.kind = CK_NONE;
+        if (strict) return p;
+        if (y2_f16_first_nchw_ok(d)) {
+            p.kind = CK_FIRST_NCHW_F16;
+            p.name = n32 ? "conv_first_mfma_f16_nchw_c3_n32" : "conv_first_mfma_f16_nchw_c3_n64";
+        } else if (first_nchw_ok(d)) {
+            p.kind = CK_FIRST_NCHW_F32;
+            p.name = n32 ? "conv_first_mfma_f32_nchw_c3_n32" : "conv_first_mfma_f32_nchw_c3_n64";
+        }
+        return p;
+    }
+    if (d->x_f16) {
+        if (strict || !y2_f16_plan(d, p)) p.name = "conv_direct_f16";
+        return p;
+    }
+    p.name = "conv_direct_f32";
+    if (strict) return p;
+    if (first_ok(d)) {
+        p.kind = CK_FIRST_F32;
+        p.name = n32 ? "conv_first_mfma_f32_c3_n32" : "conv_first_mfma_f32_c3_n64";
+        return p;
+    }
+    const bool mfma = d->x_halo == 0 && mfma_ok(d) && pick_variant(d, p);
+    if (c32_f32_ok(d)) {
+        p.kind = CK_C32_F32;
+        p.name = "conv_c32_f32_16x16";
+    } else if (mfma) {
+        p.kind = CK_MFMA_F32;
+        p.name = p.v->name;
+        tile_shape(d, p);
+        if (p.sk_wgs > 0) p.ws = (size_t)2 * p.sk_wgs * p.sk_v->bm * p.sk_v->bn * sizeof(float);    // stream-K piece slots
+        else if (p.skh_tiles > 0) p.ws = skh_ws_bytes(*p.tile);                                     // one slot and one flag per workgroup
+        else if (p.tile_ksplit > 1) p.ws = (size_t)p.tile_ksplit * d->batch * d->out_h * d->out_w * d->n * sizeof(float);
+    } else if (stem_ok(d)) {
+        p.kind = CK_STEM;
+        p.name = "conv_stem_mfma_f32";
+    }
+    return p;
+}
+
+// The first-layer / stem queries: may the engine give layer 0 (or a conv behind a [crop]) the input form these kernels read?
 extern "C" int y2h_conv_stem_halo(const y2h_conv *d)
 {
     y2h_conv t = *d;
@@ -1710,36 +1769,148 @@ extern "C" int y2h_conv_first_layer_nchw_ok(const y2h_conv *d)
     t.x_halo = 0; t.x_f16 = 0; t.x_nchw = 1;
     if (!t.x) t.x = (const float *)(uintptr_t)256;
     if (!t.w_packed) t.w_packed = (const float *)(uintptr_t)256;
-    return (t.y_f16 ? y2_f16_first_nchw_ok(&t) || first_nchw_ok(&t) : first_nchw_ok(&t)) ? 1 : 0;
+    const ConvKind k = conv_plan(&t, 0).kind;
+    return k == CK_FIRST_NCHW_F16 || k == CK_FIRST_NCHW_F32 ? 1 : 0;
 }
 
 extern "C" int y2h_conv_uses_mfma(const y2h_conv *d)
 {
-    if (d->x_nchw) return (y2_f16_first_nchw_ok(d) || first_nchw_ok(d)) ? 1 : 0;
-    if (d->x_f16) return (y2_f16_first_ok(d) || y2_f16_conv_ok(d)) ? 1 : 0;
-    return first_ok(d) || (d->x_halo == 0 && mfma_ok(d) && pick_variant(d)) || (d->c <= 4 && stem_ok(d)) ? 1 : 0;
+    const ConvKind k = conv_plan(d, 0).kind;
+    return k != CK_NONE && k != CK_DIRECT ? 1 : 0;
 }
 
-extern "C" const char *y2h_conv_variant(const y2h_conv *d, int strict)
+extern "C" const char *y2h_conv_variant(const y2h_conv *d, int strict) { return conv_plan(d, strict).name; }
+
+// ---------------------------------------------------------------------------
+// launch routines, one per kind of the fp32 side (the fp16 side: y2_f16_launch)
+// ---------------------------------------------------------------------------
+// first-layer kernel: the input with a one-pixel halo, or the NCHW planes of the network input (x_nchw)
+static int first_launch(const y2h_conv *d, ConvK &a, y2h_stream s)
 {
-    if (d->x_nchw) {
-        if (!strict && y2_f16_first_nchw_ok(d)) return d->n <= 32 ? "conv_first_mfma_f16_nchw_c3_n32" : "conv_first_mfma_f16_nchw_c3_n64";
-        if (!strict && first_nchw_ok(d)) return d->n <= 32 ? "conv_first_mfma_f32_nchw_c3_n32" : "conv_first_mfma_f32_nchw_c3_n64";
-        return nullptr;
+    a.nchw = d->x_nchw;
+    a.w = d->w_packed;
+    a.npix = d->batch * d->h * d->w;
+    a.xbytes = d->x_nchw ? (unsigned)((size_t)d->batch * 3 * d->h * d->w * 4) : (unsigned)((size_t)d->batch * (d->h + 2) * (d->w + 2) * d->ldx * 4);
+    const long ntiles = ((long)a.npix + 31) / 32;
+    long blocks = (ntiles + 3) / 4;
+    void (*fn)(ConvK) = d->n <= 32 ? conv_first_kernel<1> : conv_first_kernel<2>;
+    const long res = resident_blocks((const void *)fn, 256, 0, 3);
+    if (blocks > res) blocks = res;              // tiles are grid-strided
+    hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(256), 0, S(s), a);
+    Y2H_LAUNCH_CHECK();
+    return Y2H_OK;
+}
+
+static int stem_launch(const y2h_conv *d, ConvK &a, y2h_stream s)
+{
+    a.w = d->w_packed;
+    a.npix = d->batch * d->out_h * d->out_w;
+    a.xbytes = (unsigned)((size_t)d->batch * (d->h + 2 * d->pad) * (d->w + 2 * d->pad) * d->ldx * 4);
+    const size_t lds = stem_lds_bytes(d);
+    const int nt = (d->n + 31) / 32;
+    void (*fn)(ConvK) = nt == 1 ? conv_stem_kernel<1> : nt == 2 ? conv_stem_kernel<2> : nt == 3 ? conv_stem_kernel<3> : conv_stem_kernel<4>;
+    Y2H_CHECK(y2h_lds_limit((const void *)fn, lds));
+    const long ntiles = ((long)a.npix + 31) / 32;
+    int bpc = (int)(160 * 1024 / lds);
+    if (bpc > 4) bpc = 4;
+    long blocks = (ntiles + 3) / 4;
+    if (blocks > 256L * bpc) blocks = 256L * bpc;
+    hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(256), lds, S(s), a);
+    Y2H_LAUNCH_CHECK();
+    return Y2H_OK;
+}
+
+// fp32 matrix-core kernel: stream-K, hybrid stream-K, XCD-ordered or plain whole tiles (+ the split-K reduction)
+static int mfma_launch(const ConvPlan &p, const y2h_conv *d, ConvK &a, y2h_stream s)
+{
+    const bool sk = p.sk_wgs > 0;
+    const Variant *v = sk ? p.sk_v : p.tile;
+    const int ksplit = sk ? 1 : p.tile_ksplit;
+    a.ksplit = ksplit;
+    if (ksplit > 1) {
+        if (!d->ws || d->ws_bytes < (size_t)ksplit * d->batch * d->out_h * d->out_w * d->n * sizeof(float)) return Y2H_EINVAL;
+        a.ws = d->ws;
     }
-    if (!strict && first_ok(d)) return d->n <= 32 ? "conv_first_mfma_f32_c3_n32" : "conv_first_mfma_f32_c3_n64";
-    if (d->x_f16) {
-        if (!strict && y2_f16_first_ok(d)) return d->n <= 32 ? "conv_first_mfma_f16_c3_n32" : "conv_first_mfma_f16_c3_n64";
-        const char *nm = strict ? nullptr : y2_f16_conv_variant(d);
-        return nm ? nm : "conv_direct_f16";
+    a.w = d->w_packed;
+    a.npix = d->batch * d->out_h * d->out_w;
+    a.xbytes = (unsigned)((size_t)d->batch * d->h * d->w * d->ldx * 4);
+    a.wbytes = (unsigned)((size_t)d->n * a.K * 4);
+    // 16-byte output stores (8-wave tiles): a pixel's filters must start on 16 bytes
+    a.ybytes = (unsigned)((size_t)(d->fuse_maxpool2 ? a.npix / 4 : a.npix) * d->ldy * 4);        // < 4 GB: mfma_ok
+    a.vec_store = d->ldy % 4 == 0 && d->n % 4 == 0 && ((uintptr_t)d->y % 16) == 0 && ksplit == 1 && !getenv("Y2_F32_SCALAR_STORES");
+    a.tiles_n = (d->n + v->bn - 1) / v->bn;
+    const long tiles_m = ((long)a.npix + v->bm - 1) / v->bm;
+    a.ntiles = (int)(tiles_m * a.tiles_n) * ksplit;
+    if (getenv("Y2_CONV_XCD_REMAP")) a.dbg |= 64;      // A/B switch; measured 0.2-0.5 % slower in the pipelined step (r02 notes)
+#ifdef Y2_F32_STAMPS
+    static unsigned long long *d_st = nullptr;
+    if (!d_st) Y2H_CHECK(hipMalloc((void **)&d_st, 1024 * 8 * 7 * sizeof(unsigned long long)));
+    Y2H_CHECK(hipMemsetAsync(d_st, 0, 1024 * 8 * 7 * sizeof(unsigned long long), S(s)));
+    a.stamps = d_st;
+#endif
+    if (sk) {
+        // stream-K: all output tiles' K loops in equal shares over sk_wgs workgroups, then the piece reduction
+        a.sk_tiles = (int)(tiles_m * a.tiles_n);
+        a.sk_wgs = p.sk_wgs;
+        a.ws = d->ws;
+        Y2H_CHECK(y2h_lds_limit((const void *)v->fn_sk, v->lds));
+        hipLaunchKernelGGL(v->fn_sk, dim3((unsigned)p.sk_wgs), dim3(v->threads), v->lds, S(s), a);
+        Y2H_LAUNCH_CHECK();
+        const long outs4 = (long)(d->fuse_maxpool2 ? a.npix / 4 : a.npix) * (a.Cout / 4);
+        hipLaunchKernelGGL(sk_reduce_kernel, dim3(y2h_grid(outs4, 256)), dim3(256), 0, S(s), a, v->bm, v->bn,
+                           d->size * d->size * (d->c / v->bk));
+        Y2H_LAUNCH_CHECK();
+        ++g_skf_launches;
+        return Y2H_OK;
     }
-    if (!strict && c32_f32_ok(d)) return "conv_c32_f32_16x16";
-    if (!strict && d->x_halo == 0 && mfma_ok(d)) {
-        Variant *v = pick_variant(d);
-        if (v) return v->name;
+    if (p.skh_tiles > 0 && !p.xcd_order) {
+        // hybrid stream-K: the partial last round's K loops in equal shares over ALL co-resident workgroups, finished in-launch
+        const long wgs = skh_slots(*v);
+        a.sk_tiles = getenv("Y2_SKH_NOSPLIT") ? 0 : p.skh_tiles;      // (diagnostic: the hybrid instantiation walking every tile whole)
+        a.sk_wgs = (int)wgs;
+        a.ws = d->ws;
+        a.sk_flags = (int *)(d->ws + (size_t)wgs * v->bm * v->bn);
+        Y2H_CHECK(hipMemsetAsync(a.sk_flags, 0, (size_t)wgs * sizeof(int), S(s)));
+        Y2H_CHECK(y2h_lds_limit((const void *)v->fn_skh, v->lds));
+        hipLaunchKernelGGL(v->fn_skh, dim3((unsigned)wgs), dim3(v->threads), v->lds, S(s), a);
+        Y2H_LAUNCH_CHECK();
+        ++g_skh_launches;
+#ifdef Y2_F32_STAMPS
+        f32_stamps_report(v, d, wgs, d_st, s);
+#endif
+        return Y2H_OK;
     }
-    if (!strict && stem_ok(d)) return "conv_stem_mfma_f32";
-    return "conv_direct_f32";
+    void (*fn)(ConvK) = v->fn;
+    if (p.xcd_order) {
+        a.xcd_order = 1;
+        a.tiles_m = p.tiles_m;
+        a.pblk = p.pblk;
+        fn = v->fn_xo;
+        ++g_xcd_order_launches;
+    }
+    Y2H_CHECK(y2h_lds_limit((const void *)fn, v->lds));
+    hipLaunchKernelGGL(fn, dim3((unsigned)p.grid), dim3(v->threads), v->lds, S(s), a);
+    Y2H_LAUNCH_CHECK();
+#ifdef Y2_F32_STAMPS
+    f32_stamps_report(v, d, p.grid, d_st, s);
+#endif
+    if (ksplit > 1) {
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(y2h_grid((long)a.npix * a.Cout, 256)), dim3(256), 0, S(s), a);
+        Y2H_LAUNCH_CHECK();
+    }
+    return Y2H_OK;
+}
+
+static int direct_launch(const y2h_conv *d, ConvK &a, y2h_stream s)
+{
+    if (d->x_halo != 0) return Y2H_EINVAL;       // only the first-layer and stem kernels read a haloed input
+    if (!d->w_ref) return Y2H_EINVAL;            // the direct kernel needs the reference-layout weights
+    a.w = d->w_ref;
+    const long total = (long)d->batch * d->out_h * d->out_w * d->n;
+    if (d->x_f16) hipLaunchKernelGGL(conv_direct_kernel<true>, dim3(y2h_grid(total, 256, 256 * 32)), dim3(256), 0, S(s), a);
+    else hipLaunchKernelGGL(conv_direct_kernel<false>, dim3(y2h_grid(total, 256, 256 * 32)), dim3(256), 0, S(s), a);
+    Y2H_LAUNCH_CHECK();
+    return Y2H_OK;
 }
 
 extern "C" int y2h_conv_forward(const y2h_conv *d, int strict, y2h_stream s)
@@ -1750,6 +1921,14 @@ extern "C" int y2h_conv_forward(const y2h_conv *d, int strict, y2h_stream s)
     if (d->out_h != (d->h + 2 * d->pad - d->size) / d->stride + 1) return Y2H_EINVAL;
     if (d->out_w != (d->w + 2 * d->pad - d->size) / d->stride + 1) return Y2H_EINVAL;
 
+    ConvPlan p = conv_plan(d, strict);
+    if (p.kind == CK_NONE) return Y2H_EINVAL;
+    // only the matrix-core kernels pool in their epilogue (the stem kernel does not take a pooled layer), and 2x2/2 windows need even dims
+    if (d->fuse_maxpool2 && (p.kind == CK_DIRECT || ((d->h | d->w) & 1))) return Y2H_EINVAL;
+    // no room in ws: stream-K runs the whole tiles of the integer split instead, hybrid stream-K every tile whole
+    if (p.skh_tiles > 0 && (!d->ws || d->ws_bytes < skh_ws_bytes(*p.tile) || ((uintptr_t)d->ws % 16) != 0)) p.skh_tiles = 0;
+    if (p.sk_wgs > 0 && (!d->ws || d->ws_bytes < p.ws || ((uintptr_t)d->y % 16) != 0 || ((uintptr_t)d->ws % 16) != 0)) p.sk_wgs = 0;
+
     ConvK a;
     memset(&a, 0, sizeof a);
     a.x = d->x; a.y = d->y;
@@ -1759,203 +1938,17 @@ extern "C" int y2h_conv_forward(const y2h_conv *d, int strict, y2h_stream s)
     a.bn = d->batch_normalize; a.act = d->activation;
     a.size = d->size; a.stride = d->stride; a.pad = d->pad; a.out_h = d->out_h; a.out_w = d->out_w; a.batch = d->batch;
     a.y_f16 = d->y_f16;
+    a.pool = d->fuse_maxpool2 ? 1 : 0;
 
-    if (d->x_nchw) {
-        // the network input itself (fp32 planes): only the fused fp16 first-layer kernel reads that layout
-        if (strict || !(y2_f16_first_nchw_ok(d) || first_nchw_ok(d))) return Y2H_EINVAL;
-        if (d->fuse_maxpool2 && ((d->h | d->w) & 1)) return Y2H_EINVAL;
-        a.pool = d->fuse_maxpool2 ? 1 : 0;
-        if (y2_f16_first_nchw_ok(d)) return y2_f16_first_nchw_launch(d, a, s);
-        a.nchw = 1;
-        a.w = d->w_packed;
-        a.npix = d->batch * d->h * d->w;
-        a.xbytes = (unsigned)((size_t)d->batch * 3 * d->h * d->w * 4);
-        const long ntiles = ((long)a.npix + 31) / 32;
-        long blocks = (ntiles + 3) / 4;
-        void (*fn)(ConvK) = d->n <= 32 ? conv_first_kernel<1> : conv_first_kernel<2>;
-        const long res = resident_blocks((const void *)fn, 256, 0, 3);
-        if (blocks > res) blocks = res;              // tiles are grid-strided
-        hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(256), 0, S(s), a);
-        Y2H_LAUNCH_CHECK();
-        return Y2H_OK;
+    switch (p.kind) {
+    case CK_FIRST_NCHW_F32:
+    case CK_FIRST_F32: return first_launch(d, a, s);
+    case CK_C32_F32: return c32_f32_launch(d, a, s);
+    case CK_MFMA_F32: return mfma_launch(p, d, a, s);
+    case CK_STEM: return stem_launch(d, a, s);
+    case CK_DIRECT: return direct_launch(d, a, s);
+    default: return y2_f16_launch(p, d, a, s);
     }
-    if (d->fuse_maxpool2) {
-        // only the matrix-core kernels pool in their epilogue, and 2x2/2 windows need even dims
-        if (strict || (d->h & 1) || (d->w & 1) ||
-            !(first_ok(d) || y2_f16_first_ok(d) || y2_f16_conv_ok(d) || (d->x_halo == 0 && mfma_ok(d) && pick_variant(d))))
-            return Y2H_EINVAL;
-        a.pool = 1;
-    }
-    if (!strict && y2_f16_first_ok(d)) return y2_f16_first_launch(d, a, s);
-    if (!strict && first_ok(d)) {
-        a.w = d->w_packed;
-        a.npix = d->batch * d->h * d->w;
-        a.xbytes = (unsigned)((size_t)d->batch * (d->h + 2) * (d->w + 2) * d->ldx * 4);
-        const long ntiles = ((long)a.npix + 31) / 32;
-        long blocks = (ntiles + 3) / 4;
-        void (*fn)(ConvK) = d->n <= 32 ? conv_first_kernel<1> : conv_first_kernel<2>;
-        const long res = resident_blocks((const void *)fn, 256, 0, 3);
-        if (blocks > res) blocks = res;              // tiles are grid-strided
-        hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(256), 0, S(s), a);
-        Y2H_LAUNCH_CHECK();
-        return Y2H_OK;
-    }
-    if (!strict && y2_f16_conv_ok(d)) return y2_f16_conv_launch(d, a, s);
-    if (!strict && c32_f32_ok(d)) return c32_f32_launch(d, a, s);
-    int ksplit = 1, sk_wgs = 0, skh_tiles = 0;
-    Variant *v = (!strict && d->x_halo == 0 && mfma_ok(d)) ? pick_variant(d, &ksplit, &sk_wgs, &skh_tiles) : nullptr;
-    if (v && skh_tiles > 0 && (!d->ws || d->ws_bytes < skh_ws_bytes(*v) || ((uintptr_t)d->ws % 16) != 0)) skh_tiles = 0;      // no room: every tile whole
-    if (v && sk_wgs > 0 && (!d->ws || d->ws_bytes < (size_t)2 * sk_wgs * v->bm * v->bn * sizeof(float) || ((uintptr_t)d->y % 16) != 0 ||
-                            ((uintptr_t)d->ws % 16) != 0)) {
-        sk_wgs = 0;                                       // no room for the piece slots: the integer split of the same descriptor
-        v = pick_variant(d, &ksplit);
-    }
-    if (!v && !strict && stem_ok(d)) {
-        a.w = d->w_packed;
-        a.npix = d->batch * d->out_h * d->out_w;
-        a.xbytes = (unsigned)((size_t)d->batch * (d->h + 2 * d->pad) * (d->w + 2 * d->pad) * d->ldx * 4);
-        const size_t lds = stem_lds_bytes(d);
-        const int nt = (d->n + 31) / 32;
-        void (*fn)(ConvK) = nt == 1 ? conv_stem_kernel<1> : nt == 2 ? conv_stem_kernel<2> : nt == 3 ? conv_stem_kernel<3> : conv_stem_kernel<4>;
-        {
-            static size_t attr_lds[16][4] = {{0}};       // per device and instantiation: largest size requested so far
-            int dev = 0;
-            Y2H_CHECK(hipGetDevice(&dev));
-            if (dev < 0 || dev >= 16 || attr_lds[dev][nt - 1] < lds) {
-                Y2H_CHECK(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                if (dev >= 0 && dev < 16) attr_lds[dev][nt - 1] = lds;
-            }
-        }
-        const long ntiles = ((long)a.npix + 31) / 32;
-        int bpc = (int)(160 * 1024 / lds);
-        if (bpc > 4) bpc = 4;
-        long blocks = (ntiles + 3) / 4;
-        if (blocks > 256L * bpc) blocks = 256L * bpc;
-        hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(256), lds, S(s), a);
-        Y2H_LAUNCH_CHECK();
-        return Y2H_OK;
-    }
-    if (d->x_halo != 0) return Y2H_EINVAL;       // only the first-layer and stem kernels read a haloed input
-    if (v) {
-        a.ksplit = ksplit;
-        if (ksplit > 1) {
-            if (!d->ws || d->ws_bytes < (size_t)ksplit * d->batch * d->out_h * d->out_w * d->n * sizeof(float)) return Y2H_EINVAL;
-            a.ws = d->ws;
-        }
-        a.w = d->w_packed;
-        a.npix = d->batch * d->out_h * d->out_w;
-        a.xbytes = (unsigned)((size_t)d->batch * d->h * d->w * d->ldx * 4);
-        a.wbytes = (unsigned)((size_t)d->n * a.K * 4);
-        // 16-byte output stores (8-wave tiles): a pixel's filters must start on 16 bytes
-        {
-            a.ybytes = (unsigned)((size_t)(d->fuse_maxpool2 ? a.npix / 4 : a.npix) * d->ldy * 4);        // < 4 GB: mfma_ok
-            a.vec_store = d->ldy % 4 == 0 && d->n % 4 == 0 && ((uintptr_t)d->y % 16) == 0 && ksplit == 1 && !getenv("Y2_F32_SCALAR_STORES");
-        }
-        a.tiles_n = (d->n + v->bn - 1) / v->bn;
-        const long tiles_m = ((long)a.npix + v->bm - 1) / v->bm;
-        int dev = 0;
-        Y2H_CHECK(hipGetDevice(&dev));
-        if (dev < 0 || dev >= 16 || !v->attr_set[dev]) {
-            Y2H_CHECK(hipFuncSetAttribute((const void *)v->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v->lds));
-            if (dev >= 0 && dev < 16) v->attr_set[dev] = true;
-        }
-        a.ntiles = (int)(tiles_m * a.tiles_n) * ksplit;
-        if (getenv("Y2_CONV_XCD_REMAP")) a.dbg |= 64;      // A/B switch; measured 0.2-0.5 % slower in the pipelined step (r02 notes)
-        long grid = 256L * variant_bpc(*v);          // persistent: at most what is co-resident
-        if (const char *g = getenv("Y2_CONV_GRID")) { if (atol(g) > 0 && atol(g) < grid) grid = atol(g); }   // tests: many tiles per workgroup on small shapes
-        if (grid > a.ntiles) grid = a.ntiles;
-        {
-            // Wide heads: when the weights are the large operand and there are many filter tiles, filter-tile-fastest numbering
-            // makes every round of workgroups stream the whole weight matrix again (yolo9000 544 b8, final 1x1: 4.3 GB fetched
-            // for 125 MB of operands, profiles/r02_9k544b8_pmc_summary.txt).  See ConvK.xcd_order.  Y2_XCD_ORDER=0/1 forces.
-            const double wb = (double)d->n * a.K * 4.0, xb = (double)a.npix * d->c * 4.0;
-            bool on = v->fn_xo && ksplit == 1 && grid >= 8 && a.tiles_n >= 16 && wb > 2.0 * xb && wb > 16e6;
-            if (const char *f = getenv("Y2_XCD_ORDER")) on = v->fn_xo && atoi(f) != 0 && ksplit == 1 && grid >= 8;
-            if (on) {
-                a.xcd_order = 1;
-                a.tiles_m = (int)tiles_m;
-                const double tile_b = (double)v->bm * d->c * d->size * d->size * 4.0;      // input bytes one pixel tile touches (upper bound)
-                long pb = (long)(3.0e6 / tile_b);
-                if (const char *f = getenv("Y2_XCD_PBLK")) pb = atol(f);
-                if (pb < 1) pb = 1;
-                if (pb > tiles_m) pb = tiles_m;
-                a.pblk = (int)pb;
-                grid -= grid % 8;
-            }
-        }
-#ifdef Y2_F32_STAMPS
-        static unsigned long long *d_st = nullptr;
-        if (!d_st) Y2H_CHECK(hipMalloc((void **)&d_st, 1024 * 8 * 7 * sizeof(unsigned long long)));
-        Y2H_CHECK(hipMemsetAsync(d_st, 0, 1024 * 8 * 7 * sizeof(unsigned long long), S(s)));
-        a.stamps = d_st;
-#endif
-        if (sk_wgs > 0) {
-            // stream-K: all output tiles' K loops in equal shares over sk_wgs workgroups, then the piece reduction
-            a.sk_tiles = (int)(tiles_m * a.tiles_n);
-            a.sk_wgs = sk_wgs;
-            a.ws = d->ws;
-            a.ksplit = 1;
-            a.xcd_order = 0;
-            if (dev < 0 || dev >= 16 || !v->attr_set_sk[dev]) {
-                Y2H_CHECK(hipFuncSetAttribute((const void *)v->fn_sk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v->lds));
-                if (dev >= 0 && dev < 16) v->attr_set_sk[dev] = true;
-            }
-            hipLaunchKernelGGL(v->fn_sk, dim3((unsigned)sk_wgs), dim3(v->threads), v->lds, S(s), a);
-            Y2H_LAUNCH_CHECK();
-            const long outs4 = (long)(d->fuse_maxpool2 ? a.npix / 4 : a.npix) * (a.Cout / 4);
-            hipLaunchKernelGGL(sk_reduce_kernel, dim3(y2h_grid(outs4, 256)), dim3(256), 0, S(s), a, v->bm, v->bn,
-                               d->size * d->size * (d->c / v->bk));
-            Y2H_LAUNCH_CHECK();
-            ++g_skf_launches;
-            return Y2H_OK;
-        }
-        if (skh_tiles > 0 && !a.xcd_order) {
-            // hybrid stream-K: the partial last round's K loops in equal shares over ALL co-resident workgroups, finished in-launch
-            const long wgs = skh_slots(*v);
-            a.sk_tiles = getenv("Y2_SKH_NOSPLIT") ? 0 : skh_tiles;      // (diagnostic: the hybrid instantiation walking every tile whole)
-            a.sk_wgs = (int)wgs;
-            a.ws = d->ws;
-            a.sk_flags = (int *)(d->ws + (size_t)wgs * v->bm * v->bn);
-            Y2H_CHECK(hipMemsetAsync(a.sk_flags, 0, (size_t)wgs * sizeof(int), S(s)));
-            if (dev < 0 || dev >= 16 || !v->attr_set_skh[dev]) {
-                Y2H_CHECK(hipFuncSetAttribute((const void *)v->fn_skh, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v->lds));
-                if (dev >= 0 && dev < 16) v->attr_set_skh[dev] = true;
-            }
-            hipLaunchKernelGGL(v->fn_skh, dim3((unsigned)wgs), dim3(v->threads), v->lds, S(s), a);
-            Y2H_LAUNCH_CHECK();
-            ++g_skh_launches;
-#ifdef Y2_F32_STAMPS
-            f32_stamps_report(v, d, wgs, d_st, s);
-#endif
-            return Y2H_OK;
-        }
-        if (a.xcd_order) {
-            ++g_xcd_order_launches;
-            if (dev < 0 || dev >= 16 || !v->attr_set_xo[dev]) {
-                Y2H_CHECK(hipFuncSetAttribute((const void *)v->fn_xo, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v->lds));
-                if (dev >= 0 && dev < 16) v->attr_set_xo[dev] = true;
-            }
-            hipLaunchKernelGGL(v->fn_xo, dim3((unsigned)grid), dim3(v->threads), v->lds, S(s), a);
-        } else {
-            hipLaunchKernelGGL(v->fn, dim3((unsigned)grid), dim3(v->threads), v->lds, S(s), a);
-        }
-        Y2H_LAUNCH_CHECK();
-#ifdef Y2_F32_STAMPS
-        f32_stamps_report(v, d, grid, d_st, s);
-#endif
-        if (ksplit > 1) {
-            hipLaunchKernelGGL(splitk_reduce_kernel, dim3(y2h_grid((long)a.npix * a.Cout, 256)), dim3(256), 0, S(s), a);
-            Y2H_LAUNCH_CHECK();
-        }
-        return Y2H_OK;
-    }
-    if (!d->w_ref) return Y2H_EINVAL;     // direct kernel needs the reference-layout weights
-    a.w = d->w_ref;
-    const long total = (long)d->batch * d->out_h * d->out_w * d->n;
-    if (d->x_f16) hipLaunchKernelGGL(conv_direct_kernel<true>, dim3(y2h_grid(total, 256, 256 * 32)), dim3(256), 0, S(s), a);
-    else hipLaunchKernelGGL(conv_direct_kernel<false>, dim3(y2h_grid(total, 256, 256 * 32)), dim3(256), 0, S(s), a);
-    Y2H_LAUNCH_CHECK();
-    return Y2H_OK;
 }
 
 // ---------------------------------------------------------------------------

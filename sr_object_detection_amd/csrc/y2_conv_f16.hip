@@ -477,7 +477,7 @@ __global__ __launch_bounds__(WM *WN * 64, MINB) void conv_mfma_f16_kernel(ConvK 
 // ---------------------------------------------------------------------------
 typedef __attribute__((address_space(3))) void lds_void;
 // Diagnostic build (-DP8_STAMPS, tools/build_variant.sh): every wave accumulates s_memtime deltas per phase segment and
-// writes them to a.ws at the end; y2_f16_conv_launch prints the averages.  Stamps cost ~10 % and serialise the fragment
+// writes them to a.ws at the end; mfma_h_launch prints the averages.  Stamps cost ~10 % and serialise the fragment
 // reads in front of the first barrier; never compiled into the product.
 #ifdef P8_STAMPS
 #define P8_STAMP(k) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[k] += t_ - st_prev; st_prev = t_; } while (0)
@@ -896,18 +896,17 @@ struct VariantH {
     int minb;
     bool m16;          // 16x16x32 MFMA variant: needs the 16-byte output stores (vec_store)
     bool p8;           // the LDS-DMA / eight-phase kernel (conv_p8_f16_kernel)
-    bool attr_set[16];
 };
 
 // MINB = workgroups per CU the register budget is sized for: 4-wave kernels with MINB 1 get the whole
 // 512-entry register file of their SIMD (one wave per SIMD), everything else 256 registers per lane
 #define VARH(BM, BN, BK, KS, WM, WN, MINB, DB, M16)                                                  \
     { "conv_mfma_f16_" #BM "x" #BN "x" #BK "_k" #KS, BM, BN, BK, KS, conv_mfma_f16_kernel<BM, BN, BK, KS, WM, WN, MINB, DB, M16>, \
-      (size_t)2 * (BM + BN) * (BK + 8) * sizeof(_Float16), WM * WN * 64, MINB, M16, false, {false} }
+      (size_t)2 * (BM + BN) * (BK + 8) * sizeof(_Float16), WM * WN * 64, MINB, M16, false }
 // same tile and name (tests and profiles address kernels by tile), different structure: see conv_p8_f16_kernel
 #define VARP8(KS)                                                                                    \
     { "conv_mfma_f16_256x256x64_k" #KS, 256, 256, 64, KS, conv_p8_f16_kernel<KS>,                      \
-      (size_t)2 * 4 * 128 * 128 + (size_t)8 * 32 * 40 * sizeof(_Float16), 512, 1, true, true, {false} }
+      (size_t)2 * 4 * 128 * 128 + (size_t)8 * 32 * 40 * sizeof(_Float16), 512, 1, true, true }
 
 static VariantH g_variants_h[] = {
     // LDS-DMA staging, 8 phases per two K-tiles (first in the table: wins the tie against the register-staged 256x256)
@@ -1108,16 +1107,7 @@ static int c32_launch(const y2h_conv *d, ConvK &a, y2h_stream s)
                                           : (lk ? conv_c32_f16_kernel<2, false, true> : conv_c32_f16_kernel<2, false, false>));
     const size_t lds = (size_t)2 * 18 * 1664 + 4 * 8 * 144;
     a.vec_store = d->ldy % 8 == 0 && d->n % 8 == 0 && ((uintptr_t)d->y % 16) == 0 && !getenv("Y2_C32_SCALAR");
-    {
-        static bool attr_set[16][8] = {{false}};         // per device and instantiation: the attribute call is not free
-        const int which = ((nf - 1) * 2 + (a.pool ? 1 : 0)) * 2 + (lk ? 1 : 0);
-        int dev = 0;
-        Y2H_CHECK(hipGetDevice(&dev));
-        if (dev < 0 || dev >= 16 || !attr_set[dev][which]) {
-            Y2H_CHECK(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            if (dev >= 0 && dev < 16) attr_set[dev][which] = true;
-        }
-    }
+    Y2H_CHECK(y2h_lds_limit((const void *)fn, lds));
     long tiles = (long)d->batch * (d->h >> 4) * (d->w >> 4);
     long grid = tiles < 512 ? tiles : 512;               // two workgroups per CU, tiles are grid-strided
     hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(256), lds, S(s), a);
@@ -1292,16 +1282,7 @@ static int c64_launch(const y2h_conv *d, ConvK &a, y2h_stream s)
                                : (lk ? conv_c64_f16_kernel<false, true> : conv_c64_f16_kernel<false, false>);
     const size_t lds = (size_t)2 * 18 * 2688 + 8 * 32 * 80;
     a.vec_store = 1;
-    {
-        static bool attr_set[16][4] = {{false}};
-        const int which = (a.pool ? 2 : 0) + (lk ? 1 : 0);
-        int dev = 0;
-        Y2H_CHECK(hipGetDevice(&dev));
-        if (dev < 0 || dev >= 16 || !attr_set[dev][which]) {
-            Y2H_CHECK(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            if (dev >= 0 && dev < 16) attr_set[dev][which] = true;
-        }
-    }
+    Y2H_CHECK(y2h_lds_limit((const void *)fn, lds));
     long tiles = (long)d->batch * (d->h >> 4) * (d->w >> 4);
     long grid = tiles < 256 ? tiles : 256;               // one workgroup per CU, tiles are grid-strided
     if (const char *g = getenv("Y2_CONV_GRID")) { if (atol(g) > 0 && atol(g) < grid) grid = atol(g); }
@@ -1310,7 +1291,7 @@ static int c64_launch(const y2h_conv *d, ConvK &a, y2h_stream s)
     return Y2H_OK;
 }
 
-bool y2_f16_conv_ok(const y2h_conv *d)
+static bool mfma_h_ok(const y2h_conv *d)
 {
     if (!d->x_f16) return false;
     if (!(d->size == 1 || d->size == 3)) return false;
@@ -1453,12 +1434,6 @@ static double tail_cost(const VariantH &v, long rows, int n, int nk)
     return 1.5 + (double)per_cu * ((double)v.bm * v.bn / 65536.0) / rel * (nk + 6.0);
 }
 
-struct P8Plan {
-    int sk_tiles, sk_wgs;          // stream-K (0: none)
-    int tail_tiles;                // 256x256 tiles handed to the tail launch (0: none)
-    VariantH *tail;
-};
-
 static P8Plan p8_plan(const y2h_conv *d, long ntiles, int tiles_n, int nk, long grid)
 {
     P8Plan pl = {0, 0, 0, nullptr};
@@ -1499,65 +1474,42 @@ static P8Plan p8_plan(const y2h_conv *d, long ntiles, int tiles_n, int nk, long 
     return pl;
 }
 
-// piece slots the plan may need for this descriptor (bytes of y2h_conv.ws)
-size_t y2_f16_conv_workspace_bytes(const y2h_conv *d);
-
-const char *y2_f16_conv_variant(const y2h_conv *d)
+static int mfma_h_launch(const ConvPlan &p, const y2h_conv *d, ConvK &a, y2h_stream s)
 {
-    if (c32_ok(d)) return "conv_c32_f16_16x16";
-    if (c64_ok(d)) return "conv_c64_f16_16x16";
-    VariantH *v = y2_f16_conv_ok(d) ? pick_h(d) : nullptr;
-    return v ? v->name : nullptr;
-}
-
-int y2_f16_conv_launch(const y2h_conv *d, ConvK &a, y2h_stream s)
-{
-    if (c32_ok(d)) return c32_launch(d, a, s);
-    if (c64_ok(d)) return c64_launch(d, a, s);
-    VariantH *v = pick_h(d);
+    const VariantH *v = p.vh;
     if (!v || !d->alpha || !d->beta) return Y2H_EINVAL;
     a.w = d->w_packed;
     a.alpha = d->alpha; a.beta = d->beta;
     a.npix = d->batch * d->h * d->w;
     a.xbytes = (unsigned)((size_t)d->batch * d->h * d->w * d->ldx * 2);
     a.wbytes = (unsigned)((size_t)d->n * a.K * 2);
-    a.tiles_n = (d->n + v->bn - 1) / v->bn;
+    a.tiles_n = p.h_tiles_n;
     a.ksplit = 1;
     if (const char *dbg = getenv("Y2_DBG")) a.dbg = atoi(dbg);
     a.vec_store = d->y_f16 && d->ldy % 8 == 0 && d->n % 8 == 0 && ((uintptr_t)d->y % 16) == 0 && !ABL(8);
-    const long tiles_m = ((long)a.npix + v->bm - 1) / v->bm;
-    int dev = 0;
-    Y2H_CHECK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 16 || !v->attr_set[dev]) {
-        Y2H_CHECK(hipFuncSetAttribute((const void *)v->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v->lds));
-        if (dev >= 0 && dev < 16) v->attr_set[dev] = true;
-    }
-    a.ntiles = (int)(tiles_m * a.tiles_n);
+    Y2H_CHECK(y2h_lds_limit((const void *)v->fn, v->lds));
+    a.ntiles = (int)p.h_ntiles;
     if (v->p8 && getenv("Y2_P8_REMAP")) a.dbg |= 64;            // A/B: XCD-contiguous placement of workgroups
-    long grid = 256L * bpc_h(*v);
-    if (const char *g = getenv("Y2_CONV_GRID")) { if (atol(g) > 0 && atol(g) < grid) grid = atol(g); }   // tests: many tiles per workgroup on small shapes
-    bool sk = false;
+    long grid = p.h_grid;
+    // stream-K needs its piece slots in y2h_conv.ws; without them the plan runs every tile whole (no tail launch either)
+    const bool sk = p.p8.sk_tiles && d->ws && d->ws_bytes >= (size_t)2 * p.p8.sk_wgs * 256 * 256 * sizeof(float);
     ConvK tl;                       // the tail launch, if the plan has one
-    VariantH *tailv = nullptr;
-    if (v->p8) {
-        const P8Plan pl = p8_plan(d, a.ntiles, a.tiles_n, d->size * d->size * (d->c / 64), grid);
-        if (pl.sk_tiles && d->ws && d->ws_bytes >= (size_t)2 * pl.sk_wgs * 256 * 256 * sizeof(float)) {
-            a.sk_tiles = pl.sk_tiles; a.sk_wgs = pl.sk_wgs; a.ws = d->ws;
-            sk = true;
-        } else if (pl.tail_tiles) {
-            tailv = pl.tail;
+    const VariantH *tailv = nullptr;
+    if (sk) {
+        a.sk_tiles = p.p8.sk_tiles; a.sk_wgs = p.p8.sk_wgs; a.ws = d->ws;
+        long need = a.ntiles - a.sk_tiles;      // whole tiles need min(grid, ntiles - sk_tiles) workgroups, the shares sk_wgs
+        if (need < a.sk_wgs) need = a.sk_wgs;
+        if (grid > need) grid = need;
+    } else {
+        if (p.p8.tail_tiles) {
+            tailv = p.p8.tail;
             tl = a;
-            a.ntiles -= pl.tail_tiles;
+            a.ntiles -= p.p8.tail_tiles;
             tl.row0 = (a.ntiles / a.tiles_n) * 256;
             tl.tiles_n = (d->n + tailv->bn - 1) / tailv->bn;
             tl.ntiles = (int)((((long)a.npix - tl.row0 + tailv->bm - 1) / tailv->bm) * tl.tiles_n);
         }
-    }
-    if (!sk && grid > a.ntiles) grid = a.ntiles;
-    if (sk) {            // whole tiles need min(grid, ntiles - sk_tiles) workgroups, the shares sk_wgs
-        long need = a.ntiles - a.sk_tiles;
-        if (need < a.sk_wgs) need = a.sk_wgs;
-        if (grid > need) grid = need;
+        if (grid > a.ntiles) grid = a.ntiles;
     }
 #ifdef P8_STAMPS
     static unsigned long long *d_st = nullptr;
@@ -1572,10 +1524,7 @@ int y2_f16_conv_launch(const y2h_conv *d, ConvK &a, y2h_stream s)
         Y2H_LAUNCH_CHECK();
     }
     if (tailv) {
-        if (dev < 0 || dev >= 16 || !tailv->attr_set[dev]) {
-            Y2H_CHECK(hipFuncSetAttribute((const void *)tailv->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tailv->lds));
-            if (dev >= 0 && dev < 16) tailv->attr_set[dev] = true;
-        }
+        Y2H_CHECK(y2h_lds_limit((const void *)tailv->fn, tailv->lds));
         long g2 = 256L * bpc_h(*tailv);
         if (g2 > tl.ntiles) g2 = tl.ntiles;
         hipLaunchKernelGGL(tailv->fn, dim3((unsigned)g2), dim3(tailv->threads), tailv->lds, S(s), tl);
@@ -1611,19 +1560,6 @@ int y2_f16_conv_launch(const y2h_conv *d, ConvK &a, y2h_stream s)
     }
 #endif
     return Y2H_OK;
-}
-
-size_t y2_f16_conv_workspace_bytes(const y2h_conv *d)
-{
-    if (c32_ok(d) || c64_ok(d) || !y2_f16_conv_ok(d)) return 0;
-    VariantH *v = pick_h(d);
-    if (!v || !v->p8) return 0;
-    const long npix = (long)d->batch * d->h * d->w;
-    const long ntiles = ((npix + 255) / 256) * ((d->n + 255) / 256);
-    long grid = 256L * bpc_h(*v);
-    if (const char *g = getenv("Y2_CONV_GRID")) { if (atol(g) > 0 && atol(g) < grid) grid = atol(g); }
-    const P8Plan pl = p8_plan(d, ntiles, (d->n + 255) / 256, d->size * d->size * (d->c / 64), grid);
-    return (size_t)2 * pl.sk_wgs * 256 * 256 * sizeof(float);
 }
 
 // ---------------------------------------------------------------------------
@@ -2036,7 +1972,7 @@ bool y2_f16_first_nchw_ok(const y2h_conv *d)
     return d->w_packed != nullptr && ((uintptr_t)d->x % 16) == 0;
 }
 
-int y2_f16_first_nchw_launch(const y2h_conv *d, ConvK &a, y2h_stream s)
+static int first_nchw_launch(const y2h_conv *d, ConvK &a, y2h_stream s)
 {
     a.w = d->w_packed;
     a.npix = d->batch * d->h * d->w;
@@ -2048,11 +1984,7 @@ int y2_f16_first_nchw_launch(const y2h_conv *d, ConvK &a, y2h_stream s)
     long blocks = 256L * per_cu;
     if (blocks > nbands) blocks = nbands;
     void (*fn)(ConvK) = d->n <= 32 ? conv_first_nchw_f16_kernel<1> : conv_first_nchw_f16_kernel<2>;
-    static bool attr[2];
-    if (!attr[d->n > 32]) {
-        if (hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) != hipSuccess) return Y2H_EHIP;
-        attr[d->n > 32] = true;
-    }
+    Y2H_CHECK(y2h_lds_limit((const void *)fn, lds));
     hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(256), lds, S(s), a);
     Y2H_LAUNCH_CHECK();
     return Y2H_OK;
@@ -2068,7 +2000,7 @@ bool y2_f16_first_ok(const y2h_conv *d)
     return xbytes < 4294967000.0 && d->w_packed != nullptr && ((uintptr_t)d->x % 8) == 0;
 }
 
-int y2_f16_first_launch(const y2h_conv *d, ConvK &a, y2h_stream s)
+static int first_launch(const y2h_conv *d, ConvK &a, y2h_stream s)
 {
     a.w = d->w_packed;
     a.npix = d->batch * d->h * d->w;
@@ -2082,4 +2014,47 @@ int y2_f16_first_launch(const y2h_conv *d, ConvK &a, y2h_stream s)
     hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(256), 0, S(s), a);
     Y2H_LAUNCH_CHECK();
     return Y2H_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The fp16 half of conv_plan (y2_conv.hip) and the launch of what it chose
+// ---------------------------------------------------------------------------
+bool y2_f16_plan(const y2h_conv *d, ConvPlan &p)
+{
+    const bool n32 = d->n <= 32;
+    if (y2_f16_first_ok(d)) {
+        p.kind = CK_FIRST_F16;
+        p.name = n32 ? "conv_first_mfma_f16_c3_n32" : "conv_first_mfma_f16_c3_n64";
+        return true;
+    }
+    if (!mfma_h_ok(d)) return false;
+    if (c32_ok(d)) { p.kind = CK_C32_F16; p.name = "conv_c32_f16_16x16"; return true; }
+    if (c64_ok(d)) { p.kind = CK_C64_F16; p.name = "conv_c64_f16_16x16"; return true; }
+    p.kind = CK_MFMA_F16;
+    p.vh = pick_h(d);
+    p.name = p.vh ? p.vh->name : "conv_direct_f16";
+    if (!p.vh) return true;
+    const VariantH &v = *p.vh;
+    const long npix = (long)d->batch * d->h * d->w;
+    p.h_tiles_n = (d->n + v.bn - 1) / v.bn;
+    p.h_ntiles = ((npix + v.bm - 1) / v.bm) * p.h_tiles_n;
+    p.h_grid = 256L * bpc_h(v);
+    if (const char *g = getenv("Y2_CONV_GRID")) { if (atol(g) > 0 && atol(g) < p.h_grid) p.h_grid = atol(g); }   // tests: many tiles per workgroup on small shapes
+    if (v.p8) {
+        p.p8 = p8_plan(d, p.h_ntiles, p.h_tiles_n, d->size * d->size * (d->c / 64), p.h_grid);
+        p.ws = (size_t)2 * p.p8.sk_wgs * 256 * 256 * sizeof(float);      // stream-K piece slots
+    }
+    return true;
+}
+
+int y2_f16_launch(const ConvPlan &p, const y2h_conv *d, ConvK &a, y2h_stream s)
+{
+    switch (p.kind) {
+    case CK_FIRST_NCHW_F16: return first_nchw_launch(d, a, s);
+    case CK_FIRST_F16: return first_launch(d, a, s);
+    case CK_C32_F16: return c32_launch(d, a, s);
+    case CK_C64_F16: return c64_launch(d, a, s);
+    case CK_MFMA_F16: return mfma_h_launch(p, d, a, s);
+    default: return Y2H_EINVAL;
+    }
 }

@@ -124,15 +124,54 @@ __device__ __forceinline__ int pool_pixel(int r, int H, int W)
     return (n * H + 2 * yo + (t >> 1)) * W + 2 * xo + (t & 1);
 }
 
-// fp16 side (y2_conv_f16.hip)
-bool y2_f16_conv_ok(const y2h_conv *d);
-const char *y2_f16_conv_variant(const y2h_conv *d);
-int y2_f16_conv_launch(const y2h_conv *d, ConvK &a, y2h_stream s);
-size_t y2_f16_conv_workspace_bytes(const y2h_conv *d);
+// Which kernel runs a convolution and how it is launched: decided once per descriptor by conv_plan (y2_conv.hip), whose
+// fp16 half is y2_f16_plan; every entry point (kernel name, weight layout, workspace size, the launch) reads the plan.
+enum ConvKind {
+    CK_NONE,                                  // no kernel takes the descriptor (an NCHW input nothing reads)
+    CK_FIRST_NCHW_F16, CK_FIRST_NCHW_F32,     // first layer reading the fp32 NCHW network input
+    CK_FIRST_F16, CK_FIRST_F32,               // first layer reading a one-pixel haloed copy (half NHWC4 / fp32 NHWC)
+    CK_C32_F16, CK_C64_F16, CK_MFMA_F16,      // fp16 matrix-core kernels
+    CK_C32_F32, CK_MFMA_F32, CK_STEM,         // fp32 matrix-core kernels
+    CK_DIRECT,                                // reference accumulation order, reference-layout weights
+};
+
+struct Variant;
+struct VariantH;
+struct P8Plan {
+    int sk_tiles, sk_wgs;          // stream-K (0: none)
+    int tail_tiles;                // 256x256 tiles handed to the tail launch (0: none)
+    VariantH *tail;
+};
+
+struct ConvPlan {
+    ConvKind kind;
+    const char *name;              // y2h_conv_variant
+    size_t ws;                     // y2h_conv_workspace_bytes
+    // fp32 matrix-core kernel.  v / ksplit: the cost model's choice among whole-tile launches with an integer K-split -- the
+    // name and the first autotune candidate.  Set whenever that kernel takes the descriptor, also when conv_c32_f32 runs it.
+    Variant *v;
+    int ksplit;
+    // What its launch runs: the stream-K form of sk_v on sk_wgs workgroups (0: none), or whole tiles of `tile`.  `tile` is v
+    // unless a stream-K candidate shifted a near-tie of the cost model, and v when stream-K is chosen: then it is the launch
+    // if y2h_conv.ws has no room for the pieces.  Its shape: the grid, the XCD-grouped tile order and the hybrid stream-K tiles.
+    Variant *sk_v;
+    int sk_wgs;
+    Variant *tile;
+    int tile_ksplit, skh_tiles;
+    long grid;
+    int xcd_order, tiles_m, pblk;
+    // fp16 matrix-core kernel (nullptr: no tile fits the descriptor -- the launch fails)
+    VariantH *vh;
+    long h_ntiles, h_grid;
+    int h_tiles_n;
+    P8Plan p8;
+};
+
+// fp16 side (y2_conv_f16.hip): fills p for an fp16-input descriptor (x_f16) and returns true when an fp16 kernel takes it
+bool y2_f16_plan(const y2h_conv *d, ConvPlan &p);
+int y2_f16_launch(const ConvPlan &p, const y2h_conv *d, ConvK &a, y2h_stream s);
 bool y2_f16_first_ok(const y2h_conv *d);
-int y2_f16_first_launch(const y2h_conv *d, ConvK &a, y2h_stream s);
 bool y2_f16_first_nchw_ok(const y2h_conv *d);
-int y2_f16_first_nchw_launch(const y2h_conv *d, ConvK &a, y2h_stream s);
 
 // Grid of a kernel that walks its tiles with a grid stride: exactly what is co-resident (256 CUs x the runtime's answer for
 // this kernel), no more -- a surplus block only starts when a resident one has finished ALL its tiles, i.e. runs a second,

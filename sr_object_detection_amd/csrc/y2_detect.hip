@@ -172,13 +172,7 @@ extern "C" int y2h_region_boxes(const y2h_decode *q, y2h_stream s)
         TreeK tk;
         tk.order = q->tree_order; tk.level_off = q->tree_level_off; tk.levels = q->tree_levels;
         const size_t lds = (size_t)q->classes * sizeof(float);
-        static bool attr_set[16] = {false};
-        int dev = 0;
-        Y2H_CHECK(hipGetDevice(&dev));
-        if (dev < 0 || dev >= 16 || !attr_set[dev]) {
-            Y2H_CHECK(hipFuncSetAttribute((const void *)decode_tree_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-            if (dev >= 0 && dev < 16) attr_set[dev] = true;
-        }
+        Y2H_CHECK(y2h_lds_limit((const void *)decode_tree_kernel, 150 * 1024));
         hipLaunchKernelGGL(decode_tree_kernel, dim3((unsigned)d.nboxes), dim3(256), lds, S(s), d, tk);
         Y2H_LAUNCH_CHECK();
     }
@@ -377,13 +371,7 @@ extern "C" int y2h_nms_sort(const float *boxes, const float *probs_in, float *pr
     while (cap < total) cap <<= 1;
     const int lds_boxes = cap <= 8192 ? NMS_LDS_BOXES : 0;           // 16384 candidates fill the LDS by themselves
     const size_t lds = (((size_t)cap * 9 + 15) & ~(size_t)15) + (size_t)lds_boxes * 16;
-    static bool attr_set[16] = {false};
-    int dev = 0;
-    Y2H_CHECK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 16 || !attr_set[dev]) {
-        Y2H_CHECK(hipFuncSetAttribute((const void *)nms_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 9));
-        if (dev >= 0 && dev < 16) attr_set[dev] = true;
-    }
+    Y2H_CHECK(y2h_lds_limit((const void *)nms_sort_kernel, 16384 * 9));
     Y2H_CHECK(hipMemsetAsync(class_counts, 0, (size_t)batch * classes * sizeof(int), S(s)));
     const long nel = (long)batch * total * classes;
     hipLaunchKernelGGL(class_count_kernel, dim3(y2h_grid(nel, 256, 256 * 32)), dim3(256), 0, S(s),
@@ -672,13 +660,7 @@ extern "C" int y2h_detect_chain(const y2h_decode *q, float nms, float *probs_nms
         while (cap < total) cap <<= 1;
         const int lds_boxes = cap <= 8192 ? NMS_LDS_BOXES : 0;
         const size_t lds = (((size_t)cap * 9 + 15) & ~(size_t)15) + (size_t)lds_boxes * 16;
-        static bool attr_set[16] = {false};
-        int dev = 0;
-        Y2H_CHECK(hipGetDevice(&dev));
-        if (dev < 0 || dev >= 16 || !attr_set[dev]) {
-            Y2H_CHECK(hipFuncSetAttribute((const void *)nms_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 9));
-            if (dev >= 0 && dev < 16) attr_set[dev] = true;
-        }
+        Y2H_CHECK(y2h_lds_limit((const void *)nms_sort_kernel, 16384 * 9));
         hipLaunchKernelGGL(nms_sort_kernel, dim3((unsigned)(q->batch * q->classes)), dim3(256), lds, S(s),
                            q->boxes, q->probs, probs_nms, class_counts, total, q->classes, q->classes, nms, cap, lds_boxes, class_counts);
         Y2H_LAUNCH_CHECK();
@@ -941,14 +923,8 @@ extern "C" int y2h_detect_tree_chain(const y2h_decode *q, float nms, float *reco
     int cap = 16;
     while (cap < total) cap <<= 1;
     const size_t lds2 = (size_t)cap * (8 + 16 + 4 + 4 + 4 + 1);
-    static bool attr_set[16] = {false};
-    int dev = 0;
-    Y2H_CHECK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 16 || !attr_set[dev]) {
-        Y2H_CHECK(hipFuncSetAttribute((const void *)decode_tree_sparse_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        Y2H_CHECK(hipFuncSetAttribute((const void *)nms_collect_sparse_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 4096 * 37));
-        if (dev >= 0 && dev < 16) attr_set[dev] = true;
-    }
+    Y2H_CHECK(y2h_lds_limit((const void *)decode_tree_sparse_kernel, 150 * 1024));
+    Y2H_CHECK(y2h_lds_limit((const void *)nms_collect_sparse_kernel, 4096 * 37));
     if (tree_best)
         hipLaunchKernelGGL(decode_tree_cand_kernel, dim3((unsigned)((d.nboxes + 255) / 256)), dim3(256), 0, S(s), d, tree_best,
                            (const int *)(tree_best + d.nboxes), cand_val, cand_cls);

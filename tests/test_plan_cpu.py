@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def _plan(*args):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "plan_dump.py")] + [str(a) for a in args],
                          check=True, capture_output=True, text=True,
-                         env={k: v for k, v in os.environ.items() if k not in ("Y2_MODEL_R1", "Y2_CONV_TILE", "Y2_CONV_KSPLIT", "Y2_CONV_GRID")}).stdout
+                         env={k: v for k, v in os.environ.items() if k not in ("Y2_CONV_TILE", "Y2_CONV_KSPLIT", "Y2_CONV_GRID")}).stdout
     plan = {}
     for line in out.splitlines():
         f = line.split()
@@ -38,3 +38,15 @@ def test_small_grid_plans_follow_the_measured_choices():
     assert q[8] == q[10] == "conv_mfma_f32_128x64x32_k3"
     assert q[12] == q[14] == q[16] == "conv_mfma_f32_64x64x32_k3"  # 34x34 256->512: 64x64, not 192x256 split 2
     assert q[4] == q[6] == "conv_mfma_f32_128x128x32_k3"
+
+
+def test_dispatch_table_unchanged():
+    """Every dispatch query of every zoo network's descriptors, fp32 and fp16, aligned and misaligned outputs, and under the
+    forcing switches, as the committed table of digests records them (tools/plan_dump.py --sweep; --sweep-rows lists the
+    answers themselves).  A deliberate plan change regenerates the table."""
+    env = {k: v for k, v in os.environ.items() if not k.startswith("Y2_")}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "plan_dump.py"), "--sweep"], check=True, capture_output=True,
+                         text=True, env=env).stdout
+    with open(os.path.join(ROOT, "tests", "golden", "conv_plan_table.txt")) as f:
+        want = f.read()
+    assert out == want, "tools/plan_dump.py --sweep differs from tests/golden/conv_plan_table.txt"

@@ -2,7 +2,9 @@
 """The tile plan of the fp32 matrix-core convolutions WITHOUT a GPU: for every conv layer of a zoo network at a given size and
 batch, what pick_variant (y2_conv.hip, host arithmetic only) would launch -- kernel name and the candidate list.  Used to
 check that a change of the cost model leaves the plan of the headline configuration alone.
-    tools/plan_dump.py yolo 608 32 [yolo 416 8 ...]"""
+    tools/plan_dump.py yolo 608 32 [yolo 416 8 ...]
+    tools/plan_dump.py --sweep       every dispatch query for every zoo network, a digest per configuration (tests/golden/conv_plan_table.txt)
+    tools/plan_dump.py --sweep-rows  the same queries, one line per conv layer: diff two builds' output (Y2_LIB) to see what moved"""
 import ctypes as C
 import os
 import sys
@@ -22,12 +24,109 @@ class Conv(C.Structure):          # include/y2_hip.h: y2h_conv
                 ("tile_bm", C.c_int), ("tile_bn", C.c_int), ("ksplit", C.c_int), ("x_nchw", C.c_int)]
 
 
+ACT = {"linear": 0, "leaky": 1, "logistic": 2, "relu": 3}
+ALIGNED, MISALIGNED = 0x30000, 0x30004          # y: 16-byte aligned, or not (the vec_ok branches)
+
+
+def _descs(net, size, batch, half, y):
+    """The descriptors of a zoo network's conv layers as the engine would build them (no device pointers needed)."""
+    layers = zoo.resolve(net, size)
+    for i, l in enumerate(layers):
+        if l["type"] != "convolutional":
+            continue
+        pool = i + 1 < len(layers) and layers[i + 1]["type"] == "maxpool" and layers[i + 1]["size"] == 2 and layers[i + 1]["stride"] == 2
+        base = dict(batch=batch, h=l["h"], w=l["w"], c=l["c"], ldx=l["c"], n=l["filters"], size=l["size"], stride=l["stride"],
+                    pad=l["pad"], out_h=l["out_h"], out_w=l["out_w"], ldy=l["filters"], fuse_maxpool2=1 if pool else 0,
+                    batch_normalize=l.get("batch_normalize", 0), activation=ACT.get(l["activation"], 0),
+                    x=0x10000, w_packed=0x20000, y=y, bias=0x40000, y_f16=half)
+        if half:
+            base.update(alpha=0x50000, beta=0x60000)
+        if i > 0:
+            yield i, dict(base, x_f16=half)
+            continue
+        # the first layer in every input form the engine may give it: plain, one-pixel halo, padding-wide halo, NCHW planes,
+        # and (fp16) the half NHWC4 haloed copy
+        forms = [dict(base), dict(base, x_halo=1), dict(base, x_nchw=1)]
+        if l["pad"] > 1:
+            forms.append(dict(base, x_halo=l["pad"]))
+        if half:
+            forms.append(dict(base, x_f16=1, x_halo=1, ldx=4))
+        for f in forms:
+            yield i, f
+
+
+def _row(lib, f, first):
+    d = Conv(**f)
+    names = [lib.y2h_conv_variant(C.byref(d), s) for s in (0, 1)]
+    bm, bn, ks = (C.c_int * 64)(), (C.c_int * 64)(), (C.c_int * 64)()
+    nc = lib.y2h_conv_candidates(C.byref(d), bm, bn, ks, 64)
+    cols = [" ".join(str(f.get(k, 0)) for k in KEY), " ".join(n.decode() if n else "-" for n in names),
+            "mfma %d" % lib.y2h_conv_uses_mfma(C.byref(d)), "ws %d" % lib.y2h_conv_workspace_bytes(C.byref(d)),
+            "cand " + (" ".join("%dx%d/%d" % (bm[k], bn[k], ks[k]) for k in range(nc)) or "-")]
+    if first:
+        cols.append("first %d %d %d stem %d" % (lib.y2h_conv_first_layer_ok(C.byref(d)), lib.y2h_conv_first_layer_f16_ok(C.byref(d)),
+                                                lib.y2h_conv_first_layer_nchw_ok(C.byref(d)), lib.y2h_conv_stem_halo(C.byref(d))))
+    return " | ".join(cols)
+
+
+KEY = ("batch", "h", "w", "c", "ldx", "x_halo", "n", "size", "stride", "pad", "fuse_maxpool2", "batch_normalize", "activation",
+       "x_f16", "y_f16", "x_nchw")
+
+# forcing switches, set in-process between calls as the tile tests do; each applies to the FORCED configurations below
+FORCED_ENV = [("Y2_CONV_TILE", "128x64"), ("Y2_CONV_TILE", "256x128"), ("Y2_CONV_KSPLIT", "2"), ("Y2_CONV_GRID", "64"),
+              ("Y2_SKF", "0"), ("Y2_SKF_WGS", "200"), ("Y2_SKH", "1"), ("Y2_SKH", "2"), ("Y2_SKH_WGS", "64"),
+              ("Y2_SK", "0"), ("Y2_SK_TILES", "4"), ("Y2_SK_WGS", "96"), ("Y2_TAIL", "0"), ("Y2_TAIL_TILE", "128x128"),
+              ("Y2_TAIL_TILES", "8"), ("Y2_C32F_MIN_TILES", "1"), ("Y2_C64_MIN_TILES", "1"), ("Y2_NO_C32F", "1"), ("Y2_NO_C64", "1"),
+              ("Y2_NO_M16", "1"), ("Y2_F16_NO_P8", "1"), ("Y2_NO_FIRST_NCHW", "1")]
+FORCED = [("yolo", 608, 32), ("yolo", 416, 1), ("yolo9000", 544, 8), ("darknet19", 448, 128), ("tiny-yolo-voc", 416, 1)]
+FORMS = [(0, ALIGNED, "f32"), (0, MISALIGNED, "f32 y+4"), (1, ALIGNED, "f16"), (1, MISALIGNED, "f16 y+4")]
+
+
+def sweep(lib, rows):
+    """For every zoo network (default size; 416 and 608 too for the full-size detectors) at batch 1, 8, 32 and 128, fp32 and fp16,
+    with y 16-byte aligned and not, and for a few of them under each forcing switch: every conv layer's descriptor with
+    y2h_conv_variant (strict 0 and 1), y2h_conv_uses_mfma, y2h_conv_workspace_bytes, the y2h_conv_candidates list and, for
+    the first layer, the four first-layer / stem queries.  rows: print those lines; else one line per configuration with a
+    digest of each form's lines (tests/golden/conv_plan_table.txt) -- where a digest moves, --sweep-rows of the two builds shows why."""
+    import hashlib
+    for k in [k for k in os.environ if k.startswith("Y2_")]:
+        del os.environ[k]
+
+    def show(tag, cases):
+        for net, size, batch in cases:
+            name = "%s%s %d b%d" % (tag, net, size, batch)
+            digests = []
+            for half, y, form in FORMS:
+                lines = [_row(lib, f, i == 0) for i, f in _descs(net, size, batch, half, y)]
+                if rows:
+                    print("\n".join("%s %s | %s" % (name, form, l) for l in lines))
+                digests.append(hashlib.sha256("\n".join(lines).encode()).hexdigest()[:12])
+            if not rows:
+                print("%s | %s" % (name, " ".join(digests)))
+
+    if not rows:
+        print("# configuration | digest of its layers' answers: " + ", ".join(f for _, _, f in FORMS))
+    cases = []
+    for net in zoo.SPECS:
+        sizes = [zoo.DEFAULT_SIZE[net]]
+        if sizes[0] >= 416 and any(l["type"] == "region" for l in zoo.resolve(net, sizes[0])):     # the full-size detectors
+            sizes += [s for s in (416, 608) if s not in sizes]
+        cases += [(net, s, b) for s in sizes for b in (1, 8, 32, 128)]
+    show("", cases)
+    for k, v in FORCED_ENV:
+        os.environ[k] = v
+        show("%s=%s " % (k, v), FORCED)
+        del os.environ[k]
+
+
 def main():
     lib = C.CDLL(os.environ.get("Y2_LIB") or os.path.join(ROOT, "sr_object_detection_amd", "libsr_yolo2.so"))
     lib.y2h_conv_variant.restype = C.c_char_p
     lib.y2h_conv_variant.argtypes = [C.POINTER(Conv), C.c_int]
     lib.y2h_conv_workspace_bytes.restype = C.c_size_t
     args = sys.argv[1:]
+    if args in (["--sweep"], ["--sweep-rows"]):
+        return sweep(lib, args == ["--sweep-rows"])
     for k in range(0, len(args), 3):
         net, size, batch = args[k], int(args[k + 1]), int(args[k + 2])
         layers = zoo.resolve(net, size)
