@@ -378,6 +378,35 @@ int y2_ingest_image(network net, image im);
 int y2_ingest_u8(network net, const unsigned char *frames, int h, int w, int c, int step, int swap_rb, int letterbox);
 int y2_detect_u8(network net, const unsigned char *frames, int h, int w, int c, int step, int swap_rb, int letterbox,
                  float thresh, float nms, int img_w, int img_h, y2_det *dets, int *counts, int max_per_image);
+/* Regions of frames of any size in one forward pass (the Kinect loop's whole frame + two hand crops,
+ * KinectUtil_with_cam.cpp:1029-1110, as one batch).  One region of an 8-bit interleaved frame in host memory
+ * (h x w x c, row pitch `step` bytes); rw = rh = 0 means the whole frame (then x and y must be 0).
+ * Item i becomes batch slot i: only its rows are packed, with a small descriptor table, into one pinned staging
+ * buffer that goes up in ONE H2D copy, and one kernel (y2h_regions_to_input) fills the whole network input -- bit
+ * for bit what y2_ingest_u8 computes for the copied crop (u8 -> planes, swap_rb, resize or letterbox).  Slots
+ * n .. net.batch-1 are zeroed; the full planned batch still runs.  Every argument is checked before any device
+ * work: n outside [1, net.batch], a NULL data pointer, step < w*c, c < net.c, a region outside its frame or a
+ * degenerate letterbox is refused with a message naming the item, and nothing is uploaded or launched. */
+typedef struct { const unsigned char *data; int h, w, c, step; int x, y, rw, rh; } y2_region;
+int y2_ingest_regions(network net, const y2_region *items, int n, int swap_rb, int letterbox);
+/* y2_ingest_regions + y2_forward_device + decode / NMS / compaction (y2_detect_resident with img_w = img_h = 1).
+ * counts[0..n-1] and dets[i*max_per_item ..] are written for the n items only; boxes are relative to each item's
+ * FRAME (y2_region_box_to_frame). */
+int y2_detect_regions(network net, const y2_region *items, int n, int swap_rb, int letterbox,
+                      float thresh, float nms, y2_det *dets, int *counts, int max_per_item);
+/* A box relative to the network input -> relative to the item's frame (W x H), in place, fp32 in this order:
+ *   letterbox:  (nw, nh) = y2h_letterbox_dims(rw, rh, net_w, net_h);
+ *               x = (x*net_w - (net_w-nw)/2) / nw,  w = w*net_w / nw,  the same for y, h  ((..)/2 is integer)
+ *   region:     x = (x*rw + rx) / W,  y = (y*rh + ry) / H,  w = w*rw / W,  h = h*rh / H   (KinectUtil_with_cam.cpp:1033-1036)
+ * A whole-frame item skips the region step (it is the identity), so without a letterbox its boxes are returned
+ * unchanged -- exactly what y2_detect_u8 returns for that frame. */
+void y2_region_box_to_frame(const y2_region *item, int net_w, int net_h, int letterbox, float *x, float *y, float *w, float *h);
+/* test_detector_img (detector.c:558) over n regions in one pass: BGR frames as the application's cv::Mat holds them
+ * (swap_rb), resized (no letterbox), nms .1, objects filled exactly as test_detector_img fills them -- appended at
+ * RecObjects[i][objectNumPerRegion[i]], which is incremented -- with boxes relative to each item's frame.
+ * RecObjects[i] holds room for l.w*l.h*l.n objects.  net.batch >= n (set_batch_network). */
+void test_detector_regions(char **names, network net, const y2_region *items, int n, float thresh,
+                           object **RecObjects, int *objectNumPerRegion);
 /* Copy layer i's activations to host as NCHW [batch][out_c][out_h][out_w] (or [batch][outputs]). */
 int y2_pull_layer_output(network net, int i, float *dst);
 /* Per-layer device time of the last forward in ms (needs y2_set_timing(net,1)); returns layers written. */

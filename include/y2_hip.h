@@ -363,6 +363,27 @@ void y2h_letterbox_dims(int iw, int ih, int w, int h, int *new_w, int *new_h);  
 /* letterbox_image (image.c:1624): tmp holds c*ih*new_w + c*new_h*new_w floats */
 int y2h_letterbox_chw(const float *src, int c, int ih, int iw, float *tmp, float *dst, int h, int w, y2h_stream s);
 
+/* One item of y2h_regions_to_input: an ih x iw rectangle of 8-bit interleaved pixels that becomes batch slot b of the
+ * network input.  Without a letterbox (nw, nh) is the network's size and dx = dy = 0; with one, (nw, nh) is
+ * y2h_letterbox_dims of the region and (dx, dy) = ((w - nw) / 2, (h - nh) / 2).  The scales are computed on the host
+ * exactly as y2h_resize_chw computes them: (float)(iw - 1) / (nw - 1) and (float)(ih - 1) / (nh - 1). */
+typedef struct y2h_region {
+    long long src;              /* byte offset of the item's first pixel from `pixels` */
+    int pitch;                  /* bytes between rows */
+    int c;                      /* bytes per pixel (channels) */
+    int iw, ih;                 /* region size */
+    int nw, nh;                 /* size it is resized to */
+    int dx, dy;                 /* where that box sits in the network input */
+    float w_scale, h_scale;
+} y2h_region;
+
+/* Fill the NCHW fp32 network input dst[batch][planes][h][w] in one launch from `n` regions (table `desc` of n
+ * entries, in device memory, pointing into `pixels`).  Slot b < n equals, bit for bit, y2h_u8_to_planes of the region
+ * followed by y2h_resize_chw to (nh, nw) -- or y2h_letterbox_chw: .5 outside the embedded box -- fused: every value is
+ * formed by the same fp32 expressions in the same order.  Slots n .. batch-1 are set to 0. */
+int y2h_regions_to_input(const y2h_region *desc, int n, const unsigned char *pixels, int batch, int planes, int swap_rb,
+                         int h, int w, float *dst, y2h_stream s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,14 @@ struct bbox_t {
     unsigned int track_id;       // 0 = untracked; tracking() assigns 1, 2, ...
 };
 
+// One region of an 8-bit interleaved frame (w x h x c, row pitch `step` bytes) for Detector::detect_regions;
+// rw = rh = 0 means the whole frame.
+struct frame_region_t {
+    const unsigned char *data;
+    int w, h, c, step;
+    int x, y, rw, rh;
+};
+
 struct image_t {
     int h, w, c;                 // CHW planes
     float *data;                 // values in [0,1]
@@ -58,6 +66,14 @@ public:
     // run on the device.  Boxes are in pixels of the frame, exactly as detect(image_t) returns them.
     YOLODLL_API std::vector<bbox_t> detect_frame(const unsigned char *data, int w, int h, int c, int step,
                                                  float thresh = 0.2f, bool bgr = true);
+
+    // Extension: several regions of frames of any size (the whole frame and the hand crops of the Kinect loop) in ONE
+    // forward pass (y2_detect_regions).  Result i holds item i's boxes in pixels of item i's FRAME, as detect_frame
+    // returns them for that frame.  Runs on a second network of the same cfg and weights, created at the first call with
+    // the batch set to the largest number of items seen so far (rebuilt only when it grows): it doubles the weight memory
+    // while in use, and detect / detect_frame / use_mean / tracking keep their own batch-1 network untouched.
+    YOLODLL_API std::vector<std::vector<bbox_t>> detect_regions(const std::vector<frame_region_t> &items,
+                                                                float thresh = 0.2f, bool bgr = true);
 
 #ifdef OPENCV
     // The OpenCV convenience surface of the reference (yolo_v2_class.hpp:59-92), same names, signatures and results, so

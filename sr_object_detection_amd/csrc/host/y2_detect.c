@@ -369,14 +369,15 @@ fetch:
     return 0;
 }
 
-static int detect_fetch(network net, y2_det *dets, int *counts, int max_per_image)
+/* unpacks the first `items` images of the batch (all of them but for y2_detect_regions) */
+static int detect_fetch_items(network net, y2_det *dets, int *counts, int max_per_image, int items)
 {
     y2_engine *e = y2_engine_of(&net);
     int b, i;
     if (!e || !e->det_pending) { y2_fail("y2_detect_fetch: nothing was enqueued (call y2_detect_enqueue after a forward)"); return -1; }
     if (e->det_pending == 1) HIPCALL_I(y2h_event_sync(e->ev_det));
     e->det_pending = 0;
-    for (b = 0; b < net.batch; ++b) {
+    for (b = 0; b < items; ++b) {
         int nb = e->h_counts[b];
         counts[b] = nb;
         if (nb > e->det_cap) nb = e->det_cap;
@@ -388,6 +389,11 @@ static int detect_fetch(network net, y2_det *dets, int *counts, int max_per_imag
         }
     }
     return 0;
+}
+
+static int detect_fetch(network net, y2_det *dets, int *counts, int max_per_image)
+{
+    return detect_fetch_items(net, dets, counts, max_per_image, net.batch);
 }
 
 static int detect_from(network net, float *d_pred, float thresh, float nms, int img_w, int img_h,
@@ -625,4 +631,181 @@ void test_detector_img(char **names, image **alphabet, network net, image im, fl
         (*objectNumPerFrame)++;
     }
     free(dets);
+}
+
+/* ------------------------------------------------------------------ */
+/* regions of frames of any size in one batch                          */
+/* ------------------------------------------------------------------ */
+/* the rectangle an item stands for: rw = rh = 0 is the whole frame */
+static void region_rect(const y2_region *it, int *x, int *y, int *rw, int *rh)
+{
+    const int whole = it->rw == 0 && it->rh == 0;
+    *x = it->x; *y = it->y;
+    *rw = whole ? it->w : it->rw;
+    *rh = whole ? it->h : it->rh;
+}
+
+/* Every refusal of y2_ingest_regions, before anything touches the device.  0 or -1 (message names the item). */
+static int regions_check(const char *who, network net, const y2_region *items, int n, int letterbox)
+{
+    int i;
+    if (!items) { y2_fail("%s: no items", who); return -1; }
+    if (n < 1 || n > net.batch) { y2_fail("%s: %d items for a batch-%d network", who, n, net.batch); return -1; }
+    for (i = 0; i < n; ++i) {
+        const y2_region *it = &items[i];
+        int x, y, rw, rh;
+        region_rect(it, &x, &y, &rw, &rh);
+        if (!it->data) { y2_fail("%s: item %d: data is NULL", who, i); return -1; }
+        if (it->h <= 0 || it->w <= 0 || it->c <= 0) { y2_fail("%s: item %d: bad frame geometry %d x %d x %d", who, i, it->h, it->w, it->c); return -1; }
+        if ((long)it->step < (long)it->w * it->c) { y2_fail("%s: item %d: step %d is less than w*c = %ld", who, i, it->step, (long)it->w * it->c); return -1; }
+        if (it->c < net.c) { y2_fail("%s: item %d: the frame has %d channels, the network reads %d", who, i, it->c, net.c); return -1; }
+        if (x < 0 || y < 0 || rw < 1 || rh < 1 || (long)x + rw > it->w || (long)y + rh > it->h) {
+            y2_fail("%s: item %d: region (%d, %d, %d x %d) is not inside its %d x %d frame", who, i, it->x, it->y, it->rw, it->rh,
+                    it->w, it->h);
+            return -1;
+        }
+        if (letterbox) {
+            int nw, nh;
+            y2h_letterbox_dims(rw, rh, net.w, net.h, &nw, &nh);
+            if (nw <= 0 || nh <= 0) { y2_fail("%s: item %d: degenerate letterbox %d x %d", who, i, nw, nh); return -1; }
+        }
+    }
+    return 0;
+}
+
+static int ingest_regions(const char *who, network net, const y2_region *items, int n, int swap_rb, int letterbox)
+{
+    y2_engine *e;
+    y2h_region *desc;
+    size_t desc_bytes, pix_bytes = 0, off, need;
+    int i, r;
+    if (regions_check(who, net, items, n, letterbox) != 0) return -1;
+    if (y2_prepare(&net) != 0) return -1;
+    e = y2_engine_of(&net);
+    HIPCALL_I(y2h_set_device(e->device));
+    desc_bytes = ((size_t)n * sizeof(y2h_region) + 63) & ~(size_t)63;
+    for (i = 0; i < n; ++i) {
+        int x, y, rw, rh;
+        region_rect(&items[i], &x, &y, &rw, &rh);
+        pix_bytes += (size_t)rh * rw * items[i].c;
+    }
+    need = desc_bytes + pix_bytes;
+    /* the last call's upload may still be reading the pinned buffer */
+    if (e->reg_pending) { HIPCALL_I(y2h_event_sync(e->ev_reg)); e->reg_pending = 0; }
+    if (need > e->reg_stage_cap) {
+        y2h_host_free(e->h_reg_stage); e->h_reg_stage = NULL; e->reg_stage_cap = 0;
+        HIPCALL_I(y2h_host_alloc((void **)&e->h_reg_stage, need));
+        e->reg_stage_cap = need;
+    }
+    if (grow((void **)&e->d_reg, &e->reg_cap, need)) { y2_fail("%s: %s", who, y2h_last_error()); return -1; }
+    if (!e->ev_reg) HIPCALL_I(y2h_event_create(&e->ev_reg));
+    desc = (y2h_region *)e->h_reg_stage;
+    memset(desc, 0, desc_bytes);
+    off = 0;
+    for (i = 0; i < n; ++i) {
+        const y2_region *it = &items[i];
+        y2h_region *d = &desc[i];
+        int x, y, rw, rh, nw = net.w, nh = net.h;
+        size_t row;
+        region_rect(it, &x, &y, &rw, &rh);
+        row = (size_t)rw * it->c;
+        if (letterbox) y2h_letterbox_dims(rw, rh, net.w, net.h, &nw, &nh);
+        d->src = (long long)off;
+        d->pitch = (int)(rw * it->c);
+        d->c = it->c;
+        d->iw = rw; d->ih = rh;
+        d->nw = nw; d->nh = nh;
+        d->dx = (net.w - nw) / 2; d->dy = (net.h - nh) / 2;
+        d->w_scale = (float)(rw - 1) / (nw - 1);           /* as y2h_resize_chw */
+        d->h_scale = (float)(rh - 1) / (nh - 1);
+        for (r = 0; r < rh; ++r)
+            memcpy(e->h_reg_stage + desc_bytes + off + (size_t)r * row, it->data + (size_t)(y + r) * it->step + (size_t)x * it->c, row);
+        off += row * rh;
+    }
+    HIPCALL_I(y2h_memcpy_h2d(e->d_reg, e->h_reg_stage, need, e->stream));
+    HIPCALL_I(y2h_event_record(e->ev_reg, e->stream));
+    e->reg_pending = 1;
+    HIPCALL_I(y2h_regions_to_input((const y2h_region *)e->d_reg, n, e->d_reg + desc_bytes, net.batch, net.c, swap_rb, net.h, net.w,
+                                   e->d_in_nchw, e->stream));
+    return 0;
+}
+
+int y2_ingest_regions(network net, const y2_region *items, int n, int swap_rb, int letterbox)
+{
+    return ingest_regions("y2_ingest_regions", net, items, n, swap_rb, letterbox);
+}
+
+void y2_region_box_to_frame(const y2_region *item, int net_w, int net_h, int letterbox, float *x, float *y, float *w, float *h)
+{
+    int rx, ry, rw, rh;
+    region_rect(item, &rx, &ry, &rw, &rh);
+    if (letterbox) {
+        int nw, nh;
+        y2h_letterbox_dims(rw, rh, net_w, net_h, &nw, &nh);
+        *x = (*x * net_w - (net_w - nw) / 2) / nw;
+        *y = (*y * net_h - (net_h - nh) / 2) / nh;
+        *w = *w * net_w / nw;
+        *h = *h * net_h / nh;
+    }
+    if (rx == 0 && ry == 0 && rw == item->w && rh == item->h) return;      /* the whole frame: identity */
+    *x = (*x * rw + rx) / item->w;
+    *y = (*y * rh + ry) / item->h;
+    *w = *w * rw / item->w;
+    *h = *h * rh / item->h;
+}
+
+int y2_detect_regions(network net, const y2_region *items, int n, int swap_rb, int letterbox,
+                      float thresh, float nms, y2_det *dets, int *counts, int max_per_item)
+{
+    int i, j;
+    if (!dets || !counts || max_per_item < 1) { y2_fail("y2_detect_regions: needs dets, counts and max_per_item >= 1"); return -1; }
+    if (ingest_regions("y2_detect_regions", net, items, n, swap_rb, letterbox) != 0) return -1;
+    if (y2_forward_device(net, NULL) != 0) return -1;
+    if (detect_enqueue(net, NULL, thresh, nms, 1, 1) != 0 || detect_fetch_items(net, dets, counts, max_per_item, n) != 0) return -1;
+    for (i = 0; i < n; ++i) {
+        const int kept = counts[i] < max_per_item ? counts[i] : max_per_item;
+        for (j = 0; j < kept; ++j) {
+            y2_det *d = &dets[(size_t)i * max_per_item + j];
+            y2_region_box_to_frame(&items[i], net.w, net.h, letterbox, &d->x, &d->y, &d->w, &d->h);
+        }
+    }
+    return 0;
+}
+
+void test_detector_regions(char **names, network net, const y2_region *items, int n, float thresh,
+                           object **RecObjects, int *objectNumPerRegion)
+{
+    const float nms = 0.1f;
+    layer l = net.layers[net.n - 1];
+    int total = l.w * l.h * l.n, i, j;
+    y2_det *dets;
+    int *counts;
+    if (!RecObjects || !objectNumPerRegion) { y2_fail("test_detector_regions: RecObjects / objectNumPerRegion is NULL"); return; }
+    if (regions_check("test_detector_regions", net, items, n, 0) != 0) return;
+    dets = calloc((size_t)n * (total > 0 ? total : 1), sizeof(y2_det));
+    counts = calloc((size_t)n, sizeof(int));
+    if (!dets || !counts) { free(dets); free(counts); y2_fail("test_detector_regions: out of memory"); return; }
+    /* the frames are the application's BGR cv::Mat bytes (ipl_to_image + rgbgr_image in front of test_detector_img) */
+    if (y2_detect_regions(net, items, n, 1, 0, thresh, nms, dets, counts, total > 0 ? total : 1) != 0) { free(dets); free(counts); return; }
+    for (i = 0; i < n; ++i) {
+        const int kept = counts[i] < total ? counts[i] : total;
+        for (j = 0; j < kept; ++j) {
+            const y2_det *d = &dets[(size_t)i * total + j];
+            object *o = &RecObjects[i][objectNumPerRegion[i]];
+            int cls = d->obj_id;
+            int offset = cls * 123457 % l.classes;
+            if (names) printf("%s: %.0f%%\n", names[cls], d->prob * 100);
+            o->x = d->x; o->y = d->y; o->w = d->w; o->h = d->h;
+            o->prob = d->prob;
+            o->objClass = cls;
+            if (names && names[cls]) { strncpy(o->name, names[cls], sizeof o->name - 1); o->name[sizeof o->name - 1] = 0; }
+            else o->name[0] = 0;
+            o->boxRGB[0] = get_color(2, offset, l.classes);
+            o->boxRGB[1] = get_color(1, offset, l.classes);
+            o->boxRGB[2] = get_color(0, offset, l.classes);
+            objectNumPerRegion[i]++;
+        }
+    }
+    free(dets);
+    free(counts);
 }

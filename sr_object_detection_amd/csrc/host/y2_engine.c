@@ -125,6 +125,8 @@ static void free_plan(network *net)
     y2h_free(e->d_u8); e->d_u8 = NULL; e->u8_cap = 0;
     y2h_free(e->d_planes); e->d_planes = NULL; e->planes_cap = 0;
     y2h_free(e->d_rtmp); e->d_rtmp = NULL; e->rtmp_cap = 0;
+    if (e->reg_pending) { y2h_event_sync(e->ev_reg); e->reg_pending = 0; }
+    y2h_free(e->d_reg); e->d_reg = NULL; e->reg_cap = 0;
     y2h_free(e->d_boxes); e->d_boxes = NULL;
     y2h_free(e->d_probs); e->d_probs = NULL;
     y2h_free(e->d_probs_nms); e->d_probs_nms = NULL;
@@ -162,6 +164,8 @@ void y2_engine_destroy(network *net)
     }
     y2h_free(e->arena);
     y2h_host_free(e->h_out_stage);
+    y2h_host_free(e->h_reg_stage);
+    if (e->ev_reg) y2h_event_destroy(e->ev_reg);
     if (e->h_out_pinned) y2h_host_free(e->h_out); else free(e->h_out);
     if (e->ev) { for (i = 0; i < e->n_ev; ++i) y2h_event_destroy(e->ev[i]); free(e->ev); }
     if (e->ev_det) y2h_event_destroy(e->ev_det);

@@ -93,6 +93,11 @@ typedef struct y2_engine {
     unsigned char *d_u8;       /* y2_detect_u8: raw frames, float planes, resize scratch (grow-only) */
     float *d_planes, *d_rtmp;
     size_t u8_cap, planes_cap, rtmp_cap;
+    /* y2_ingest_regions: descriptor table + packed region rows, staged in pinned memory and sent up in one copy */
+    unsigned char *h_reg_stage, *d_reg;  /* both grow-only */
+    size_t reg_stage_cap, reg_cap;
+    y2h_event ev_reg;                    /* recorded behind that copy: the staging buffer may be refilled after it */
+    int reg_pending;
     float *d_ws;               /* split-K scratch shared by all conv layers */
     size_t ws_bytes;
     float *h_out;              /* what network_predict returns; allocated at parse time like the reference's

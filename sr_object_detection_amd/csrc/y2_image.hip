@@ -104,6 +104,100 @@ extern "C" int y2h_letterbox_chw(const float *src, int c, int ih, int iw, float 
     return y2h_embed_chw(resized, c, nh, nw, dst, h, w, (w - nw) / 2, (h - nh) / 2, s);
 }
 
+// ---------------------------------------------------------------------------
+// A batch of regions of any size in one launch: u8_to_planes + resize_cols + resize_rows (+ fill / embed when
+// letterboxing) fused per output pixel.  The chain's intermediates are recomputed where they are needed, from the same
+// expressions in the same order (this file is built with -ffp-contract=off):
+//   plane value      lut[v] = (float)((double)v / 255.)                         u8_to_planes_kernel
+//   column pass      (1-dx)*p[ix] + dx*p[ix+1], or p[iw-1] when col == nw-1 || iw == 1      resize_cols_kernel
+//   row pass         (1-dy)*part(iy), + dy*part(iy+1) unless r == nh-1 || ih == 1            resize_rows_kernel
+//   letterbox        .5 outside [dx, dx+nw) x [dy, dy+nh)                        fill_kernel + embed_kernel
+// Each thread writes four consecutive pixels of one output row in every plane (one 16-byte store per plane when the
+// rows allow it); one block row of the grid per batch slot, slots past n are zeroed.
+// ---------------------------------------------------------------------------
+struct RegionPix {                       // one source row of a region, one plane
+    const unsigned char *row;
+    int c;
+    const float *lut;
+    __device__ float at(int j) const { return lut[row[(size_t)j * c]]; }
+};
+
+__device__ __forceinline__ float region_col(const RegionPix &p, int col, int iw, int nw, float w_scale)
+{
+    if (col == nw - 1 || iw == 1) return p.at(iw - 1);
+    const float sx = col * w_scale;
+    const float dx = sx - (int)sx;
+    const int ix = min((int)sx, iw - 2);     // never clamps for a host-computed scale; keeps the reads in the region
+    return (1 - dx) * p.at(ix) + dx * p.at(ix + 1);
+}
+
+__global__ __launch_bounds__(256) void regions_to_input_kernel(const y2h_region *__restrict__ desc, int n,
+                                                               const unsigned char *__restrict__ pixels, int planes,
+                                                               int swap_rb, int h, int w, int vec, float *__restrict__ dst)
+{
+    __shared__ float lut[256];
+    const int b = blockIdx.y;
+    const long gw = (w + 3) / 4;
+    const long g = (long)blockIdx.x * 256 + threadIdx.x;
+    const int Y = (int)(g / gw), X0 = (int)(g - (long)Y * gw) * 4;
+    const size_t plane = (size_t)h * w;
+    float *o = dst + (size_t)b * planes * plane + (size_t)Y * w + X0;
+    const int nx = min(4, w - X0);
+    if (b >= n) {                        // padded slot: deterministic zeros (uniform per block)
+        if (Y >= h) return;
+        for (int k = 0; k < planes; ++k) {
+            if (vec) *(float4 *)(o + k * plane) = make_float4(0.f, 0.f, 0.f, 0.f);
+            else for (int i = 0; i < nx; ++i) o[k * plane + i] = 0.f;
+        }
+        return;
+    }
+    lut[threadIdx.x] = (float)((double)threadIdx.x / 255.);
+    __syncthreads();
+    if (Y >= h) return;
+    const y2h_region d = desc[b];
+    const unsigned char *src = pixels + d.src;
+    const int y = Y - d.dy;
+    const bool row_in = y >= 0 && y < d.nh;
+    int iy = 0;
+    float dy = 0.f;
+    bool two = false;
+    if (row_in) {
+        const float sy = y * d.h_scale;
+        iy = min(max((int)sy, 0), d.ih - 1);
+        dy = sy - (int)sy;
+        two = !(y == d.nh - 1 || d.ih == 1);
+    }
+    const int iy1 = min(iy + 1, d.ih - 1);
+    for (int k = 0; k < planes; ++k) {
+        int sk = k;
+        if (swap_rb && d.c >= 3) sk = (k == 0) ? 2 : (k == 2 ? 0 : k);
+        const RegionPix p0{src + (size_t)iy * d.pitch + sk, d.c, lut};
+        const RegionPix p1{src + (size_t)iy1 * d.pitch + sk, d.c, lut};
+        float v[4];
+        for (int i = 0; i < 4; ++i) {
+            const int x = X0 + i - d.dx;
+            if (i >= nx || !row_in || x < 0 || x >= d.nw) { v[i] = .5f; continue; }
+            float val = (1 - dy) * region_col(p0, x, d.iw, d.nw, d.w_scale);
+            if (two) val = val + dy * region_col(p1, x, d.iw, d.nw, d.w_scale);
+            v[i] = val;
+        }
+        if (vec) *(float4 *)(o + k * plane) = make_float4(v[0], v[1], v[2], v[3]);
+        else for (int i = 0; i < nx; ++i) o[k * plane + i] = v[i];
+    }
+}
+
+extern "C" int y2h_regions_to_input(const y2h_region *desc, int n, const unsigned char *pixels, int batch, int planes,
+                                    int swap_rb, int h, int w, float *dst, y2h_stream s)
+{
+    if (!desc || !pixels || !dst || n < 0 || n > batch || batch <= 0 || planes <= 0 || h <= 0 || w <= 0) return Y2H_EINVAL;
+    const int vec = (w % 4 == 0) && ((uintptr_t)dst % 16 == 0);
+    const long groups = (long)h * ((w + 3) / 4);
+    hipLaunchKernelGGL(regions_to_input_kernel, dim3((unsigned)((groups + 255) / 256), (unsigned)batch), dim3(256), 0, S(s),
+                       desc, n, pixels, planes, swap_rb, h, w, vec, dst);
+    Y2H_LAUNCH_CHECK();
+    return Y2H_OK;
+}
+
 // utils.c:420-432 mean_arrays on device buffers: avg = 0; for j: avg += frame j; avg /= n  (fp32, frame order)
 __global__ __launch_bounds__(256) void mean_frames_kernel(const float *__restrict__ frames, int n, long els, float *__restrict__ avg)
 {

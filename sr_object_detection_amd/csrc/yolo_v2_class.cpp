@@ -29,6 +29,13 @@ struct DetectorState {
     network net;
     std::vector<unsigned int> next_track_id;     // per class
     std::vector<y2_det> dets;                    // compact detections of the last call
+    // detect_regions: a second network of the same files, batch = the most items seen so far (0: not created yet)
+    std::string cfg, weights;
+    int gpu_id = 0;
+    network regions_net;
+    int regions_batch = 0;
+    std::vector<y2_det> regions_dets;
+    std::vector<int> regions_counts;
 };
 
 DetectorState &state_of(const std::shared_ptr<void> &p) { return *static_cast<DetectorState *>(p.get()); }
@@ -69,6 +76,7 @@ Detector::Detector(std::string cfg_filename, std::string weight_filename, int gp
     gpu_index = saved;
     if (!st->net.layers) throw std::runtime_error(std::string("cannot build network: ") + y2_last_error());
     st->net.gpu_index = gpu_id;
+    st->cfg = cfg_filename; st->weights = weight_filename; st->gpu_id = gpu_id;
     if (!weight_filename.empty()) load_weights(&st->net, const_cast<char *>(weight_filename.c_str()));
     set_batch_network(&st->net, 1);
     const layer &l = st->net.layers[st->net.n - 1];
@@ -79,7 +87,10 @@ Detector::Detector(std::string cfg_filename, std::string weight_filename, int gp
 Detector::~Detector()
 {
     DeviceGuard guard;
-    if (detector_gpu_ptr) free_network(state_of(detector_gpu_ptr).net);
+    if (!detector_gpu_ptr) return;
+    DetectorState &st = state_of(detector_gpu_ptr);
+    free_network(st.net);
+    if (st.regions_batch > 0) free_network(st.regions_net);
 }
 
 int Detector::get_net_width() const { return state_of(detector_gpu_ptr).net.w; }
@@ -161,6 +172,47 @@ std::vector<bbox_t> Detector::detect_frame(const unsigned char *data, int w, int
         const y2_det &d = st.dets[i];
         out.push_back(to_bbox(d.x, d.y, d.w, d.h, d.prob, d.obj_id, w, h));
     }
+    return out;
+}
+
+std::vector<std::vector<bbox_t>> Detector::detect_regions(const std::vector<frame_region_t> &items, float thresh, bool bgr)
+{
+    DeviceGuard guard;
+    DetectorState &st = state_of(detector_gpu_ptr);
+    const int n = (int)items.size();
+    if (n < 1) throw std::runtime_error("detect_regions: no items");
+    if (st.regions_batch == 0) {
+        const int saved = gpu_index;
+        gpu_index = st.gpu_id;
+        st.regions_net = parse_network_cfg(const_cast<char *>(st.cfg.c_str()));
+        gpu_index = saved;
+        if (!st.regions_net.layers) throw std::runtime_error(std::string("cannot build network: ") + y2_last_error());
+        st.regions_net.gpu_index = st.gpu_id;
+        if (!st.weights.empty()) load_weights(&st.regions_net, const_cast<char *>(st.weights.c_str()));
+    }
+    if (n > st.regions_batch) {                  // grows only: the plan is rebuilt at the next call into the engine
+        set_batch_network(&st.regions_net, n);
+        st.regions_batch = n;
+    }
+    std::vector<y2_region> r(n);
+    for (int i = 0; i < n; ++i) {
+        const frame_region_t &f = items[i];
+        r[i].data = f.data; r[i].h = f.h; r[i].w = f.w; r[i].c = f.c; r[i].step = f.step;
+        r[i].x = f.x; r[i].y = f.y; r[i].rw = f.rw; r[i].rh = f.rh;
+    }
+    const layer &last = st.regions_net.layers[st.regions_net.n - 1];
+    const int total = std::max(last.w * last.h * last.n, 1);
+    st.regions_dets.resize((size_t)n * total);
+    st.regions_counts.assign(n, 0);
+    if (y2_detect_regions(st.regions_net, r.data(), n, bgr ? 1 : 0, 0, thresh, nms, st.regions_dets.data(), st.regions_counts.data(),
+                          total) != 0)
+        throw std::runtime_error(y2_last_error());
+    std::vector<std::vector<bbox_t>> out(n);
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < std::min(st.regions_counts[i], total); ++j) {
+            const y2_det &d = st.regions_dets[(size_t)i * total + j];
+            out[i].push_back(to_bbox(d.x, d.y, d.w, d.h, d.prob, d.obj_id, items[i].w, items[i].h));
+        }
     return out;
 }
 

@@ -100,6 +100,11 @@ class Det(C.Structure):
                 ("obj_id", C.c_int)]
 
 
+class Region(C.Structure):   # include/sr_yolo2.h y2_region
+    _fields_ = [("data", C.c_void_p), ("h", C.c_int), ("w", C.c_int), ("c", C.c_int), ("step", C.c_int),
+                ("x", C.c_int), ("y", C.c_int), ("rw", C.c_int), ("rh", C.c_int)]
+
+
 DET_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("w", "<f4"), ("h", "<f4"), ("prob", "<f4"), ("obj_id", "<i4")])
 
 LAYER_TYPES = ["CONVOLUTIONAL", "DECONVOLUTIONAL", "CONNECTED", "MAXPOOL", "SOFTMAX", "DETECTION", "DROPOUT", "CROP",
@@ -165,6 +170,12 @@ def lib():
     L.y2_ingest_u8.argtypes = [CNetwork, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.y2_detect_u8.argtypes = [CNetwork, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+    L.y2_ingest_regions.argtypes = [CNetwork, C.POINTER(Region), C.c_int, C.c_int, C.c_int]
+    L.y2_detect_regions.argtypes = [CNetwork, C.POINTER(Region), C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                    C.c_void_p, C.c_void_p, C.c_int]
+    L.y2_region_box_to_frame.argtypes = [C.POINTER(Region), C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_float)] * 4
+    L.test_detector_regions.argtypes = [C.POINTER(C.c_char_p), CNetwork, C.POINTER(Region), C.c_int, C.c_float,
+                                        C.POINTER(C.POINTER(Object)), C.POINTER(C.c_int)]
     L.y2h_u8_to_planes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int,
                                    C.c_void_p, C.c_void_p]
     L.top_predictions.argtypes = [CNetwork, C.c_int, C.c_void_p]
@@ -255,6 +266,33 @@ def _check():
 
 def _ptr(a: np.ndarray):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def regions(items):
+    """items: list of (frame uint8 [h][w][c] or [h][w], (x, y, rw, rh) or None = the whole frame) -> (Region array,
+    frames kept alive for the call).  A frame whose rows are padded (a view of a wider buffer) is passed with its
+    row pitch as `step`, without a copy."""
+    arr = (Region * max(len(items), 1))()
+    keep = []
+    for i, (frame, rect) in enumerate(items):
+        f = np.asarray(frame)
+        if f.ndim == 2:
+            f = f[:, :, None]
+        if f.dtype != np.uint8 or f.strides[2] != 1 or f.strides[1] != f.shape[2] or f.strides[0] < f.shape[1] * f.shape[2]:
+            f = np.ascontiguousarray(f, dtype=np.uint8)
+        keep.append(f)
+        h, w, c = f.shape
+        x, y, rw, rh = rect if rect is not None else (0, 0, 0, 0)
+        arr[i] = Region(f.ctypes.data, h, w, c, f.strides[0], x, y, rw, rh)
+    return arr, keep
+
+
+def region_box_to_frame(item, net_w: int, net_h: int, letterbox: bool, box):
+    """y2_region_box_to_frame: (x, y, w, h) relative to the network input -> relative to the item's frame (fp32)"""
+    arr, keep = regions([item])
+    v = [C.c_float(float(b)) for b in box]
+    lib().y2_region_box_to_frame(arr, net_w, net_h, int(letterbox), *[C.byref(t) for t in v])
+    return np.array([t.value for t in v], dtype=np.float32)
 
 
 def _rows(probs: np.ndarray):
@@ -592,6 +630,27 @@ class Network:
             raise Y2Error("ingest_u8: %d frames for a batch-%d network" % (b, self.net.batch))
         if lib().y2_ingest_u8(self.net, _ptr(frames), h, w, c, w * c, int(swap_rb), int(letterbox)) != 0:
             raise Y2Error("y2_ingest_u8: " + _check())
+
+    def ingest_regions(self, items, swap_rb: bool = True, letterbox: bool = False) -> None:
+        """y2_ingest_regions: items = [(frame uint8 [h][w][c], (x, y, rw, rh) | None)], one per batch slot from 0"""
+        arr, keep = regions(items)
+        if lib().y2_ingest_regions(self.net, arr, len(items), int(swap_rb), int(letterbox)) != 0:
+            raise Y2Error(_check())
+
+    def detect_regions(self, items, thresh: float, nms: float, swap_rb: bool = True, letterbox: bool = False,
+                       max_per_item: int | None = None):
+        """y2_detect_regions: one forward pass over the items; ([dets of item i], counts[n]) with boxes relative to
+        each item's frame"""
+        arr, keep = regions(items)
+        n = len(items)
+        l = self.last
+        cap = max_per_item or l.w * l.h * l.n
+        dets = np.zeros((max(n, 1), cap), dtype=DET_DTYPE)
+        counts = np.zeros(max(n, 1), dtype=np.int32)
+        if lib().y2_detect_regions(self.net, arr, n, int(swap_rb), int(letterbox), thresh, nms, _ptr(dets), _ptr(counts),
+                                   cap) != 0:
+            raise Y2Error(_check())
+        return [dets[i, :min(int(counts[i]), cap)].copy() for i in range(n)], counts[:n]
 
     def validate_detector_frames(self, frames: np.ndarray, paths, orig_w, orig_h, prefix: str, eval: str = "voc",
                                  names=None, map_: np.ndarray | None = None) -> None:
