@@ -132,6 +132,11 @@ struct layer {
     /* [crop] (crop_layer.c:16-46; `scale` above holds crop_height / h for resize_crop_layer) */
     int flip, noadjust;
     float angle, saturation, exposure, shift;
+    /* [rnn] / [gru] (rnn_layer.c:29-60, gru_layer.c:29-87): `batch` is B = net.batch / steps sequences, each run for
+     * `steps` time steps per forward.  Every sub-layer is a host [connected] layer holding its parameters. */
+    int steps, hidden, shortcut;
+    struct layer *input_layer, *self_layer, *output_layer;                  /* [rnn] */
+    struct layer *input_z_layer, *state_z_layer, *input_r_layer, *state_r_layer, *input_h_layer, *state_h_layer;   /* [gru] */
 };
 
 /* network.h:19-67, forward-path subset */
@@ -185,6 +190,12 @@ int resize_network(network *net, int w, int h);                  /* network.c:32
 float *network_predict(network net, float *input);               /* network.c:458 */
 float *network_predict_gpu(network net, float *input);           /* network_kernels.cu:392 */
 float *get_network_output(network net);                          /* network.c:173 */
+/* rnn.c:116: zero item b's hidden state in every [rnn] / [gru] layer; b = -1 zeroes every item (an extension).
+ * Recurrent networks read and write rows step-major: row t*B + b is step t of sequence b (B = net.batch / time_steps).
+ * The state lives in HBM; it is zeroed when the plan is built (the first predict, set_batch_network) and by this call,
+ * and nothing else touches it: every forward (network_predict, y2_forward_device, y2_feed_forward, a graph replay)
+ * starts from the state the previous one left.  Runs on the engine stream, ordered with the forwards. */
+void reset_rnn_state(network net, int b);
 float *get_network_output_gpu(network net);                      /* network_kernels.cu:385 */
 int get_network_output_size(network net);                        /* network.c:390 */
 int get_network_input_size(network net);                         /* network.c:397 */

@@ -384,6 +384,43 @@ typedef struct y2h_region {
 int y2h_regions_to_input(const y2h_region *desc, int n, const unsigned char *pixels, int batch, int planes, int swap_rb,
                          int h, int w, float *dst, y2h_stream s);
 
+/* ---- recurrent layers ([rnn] / [gru], y2_recurrent.hip) ----
+ * One launch computes n dense columns over `rows` (<= a few dozen) input rows, the sub-layer's epilogue (batch-norm with
+ * the rolling statistics, bias, any activation, in the reference's order) and then the mode's combine:
+ *   DENSE   out[r][j] = v                                          (a hoisted projection of a small batch)
+ *   RNN     out[r][j] = ((shortcut ? state : 0) + proj[r][j]) + v  (rnn_layer.c:97-111); out2 (if set) gets a copy
+ *   GRU_ZR  columns j < h:  out[r][j] = z = sigma(proj_z + v);  columns h + j:  out2[r][j] = f = state * sigma(proj_r + v)
+ *   GRU_H   y = z*state + (1-z)*sigma(proj_h + v) -> out[r][j] (the state, in place: only column j reads it) and out2[r][j]
+ * with proj = the step's rows of the hoisted input projections ([rows][h]; GRU: [rows][3h] = z | r | h columns) and
+ * sigma(x) = (float)(1/(1+exp(-(double)x))) (gru_layer.c:154-171, blas.c:49-55).  Each product and sum is rounded on
+ * its own.
+ * form Y2H_REC_SKINNY: weight streaming -- the x rows are staged in LDS once per workgroup, a wave streams the weight
+ * rows of its columns once with 16-byte loads, lanes split k and a fixed butterfly reduces (no atomics: two runs are
+ * bitwise equal).  Needs y2h_rec_skinny_ok(rows, k).  Column j always runs in the same workgroup, so a step finds its
+ * weight slice in the same XCD's L2 as the step before.
+ * form Y2H_REC_REF: one thread per value, the dot product in the reference's order (gemm_nt, gemm.c:90-106), bit-identical
+ * to the CPU path; with `pre` set the dense values are read from there instead (combine only). */
+enum { Y2H_REC_DENSE = 0, Y2H_REC_RNN = 1, Y2H_REC_GRU_ZR = 2, Y2H_REC_GRU_H = 3 };
+enum { Y2H_REC_REF = 0, Y2H_REC_SKINNY = 1 };
+#define Y2H_REC_SKINNY_MAX_ROWS 8
+typedef struct {
+    const float *x;              /* [rows][k] input rows of the dense product                                */
+    const float *w;              /* [n][k] weights (the reference's [outputs][inputs])                       */
+    const float *bias, *mean, *scale;
+    const double *rinv;          /* 1 / (sqrt(var) + 1e-6f) in double, as for a convolution                  */
+    int bn, act;                 /* act: any Y2H_ACT_*                                                       */
+    const float *pre;            /* [rows][n] dense values made elsewhere (Y2H_REC_REF only), or NULL        */
+    int rows, k, n, h;
+    int mode, shortcut;
+    const float *proj;           /* hoisted input projections of this step                                  */
+    const float *state;          /* [rows][h] state before the step                                          */
+    float *out, *out2;
+    const float *z;              /* GRU_H: [rows][h] z of this step                                          */
+    float *xcopy;                /* if set, the launch also copies the x rows there ([rows][k])              */
+} y2h_rec_args;
+int y2h_rec_skinny_ok(int rows, int k);
+int y2h_rec_step(const y2h_rec_args *a, int form, y2h_stream s);
+
 #ifdef __cplusplus
 }
 #endif

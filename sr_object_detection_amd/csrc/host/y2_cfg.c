@@ -13,7 +13,8 @@
  *
  * Sections built: the YOLOv2 / Darknet-19 forward path ([convolutional] [maxpool] [route] [reorg] [region] [avgpool]
  * [softmax], [cost] which does nothing at inference) plus the heads SURVEY 8(f)-4 admits ([shortcut], the YOLOv1
- * head [connected] [dropout] [detection]) and [crop] [local] [batchnorm]; any other section ([rnn], [gru], ...)
+ * head [connected] [dropout] [detection]) and [crop] [local] [batchnorm], and the recurrent [rnn] / [gru]
+ * (parser.c:188-212; rnn_layer.c:29-60, gru_layer.c:29-87) behind a flat input; any other section ([crnn], ...)
  * is an error rather than a silent skip.  No device memory is touched here:
  * HBM buffers are planned at the first predict (y2_engine.c).
  */
@@ -492,6 +493,112 @@ static layer make_connected(list *o, shape p)
     return l;
 }
 
+/* connected_layer.c:13-89 without a network position: a recurrent layer's sub-layer (rnn_layer.c:39-55,
+ * gru_layer.c:39-72).  batch = B, the sequences the layer runs; weights [outputs][inputs] */
+static layer *make_sublayer(int batch, int inputs, int outputs, ACTIVATION act, int batch_normalize)
+{
+    layer *l = calloc(1, sizeof(layer));
+    int i;
+    l->type = CONNECTED;
+    l->batch = batch;
+    l->inputs = inputs; l->outputs = outputs;
+    l->h = 1; l->w = 1; l->c = inputs;
+    l->out_h = 1; l->out_w = 1; l->out_c = outputs;
+    l->n = outputs; l->size = 1; l->stride = 1;
+    l->activation = act;
+    l->batch_normalize = batch_normalize;
+    l->weights = calloc((size_t)outputs * inputs, sizeof(float));
+    l->biases = calloc(outputs, sizeof(float));
+    if (batch_normalize) {
+        l->scales = calloc(outputs, sizeof(float));
+        for (i = 0; i < outputs; ++i) l->scales[i] = 1;
+        l->rolling_mean = calloc(outputs, sizeof(float));
+        l->rolling_variance = calloc(outputs, sizeof(float));
+    }
+    fprintf(stderr, "\t\tconnected                            %4d  ->  %4d\n", inputs, outputs);
+    return l;
+}
+
+/* a recurrent layer reads a flat [steps*B][inputs] vector: the input of a [net] that declares only inputs= (as the
+ * first layer: the engine reads the caller's rows there), or a dense layer ([rnn] [gru] [connected] [softmax], or a
+ * [dropout] behind one of them) */
+static int flat_before(const network *net, int index)
+{
+    int p = index - 1;
+    if (index == 0) return !(net->h || net->w || net->c) && net->inputs > 0;
+    while (p > 0 && net->layers[p].type == DROPOUT) --p;
+    switch (net->layers[p].type) {
+    case RNN: case GRU: case CONNECTED: case SOFTMAX: return 1;
+    default: return 0;                        /* a [dropout] on the network input included */
+    }
+}
+
+static int recurrent_shape_ok(const char *t, shape p, network *net, int steps)
+{
+    if (!flat_before(net, p.index) || p.inputs <= 0) {
+        y2_fail("layer type %s after an image-shaped input is outside the YOLOv2/Darknet-19 forward path this engine "
+                "implements (a recurrent layer needs a flat input: a [net] with inputs= only, or a dense layer)", t);
+        return 0;
+    }
+    if (steps <= 0 || p.batch % steps) { y2_fail("%s: batch %d is not a multiple of time_steps %d", t, p.batch, steps); return 0; }
+    return 1;
+}
+
+/* parser.c:188-202 parse_rnn + rnn_layer.c:29-60: three [connected] sub-layers input (inputs -> hidden), self
+ * (hidden -> hidden) and output (hidden -> outputs); state [B][hidden] */
+static layer make_rnn(list *o, shape p, network *net, int steps)
+{
+    layer l;
+    int logistic;
+    ACTIVATION act, self_act;
+    memset(&l, 0, sizeof l);
+    l.type = RNN;
+    l.outputs = option_find_int(o, "output", 1);
+    l.hidden = option_find_int(o, "hidden", 1);
+    act = activation_by_name(option_find_str(o, "activation", "logistic"));
+    l.activation = act;
+    l.batch_normalize = option_find_int_quiet(o, "batch_normalize", 0);
+    logistic = option_find_int_quiet(o, "logistic", 0);
+    l.shortcut = option_find_int_quiet(o, "shortcut", 0);
+    if (!recurrent_shape_ok("[rnn]", p, net, steps)) return l;
+    if (l.outputs <= 0 || l.hidden <= 0) { y2_fail("bad rnn layer geometry"); return l; }
+    l.steps = steps;
+    l.batch = p.batch / steps;
+    l.inputs = p.inputs;
+    fprintf(stderr, "RNN Layer: %d inputs, %d outputs\n", l.inputs, l.outputs);
+    self_act = logistic == 2 ? LOGGY : (logistic == 1 ? LOGISTIC : act);
+    l.input_layer = make_sublayer(l.batch, l.inputs, l.hidden, act, l.batch_normalize);
+    l.self_layer = make_sublayer(l.batch, l.hidden, l.hidden, self_act, l.batch_normalize);
+    l.output_layer = make_sublayer(l.batch, l.hidden, l.outputs, act, l.batch_normalize);
+    return l;
+}
+
+/* parser.c:204-212 parse_gru + gru_layer.c:29-87: six LINEAR [connected] sub-layers, state [B][outputs] */
+static layer make_gru(list *o, shape p, network *net, int steps)
+{
+    layer l;
+    int h, bn;
+    memset(&l, 0, sizeof l);
+    l.type = GRU;
+    l.outputs = option_find_int(o, "output", 1);
+    l.batch_normalize = option_find_int_quiet(o, "batch_normalize", 0);
+    if (!recurrent_shape_ok("[gru]", p, net, steps)) return l;
+    if (l.outputs <= 0) { y2_fail("bad gru layer geometry"); return l; }
+    l.steps = steps;
+    l.batch = p.batch / steps;
+    l.inputs = p.inputs;
+    l.activation = LOGISTIC;                  /* the gates and the candidate: gru_layer.c:160-171 */
+    h = l.outputs; bn = l.batch_normalize;
+    fprintf(stderr, "GRU Layer: %d inputs, %d outputs\n", l.inputs, l.outputs);
+    l.input_z_layer = make_sublayer(l.batch, l.inputs, h, LINEAR, bn);
+    l.state_z_layer = make_sublayer(l.batch, h, h, LINEAR, bn);
+    l.input_r_layer = make_sublayer(l.batch, l.inputs, h, LINEAR, bn);
+    l.state_r_layer = make_sublayer(l.batch, h, h, LINEAR, bn);
+    l.input_h_layer = make_sublayer(l.batch, l.inputs, h, LINEAR, bn);
+    l.state_h_layer = make_sublayer(l.batch, h, h, LINEAR, bn);
+    return l;
+}
+
 /* parser.c:319-341 parse_crop + crop_layer.c:16-46.  At inference the layer is a centred window of the input,
  * mapped to [-1,1] unless noadjust (crop_layer.c:69-105); flip/angle/saturation/exposure only act in training. */
 static layer make_crop(list *o, shape p)
@@ -857,6 +964,8 @@ network parse_network_cfg(char *filename)    /* parser.c:585-700 */
         else if (is_type(t, "[avgpool]", "[avg]")) l = make_avgpool(p);
         else if (is_type(t, "[softmax]", "[soft]")) { l = make_softmax(s->options, p); net.hierarchy = l.softmax_tree; }
         else if (is_type(t, "[cost]", NULL)) l = make_cost(s->options, p);
+        else if (is_type(t, "[rnn]", NULL)) l = make_rnn(s->options, p, &net, net.time_steps);
+        else if (is_type(t, "[gru]", NULL)) l = make_gru(s->options, p, &net, net.time_steps);
         else {
             memset(&l, 0, sizeof l);
             y2_fail("layer type %s is outside the YOLOv2/Darknet-19 forward path this engine implements", t);

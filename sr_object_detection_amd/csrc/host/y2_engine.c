@@ -112,6 +112,11 @@ static void free_plan(network *net)
         y2h_free(d->d_flat); d->d_flat = NULL;
         y2h_free(d->d_halo); d->d_halo = NULL; d->halo_px = 0;
         y2h_free(d->d_bin); d->d_bin = NULL;
+        y2h_free(d->d_state); d->d_state = NULL;
+        y2h_free(d->d_proj); d->d_proj = NULL;
+        y2h_free(d->d_hist); d->d_hist = NULL;
+        y2h_free(d->d_zf); d->d_zf = NULL;
+        y2h_free(d->d_tmp); d->d_tmp = NULL;
         d->placed_in = -1; d->alias_of = -1; d->copy_mask = 0;
         d->fused_pool = 0; d->fused_into = -1;
         d->out_half = 0;
@@ -253,9 +258,18 @@ static void conv_desc(const network *net, int i, y2h_conv *c, const float *x, in
     }
 }
 
+static int is_recurrent(const layer *l) { return l->type == RNN || l->type == GRU; }
+
+/* a recurrent first layer behind a [net] with inputs= only reads the caller's rows as they are */
+static int flat_input(const network *net)
+{
+    return net->n > 0 && is_recurrent(&net->layers[0]) && !(net->h && net->w && net->c);
+}
+
 static void input_view(const network *net, int i, const float **x, int *ldx)
 {
     const y2_engine *e = y2_engine_of(net);
+    if (i == 0 && flat_input(net)) { *x = e->cur_input; *ldx = net->inputs; return; }
     if (i == 0) { *x = (e->in_halo == 3) ? e->cur_input : e->d_in_nhwc; *ldx = (e->in_halo == 2) ? 4 : net->c; }
     else {
         const y2_ldev *p = ld_of(&net->layers[i - 1]);
@@ -282,7 +296,7 @@ static int producer_of(const network *net, int i)
 static int is_flat(const network *net, int i)
 {
     switch (net->layers[i].type) {
-    case REGION: case AVGPOOL: case SOFTMAX: case CONNECTED: case DETECTION: return 1;
+    case REGION: case AVGPOOL: case SOFTMAX: case CONNECTED: case DETECTION: case RNN: case GRU: return 1;
     case DROPOUT: case COST: return i > 0 ? is_flat(net, i - 1) : 0;
     default: return 0;
     }
@@ -324,6 +338,8 @@ static unsigned short f32_to_f16_rne(float f)
     }
 }
 
+static void rec_pack(unsigned char *host, const y2_ldev *d, const layer *l);
+
 static int upload_weights(network *net)
 {
     y2_engine *e = y2_engine_of(net);
@@ -339,6 +355,7 @@ static int upload_weights(network *net)
         float *wp, *b;
         int K, co, ci, kh, kw, f;
         const int w_half = (i > 0) && ld_of(&net->layers[i - 1])->out_half;   /* half input -> half weights */
+        if (is_recurrent(l)) { rec_pack(host, d, l); continue; }
         if (l->type == BATCHNORM) {
             double *r = (double *)(host + d->off_rinv);
             memcpy(host + d->off_mean, l->rolling_mean, l->c * sizeof(float));
@@ -466,6 +483,264 @@ static int size_workspace(network *net)
 }
 
 /* ------------------------------------------------------------------ */
+/* [rnn] / [gru]                                                       */
+/* ------------------------------------------------------------------ */
+/* A forward of T steps over B sequences:
+ *   1. every step's input projection in ONE dense product over the T*B input rows (rnn: input layer; gru: input z|r|h as
+ *      one product of 3*outputs columns) into d_proj;
+ *   2. the step loop (skinny / reference-order forms; the matrix-core form adds its product launch in front of each) --
+ *      rnn: one launch per step (self product + the state combine), writing the step's state into
+ *      d_hist[t] (a second buffer: every column reads the whole previous state); gru: launch A reads the state and writes
+ *      z and f = state*r, launch B reads f and column j of the state and writes column j in place;
+ *   3. rnn: the output layer as ONE dense product over the T states in d_hist.
+ * The state lives in d_state at the end of every forward whatever T is: a recorded graph reads it there at its next
+ * replay.  Each row goes through the same per-row arithmetic whichever of the forms below runs it. */
+static int rec_hidden(const layer *l) { return l->type == RNN ? l->hidden : l->outputs; }
+
+/* the sub-layers of block k, stacked by rows */
+static int rec_subs(const layer *l, int k, const layer **s)
+{
+    if (l->type == RNN) { s[0] = k == 0 ? l->input_layer : (k == 1 ? l->self_layer : l->output_layer); return 1; }
+    if (k == 0) { s[0] = l->input_z_layer; s[1] = l->input_r_layer; s[2] = l->input_h_layer; return 3; }
+    if (k == 1) { s[0] = l->state_z_layer; s[1] = l->state_r_layer; return 2; }
+    s[0] = l->state_h_layer;
+    return 1;
+}
+
+static size_t rec_layout(y2_ldev *d, const layer *l, size_t off)
+{
+    int k;
+    for (k = 0; k < 3; ++k) {
+        const layer *s[3];
+        const int m = rec_subs(l, k, s);
+        d->rd[k].n = s[0]->outputs * m; d->rd[k].k = s[0]->inputs;
+        d->rd[k].bn = s[0]->batch_normalize; d->rd[k].act = s[0]->activation;
+        d->rd[k].off_w = off; off = align_up(off + (size_t)d->rd[k].n * d->rd[k].k * sizeof(float), 256);
+        d->rd[k].off_bias = off; off = align_up(off + d->rd[k].n * sizeof(float), 64);
+        if (d->rd[k].bn) {
+            d->rd[k].off_mean = off; off = align_up(off + d->rd[k].n * sizeof(float), 64);
+            d->rd[k].off_scale = off; off = align_up(off + d->rd[k].n * sizeof(float), 64);
+            d->rd[k].off_rinv = off; off = align_up(off + d->rd[k].n * sizeof(double), 64);
+        }
+    }
+    return off;
+}
+
+static void rec_pack(unsigned char *host, const y2_ldev *d, const layer *l)
+{
+    int k, m, f;
+    for (k = 0; k < 3; ++k) {
+        const layer *s[3];
+        const int subs = rec_subs(l, k, s), K = d->rd[k].k;
+        for (m = 0; m < subs; ++m) {
+            const int n = s[m]->outputs, o = m * n;
+            memcpy(host + d->rd[k].off_w + (size_t)o * K * sizeof(float), s[m]->weights, (size_t)n * K * sizeof(float));
+            memcpy(host + d->rd[k].off_bias + o * sizeof(float), s[m]->biases, n * sizeof(float));
+            if (d->rd[k].bn) {
+                double *r = (double *)(host + d->rd[k].off_rinv) + o;
+                memcpy(host + d->rd[k].off_mean + o * sizeof(float), s[m]->rolling_mean, n * sizeof(float));
+                memcpy(host + d->rd[k].off_scale + o * sizeof(float), s[m]->scales, n * sizeof(float));
+                for (f = 0; f < n; ++f) r[f] = 1.0 / (sqrt((double)s[m]->rolling_variance[f]) + (double).000001f);   /* blas.c:122 */
+            }
+        }
+    }
+}
+
+static void rec_args(const y2_engine *e, const y2_ldev *d, int k, const float *x, int rows, y2h_rec_args *a)
+{
+    memset(a, 0, sizeof *a);
+    a->x = x; a->rows = rows; a->k = d->rd[k].k; a->n = d->rd[k].n;
+    a->w = (const float *)(e->arena + d->rd[k].off_w);
+    a->bias = (const float *)(e->arena + d->rd[k].off_bias);
+    a->bn = d->rd[k].bn; a->act = act_code(d->rd[k].act);
+    if (a->bn) {
+        a->mean = (const float *)(e->arena + d->rd[k].off_mean);
+        a->scale = (const float *)(e->arena + d->rd[k].off_scale);
+        a->rinv = (const double *)(e->arena + d->rd[k].off_rinv);
+    }
+}
+
+/* block k as a [connected] layer over `rows` flat rows: a 1x1 convolution over a 1x1 image */
+static void rec_conv_desc(const y2_engine *e, const y2_ldev *d, int k, const float *x, int rows, float *y, y2h_conv *c)
+{
+    memset(c, 0, sizeof *c);
+    c->batch = rows; c->h = 1; c->w = 1; c->c = d->rd[k].k; c->ldx = d->rd[k].k;
+    c->n = d->rd[k].n; c->size = 1; c->stride = 1; c->pad = 0; c->out_h = 1; c->out_w = 1; c->ldy = d->rd[k].n;
+    c->batch_normalize = d->rd[k].bn;
+    c->activation = act_for_kernel(d->rd[k].act);
+    c->x = x; c->y = y;
+    c->ws = e->d_ws; c->ws_bytes = e->ws_bytes;
+    c->w_packed = e->arena ? (const float *)(e->arena + d->rd[k].off_w) : (const float *)(uintptr_t)256;
+    c->w_ref = c->w_packed;               /* a flat input: the packed layout is the reference's [n][k] */
+    if (e->arena) {
+        c->bias = (const float *)(e->arena + d->rd[k].off_bias);
+        if (c->batch_normalize) {
+            c->mean = (const float *)(e->arena + d->rd[k].off_mean);
+            c->scale = (const float *)(e->arena + d->rd[k].off_scale);
+            c->rinv = (const double *)(e->arena + d->rd[k].off_rinv);
+        }
+    }
+}
+
+/* The one place that decides how block k of a recurrent layer runs over `rows` rows, once per plan: in strict mode the
+ * reference-order kernel; otherwise the skinny weight-streaming kernel while the rows fit it, above that the fp32
+ * matrix-core [connected] path where its kernels take the shape (the plan's own buffers are aligned; a caller's input is
+ * copied into an aligned one, enqueue_forward), and the reference-order kernel where they do not.
+ * Y2_RNN_STEP=skinny|mfma forces the step's blocks (a forced skinny step that does not fit is refused: -1). */
+static int rec_form(const y2_engine *e, const y2_ldev *d, int k, int rows, int step)
+{
+    const char *f = step ? getenv("Y2_RNN_STEP") : NULL;
+    y2h_conv c;
+    if (e->strict) return Y2_REC_REF;
+    if (f && strcmp(f, "skinny") == 0) return y2h_rec_skinny_ok(rows, d->rd[k].k) ? Y2_REC_SKINNY : -1;
+    if (!(f && strcmp(f, "mfma") == 0) && y2h_rec_skinny_ok(rows, d->rd[k].k)) return Y2_REC_SKINNY;
+    rec_conv_desc(e, d, k, (const float *)(uintptr_t)256, rows, (float *)(uintptr_t)256, &c);
+    c.w_packed = c.w_ref = (const float *)(uintptr_t)256;
+    return y2h_conv_uses_mfma(&c) ? Y2_REC_MFMA : Y2_REC_REF;
+}
+
+/* what runs: rec_skinny_kernel, the matrix-core [connected] kernels, or rec_ref_kernel */
+static const char *rec_form_name(int f) { return f == Y2_REC_REF ? "ref" : (f == Y2_REC_SKINNY ? "skinny" : "mfma"); }
+
+/* block k runs in the step loop over B rows, or hoisted over all B*T rows (the input product; the rnn output product) */
+static int rec_is_step(const layer *l, int k) { return !(k == 0 || (l->type == RNN && k == 2)); }
+static int rec_rows(const layer *l, int k) { return rec_is_step(l, k) ? l->batch : l->batch * l->steps; }
+
+/* y[rows][n] = block k over x[rows][k] in the block's form; xcopy (if set) also receives the x rows */
+static int rec_dense(y2_engine *e, const y2_ldev *d, int k, const float *x, int rows, float *y, float *xcopy)
+{
+    y2h_rec_args a;
+    y2h_conv c;
+    if (d->rd[k].form != Y2_REC_MFMA) {
+        rec_args(e, d, k, x, rows, &a);
+        a.mode = Y2H_REC_DENSE; a.out = y; a.xcopy = xcopy;
+        HIPCALL(y2h_rec_step(&a, d->rd[k].form == Y2_REC_SKINNY ? Y2H_REC_SKINNY : Y2H_REC_REF, e->stream));
+        return 0;
+    }
+    rec_conv_desc(e, d, k, x, rows, y, &c);
+    HIPCALL(y2h_conv_forward(&c, 0, e->stream));
+    if (!act_in_kernel(d->rd[k].act)) HIPCALL(y2h_activate_array(y, d->rd[k].n, rows, d->rd[k].n, act_code(d->rd[k].act), e->stream));
+    if (xcopy) HIPCALL(y2h_memcpy_d2d(xcopy, x, (size_t)rows * d->rd[k].k * sizeof(float), e->stream));
+    return 0;
+}
+
+/* buffers, forms and the kernel name of recurrent layer i; the state starts at zero */
+static int rec_plan(network *net, int i)
+{
+    y2_engine *e = y2_engine_of(net);
+    layer *l = &net->layers[i];
+    y2_ldev *d = ld_of(l);
+    const int B = l->batch, T = l->steps, H = rec_hidden(l);
+    const size_t rows = (size_t)B * T;
+    int k, tmp = 0;
+    if (i > 0 && !is_flat(net, producer_of(net, i))) { y2_fail("layer %d (%s) needs a flat input", i, get_layer_string(l->type)); return -1; }
+    rec_layout(d, l, 0);                     /* the blocks' shapes (the arena offsets are laid out again with the arena) */
+    for (k = 0; k < 3; ++k) {
+        const int step = rec_is_step(l, k);
+        d->rd[k].form = rec_form(e, d, k, rec_rows(l, k), step);
+        if (d->rd[k].form < 0) {
+            y2_fail("layer %d (%s): Y2_RNN_STEP=skinny, but %d sequences of %d values do not fit the skinny kernel (at most %d "
+                    "rows, 64 KB of rows)", i, get_layer_string(l->type), B, H, Y2H_REC_SKINNY_MAX_ROWS);
+            return -1;
+        }
+        if (step && d->rd[k].form == Y2_REC_MFMA) tmp = 1;
+    }
+    HIPCALL(y2h_malloc((void **)&d->d_state, (size_t)B * H * sizeof(float)));
+    HIPCALL(y2h_memset(d->d_state, 0, (size_t)B * H * sizeof(float), e->stream));
+    HIPCALL(y2h_malloc((void **)&d->d_proj, rows * (l->type == GRU ? 3 : 1) * H * sizeof(float)));
+    if (l->type == RNN) HIPCALL(y2h_malloc((void **)&d->d_hist, rows * H * sizeof(float)));
+    else HIPCALL(y2h_malloc((void **)&d->d_zf, (size_t)2 * B * H * sizeof(float)));
+    if (tmp) HIPCALL(y2h_malloc((void **)&d->d_tmp, (size_t)2 * B * H * sizeof(float)));
+    HIPCALL(y2h_malloc((void **)&d->out_alloc, rows * l->outputs * sizeof(float)));
+    d->out = d->out_alloc; d->out_ld = l->outputs;
+    if (l->type == RNN)
+        snprintf(d->kname, sizeof d->kname, "rnn(input:%s step:%s output:%s)", rec_form_name(d->rd[0].form),
+                 rec_form_name(d->rd[1].form), rec_form_name(d->rd[2].form));
+    else
+        snprintf(d->kname, sizeof d->kname, "gru(input:%s step:%s+%s)", rec_form_name(d->rd[0].form), rec_form_name(d->rd[1].form),
+                 rec_form_name(d->rd[2].form));
+    d->kernel = d->kname;
+    return 0;
+}
+
+/* split-K scratch for the matrix-core forms of the recurrent products */
+static int rec_workspace(network *net)
+{
+    y2_engine *e = y2_engine_of(net);
+    size_t need = 0, b;
+    int i, k;
+    for (i = 0; i < net->n; ++i) {
+        const layer *l = &net->layers[i];
+        const y2_ldev *d = ld_of(l);
+        y2h_conv c;
+        if (!is_recurrent(l)) continue;
+        for (k = 0; k < 3; ++k) {
+            if (d->rd[k].form != Y2_REC_MFMA) continue;
+            rec_conv_desc(e, d, k, (const float *)(uintptr_t)256, rec_rows(l, k), (float *)(uintptr_t)256, &c);
+            b = y2h_conv_workspace_bytes(&c);
+            if (b > need) need = b;
+        }
+    }
+    if (need > e->ws_bytes) {
+        y2h_free(e->d_ws); e->d_ws = NULL; e->ws_bytes = 0;
+        HIPCALL(y2h_malloc((void **)&e->d_ws, need));
+        e->ws_bytes = need;
+    }
+    return 0;
+}
+
+/* one step's block k: the skinny or reference-order kernel computes the product and the combine in one launch; the
+ * matrix-core form writes the product to d_tmp and the reference-order kernel combines */
+static int rec_step(y2_engine *e, const y2_ldev *d, int k, y2h_rec_args *a)
+{
+    if (d->rd[k].form == Y2_REC_MFMA) {
+        if (rec_dense(e, d, k, a->x, a->rows, d->d_tmp, NULL) != 0) return -1;
+        a->pre = d->d_tmp;
+    }
+    HIPCALL(y2h_rec_step(a, d->rd[k].form == Y2_REC_SKINNY ? Y2H_REC_SKINNY : Y2H_REC_REF, e->stream));
+    return 0;
+}
+
+static int rec_forward(network *net, int i, const float *x)
+{
+    y2_engine *e = y2_engine_of(net);
+    layer *l = &net->layers[i];
+    y2_ldev *d = ld_of(l);
+    const int B = l->batch, T = l->steps, H = rec_hidden(l);
+    const size_t bh = (size_t)B * H;
+    y2h_rec_args a;
+    int t;
+    if (rec_dense(e, d, 0, x, B * T, d->d_proj, NULL) != 0) return -1;
+    for (t = 0; t < T; ++t) {
+        if (l->type == RNN) {
+            const float *prev = t == 0 ? d->d_state : d->d_hist + (t - 1) * bh;
+            rec_args(e, d, 1, prev, B, &a);
+            a.mode = Y2H_REC_RNN; a.h = H; a.shortcut = l->shortcut;
+            a.proj = d->d_proj + t * bh; a.state = prev;
+            a.out = d->d_hist + t * bh;
+            a.out2 = (t == T - 1 && T > 1) ? d->d_state : NULL;     /* the last step reads d_hist[T-2], not d_state */
+            if (rec_step(e, d, 1, &a) != 0) return -1;
+        } else {
+            float *z = d->d_zf, *f = d->d_zf + bh;
+            rec_args(e, d, 1, d->d_state, B, &a);
+            a.mode = Y2H_REC_GRU_ZR; a.h = H;
+            a.proj = d->d_proj + t * 3 * bh; a.state = d->d_state;
+            a.out = z; a.out2 = f;
+            if (rec_step(e, d, 1, &a) != 0) return -1;
+            rec_args(e, d, 2, f, B, &a);
+            a.mode = Y2H_REC_GRU_H; a.h = H;
+            a.proj = d->d_proj + t * 3 * bh; a.state = d->d_state; a.z = z;
+            a.out = d->d_state; a.out2 = d->out + t * bh;
+            if (rec_step(e, d, 2, &a) != 0) return -1;
+        }
+    }
+    /* rnn: the output product over the T states; at T = 1 the one step could not write d_state (every workgroup reads it),
+     * so this launch, which reads d_hist[0] anyway, also copies it there */
+    if (l->type == RNN && rec_dense(e, d, 2, d->d_hist, B * T, d->out, T == 1 ? d->d_state : NULL) != 0) return -1;
+    return 0;
+}
+
+/* ------------------------------------------------------------------ */
 /* tile autotuning (y2_set_autotune)                                   */
 /* ------------------------------------------------------------------ */
 /* Measured choices are remembered per layer shape for the life of the process, so that re-plans (set_batch_network,
@@ -585,8 +860,18 @@ int y2_engine_build(network *net)
     if (!e->stream) HIPCALL(y2h_stream_create(&e->stream));
     free_plan(net);
 
-    /* every layer follows the network batch (set_batch_network only rewrites the field) */
-    for (i = 0; i < net->n; ++i) net->layers[i].batch = net->batch;
+    /* every layer follows the network batch (set_batch_network only rewrites the field); a recurrent layer runs
+     * net.batch / steps sequences (rnn_layer.c:32) */
+    for (i = 0; i < net->n; ++i) {
+        layer *l = &net->layers[i];
+        l->batch = net->batch;
+        if (!is_recurrent(l)) continue;
+        if (l->steps <= 0 || net->batch % l->steps) {
+            y2_fail("layer %d (%s): batch %d is not a multiple of time_steps %d", i, get_layer_string(l->type), net->batch, l->steps);
+            return -1;
+        }
+        l->batch = net->batch / l->steps;
+    }
 
     /* pass 1: let the sources of concatenating routes write into the route buffer */
     for (i = 0; i < net->n; ++i) {
@@ -658,7 +943,7 @@ int y2_engine_build(network *net)
                 if (pd && pd->out_half) { y2_fail("fp16 mode: layer %d (%s) needs an fp32 producer (a convolutional or avgpool layer)", i, get_layer_string(l->type)); return -1; }
                 break;
             case COST: d->out_half = pd ? pd->out_half : 0; break;
-            case SHORTCUT: case CONNECTED: case DETECTION: case DROPOUT: case CROP: case LOCAL: case BATCHNORM:
+            case SHORTCUT: case CONNECTED: case DETECTION: case DROPOUT: case CROP: case LOCAL: case BATCHNORM: case RNN: case GRU:
                 y2_fail("fp16 mode: layer %d (%s) has no half-precision kernel", i, get_layer_string(l->type)); return -1;
             default: break;
             }
@@ -738,6 +1023,9 @@ int y2_engine_build(network *net)
             d->out = d->d_flat; d->out_ld = l->outputs;
             d->kernel = l->type == DETECTION ? (l->softmax ? "detection(copy+softmax)" : "detection(copy)") : "connected";
         } break;
+        case RNN: case GRU:
+            if (rec_plan(net, i) != 0) return -1;
+            break;
         case DROPOUT: {
             y2_ldev *sd = i > 0 ? ld_of(&net->layers[i - 1]) : NULL;
             if (!sd) { y2_fail("dropout layer %d has no input layer", i); return -1; }
@@ -918,6 +1206,7 @@ int y2_engine_build(network *net)
             d->off_rinv = off; off = align_up(off + l->c * sizeof(double), 64);
             continue;
         }
+        if (is_recurrent(l)) { off = rec_layout(d, l, off); continue; }
         if (l->type == LOCAL) {
             d->off_w_packed = off; off = align_up(off + (size_t)l->out_h * l->out_w * l->n * l->size * l->size * l->c * sizeof(float), 256);
             d->off_bias = off; off = align_up(off + (size_t)l->outputs * sizeof(float), 64);
@@ -958,7 +1247,7 @@ int y2_engine_build(network *net)
         if (l->type == CONNECTED && !d->uses_mfma) d->kernel = "connected_ref";
         if (d->fused_pool) { snprintf(d->kname, sizeof d->kname, "%s+maxpool2", d->kernel); d->kernel = d->kname; }
     }
-    if (size_workspace(net) != 0) return -1;
+    if (size_workspace(net) != 0 || rec_workspace(net) != 0) return -1;
     {   /* The packed arena is only valid for the layout it was filled for: a re-plan may move a layer between the
          * matrix-core and the reference-layout form, or switch the weights to half, without changing the total size.
          * Signature = FNV-1a over every per-layer offset and form flag. */
@@ -967,6 +1256,10 @@ int y2_engine_build(network *net)
         for (i = 0; i < net->n; ++i) {
             const layer *l = &net->layers[i];
             const y2_ldev *d = ld_of(l);
+            if (is_recurrent(l)) {
+                for (k = 0; k < 3; ++k) { SIG_MIX(i); SIG_MIX(d->rd[k].off_w); SIG_MIX(d->rd[k].off_bias); SIG_MIX(d->rd[k].bn ? d->rd[k].off_rinv + 1 : 0); }
+                continue;
+            }
             if (l->type != CONVOLUTIONAL && l->type != CONNECTED && l->type != LOCAL && l->type != BATCHNORM) continue;
             SIG_MIX(i); SIG_MIX(d->off_w_packed); SIG_MIX(d->has_w_ref ? d->off_w_ref + 1 : 0); SIG_MIX(d->off_bias);
             SIG_MIX(d->uses_mfma); SIG_MIX((i > 0) && ld_of(&net->layers[i - 1])->out_half);
@@ -1046,9 +1339,20 @@ int y2_engine_forward(network *net, const float *d_input_nchw)
     y2_engine *e;
     if (ensure_built(net) != 0) return -1;
     e = y2_engine_of(net);
-    if (net->c <= 0 || net->h <= 0 || net->w <= 0) { y2_fail("network input must be an image (h,w,c > 0)"); return -1; }
+    if ((net->c <= 0 || net->h <= 0 || net->w <= 0) && !flat_input(net)) { y2_fail("network input must be an image (h,w,c > 0)"); return -1; }
     if (!d_input_nchw) d_input_nchw = e->d_in_nchw;     /* filled by y2_ingest_u8 */
     if (!e->graph_on || e->timing || e->strict) return enqueue_forward(net, d_input_nchw);
+    {   /* a recording bakes in each softmax's temperature, which callers write between calls (test_char_rnn, rnn.c:244) */
+        uint64_t sig = 1469598103934665603ull;
+        int i;
+        for (i = 0; i < net->n; ++i) {
+            uint32_t b;
+            if (net->layers[i].type != SOFTMAX) continue;
+            memcpy(&b, &net->layers[i].temperature, sizeof b);
+            sig = (sig ^ b) * 1099511628211ull;
+        }
+        if (sig != e->graph_params) { drop_graphs(e); e->graph_params = sig; }
+    }
     /* y2_set_detect_overlap together with graph replay: the wait that keeps this forward's region layer from overwriting
      * d_region while the previous batch's decode / NMS still read it on det_stream cannot live inside the graph (it would
      * be captured once, against whatever det_pending was then, on an event recorded outside the capture).  It is issued
@@ -1086,7 +1390,14 @@ static int enqueue_forward(network *net, const float *d_input_nchw)
     y2_engine *e = y2_engine_of(net);
     int i, k;
     e->cur_input = d_input_nchw;
-    if (e->in_halo == 3 && (!e->half || ((uintptr_t)d_input_nchw % 16) == 0))
+    if (flat_input(net)) {
+        /* a recurrent first layer reads the caller's rows; the plan chose its forms for a 16-byte aligned buffer */
+        if (((uintptr_t)d_input_nchw % 16) != 0 && d_input_nchw != e->d_in_nchw) {
+            HIPCALL(y2h_memcpy_d2d(e->d_in_nchw, d_input_nchw, e->in_floats * sizeof(float), e->stream));
+            e->cur_input = e->d_in_nchw;
+        }
+    }
+    else if (e->in_halo == 3 && (!e->half || ((uintptr_t)d_input_nchw % 16) == 0))
         ;                                                       /* the first layer reads d_input_nchw (fp32 kernel: dword loads, any float pointer) */
     else if (e->in_halo == 3) {
         /* the fp16 first-layer kernel reads the planes with 16-byte loads: a caller's pointer that is not 16-byte aligned
@@ -1207,6 +1518,9 @@ static int enqueue_forward(network *net, const float *d_input_nchw)
             if (!act_in_kernel(l->activation))
                 HIPCALL(y2h_activate_array(d->d_flat, l->outputs, (long)l->batch, l->outputs, act_code(l->activation), e->stream));
         } break;
+        case RNN: case GRU:
+            if (rec_forward(net, i, x) != 0) return -1;
+            break;
         case DROPOUT:
             break;                    /* dropout_layer.c:34: nothing happens at inference; the output is the input */
         case DETECTION: {
@@ -1455,7 +1769,7 @@ int y2_pull_layer_output(network net, int i, float *dst)
     if (!e || !e->built || i < 0 || i >= net.n) { y2_fail("y2_pull_layer_output: no forward has run"); return -1; }
     l = &net.layers[i];
     d = ld_of(l);
-    n = (size_t)l->batch * l->outputs;
+    n = (size_t)l->batch * (is_recurrent(l) ? l->steps : 1) * l->outputs;     /* a recurrent layer: all T steps */
     if (d->fused_pool) {
         y2_fail("layer %d is fused with the maxpool behind it and its full-resolution output is never stored; "
                 "call y2_set_fusion(&net, 0) (or set Y2_NO_FUSE=1) to inspect it", i);
@@ -1492,14 +1806,26 @@ void set_batch_network(network *net, int b)  /* network.c:308-320 */
 {
     int i;
     if (b <= 0) { y2_fail("set_batch_network: batch %d", b); return; }
+    for (i = 0; i < net->n; ++i)
+        if (is_recurrent(&net->layers[i]) && b % net->layers[i].steps) {
+            y2_fail("set_batch_network: batch %d is not a multiple of time_steps %d (layer %d)", b, net->layers[i].steps, i);
+            return;
+        }
+    for (i = 0; i < net->n; ++i)
+        if (is_recurrent(&net->layers[i])) { y2_engine_invalidate(net); break; }   /* the re-plan zeroes the state */
     net->batch = b;
-    for (i = 0; i < net->n; ++i) net->layers[i].batch = b;
+    for (i = 0; i < net->n; ++i) net->layers[i].batch = is_recurrent(&net->layers[i]) ? b / net->layers[i].steps : b;
     y2_engine_host_output(net);     /* HBM buffers are re-planned at the next predict if the batch changed */
 }
 
 int resize_network(network *net, int w, int h)   /* network.c:322-388 */
 {
     int i, inputs = 0, k;
+    for (i = 0; i < net->n; ++i)
+        if (is_recurrent(&net->layers[i])) {       /* the reference errors too: "Cannot resize this type of layer" */
+            y2_fail("resize_network: layer %d (%s) cannot be resized", i, get_layer_string(net->layers[i].type));
+            return -1;
+        }
     net->w = w; net->h = h;
     net->inputs = w * h * net->c;
     for (i = 0; i < net->n; ++i) {
@@ -1595,9 +1921,45 @@ void free_network(network net)               /* network.c:592-609 */
         free(l->weights); free(l->biases); free(l->scales); free(l->rolling_mean); free(l->rolling_variance);
         free(l->input_layers); free(l->input_sizes); free(l->map); free(l->cost);
         free_tree(l->softmax_tree);
+        if (is_recurrent(l)) {
+            layer *subs[9] = { l->input_layer, l->self_layer, l->output_layer, l->input_z_layer, l->state_z_layer, l->input_r_layer,
+                               l->state_r_layer, l->input_h_layer, l->state_h_layer };
+            int k;
+            for (k = 0; k < 9; ++k) {
+                if (!subs[k]) continue;
+                free(subs[k]->weights); free(subs[k]->biases); free(subs[k]->scales); free(subs[k]->rolling_mean);
+                free(subs[k]->rolling_variance); free(subs[k]);
+            }
+        }
     }
     free(net.layers);
     free(net.seen);
+}
+
+void reset_rnn_state(network net, int b)      /* rnn.c:116-127 */
+{
+    y2_engine *e = y2_engine_of(&net);
+    int i;
+    if (!e) { y2_fail("reset_rnn_state: network has no engine (was it built by parse_network_cfg?)"); return; }
+    for (i = 0; i < net.n; ++i) {
+        const layer *l = &net.layers[i];
+        const int B = is_recurrent(l) ? net.batch / l->steps : 0;
+        if (is_recurrent(l) && (b < -1 || b >= B)) { y2_fail("reset_rnn_state: item %d outside the %d sequences of layer %d", b, B, i); return; }
+    }
+    /* before the first forward (or a re-plan) there is nothing to clear: the plan starts every state at zero */
+    if (!e->built || e->built_batch != net.batch) return;
+    if (y2h_set_device(e->device) != 0) { y2_fail("reset_rnn_state: %s", y2h_last_error()); return; }
+    for (i = 0; i < net.n; ++i) {
+        const layer *l = &net.layers[i];
+        const y2_ldev *d = ld_of(l);
+        size_t H;
+        if (!is_recurrent(l) || !d->d_state) continue;
+        H = (size_t)rec_hidden(l);
+        if (y2h_memset(d->d_state + (b < 0 ? 0 : (size_t)b * H), 0, (b < 0 ? (size_t)l->batch : 1) * H * sizeof(float), e->stream) != 0) {
+            y2_fail("reset_rnn_state: %s", y2h_last_error());
+            return;
+        }
+    }
 }
 
 void top_predictions(network net, int k, int *index)   /* network.c:449-454 */
@@ -1623,6 +1985,8 @@ char *get_layer_string(LAYER_TYPE a)         /* network.c:73-130 */
     case CONNECTED: return "connected";
     case DROPOUT: return "dropout";
     case DETECTION: return "detection";
+    case RNN: return "rnn";
+    case GRU: return "gru";
     default: return "none";
     }
 }

@@ -45,7 +45,19 @@ typedef struct y2_ldev {
     int halo_px;
     float *d_bin;              /* xnor=1 convolution: its input binarized to +-1 ([batch][h][w][c], contiguous) */
     const char *kernel;        /* name for profiles */
+    /* [rnn] / [gru]: the sub-layers packed into the arena as three dense blocks, [n][k] weights each
+     * (rnn: input, self, output; gru: input z|r|h stacked by rows, state z|r, state h); `form` is the Y2_REC_* the block
+     * runs in, decided once per plan (y2_engine.c rec_form) */
+    struct { size_t off_w, off_bias, off_mean, off_scale, off_rinv; int n, k, bn; ACTIVATION act; int form; } rd[3];
+    float *d_state;            /* [B][hidden]: persists across forwards; zeroed at plan build and by reset_rnn_state */
+    float *d_proj;             /* [T*B][hidden | 3*outputs]: every step's input projections, one GEMM per forward */
+    float *d_hist;             /* rnn: [T*B][hidden] the states of this forward, read by the output GEMM */
+    float *d_zf;               /* gru: z and f of the current step, [2][B][outputs] */
+    float *d_tmp;              /* matrix-core step form: the step's dense values, [B][2*outputs] */
 } y2_ldev;
+
+/* how a recurrent layer's dense products run (y2_engine.c rec_form) */
+enum { Y2_REC_REF = 0, Y2_REC_SKINNY = 1, Y2_REC_MFMA = 2 };
 
 typedef struct y2_engine {
     int device;
@@ -69,6 +81,7 @@ typedef struct y2_engine {
     y2h_event ev_fwd;          /* recorded on `stream` behind the forward pass whose region output the detect chain reads */
     int det_pending;           /* 1: wait for ev_det in y2_detect_fetch, 2: already fetched synchronously */
     int graph_on;
+    uint64_t graph_params;     /* hash of the layer fields a recording bakes in that callers may write (softmax temperature) */
     y2h_graph graph;           /* the graph in use (one of graphs[]) */
     const float *graph_src;
     y2h_graph graphs[4];       /* recorded forward passes by input pointer (a double-buffered feed alternates between two) */

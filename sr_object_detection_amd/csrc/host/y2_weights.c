@@ -6,7 +6,8 @@
  * revision; `seen` as int32 when major*10+minor < 2, else uint64; then for
  * every [convolutional] layer in order: biases[n]; if batch_normalize (and not
  * dontloadscales): scales[n], rolling_mean[n], rolling_variance[n]; then
- * weights[n][c][size][size] -- raw little-endian fp32.  `flipped` layers are
+ * weights[n][c][size][size] -- raw little-endian fp32.  An [rnn] holds three [connected] records (input, self,
+ * output), a [gru] six (input_z, input_r, input_h, state_z, state_r, state_h: parser.c:1054-1066, :850-868).  `flipped` layers are
  * transposed after reading (parser.c:884,997).
  *
  * The arrays read here are the HOST copies in the reference's layout; the
@@ -26,6 +27,45 @@ static void transpose_in_place(float *a, int rows, int cols)
     for (r = 0; r < rows; ++r) for (c = 0; c < cols; ++c) t[(size_t)c * rows + r] = a[(size_t)r * cols + c];
     memcpy(a, t, (size_t)rows * cols * sizeof(float));
     free(t);
+}
+
+/* parser.c:897-913 load_connected_weights for a recurrent layer's sub-layer; 0, or -1 on a short read */
+static int load_sublayer(layer *l, FILE *fp, int transpose)
+{
+    const size_t num = (size_t)l->outputs * l->inputs;
+    if (fread(l->biases, sizeof(float), l->outputs, fp) != (size_t)l->outputs) return -1;
+    if (fread(l->weights, sizeof(float), num, fp) != num) return -1;
+    if (transpose) transpose_in_place(l->weights, l->inputs, l->outputs);
+    if (l->batch_normalize && !l->dontloadscales) {
+        if (fread(l->scales, sizeof(float), l->outputs, fp) != (size_t)l->outputs) return -1;
+        if (fread(l->rolling_mean, sizeof(float), l->outputs, fp) != (size_t)l->outputs) return -1;
+        if (fread(l->rolling_variance, sizeof(float), l->outputs, fp) != (size_t)l->outputs) return -1;
+    }
+    return 0;
+}
+
+/* parser.c:806-820 save_connected_weights */
+static void save_sublayer(const layer *l, FILE *fp)
+{
+    fwrite(l->biases, sizeof(float), l->outputs, fp);
+    fwrite(l->weights, sizeof(float), (size_t)l->outputs * l->inputs, fp);
+    if (l->batch_normalize) {
+        fwrite(l->scales, sizeof(float), l->outputs, fp);
+        fwrite(l->rolling_mean, sizeof(float), l->outputs, fp);
+        fwrite(l->rolling_variance, sizeof(float), l->outputs, fp);
+    }
+}
+
+/* the sub-layers of an [rnn] / [gru] in the file's order (parser.c:1054-1066 load, :850-868 save); returns the count */
+static int sublayers_in_file_order(const layer *l, layer **s)
+{
+    if (l->type == RNN) { s[0] = l->input_layer; s[1] = l->self_layer; s[2] = l->output_layer; return 3; }
+    if (l->type == GRU) {
+        s[0] = l->input_z_layer; s[1] = l->input_r_layer; s[2] = l->input_h_layer;
+        s[3] = l->state_z_layer; s[4] = l->state_r_layer; s[5] = l->state_h_layer;
+        return 6;
+    }
+    return 0;
 }
 
 void load_weights_upto(network *net, char *filename, int cutoff)
@@ -56,6 +96,19 @@ void load_weights_upto(network *net, char *filename, int cutoff)
         layer *l = &net->layers[i];
         size_t num;
         if (l->dontload) continue;
+        if (l->type == RNN || l->type == GRU) {
+            layer *subs[6];
+            int k, m = sublayers_in_file_order(l, subs), bad = 0;
+            for (k = 0; k < m && !bad; ++k) bad = load_sublayer(subs[k], fp, major > 1000 || minor > 1000) != 0;
+            if (bad) {
+                /* unlike the reference, which runs on with whatever the short read left, a recurrent layer with half its
+                 * weights is refused: its state would carry the damage into every later call */
+                fclose(fp);
+                y2_fail("load_weights: %s ends inside the weights of layer %d (%s)", filename, i, get_layer_string(l->type));
+                return;
+            }
+            continue;
+        }
         if (l->type == CONNECTED) {                  /* parser.c:897-913 load_connected_weights */
             num = (size_t)l->outputs * l->inputs;
             if (fread(l->biases, sizeof(float), l->outputs, fp) != (size_t)l->outputs) break;
@@ -114,6 +167,12 @@ void save_weights_upto(network net, char *filename, int cutoff)
     fwrite(hdr, 4, 4, fp);
     for (i = 0; i < net.n && i < cutoff; ++i) {
         layer *l = &net.layers[i];
+        if (l->type == RNN || l->type == GRU) {
+            layer *subs[6];
+            int k, m = sublayers_in_file_order(l, subs);
+            for (k = 0; k < m; ++k) save_sublayer(subs[k], fp);
+            continue;
+        }
         if (l->type == CONNECTED) {                  /* parser.c:806-820 save_connected_weights */
             fwrite(l->biases, sizeof(float), l->outputs, fp);
             fwrite(l->weights, sizeof(float), (size_t)l->outputs * l->inputs, fp);

@@ -57,3 +57,36 @@ inline hipError_t y2h_lds_limit(const void *fn, size_t bytes)
     if (e == hipSuccess) have = bytes;
     return e;
 }
+
+// every activation of activations.h:21-54, with the reference's own promotion rules (float x, double constants, the
+// result rounded to float on return)
+__device__ inline float activate_any(float x, int act)
+{
+    const double xd = (double)x;
+    switch (act) {
+    case Y2H_ACT_LINEAR: return x;
+    case Y2H_ACT_LEAKY: return (x > 0) ? x : (float)(.1 * xd);
+    case Y2H_ACT_LOGISTIC: return (float)(1. / (1. + exp(-xd)));
+    case Y2H_ACT_RELU: return x * (float)(x > 0);
+    case Y2H_ACT_RELIE: return (x > 0) ? x : (float)(.01 * xd);
+    case Y2H_ACT_RAMP: return (float)((double)(x * (float)(x > 0)) + .1 * xd);
+    case Y2H_ACT_TANH: { const float t = 2 * x; return (float)((exp((double)t) - 1) / (exp((double)t) + 1)); }
+    case Y2H_ACT_PLSE:
+        if (x < -4) return (float)(.01 * (double)(x + 4));
+        if (x > 4) return (float)(.01 * (double)(x - 4) + 1);
+        return (float)(.125 * xd + .5);
+    case Y2H_ACT_ELU: return (float)((double)((float)(x >= 0) * x) + (double)(x < 0) * (exp(xd) - 1));
+    case Y2H_ACT_LOGGY: return (float)(2. / (1. + exp(-xd)) - 1);
+    case Y2H_ACT_STAIR: {
+        const int n = (int)floor(xd);
+        if (n % 2 == 0) return (float)floor(xd / 2.);
+        return (float)((double)(x - (float)n) + floor(xd / 2.));
+    }
+    case Y2H_ACT_HARDTAN: return x < -1 ? -1.f : (x > 1 ? 1.f : x);
+    case Y2H_ACT_LHTAN:
+        if (x < 0) return (float)(.001 * xd);
+        if (x > 1) return (float)(.001 * (double)(x - 1) + 1);
+        return x;
+    }
+    return x;
+}

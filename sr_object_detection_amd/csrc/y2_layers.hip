@@ -621,39 +621,6 @@ extern "C" int y2h_batchnorm(const float *x, int ldx, float *y, int ldy, long pi
 // k = (c, kh, kw) order, product and sum rounded separately -- the arithmetic of gemm_nn (gemm.c:74-88).
 // ---------------------------------------------------------------------------
 
-// every activation of activations.h:21-54, with the reference's own promotion rules (float x, double constants, the
-// result rounded to float on return)
-__device__ float activate_any(float x, int act)
-{
-    const double xd = (double)x;
-    switch (act) {
-    case Y2H_ACT_LINEAR: return x;
-    case Y2H_ACT_LEAKY: return (x > 0) ? x : (float)(.1 * xd);
-    case Y2H_ACT_LOGISTIC: return (float)(1. / (1. + exp(-xd)));
-    case Y2H_ACT_RELU: return x * (float)(x > 0);
-    case Y2H_ACT_RELIE: return (x > 0) ? x : (float)(.01 * xd);
-    case Y2H_ACT_RAMP: return (float)((double)(x * (float)(x > 0)) + .1 * xd);
-    case Y2H_ACT_TANH: { const float t = 2 * x; return (float)((exp((double)t) - 1) / (exp((double)t) + 1)); }
-    case Y2H_ACT_PLSE:
-        if (x < -4) return (float)(.01 * (double)(x + 4));
-        if (x > 4) return (float)(.01 * (double)(x - 4) + 1);
-        return (float)(.125 * xd + .5);
-    case Y2H_ACT_ELU: return (float)((double)((float)(x >= 0) * x) + (double)(x < 0) * (exp(xd) - 1));
-    case Y2H_ACT_LOGGY: return (float)(2. / (1. + exp(-xd)) - 1);
-    case Y2H_ACT_STAIR: {
-        const int n = (int)floor(xd);
-        if (n % 2 == 0) return (float)floor(xd / 2.);
-        return (float)((double)(x - (float)n) + floor(xd / 2.));
-    }
-    case Y2H_ACT_HARDTAN: return x < -1 ? -1.f : (x > 1 ? 1.f : x);
-    case Y2H_ACT_LHTAN:
-        if (x < 0) return (float)(.001 * xd);
-        if (x > 1) return (float)(.001 * (double)(x - 1) + 1);
-        return x;
-    }
-    return x;
-}
-
 // binarize_cpu (convolutional_layer.c:52-58): +1 where the value is positive, -1 elsewhere; NHWC in, contiguous NHWC out
 __global__ __launch_bounds__(256) void binarize_kernel(const float *__restrict__ x, int ldx, float *__restrict__ y, int c, long total)
 {

@@ -53,7 +53,10 @@ class Object(C.Structure):   # utils.h:14-28
 
 
 class Layer(C.Structure):    # include/sr_yolo2.h struct layer
-    _fields_ = [
+    pass
+
+
+Layer._fields_ = [
         ("type", C.c_int), ("activation", C.c_int), ("cost_type", C.c_int),
         ("batch_normalize", C.c_int), ("batch", C.c_int), ("flipped", C.c_int),
         ("inputs", C.c_int), ("outputs", C.c_int),
@@ -78,6 +81,10 @@ class Layer(C.Structure):    # include/sr_yolo2.h struct layer
         ("side", C.c_int), ("forced", C.c_int), ("probability", C.c_float),
         ("flip", C.c_int), ("noadjust", C.c_int), ("angle", C.c_float), ("saturation", C.c_float),
         ("exposure", C.c_float), ("shift", C.c_float),
+        ("steps", C.c_int), ("hidden", C.c_int), ("shortcut", C.c_int),
+        ("input_layer", C.POINTER(Layer)), ("self_layer", C.POINTER(Layer)), ("output_layer", C.POINTER(Layer)),
+        ("input_z_layer", C.POINTER(Layer)), ("state_z_layer", C.POINTER(Layer)), ("input_r_layer", C.POINTER(Layer)),
+        ("state_r_layer", C.POINTER(Layer)), ("input_h_layer", C.POINTER(Layer)), ("state_h_layer", C.POINTER(Layer)),
     ]
 
 
@@ -140,6 +147,7 @@ def lib():
     L.get_network_output.restype = C.POINTER(C.c_float)
     L.get_network_output.argtypes = [CNetwork]
     L.get_network_output_size.argtypes = [CNetwork]
+    L.reset_rnn_state.argtypes = [CNetwork, C.c_int]
     L.get_network_input_size.argtypes = [CNetwork]
     L.get_region_boxes.argtypes = [Layer, C.c_int, C.c_int, C.c_float, C.POINTER(C.POINTER(C.c_float)),
                                    C.c_void_p, C.c_int, C.c_void_p]
@@ -352,6 +360,18 @@ class Network:
         if not p:
             raise Y2Error("network_predict: " + _check())
         return np.ctypeslib.as_array(p, shape=(self.net.batch * self.output_size,)).copy()
+
+    def reset_rnn_state(self, b: int = -1) -> None:
+        """rnn.c:116: zero item b's state in every [rnn] / [gru] layer (b = -1: every item), ordered with the forwards"""
+        L = lib()
+        L.reset_rnn_state(self.net, b)
+        if L.y2_failed_and_clear():
+            raise Y2Error("reset_rnn_state: " + _check())
+
+    def set_temperature(self, t: float) -> None:
+        """test_char_rnn (rnn.c:244): the temperature on every layer; [softmax] reads it at each call"""
+        for i in range(self.net.n):
+            self.net.layers[i].temperature = t
 
     @property
     def output_size(self) -> int:

@@ -162,3 +162,34 @@ def write_map(path: str, n_entries: int, n_nodes: int, seed: int = 9001) -> list
         for v in idx:
             f.write("%d\n" % v)
     return idx
+
+
+def write_recurrent_weights(path: str, name: str, seed: int) -> int:
+    """.weights of a zoo.RECURRENT network: every [connected] record (biases, weights [outputs][inputs], then scales /
+    rolling mean / rolling variance with batch-norm, parser.c:806-820) in the file order of parser.c:850-868.  Weights
+    are U(-a,a) with a = sqrt(3/K), so a state stays O(1) over many steps."""
+    from sr_object_detection_amd import zoo
+    with open(path, "wb") as f:
+        f.write(struct.pack("<iii", 0, 1, 0))
+        f.write(struct.pack("<i", 0))
+        for ri, (n, K, bn) in enumerate(zoo.recurrent_records(name)):
+            s = seed * 1000003 + 800000 + ri * 7919
+            a = math.sqrt(3.0 / K)
+            f.write(uniform(s + 1, n, -0.1, 0.1).tobytes())
+            f.write(uniform(s + 5, n * K, -a, a).tobytes())
+            if bn:
+                f.write(uniform(s + 2, n, 0.8, 1.2).tobytes())
+                f.write(uniform(s + 3, n, -0.1, 0.1).tobytes())
+                f.write(uniform(s + 4, n, 0.5, 1.5).tobytes())
+        return f.tell()
+
+
+def char_rows(seed: int, batch: int, steps: int, inputs: int, onehot: bool) -> np.ndarray:
+    """[steps*batch][inputs] step-major input rows (row t*batch + b is step t of sequence b): one-hot characters drawn
+    from a seeded sequence, or dense values in [0,1)"""
+    if onehot:
+        chars = (splitmix64(seed, steps * batch) % np.uint64(inputs)).astype(np.int64)
+        x = np.zeros((steps * batch, inputs), np.float32)
+        x[np.arange(steps * batch), chars] = 1
+        return x
+    return uniform01(seed, steps * batch * inputs).reshape(steps * batch, inputs)

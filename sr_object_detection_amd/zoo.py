@@ -353,3 +353,56 @@ def conv_flops(layers) -> float:
     """The reference's own FLOP count, 2*M*N*K summed over convs (src_yolo2/darknet.c:115-131)."""
     return float(sum(2.0 * l["filters"] * l["size"] ** 2 * l["c"] * l["out_h"] * l["out_w"]
                      for l in layers if l["type"] == "convolutional"))
+
+
+# Recurrent networks: [rnn] / [gru] behind a [net] that declares only inputs= (cfg/rnn.cfg, cfg/gru.cfg and smaller
+# cases).  Kept apart from SPECS, whose every entry tools/plan_dump.py --sweep walks.  name -> (inputs, layers), a layer
+# being ("rnn", output, hidden, activation, batch_normalize, logistic, shortcut) | ("gru", output, batch_normalize) |
+# ("connected", output, activation) | ("softmax",) | ("cost",).
+RECURRENT = {
+    "rnn": (256, [("rnn", 1024, 1024, "leaky", 1, 0, 0)] * 3 + [("connected", 256, "leaky"), ("softmax",), ("cost",)]),
+    "gru": (256, [("gru", 1024, 1)] * 3 + [("connected", 256, "linear"), ("softmax",), ("cost",)]),
+    # shortcut=1, logistic=1 and logistic=2, each with and without batch-norm; hidden 30 has no 16-byte rows
+    "rnn-mini": (30, [("rnn", 36, 36, "logistic", 1, 0, 1), ("rnn", 32, 30, "logistic", 0, 0, 1), ("rnn", 36, 36, "tanh", 1, 1, 0),
+                      ("rnn", 36, 32, "leaky", 0, 1, 0), ("rnn", 40, 36, "leaky", 1, 2, 0), ("rnn", 28, 36, "logistic", 0, 2, 0),
+                      ("connected", 30, "leaky"), ("softmax",), ("cost",)]),
+    "gru-mini": (30, [("gru", 36, 1), ("gru", 30, 0), ("connected", 30, "linear"), ("softmax",), ("cost",)]),
+}
+
+
+def recurrent_cfg_text(name: str, batch: int, time_steps: int) -> str:
+    """cfg text of a RECURRENT entry: `batch` sequences of `time_steps` steps per forward (net.batch = batch*time_steps)"""
+    inputs, layers = RECURRENT[name]
+    out = ["[net]", "subdivisions=1", "inputs=%d" % inputs, "batch=%d" % batch, "time_steps=%d" % time_steps, ""]
+    for e in layers:
+        out.append("[%s]" % e[0])
+        if e[0] == "rnn":
+            out += ["batch_normalize=%d" % e[4], "output=%d" % e[1], "hidden=%d" % e[2], "activation=%s" % e[3]]
+            out += (["logistic=%d" % e[5]] if e[5] else []) + (["shortcut=1"] if e[6] else [])
+        elif e[0] == "gru":
+            out += ["batch_normalize=%d" % e[2], "output=%d" % e[1]]
+        elif e[0] == "connected":
+            out += ["output=%d" % e[1], "activation=%s" % e[2]]
+        elif e[0] == "cost":
+            out += ["type=sse"]
+        out.append("")
+    return "\n".join(out)
+
+
+def recurrent_records(name: str):
+    """the [connected] records of the .weights file in file order: (outputs, inputs, batch_normalize) per record"""
+    inputs, layers = RECURRENT[name]
+    recs = []
+    for e in layers:
+        if e[0] == "rnn":
+            out, hid, bn = e[1], e[2], e[4]
+            recs += [(hid, inputs, bn), (hid, hid, bn), (out, hid, bn)]
+            inputs = out
+        elif e[0] == "gru":
+            out, bn = e[1], e[2]
+            recs += [(out, inputs, bn)] * 3 + [(out, out, bn)] * 3
+            inputs = out
+        elif e[0] == "connected":
+            recs.append((e[1], inputs, 0))
+            inputs = e[1]
+    return recs
