@@ -16,7 +16,7 @@
  * head [connected] [dropout] [detection]) and [crop] [local] [batchnorm], and the recurrent [rnn] / [gru]
  * (parser.c:188-212; rnn_layer.c:29-60, gru_layer.c:29-87) behind a flat input; any other section ([crnn], ...)
  * is an error rather than a silent skip.  No device memory is touched here:
- * HBM buffers are planned at the first predict (y2_engine.c).
+ * HBM buffers are planned at the first predict (y2_plan.c).
  */
 #include <stdarg.h>
 #include <stdio.h>

@@ -17,13 +17,6 @@
 #include <string.h>
 #include "y2_internal.h"
 
-#define HIPCALL(expr) do { int rc_ = (expr); if (rc_ != 0) { y2_fail("%s failed (%d): %s", #expr, rc_, y2h_last_error()); return; } } while (0)
-/* inside functions that own scratch buffers: report, then release them at `cleanup:` */
-#define HIPCALL_C(expr) do { int rc_ = (expr); if (rc_ != 0) { y2_fail("%s failed (%d): %s", #expr, rc_, y2h_last_error()); goto cleanup; } } while (0)
-#define HIPCALL_I(expr) do { int rc_ = (expr); if (rc_ != 0) { y2_fail("%s failed (%d): %s", #expr, rc_, y2h_last_error()); return -1; } } while (0)
-
-static y2_ldev *ld_of(const layer *l) { return (y2_ldev *)l->dev; }
-
 /* get_region_boxes: l.output is a HOST pointer the caller may have replaced
  * (yolo_v2_class.cpp:211 substitutes the 3-frame mean).  When it still is the
  * engine's own output buffer the tensor is already in HBM and is not re-sent. */
@@ -39,8 +32,8 @@ void get_region_boxes(layer l, int w, int h, float thresh, float **probs, box *b
     if (l.type != REGION || !d || !d->eng || !d->eng->built) { y2_fail("get_region_boxes: layer is not a prepared region layer"); return; }
     if (!l.output) { y2_fail("get_region_boxes: l.output is NULL"); return; }
     e = d->eng;
-    HIPCALL(y2h_set_device(e->device));
-    if (e->det_pending == 1 && e->det_overlap) HIPCALL(y2h_event_sync(e->ev_det));   /* the shared decode scratch is in use on det_stream */
+    HIP_OR_RET(y2h_set_device(e->device));
+    if (e->det_pending == 1 && e->det_overlap) HIP_OR_RET(y2h_event_sync(e->ev_det));   /* the shared decode scratch is in use on det_stream */
     memset(&q, 0, sizeof q);
     q.batch = 1; q.w = l.w; q.h = l.h; q.num = l.n; q.classes = l.classes;
     q.img_w = w; q.img_h = h; q.thresh = thresh; q.only_objectness = only_objectness; q.classfix = l.classfix;
@@ -50,27 +43,27 @@ void get_region_boxes(layer l, int w, int h, float thresh, float **probs, box *b
     if (l.output >= e->h_out && l.output < e->h_out + e->out_floats && (size_t)(l.output - e->h_out) % l.outputs == 0) {
         d_pred = d->d_region + (l.output - e->h_out);           /* batch item (l.output - h_out)/outputs */
     } else {
-        HIPCALL_C(y2h_malloc((void **)&d_tmp_pred, pred_floats * sizeof(float)));
-        HIPCALL_C(y2h_memcpy_h2d(d_tmp_pred, l.output, pred_floats * sizeof(float), e->stream));
+        HIP_OR_CLEANUP(y2h_malloc((void **)&d_tmp_pred, pred_floats * sizeof(float)));
+        HIP_OR_CLEANUP(y2h_memcpy_h2d(d_tmp_pred, l.output, pred_floats * sizeof(float), e->stream));
         d_pred = d_tmp_pred;
     }
     if (map && l.softmax_tree) {
         if (map == l.map && d->d_map) q.map = d->d_map;
         else {
-            HIPCALL_C(y2h_malloc((void **)&d_tmp_map, 200 * sizeof(int)));
-            HIPCALL_C(y2h_memcpy_h2d(d_tmp_map, map, 200 * sizeof(int), e->stream));
+            HIP_OR_CLEANUP(y2h_malloc((void **)&d_tmp_map, 200 * sizeof(int)));
+            HIP_OR_CLEANUP(y2h_memcpy_h2d(d_tmp_map, map, 200 * sizeof(int), e->stream));
             q.map = d_tmp_map;
         }
     }
     q.pred = d_pred; q.boxes = e->d_boxes; q.probs = e->d_probs;
-    if (q.map) HIPCALL_C(y2h_memset(e->d_probs, 0, (size_t)total * l.classes * sizeof(float), e->stream));
-    HIPCALL_C(y2h_region_boxes(&q, e->stream));
+    if (q.map) HIP_OR_CLEANUP(y2h_memset(e->d_probs, 0, (size_t)total * l.classes * sizeof(float), e->stream));
+    HIP_OR_CLEANUP(y2h_region_boxes(&q, e->stream));
     h_probs = malloc((size_t)total * l.classes * sizeof(float));
-    HIPCALL_C(y2h_memcpy_d2h(boxes, e->d_boxes, (size_t)total * sizeof(box), e->stream));
-    HIPCALL_C(y2h_memcpy_d2h(h_probs, e->d_probs, (size_t)total * l.classes * sizeof(float), e->stream));
+    HIP_OR_CLEANUP(y2h_memcpy_d2h(boxes, e->d_boxes, (size_t)total * sizeof(box), e->stream));
+    HIP_OR_CLEANUP(y2h_memcpy_d2h(h_probs, e->d_probs, (size_t)total * l.classes * sizeof(float), e->stream));
     if (l.softmax_tree)      /* the reference rewrites the class scores in l.output in place (region_layer.c:350) */
-        HIPCALL_C(y2h_memcpy_d2h(l.output, d_pred, pred_floats * sizeof(float), e->stream));
-    HIPCALL_C(y2h_stream_sync(e->stream));
+        HIP_OR_CLEANUP(y2h_memcpy_d2h(l.output, d_pred, pred_floats * sizeof(float), e->stream));
+    HIP_OR_CLEANUP(y2h_stream_sync(e->stream));
     {
         int ncopy = (q.map) ? 200 : l.classes;               /* with a map only 200 entries per row are written */
         for (i = 0; i < total; ++i) memcpy(probs[i], h_probs + (size_t)i * l.classes, ncopy * sizeof(float));
@@ -94,20 +87,20 @@ void get_detection_boxes(layer l, int w, int h, float thresh, float **probs, box
     if (!l.output) { y2_fail("get_detection_boxes: l.output is NULL"); return; }
     e = d->eng;
     if (!e->d_boxes || e->det_total < total) { y2_fail("get_detection_boxes: the detection layer is not the network's output layer"); return; }
-    HIPCALL(y2h_set_device(e->device));
+    HIP_OR_RET(y2h_set_device(e->device));
     if (l.output >= e->h_out && l.output < e->h_out + e->out_floats && (size_t)(l.output - e->h_out) % l.outputs == 0)
         d_pred = d->d_flat + (l.output - e->h_out);
     else {
-        HIPCALL_C(y2h_malloc((void **)&d_tmp, (size_t)l.outputs * sizeof(float)));
-        HIPCALL_C(y2h_memcpy_h2d(d_tmp, l.output, (size_t)l.outputs * sizeof(float), e->stream));
+        HIP_OR_CLEANUP(y2h_malloc((void **)&d_tmp, (size_t)l.outputs * sizeof(float)));
+        HIP_OR_CLEANUP(y2h_memcpy_h2d(d_tmp, l.output, (size_t)l.outputs * sizeof(float), e->stream));
         d_pred = d_tmp;
     }
-    HIPCALL_C(y2h_detection_boxes(d_pred, (long)l.outputs, 1, l.side, l.n, l.classes, l.sqrt, w, h, thresh, only_objectness,
+    HIP_OR_CLEANUP(y2h_detection_boxes(d_pred, (long)l.outputs, 1, l.side, l.n, l.classes, l.sqrt, w, h, thresh, only_objectness,
                                 e->d_boxes, e->d_probs, e->stream));
     h_probs = malloc((size_t)total * l.classes * sizeof(float));
-    HIPCALL_C(y2h_memcpy_d2h(boxes, e->d_boxes, (size_t)total * sizeof(box), e->stream));
-    HIPCALL_C(y2h_memcpy_d2h(h_probs, e->d_probs, (size_t)total * l.classes * sizeof(float), e->stream));
-    HIPCALL_C(y2h_stream_sync(e->stream));
+    HIP_OR_CLEANUP(y2h_memcpy_d2h(boxes, e->d_boxes, (size_t)total * sizeof(box), e->stream));
+    HIP_OR_CLEANUP(y2h_memcpy_d2h(h_probs, e->d_probs, (size_t)total * l.classes * sizeof(float), e->stream));
+    HIP_OR_CLEANUP(y2h_stream_sync(e->stream));
     for (i = 0; i < total; ++i) memcpy(probs[i], h_probs + (size_t)i * l.classes, l.classes * sizeof(float));
 cleanup:
     free(h_probs);
@@ -121,23 +114,23 @@ static int nms_scratch(size_t nboxes, size_t nprobs, size_t nclasses)
 {
     int dev = 0;
     if (y2h_device_count() <= 0) { y2_fail("do_nms: no HIP device visible and this library has no CPU path"); return -1; }
-    HIPCALL_I(y2h_get_device(&dev));
+    HIP_OR_ERR(y2h_get_device(&dev));
     if (g_nms.device != dev) {
         g_nms.d_boxes = g_nms.d_probs = g_nms.d_probs_in = NULL; g_nms.d_counts = NULL;
         g_nms.boxes_cap = g_nms.probs_cap = g_nms.counts_cap = 0; g_nms.stream = NULL;   /* per-device scratch */
         g_nms.device = dev;
     }
-    if (!g_nms.stream) HIPCALL_I(y2h_stream_create(&g_nms.stream));
-    if (nboxes > g_nms.boxes_cap) { y2h_free(g_nms.d_boxes); HIPCALL_I(y2h_malloc((void **)&g_nms.d_boxes, nboxes * sizeof(float))); g_nms.boxes_cap = nboxes; }
+    if (!g_nms.stream) HIP_OR_ERR(y2h_stream_create(&g_nms.stream));
+    if (nboxes > g_nms.boxes_cap) { y2h_free(g_nms.d_boxes); HIP_OR_ERR(y2h_malloc((void **)&g_nms.d_boxes, nboxes * sizeof(float))); g_nms.boxes_cap = nboxes; }
     if (nprobs > g_nms.probs_cap) {
         y2h_free(g_nms.d_probs); y2h_free(g_nms.d_probs_in);
-        HIPCALL_I(y2h_malloc((void **)&g_nms.d_probs, nprobs * sizeof(float)));
-        HIPCALL_I(y2h_malloc((void **)&g_nms.d_probs_in, nprobs * sizeof(float)));
+        HIP_OR_ERR(y2h_malloc((void **)&g_nms.d_probs, nprobs * sizeof(float)));
+        HIP_OR_ERR(y2h_malloc((void **)&g_nms.d_probs_in, nprobs * sizeof(float)));
         g_nms.probs_cap = nprobs;
     }
     if (nclasses > g_nms.counts_cap) {
         y2h_free(g_nms.d_counts);
-        HIPCALL_I(y2h_malloc((void **)&g_nms.d_counts, nclasses * sizeof(int)));
+        HIP_OR_ERR(y2h_malloc((void **)&g_nms.d_counts, nclasses * sizeof(int)));
         g_nms.counts_cap = nclasses;
     }
     return 0;
@@ -151,15 +144,15 @@ static void nms_host(box *boxes, float **probs, int total, int classes, float th
     if (nms_scratch((size_t)total * 4, (size_t)total * classes, (size_t)classes) != 0) return;
     flat = malloc((size_t)total * classes * sizeof(float));
     for (i = 0; i < total; ++i) memcpy(flat + (size_t)i * classes, probs[i], classes * sizeof(float));
-    HIPCALL(y2h_memcpy_h2d(g_nms.d_boxes, boxes, (size_t)total * sizeof(box), g_nms.stream));
-    HIPCALL(y2h_memcpy_h2d(g_nms.d_probs, flat, (size_t)total * classes * sizeof(float), g_nms.stream));
+    HIP_OR_RET(y2h_memcpy_h2d(g_nms.d_boxes, boxes, (size_t)total * sizeof(box), g_nms.stream));
+    HIP_OR_RET(y2h_memcpy_h2d(g_nms.d_probs, flat, (size_t)total * classes * sizeof(float), g_nms.stream));
     if (sorted) {
-        HIPCALL(y2h_memcpy_d2d(g_nms.d_probs_in, g_nms.d_probs, (size_t)total * classes * sizeof(float), g_nms.stream));
-        HIPCALL(y2h_nms_sort(g_nms.d_boxes, g_nms.d_probs_in, g_nms.d_probs, 1, total, classes, classes, thresh, g_nms.d_counts, g_nms.stream));
+        HIP_OR_RET(y2h_memcpy_d2d(g_nms.d_probs_in, g_nms.d_probs, (size_t)total * classes * sizeof(float), g_nms.stream));
+        HIP_OR_RET(y2h_nms_sort(g_nms.d_boxes, g_nms.d_probs_in, g_nms.d_probs, 1, total, classes, classes, thresh, g_nms.d_counts, g_nms.stream));
     }
-    else HIPCALL(y2h_nms(g_nms.d_boxes, g_nms.d_probs, 1, total, classes, classes, thresh, g_nms.stream));
-    HIPCALL(y2h_memcpy_d2h(flat, g_nms.d_probs, (size_t)total * classes * sizeof(float), g_nms.stream));
-    HIPCALL(y2h_stream_sync(g_nms.stream));
+    else HIP_OR_RET(y2h_nms(g_nms.d_boxes, g_nms.d_probs, 1, total, classes, classes, thresh, g_nms.stream));
+    HIP_OR_RET(y2h_memcpy_d2h(flat, g_nms.d_probs, (size_t)total * classes * sizeof(float), g_nms.stream));
+    HIP_OR_RET(y2h_stream_sync(g_nms.stream));
     for (i = 0; i < total; ++i) memcpy(probs[i], flat + (size_t)i * classes, classes * sizeof(float));
     free(flat);
 }
@@ -243,16 +236,16 @@ static int img_scratch(const char *who, size_t ns, size_t nt, size_t nd)
     int dev = 0;
     if (y2h_device_count() <= 0) { y2_fail("%s: no HIP device visible and this library has no CPU path", who); return -1; }
     if (gpu_index >= 0) y2h_set_device(gpu_index);
-    HIPCALL_I(y2h_get_device(&dev));
+    HIP_OR_ERR(y2h_get_device(&dev));
     if (g_img.device != dev) {
         g_img.d_src = g_img.d_tmp = g_img.d_dst = NULL;
         g_img.src_cap = g_img.tmp_cap = g_img.dst_cap = 0; g_img.stream = NULL;      /* per-device scratch */
         g_img.device = dev;
     }
-    if (!g_img.stream) HIPCALL_I(y2h_stream_create(&g_img.stream));
-    if (ns > g_img.src_cap) { y2h_free(g_img.d_src); g_img.d_src = NULL; g_img.src_cap = 0; HIPCALL_I(y2h_malloc((void **)&g_img.d_src, ns * 4)); g_img.src_cap = ns; }
-    if (nt > g_img.tmp_cap) { y2h_free(g_img.d_tmp); g_img.d_tmp = NULL; g_img.tmp_cap = 0; HIPCALL_I(y2h_malloc((void **)&g_img.d_tmp, nt * 4)); g_img.tmp_cap = nt; }
-    if (nd > g_img.dst_cap) { y2h_free(g_img.d_dst); g_img.d_dst = NULL; g_img.dst_cap = 0; HIPCALL_I(y2h_malloc((void **)&g_img.d_dst, nd * 4)); g_img.dst_cap = nd; }
+    if (!g_img.stream) HIP_OR_ERR(y2h_stream_create(&g_img.stream));
+    if (ns > g_img.src_cap) { y2h_free(g_img.d_src); g_img.d_src = NULL; g_img.src_cap = 0; HIP_OR_ERR(y2h_malloc((void **)&g_img.d_src, ns * 4)); g_img.src_cap = ns; }
+    if (nt > g_img.tmp_cap) { y2h_free(g_img.d_tmp); g_img.d_tmp = NULL; g_img.tmp_cap = 0; HIP_OR_ERR(y2h_malloc((void **)&g_img.d_tmp, nt * 4)); g_img.tmp_cap = nt; }
+    if (nd > g_img.dst_cap) { y2h_free(g_img.d_dst); g_img.d_dst = NULL; g_img.dst_cap = 0; HIP_OR_ERR(y2h_malloc((void **)&g_img.d_dst, nd * 4)); g_img.dst_cap = nd; }
     return 0;
 }
 
@@ -288,25 +281,25 @@ static int detect_enqueue(network net, float *d_pred, float thresh, float nms, i
     l = &net.layers[e->out_layer];
     d = ld_of(l);
     if (l->type != REGION && l->type != DETECTION) { y2_fail("y2_detect_resident: the network does not end in a region or detection layer"); return -1; }
-    HIPCALL_I(y2h_set_device(e->device));
-    if (e->det_pending == 1) HIPCALL_I(y2h_event_sync(e->ev_det));      /* an enqueue that was never fetched: its scratch is ours again */
+    HIP_OR_ERR(y2h_set_device(e->device));
+    if (e->det_pending == 1) HIP_OR_ERR(y2h_event_sync(e->ev_det));      /* an enqueue that was never fetched: its scratch is ours again */
     e->det_pending = 0;
-    if (!e->ev_det) HIPCALL_I(y2h_event_create(&e->ev_det));
+    if (!e->ev_det) HIP_OR_ERR(y2h_event_create(&e->ev_det));
     /* y2_set_detect_overlap (region heads, resident output): the chain runs on its own stream behind an event of the
      * forward pass that produced d_region; the next forward pass waits for ev_det before its region layer writes
      * d_region again (enqueue_forward), and nothing else touches the chain's scratch until y2_detect_fetch. */
     ds = e->stream;
     if (e->det_overlap && !d_pred && l->type == REGION) {
-        if (!e->det_stream) HIPCALL_I(y2h_stream_create(&e->det_stream));
-        if (!e->ev_fwd) HIPCALL_I(y2h_event_create(&e->ev_fwd));
-        HIPCALL_I(y2h_event_record(e->ev_fwd, e->stream));
-        HIPCALL_I(y2h_stream_wait_event(e->det_stream, e->ev_fwd));
+        if (!e->det_stream) HIP_OR_ERR(y2h_stream_create(&e->det_stream));
+        if (!e->ev_fwd) HIP_OR_ERR(y2h_event_create(&e->ev_fwd));
+        HIP_OR_ERR(y2h_event_record(e->ev_fwd, e->stream));
+        HIP_OR_ERR(y2h_stream_wait_event(e->det_stream, e->ev_fwd));
         ds = e->det_stream;
     }
     if (!d_pred) d_pred = l->type == REGION ? d->d_region : d->d_flat;
     memset(&q, 0, sizeof q);
     if (l->type == DETECTION) {           /* YOLOv1 head: detection_layer.c:222 decode, then the same NMS / compaction */
-        HIPCALL_I(y2h_detection_boxes(d_pred, (long)l->outputs, net.batch, l->side, l->n, l->classes, l->sqrt, img_w, img_h,
+        HIP_OR_ERR(y2h_detection_boxes(d_pred, (long)l->outputs, net.batch, l->side, l->n, l->classes, l->sqrt, img_w, img_h,
                                       thresh, 0, e->d_boxes, e->d_probs, ds));
     } else {
     q.batch = net.batch; q.w = l->w; q.h = l->h; q.num = l->n; q.classes = l->classes;
@@ -318,40 +311,40 @@ static int detect_enqueue(network net, float *d_pred, float thresh, float nms, i
     if (y2h_detect_chain_ok(&q)) {
         /* plain head: decode + NMS + compaction in three launches (the class counts stay zero between calls) */
         if (!e->class_counts_zeroed) {
-            HIPCALL_I(y2h_memset(e->d_class_counts, 0, (size_t)net.batch * l->classes * sizeof(int), ds));
+            HIP_OR_ERR(y2h_memset(e->d_class_counts, 0, (size_t)net.batch * l->classes * sizeof(int), ds));
             e->class_counts_zeroed = 1;
         }
-        HIPCALL_I(y2h_detect_chain(&q, nms, e->d_probs_nms, e->d_class_counts, e->d_records, e->d_counts, e->det_cap, e->d_best, ds));
+        HIP_OR_ERR(y2h_detect_chain(&q, nms, e->d_probs_nms, e->d_class_counts, e->d_records, e->d_counts, e->det_cap, e->d_best, ds));
         goto fetch;
     }
     if (y2h_detect_tree_chain_ok(&q)) {
         /* tree head without a map (yolo9000): one (class, score) pair per box instead of the dense score arrays, two launches */
-        HIPCALL_I(y2h_detect_tree_chain(&q, nms, e->d_records, e->d_counts, e->det_cap, e->d_best,
+        HIP_OR_ERR(y2h_detect_tree_chain(&q, nms, e->d_records, e->d_counts, e->det_cap, e->d_best,
                                         (d_pred == d->d_region && d->tree_best_valid) ? d->d_tree_best : NULL, ds));
         goto fetch;
     }
-    HIPCALL_I(y2h_region_boxes(&q, ds));
+    HIP_OR_ERR(y2h_region_boxes(&q, ds));
     }
     final_probs = e->d_probs;
     e->class_counts_zeroed = 0;               /* y2h_nms_sort leaves its counts behind */
     if (nms > 0) {
-        HIPCALL_I(y2h_memcpy_d2d(e->d_probs_nms, e->d_probs, (size_t)net.batch * e->det_total * l->classes * sizeof(float), ds));
-        HIPCALL_I(y2h_nms_sort(e->d_boxes, e->d_probs, e->d_probs_nms, net.batch, e->det_total, l->classes, l->classes, nms, e->d_class_counts, ds));
+        HIP_OR_ERR(y2h_memcpy_d2d(e->d_probs_nms, e->d_probs, (size_t)net.batch * e->det_total * l->classes * sizeof(float), ds));
+        HIP_OR_ERR(y2h_nms_sort(e->d_boxes, e->d_probs, e->d_probs_nms, net.batch, e->det_total, l->classes, l->classes, nms, e->d_class_counts, ds));
         final_probs = e->d_probs_nms;
     }
-    HIPCALL_I(y2h_collect(e->d_boxes, final_probs, net.batch, e->det_total, l->classes, l->classes, thresh,
+    HIP_OR_ERR(y2h_collect(e->d_boxes, final_probs, net.batch, e->det_total, l->classes, l->classes, thresh,
                           e->d_records, e->d_counts, e->det_cap, e->d_best, ds));
 fetch:
-    HIPCALL_I(y2h_memcpy_d2h(e->h_counts, e->d_counts, (size_t)net.batch * sizeof(int), ds));
+    HIP_OR_ERR(y2h_memcpy_d2h(e->h_counts, e->d_counts, (size_t)net.batch * sizeof(int), ds));
     keep = 0;
     if ((size_t)net.batch * e->det_cap * 6 * sizeof(float) <= ((size_t)8 << 20)) {
         /* small enough: fetch every record block with the counts, one copy and one sync per batch */
-        HIPCALL_I(y2h_memcpy_d2h(e->h_records, e->d_records, (size_t)net.batch * e->det_cap * 6 * sizeof(float), ds));
-        HIPCALL_I(y2h_event_record(e->ev_det, ds));
+        HIP_OR_ERR(y2h_memcpy_d2h(e->h_records, e->d_records, (size_t)net.batch * e->det_cap * 6 * sizeof(float), ds));
+        HIP_OR_ERR(y2h_event_record(e->ev_det, ds));
         e->det_pending = 1;                   /* detect_fetch waits for the event */
         return 0;
     } else {
-        HIPCALL_I(y2h_stream_sync(ds));
+        HIP_OR_ERR(y2h_stream_sync(ds));
         for (b = 0; b < net.batch; ++b) if (e->h_counts[b] > keep) keep = e->h_counts[b];
         if (keep > e->det_cap) keep = e->det_cap;
     }
@@ -360,10 +353,10 @@ fetch:
         for (b = 0; b < net.batch; ++b) {
             int nb = e->h_counts[b] < e->det_cap ? e->h_counts[b] : e->det_cap;
             if (nb > 0)
-                HIPCALL_I(y2h_memcpy_d2h(e->h_records + (size_t)b * e->det_cap * 6, e->d_records + (size_t)b * e->det_cap * 6,
+                HIP_OR_ERR(y2h_memcpy_d2h(e->h_records + (size_t)b * e->det_cap * 6, e->d_records + (size_t)b * e->det_cap * 6,
                                          (size_t)nb * 6 * sizeof(float), ds));
         }
-        HIPCALL_I(y2h_stream_sync(ds));
+        HIP_OR_ERR(y2h_stream_sync(ds));
     }
     e->det_pending = 2;                       /* wide heads (yolo9000): fetched synchronously above */
     return 0;
@@ -375,7 +368,7 @@ static int detect_fetch_items(network net, y2_det *dets, int *counts, int max_pe
     y2_engine *e = y2_engine_of(&net);
     int b, i;
     if (!e || !e->det_pending) { y2_fail("y2_detect_fetch: nothing was enqueued (call y2_detect_enqueue after a forward)"); return -1; }
-    if (e->det_pending == 1) HIPCALL_I(y2h_event_sync(e->ev_det));
+    if (e->det_pending == 1) HIP_OR_ERR(y2h_event_sync(e->ev_det));
     e->det_pending = 0;
     for (b = 0; b < items; ++b) {
         int nb = e->h_counts[b];
@@ -434,21 +427,21 @@ int y2_detect_mean(network net, float thresh, float nms, int img_w, int img_h, y
     y2_ldev *d;
     size_t els;
     if (!e || !e->built) { y2_fail("y2_detect_mean: run a forward first"); return -1; }
-    if (e->det_pending == 1 && e->det_overlap) HIPCALL_I(y2h_event_sync(e->ev_det));
+    if (e->det_pending == 1 && e->det_overlap) HIP_OR_ERR(y2h_event_sync(e->ev_det));
     l = &net.layers[e->out_layer];
     d = ld_of(l);
     if (l->type != REGION || net.batch != 1) { y2_fail("y2_detect_mean: needs a batch-1 network ending in a region layer"); return -1; }
-    HIPCALL_I(y2h_set_device(e->device));
+    HIP_OR_ERR(y2h_set_device(e->device));
     els = (size_t)l->outputs;
     if (!e->d_mean_ring || e->mean_els != els) {
         y2h_free(e->d_mean_ring); e->d_mean_ring = NULL;
-        HIPCALL_I(y2h_malloc((void **)&e->d_mean_ring, 4 * els * sizeof(float)));      /* 3 slots + the average */
-        HIPCALL_I(y2h_memset(e->d_mean_ring, 0, 4 * els * sizeof(float), e->stream));
+        HIP_OR_ERR(y2h_malloc((void **)&e->d_mean_ring, 4 * els * sizeof(float)));      /* 3 slots + the average */
+        HIP_OR_ERR(y2h_memset(e->d_mean_ring, 0, 4 * els * sizeof(float), e->stream));
         e->mean_els = els; e->mean_index = 0;
     }
-    HIPCALL_I(y2h_memcpy_d2d(e->d_mean_ring + (size_t)e->mean_index * els, d->d_region, els * sizeof(float), e->stream));
+    HIP_OR_ERR(y2h_memcpy_d2d(e->d_mean_ring + (size_t)e->mean_index * els, d->d_region, els * sizeof(float), e->stream));
     e->mean_index = (e->mean_index + 1) % 3;
-    HIPCALL_I(y2h_mean_frames(e->d_mean_ring, 3, (long)els, e->d_mean_ring + 3 * els, e->stream));
+    HIP_OR_ERR(y2h_mean_frames(e->d_mean_ring, 3, (long)els, e->d_mean_ring + 3 * els, e->stream));
     return detect_from(net, e->d_mean_ring + 3 * els, thresh, nms, img_w, img_h, dets, counts, max_per_image);
 }
 
@@ -458,7 +451,7 @@ int y2_detect(network net, float *input, float thresh, float nms, int img_w, int
     y2_engine *e;
     if (y2_prepare(&net) != 0) return -1;
     e = y2_engine_of(&net);
-    HIPCALL_I(y2h_memcpy_h2d(e->d_in_nchw, input, e->in_floats * sizeof(float), e->stream));
+    HIP_OR_ERR(y2h_memcpy_h2d(e->d_in_nchw, input, e->in_floats * sizeof(float), e->stream));
     if (y2_forward_device(net, e->d_in_nchw) != 0) return -1;
     return y2_detect_resident(net, thresh, nms, img_w, img_h, dets, counts, max_per_image);
 }
@@ -525,12 +518,12 @@ int y2_ingest_u8_device(network net, const unsigned char *d_frames, int h, int w
     if (c < net.c) { y2_fail("y2_ingest_u8: frames have %d channels, the network reads %d", c, net.c); return -1; }
     if (y2_prepare(&net) != 0) return -1;
     e = y2_engine_of(&net);
-    HIPCALL_I(y2h_set_device(e->device));
+    HIP_OR_ERR(y2h_set_device(e->device));
     planes = net.c;                       /* a 4th (alpha) plane is never read by the network (detector.c:567) */
     frame_bytes = (size_t)step * h;
     nplanes = (size_t)net.batch * planes * h * w;
     if (w == net.w && h == net.h) {
-        HIPCALL_I(y2h_u8_to_planes(d_frames, net.batch, h, w, c, step, (long)frame_bytes, planes, swap_rb, e->d_in_nchw, e->stream));
+        HIP_OR_ERR(y2h_u8_to_planes(d_frames, net.batch, h, w, c, step, (long)frame_bytes, planes, swap_rb, e->d_in_nchw, e->stream));
         return 0;
     }
     if (letterbox) y2h_letterbox_dims(w, h, net.w, net.h, &nw, &nh);
@@ -539,10 +532,10 @@ int y2_ingest_u8_device(network net, const unsigned char *d_frames, int h, int w
     if (grow((void **)&e->d_planes, &e->planes_cap, nplanes * 4) || grow((void **)&e->d_rtmp, &e->rtmp_cap, ntmp * 4)) {
         y2_fail("y2_ingest_u8: %s", y2h_last_error()); return -1;
     }
-    HIPCALL_I(y2h_u8_to_planes(d_frames, net.batch, h, w, c, step, (long)frame_bytes, planes, swap_rb, e->d_planes, e->stream));
+    HIP_OR_ERR(y2h_u8_to_planes(d_frames, net.batch, h, w, c, step, (long)frame_bytes, planes, swap_rb, e->d_planes, e->stream));
     /* planes are independent in resize/embed, so the whole batch goes through as batch*planes planes */
-    if (letterbox) HIPCALL_I(y2h_letterbox_chw(e->d_planes, net.batch * planes, h, w, e->d_rtmp, e->d_in_nchw, net.h, net.w, e->stream));
-    else HIPCALL_I(y2h_resize_chw(e->d_planes, net.batch * planes, h, w, e->d_rtmp, e->d_in_nchw, net.h, net.w, e->stream));
+    if (letterbox) HIP_OR_ERR(y2h_letterbox_chw(e->d_planes, net.batch * planes, h, w, e->d_rtmp, e->d_in_nchw, net.h, net.w, e->stream));
+    else HIP_OR_ERR(y2h_resize_chw(e->d_planes, net.batch * planes, h, w, e->d_rtmp, e->d_in_nchw, net.h, net.w, e->stream));
     return 0;
 }
 
@@ -553,10 +546,10 @@ int y2_ingest_u8(network net, const unsigned char *frames, int h, int w, int c, 
     if (!frames || h <= 0 || w <= 0 || c <= 0 || step < w * c) { y2_fail("y2_ingest_u8: bad frame geometry"); return -1; }
     if (y2_prepare(&net) != 0) return -1;
     e = y2_engine_of(&net);
-    HIPCALL_I(y2h_set_device(e->device));
+    HIP_OR_ERR(y2h_set_device(e->device));
     frame_bytes = (size_t)step * h;
     if (grow((void **)&e->d_u8, &e->u8_cap, frame_bytes * net.batch)) { y2_fail("y2_ingest_u8: %s", y2h_last_error()); return -1; }
-    HIPCALL_I(y2h_memcpy_h2d(e->d_u8, frames, frame_bytes * net.batch, e->stream));
+    HIP_OR_ERR(y2h_memcpy_h2d(e->d_u8, frames, frame_bytes * net.batch, e->stream));
     return y2_ingest_u8_device(net, e->d_u8, h, w, c, step, swap_rb, letterbox);
 }
 
@@ -572,17 +565,17 @@ int y2_ingest_image(network net, image im)
     if (net.batch != 1) { y2_fail("y2_ingest_image: set_batch_network(&net, 1) first"); return -1; }
     if (y2_prepare(&net) != 0) return -1;
     e = y2_engine_of(&net);
-    HIPCALL_I(y2h_set_device(e->device));
+    HIP_OR_ERR(y2h_set_device(e->device));
     if (im.w == net.w && im.h == net.h) {
-        HIPCALL_I(y2h_memcpy_h2d(e->d_in_nchw, im.data, plane * net.c * sizeof(float), e->stream));
+        HIP_OR_ERR(y2h_memcpy_h2d(e->d_in_nchw, im.data, plane * net.c * sizeof(float), e->stream));
         return 0;
     }
     ntmp = (size_t)net.c * im.h * net.w;
     if (grow((void **)&e->d_planes, &e->planes_cap, plane * net.c * 4) || grow((void **)&e->d_rtmp, &e->rtmp_cap, ntmp * 4)) {
         y2_fail("y2_ingest_image: %s", y2h_last_error()); return -1;
     }
-    HIPCALL_I(y2h_memcpy_h2d(e->d_planes, im.data, plane * net.c * sizeof(float), e->stream));
-    HIPCALL_I(y2h_resize_chw(e->d_planes, net.c, im.h, im.w, e->d_rtmp, e->d_in_nchw, net.h, net.w, e->stream));
+    HIP_OR_ERR(y2h_memcpy_h2d(e->d_planes, im.data, plane * net.c * sizeof(float), e->stream));
+    HIP_OR_ERR(y2h_resize_chw(e->d_planes, net.c, im.h, im.w, e->d_rtmp, e->d_in_nchw, net.h, net.w, e->stream));
     return 0;
 }
 
@@ -682,7 +675,7 @@ static int ingest_regions(const char *who, network net, const y2_region *items, 
     if (regions_check(who, net, items, n, letterbox) != 0) return -1;
     if (y2_prepare(&net) != 0) return -1;
     e = y2_engine_of(&net);
-    HIPCALL_I(y2h_set_device(e->device));
+    HIP_OR_ERR(y2h_set_device(e->device));
     desc_bytes = ((size_t)n * sizeof(y2h_region) + 63) & ~(size_t)63;
     for (i = 0; i < n; ++i) {
         int x, y, rw, rh;
@@ -691,14 +684,14 @@ static int ingest_regions(const char *who, network net, const y2_region *items, 
     }
     need = desc_bytes + pix_bytes;
     /* the last call's upload may still be reading the pinned buffer */
-    if (e->reg_pending) { HIPCALL_I(y2h_event_sync(e->ev_reg)); e->reg_pending = 0; }
+    if (e->reg_pending) { HIP_OR_ERR(y2h_event_sync(e->ev_reg)); e->reg_pending = 0; }
     if (need > e->reg_stage_cap) {
         y2h_host_free(e->h_reg_stage); e->h_reg_stage = NULL; e->reg_stage_cap = 0;
-        HIPCALL_I(y2h_host_alloc((void **)&e->h_reg_stage, need));
+        HIP_OR_ERR(y2h_host_alloc((void **)&e->h_reg_stage, need));
         e->reg_stage_cap = need;
     }
     if (grow((void **)&e->d_reg, &e->reg_cap, need)) { y2_fail("%s: %s", who, y2h_last_error()); return -1; }
-    if (!e->ev_reg) HIPCALL_I(y2h_event_create(&e->ev_reg));
+    if (!e->ev_reg) HIP_OR_ERR(y2h_event_create(&e->ev_reg));
     desc = (y2h_region *)e->h_reg_stage;
     memset(desc, 0, desc_bytes);
     off = 0;
@@ -722,10 +715,10 @@ static int ingest_regions(const char *who, network net, const y2_region *items, 
             memcpy(e->h_reg_stage + desc_bytes + off + (size_t)r * row, it->data + (size_t)(y + r) * it->step + (size_t)x * it->c, row);
         off += row * rh;
     }
-    HIPCALL_I(y2h_memcpy_h2d(e->d_reg, e->h_reg_stage, need, e->stream));
-    HIPCALL_I(y2h_event_record(e->ev_reg, e->stream));
+    HIP_OR_ERR(y2h_memcpy_h2d(e->d_reg, e->h_reg_stage, need, e->stream));
+    HIP_OR_ERR(y2h_event_record(e->ev_reg, e->stream));
     e->reg_pending = 1;
-    HIPCALL_I(y2h_regions_to_input((const y2h_region *)e->d_reg, n, e->d_reg + desc_bytes, net.batch, net.c, swap_rb, net.h, net.w,
+    HIP_OR_ERR(y2h_regions_to_input((const y2h_region *)e->d_reg, n, e->d_reg + desc_bytes, net.batch, net.c, swap_rb, net.h, net.w,
                                    e->d_in_nchw, e->stream));
     return 0;
 }

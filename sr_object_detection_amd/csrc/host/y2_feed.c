@@ -19,8 +19,6 @@
 #include <string.h>
 #include "y2_internal.h"
 
-#define HIPCALL_I(expr) do { int rc_ = (expr); if (rc_ != 0) { y2_fail("%s failed (%d): %s", #expr, rc_, y2h_last_error()); return -1; } } while (0)
-
 void y2_feed_close(network *net)
 {
     y2_engine *e = y2_engine_of(net);
@@ -49,7 +47,7 @@ int y2_feed_open(network *net, int slots, size_t slot_bytes)
     if (y2_prepare(net) != 0) return -1;
     e = y2_engine_of(net);
     y2_feed_close(net);
-    HIPCALL_I(y2h_set_device(e->device));
+    HIP_OR_ERR(y2h_set_device(e->device));
     if (!slot_bytes) slot_bytes = e->in_floats * sizeof(float);
     e->feed_host = calloc(slots, sizeof(void *)); e->feed_dev = calloc(slots, sizeof(void *));
     e->feed_up = calloc(slots, sizeof(y2h_event)); e->feed_done = calloc(slots, sizeof(y2h_event));
@@ -61,12 +59,12 @@ int y2_feed_open(network *net, int slots, size_t slot_bytes)
         return -1;
     }
     e->feed_slots = slots; e->feed_bytes = slot_bytes;
-    HIPCALL_I(y2h_stream_create(&e->feed_stream));
+    HIP_OR_ERR(y2h_stream_create(&e->feed_stream));
     for (i = 0; i < slots; ++i) {
-        HIPCALL_I(y2h_host_alloc(&e->feed_host[i], slot_bytes));
-        HIPCALL_I(y2h_malloc(&e->feed_dev[i], slot_bytes));
-        HIPCALL_I(y2h_event_create(&e->feed_up[i]));
-        HIPCALL_I(y2h_event_create(&e->feed_done[i]));
+        HIP_OR_ERR(y2h_host_alloc(&e->feed_host[i], slot_bytes));
+        HIP_OR_ERR(y2h_malloc(&e->feed_dev[i], slot_bytes));
+        HIP_OR_ERR(y2h_event_create(&e->feed_up[i]));
+        HIP_OR_ERR(y2h_event_create(&e->feed_done[i]));
     }
     return 0;
 }
@@ -99,11 +97,11 @@ int y2_feed_submit(network net, int slot, size_t bytes)
     if (!e) return -1;
     if (!bytes) bytes = e->feed_bytes;
     if (bytes > e->feed_bytes) { y2_fail("y2_feed_submit: %zu bytes into a %zu-byte slot", bytes, e->feed_bytes); return -1; }
-    HIPCALL_I(y2h_set_device(e->device));
+    HIP_OR_ERR(y2h_set_device(e->device));
     /* the HBM copy of this slot may still be read by the forward that was fed from it */
-    if (e->feed_used[slot]) HIPCALL_I(y2h_stream_wait_event(e->feed_stream, e->feed_done[slot]));
-    HIPCALL_I(y2h_memcpy_h2d(e->feed_dev[slot], e->feed_host[slot], bytes, e->feed_stream));
-    HIPCALL_I(y2h_event_record(e->feed_up[slot], e->feed_stream));
+    if (e->feed_used[slot]) HIP_OR_ERR(y2h_stream_wait_event(e->feed_stream, e->feed_done[slot]));
+    HIP_OR_ERR(y2h_memcpy_h2d(e->feed_dev[slot], e->feed_host[slot], bytes, e->feed_stream));
+    HIP_OR_ERR(y2h_event_record(e->feed_up[slot], e->feed_stream));
     return 0;
 }
 
@@ -111,7 +109,7 @@ int y2_feed_wait_host(network net, int slot)
 {
     y2_engine *e = feed_of(&net, slot, "y2_feed_wait_host");
     if (!e) return -1;
-    HIPCALL_I(y2h_event_sync(e->feed_up[slot]));
+    HIP_OR_ERR(y2h_event_sync(e->feed_up[slot]));
     return 0;
 }
 
@@ -120,10 +118,10 @@ int y2_feed_forward(network net, int slot)
     y2_engine *e = feed_of(&net, slot, "y2_feed_forward");
     if (!e) return -1;
     if (e->feed_bytes < e->in_floats * sizeof(float)) { y2_fail("y2_feed_forward: the slots hold %zu bytes, a float batch needs %zu", e->feed_bytes, e->in_floats * sizeof(float)); return -1; }
-    HIPCALL_I(y2h_set_device(e->device));
-    HIPCALL_I(y2h_stream_wait_event(e->stream, e->feed_up[slot]));
+    HIP_OR_ERR(y2h_set_device(e->device));
+    HIP_OR_ERR(y2h_stream_wait_event(e->stream, e->feed_up[slot]));
     if (y2_forward_device(net, (const float *)e->feed_dev[slot]) != 0) return -1;
-    HIPCALL_I(y2h_event_record(e->feed_done[slot], e->stream));
+    HIP_OR_ERR(y2h_event_record(e->feed_done[slot], e->stream));
     e->feed_used[slot] = 1;
     return 0;
 }
@@ -133,11 +131,11 @@ int y2_feed_forward_u8(network net, int slot, int h, int w, int c, int step, int
     y2_engine *e = feed_of(&net, slot, "y2_feed_forward_u8");
     if (!e) return -1;
     if (h <= 0 || step <= 0 || (size_t)step * h * net.batch > e->feed_bytes) { y2_fail("y2_feed_forward_u8: %d frames of %d x %d bytes do not fit a %zu-byte slot", net.batch, h, step, e->feed_bytes); return -1; }
-    HIPCALL_I(y2h_set_device(e->device));
-    HIPCALL_I(y2h_stream_wait_event(e->stream, e->feed_up[slot]));
+    HIP_OR_ERR(y2h_set_device(e->device));
+    HIP_OR_ERR(y2h_stream_wait_event(e->stream, e->feed_up[slot]));
     if (y2_ingest_u8_device(net, (const unsigned char *)e->feed_dev[slot], h, w, c, step, swap_rb, letterbox) != 0) return -1;
     /* the conversion kernels have read the slot once they are done: the forward itself reads the network's own input buffer */
-    HIPCALL_I(y2h_event_record(e->feed_done[slot], e->stream));
+    HIP_OR_ERR(y2h_event_record(e->feed_done[slot], e->stream));
     e->feed_used[slot] = 1;
     return y2_forward_device(net, NULL);
 }

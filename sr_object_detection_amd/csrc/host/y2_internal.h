@@ -47,7 +47,7 @@ typedef struct y2_ldev {
     const char *kernel;        /* name for profiles */
     /* [rnn] / [gru]: the sub-layers packed into the arena as three dense blocks, [n][k] weights each
      * (rnn: input, self, output; gru: input z|r|h stacked by rows, state z|r, state h); `form` is the Y2_REC_* the block
-     * runs in, decided once per plan (y2_engine.c rec_form) */
+     * runs in, decided once per plan (y2_rec.c rec_form) */
     struct { size_t off_w, off_bias, off_mean, off_scale, off_rinv; int n, k, bn; ACTIVATION act; int form; } rd[3];
     float *d_state;            /* [B][hidden]: persists across forwards; zeroed at plan build and by reset_rnn_state */
     float *d_proj;             /* [T*B][hidden | 3*outputs]: every step's input projections, one GEMM per forward */
@@ -56,7 +56,7 @@ typedef struct y2_ldev {
     float *d_tmp;              /* matrix-core step form: the step's dense values, [B][2*outputs] */
 } y2_ldev;
 
-/* how a recurrent layer's dense products run (y2_engine.c rec_form) */
+/* how a recurrent layer's dense products run (y2_rec.c rec_form) */
 enum { Y2_REC_REF = 0, Y2_REC_SKINNY = 1, Y2_REC_MFMA = 2 };
 
 typedef struct y2_engine {
@@ -67,10 +67,9 @@ typedef struct y2_engine {
     int fusion, built_fusion;  /* conv+maxpool fusion enabled / state of the current plan */
     int half, built_half;      /* fp16 storage requested (y2_set_half) / state of the current plan */
     int autotune, built_autotune; /* measure the conv tile shapes at plan time (y2_set_autotune) */
-    int in_halo;               /* the NHWC copy of the input carries a zero border (2: the half NHWC4 form; 3: no copy at all,
-                                  the fp16 first layer reads the fp32 NCHW input) */
-    const float *cur_input;    /* the NCHW input of the forward pass being enqueued (in_halo 3) */
-    int in_halo_px;            /* its width in pixels: 1 for the 3x3 first-layer kernels, the padding for the stem kernel */
+    int in_form;               /* Y2_IN_*: how the network input reaches layer 0 (y2_plan.c choose_input_form) */
+    const float *cur_input;    /* the NCHW input of the forward pass being enqueued (Y2_IN_NCHW, a flat recurrent input) */
+    int in_halo_px;            /* the border's width in pixels: 1 for the 3x3 first-layer kernels, the padding for the stem kernel */
     /* hipGraph replay of the forward launch sequence (y2_set_graph): recorded for one input pointer, dropped with the plan */
     y2h_event ev_out;          /* recorded behind the output copy of y2_output_enqueue */
     int out_pending;
@@ -95,6 +94,7 @@ typedef struct y2_engine {
     /* weight arena */
     unsigned char *arena;
     size_t arena_bytes;
+    size_t arena_need;         /* bytes the layout of the plan being built asks for (y2_arena_layout) */
     int arena_pending;         /* the arena was laid out for a fill from outside (y2_weights_arena) that has not happened yet */
     int class_counts_zeroed;   /* d_class_counts is all zero (the three-launch detect chain keeps it so) */
     int capturing;             /* inside the hipGraph capture of a forward pass (no cross-stream waits may be recorded) */
@@ -150,21 +150,71 @@ typedef struct y2_engine {
     int n_layers;
 } y2_engine;
 
+/* How the network input (fp32 NCHW) reaches layer 0: a plain NHWC copy; an NHWC copy with a zero border of in_halo_px
+ * pixels (no tap bounds tests in the first-layer / stem kernels); a half [b][h+2][w+2][4] copy for the fp16 first-layer
+ * kernel; or no copy at all, the first-layer kernel reads the NCHW planes itself. */
+enum { Y2_IN_NHWC = 0, Y2_IN_NHWC_HALO = 1, Y2_IN_NHWC4_HALO_F16 = 2, Y2_IN_NCHW = 3 };
+/* what each form means for layer 0's descriptor and for the engine's NHWC input buffer (y2_plan.c y2_input_form) */
+typedef struct { size_t floats; int ldx, x_halo, x_f16, x_nchw; } y2_in_form;
+
 /* error handling: mode 0 = the reference's contract (message + exit), 1 = record and return */
 void y2_fail(const char *fmt, ...);
 int y2_error_mode(void);
 int y2_failed(void);           /* and clear */
 
-/* engine */
+/* call, report a failure, and then: return -1 / return / release scratch buffers at `cleanup:` */
+#define HIPCALL(expr, text, onfail) do { int rc_ = (expr); if (rc_ != 0) { y2_fail("%s failed (%d): %s", text, rc_, y2h_last_error()); onfail; } } while (0)
+#define HIP_OR_ERR(expr) HIPCALL(expr, #expr, return -1)
+#define HIP_OR_RET(expr) HIPCALL(expr, #expr, return)
+#define HIP_OR_CLEANUP(expr) HIPCALL(expr, #expr, goto cleanup)
+
+/* a 256-byte aligned pointer that stands in for arena / buffer addresses in shape queries made before they exist */
+#define Y2_ALIGNED_STANDIN ((float *)(uintptr_t)256)
+
+static inline y2_ldev *ld_of(const layer *l) { return (y2_ldev *)l->dev; }
+static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+static inline int is_recurrent(const layer *l) { return l->type == RNN || l->type == GRU; }
+
+/* engine (y2_engine.c) */
 y2_engine *y2_engine_of(const network *net);
 int y2_engine_create(network *net);
 void y2_engine_destroy(network *net);
 void y2_engine_invalidate(network *net);
 void y2_engine_host_output(network *net);
-int y2_engine_build(network *net);
+void y2_drop_graphs(y2_engine *e);
+int y2_enqueue_forward(network *net, const float *d_input_nchw);
+int y2_activate_after(y2_engine *e, ACTIVATION a, float *y, int ld, long rows, int n);
 int y2_engine_forward(network *net, const float *d_input_nchw);
 int y2_engine_fetch_output(network *net);
 int y2_ingest_u8_device(network net, const unsigned char *d_frames, int h, int w, int c, int step, int swap_rb, int letterbox);
+
+/* plan (y2_plan.c) */
+int y2_engine_build(network *net);
+void y2_free_plan(network *net);
+int y2_act_code(ACTIVATION a);
+int y2_act_in_kernel(ACTIVATION a);
+int y2_act_for_kernel(ACTIVATION a);
+int y2_flat_input(const network *net);
+int y2_producer_of(const network *net, int i);
+int y2_is_flat(const network *net, int i);
+void y2_input_form(const network *net, y2_in_form *f);
+void y2_input_view(const network *net, int i, const float **x, int *ldx);
+void y2_conv_desc(const network *net, int i, y2h_conv *c, const float *x, int ldx);
+
+/* weight arena (y2_arena.c) */
+void y2_bn_slots(size_t *off, int n, size_t *mean, size_t *scale, size_t *rinv);
+void y2_fill_rinv(double *dst, const float *var, int n);
+void y2_arena_layout(network *net);
+int y2_arena_commit(network *net);
+int y2_upload_weights(network *net);
+
+/* [rnn] / [gru] (y2_rec.c) */
+int y2_rec_hidden(const layer *l);
+int y2_rec_plan(network *net, int i);
+size_t y2_rec_layout(y2_ldev *d, const layer *l, size_t off);
+void y2_rec_pack(unsigned char *host, const y2_ldev *d, const layer *l);
+size_t y2_rec_workspace_bytes(const network *net);
+int y2_rec_forward(network *net, int i, const float *x);
 
 /* cfg helpers shared with other files */
 char *y2_fgetl(FILE *fp);

@@ -12,7 +12,7 @@
  *
  * The arrays read here are the HOST copies in the reference's layout; the
  * engine re-packs them into the kernel layout and uploads them at the next
- * predict (y2_engine.c upload_weights).
+ * predict (y2_arena.c y2_upload_weights).
  */
 #include <math.h>
 #include <stdio.h>

@@ -8,13 +8,21 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$(mktemp -d)
 C=$ROOT/sr_object_detection_amd/csrc
 SAN="-fsanitize=address,undefined -fno-omit-frame-pointer -O1 -g -fPIC"
-g++ $SAN -std=c++17 -c $C/y2_imgfile.cpp -o $OUT/y2_imgfile.o
-for f in y2_cfg y2_weights y2_engine y2_detect y2_eval y2_comm y2_feed; do
+# Host sources are every host/*.c and every *.cpp; the device objects are whatever else the Makefile built, so a
+# new source file is picked up on either side without touching this script.
+HOST=$(cd $C/host && ls *.c | sed 's/\.c$//')
+CXX_SRC=$(cd $C && ls *.cpp | sed 's/\.cpp$//')
+for f in $HOST; do
     gcc $SAN -ffp-contract=off -std=gnu11 -I$ROOT/include -I$C/host -c $C/host/$f.c -o $OUT/$f.o
 done
-g++ $SAN -std=c++17 -I$ROOT/include -I$C/host -c $C/yolo_v2_class.cpp -o $OUT/yolo_v2_class.o
-g++ -shared -fPIC -fsanitize=address,undefined -o $OUT/libsr_yolo2.so $C/build/y2_runtime.o $C/build/y2_conv.o $C/build/y2_conv_f16.o \
-    $C/build/y2_layers.o $C/build/y2_layers_f16.o $C/build/y2_detect_dev.o $C/build/y2_image.o $OUT/*.o -L/opt/rocm/lib -lamdhip64 -lm -lstdc++ -ldl
+for f in $CXX_SRC; do
+    g++ $SAN -std=c++17 -I$ROOT/include -I$C/host -c $C/$f.cpp -o $OUT/$f.o
+done
+DEV=""
+for o in $C/build/*.o; do
+    case " $(echo $HOST $CXX_SRC) " in *" $(basename $o .o) "*) ;; *) DEV="$DEV $o" ;; esac
+done
+g++ -shared -fPIC -fsanitize=address,undefined -Wl,--no-undefined -o $OUT/libsr_yolo2.so $DEV $OUT/*.o -L/opt/rocm/lib -lamdhip64 -lm -lstdc++ -ldl
 cp $ROOT/oracle/liby2oracle.so $OUT/liby2oracle.orig
 trap 'cp $OUT/liby2oracle.orig $ROOT/oracle/liby2oracle.so; touch $ROOT/oracle/liby2oracle.so' EXIT
 gcc $SAN -fopenmp -ffp-contract=off -shared -o $ROOT/oracle/liby2oracle.so $ROOT/oracle/y2_oracle.c -lm
