@@ -196,6 +196,43 @@ float *get_network_output(network net);                          /* network.c:17
  * and nothing else touches it: every forward (network_predict, y2_forward_device, y2_feed_forward, a graph replay)
  * starts from the state the previous one left.  Runs on the engine stream, ordered with the forwards. */
 void reset_rnn_state(network net, int b);
+
+/* ---- text generation and scoring with [rnn] / [gru] networks (rnn.c) ----
+ * The reference's entry points, and the y2_rnn_* calls they are written on.  The per-character loop runs on the device:
+ * the sampled character becomes the next input row without leaving HBM, and the characters of one call are enqueued
+ * with no host sync in between.  Tokens are step-major like the rows: [step][B], B = net.batch / time_steps sequences.
+ * Refused with a message: a network without a recurrent layer, time_steps > 1 for generation, outputs < inputs, a seed
+ * or text token outside [0, inputs) (a negative `char` included).  Strict mode, y2_set_graph and y2_set_timing work as
+ * for network_predict. */
+/* rnn.c:225: srand(rseed); the temperature on every layer; the first len-1 seed characters are predicted and printed,
+ * the last one is the first generating input (an empty seed starts from token 0); num characters by the rule of
+ * rnn.c:273-276 / sample_array (utils.c:520), printed "%c" or, with a token file, "%s ", then a newline.  The reference
+ * draws its uniforms from a rand() stream that parse_network_cfg's weight initialisers (connected_layer.c) have
+ * advanced; nothing is drawn at parse time here, so draw i uses the i-th value after srand(rseed). */
+void test_char_rnn(char *cfgfile, char *weightfile, int num, char *seed, float temp, int rseed, char *token_file);
+/* rnn.c:379: the seed is predicted, then the text on stdin is scored: per character the line of rnn.c:416 */
+void valid_char_rnn(char *cfgfile, char *weightfile, char *seed);
+/* rnn.c:420: per line on stdin: reset_rnn_state(net, 0), the seed, the line, a space; prints the line and ",%g" per value
+ * of layer 0's output */
+void vec_char_rnn(char *cfgfile, char *weightfile, char *seed);
+char **read_tokens(char *filename, size_t *read);                /* rnn.c:39: one token per line */
+/* srand(rseed), then u[i] = rand_uniform(0, 1) (utils.c:603-610: (float)rand() / RAND_MAX in float) for i < n: the
+ * reference's generator (libc rand) and so its stream. */
+int y2_rnn_uniforms(int rseed, int n, float *u);
+/* Generate num characters on each of the B sequences, from the network's current state and temperature: the first
+ * seed_len-1 rows of seed ([seed_len][B]) are predicted, the last is the first input (seed_len 0: token 0); draw i of
+ * sequence b uses uniforms[i*B+b] and lands in tokens[i*B+b]; probs (or NULL) receives the row each draw sampled from,
+ * [num][B][outputs].  n of the rule is the network's input size.  One sync, at the end; the state afterwards is the one
+ * num-1+seed_len forwards leave, and a call seeded with the last row of tokens goes on where this one stopped. */
+int y2_rnn_generate(network net, const int *seed, int seed_len, int num, const float *uniforms, int *tokens, float *probs);
+/* Teacher-forced scoring of tokens ([n][B]): p_next[t*B+b] is the probability the network gave to tokens[t+1][b] after
+ * reading tokens[0..t][b], for t < n-1; probs (or NULL) receives the rows, [n-1][B][outputs].  With time_steps T one
+ * forward scores T characters per sequence; n-1 must be a multiple of T.  The state carries on across calls. */
+int y2_rnn_score(network net, const int *tokens, int n, float *p_next, float *probs);
+/* valid_char_rnn's books (rnn.c:402-416) over a text of n characters and the n-1 values y2_rnn_score gave for it: a float
+ * sum of log(p)/(float)log(2), words counted on ' ', '\n', '\t' of the following character; the two values of :416
+ * as floats (+inf where 2^(-sum/words) is beyond a float). */
+int y2_rnn_perplexity(const float *p_next, const unsigned char *text, int n, float *perplexity, float *word_perplexity);
 float *get_network_output_gpu(network net);                      /* network_kernels.cu:385 */
 int get_network_output_size(network net);                        /* network.c:390 */
 int get_network_input_size(network net);                         /* network.c:397 */

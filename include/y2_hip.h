@@ -77,6 +77,7 @@ int         y2h_host_register(void *ptr, size_t bytes);
 int         y2h_host_unregister(void *ptr);
 int         y2h_memcpy_h2d(void *dst, const void *src, size_t bytes, y2h_stream s);
 int         y2h_memcpy_d2h(void *dst, const void *src, size_t bytes, y2h_stream s);
+unsigned long y2h_d2h_copies(void);      /* y2h_memcpy_d2h calls of this process that moved bytes */
 int         y2h_memcpy_d2d(void *dst, const void *src, size_t bytes, y2h_stream s);
 int         y2h_memset(void *dst, int value, size_t bytes, y2h_stream s);
 int         y2h_stream_create(y2h_stream *s);
@@ -420,6 +421,22 @@ typedef struct {
 } y2h_rec_args;
 int y2h_rec_skinny_ok(int rows, int k);
 int y2h_rec_step(const y2h_rec_args *a, int form, y2h_stream s);
+
+/* ---- character generation and scoring on [rnn] / [gru] networks (y2_recurrent.hip) ----
+ * y2h_rnn_sample: one workgroup per sequence b < seqs draws the next character from row b of `out` ([seqs][outputs], read
+ *   only) by the rule of test_char_rnn (rnn.c:273-276) and sample_array (utils.c:520-531) over the first n values
+ *   (n <= outputs, n <= 16384): a value < .0001 (compared in double) counts as 0; the fp32 sum ascending from 0; every
+ *   value times (float)(1. / sum); r = u[b], r = r - a[i] ascending, the first i with r <= 0, else n - 1.  It writes
+ *   next[b] = i and moves the 1 of input row b (x: [seqs][n]) from column prev[b] to column i.  probs (if set) receives
+ *   the rows as they are, [seqs][outputs].
+ * y2h_rnn_feed: x[r][j] = (tok[r] == j) for r < rows -- the one-hot input rows of one forward, step-major like tok.
+ * y2h_rnn_score: p_next[r] = out[r][next[r]] for r < rows; probs (if set) receives the rows, [rows][outputs].
+ * Tokens must lie in [0, inputs) / [0, outputs): the callers check them on the host. */
+int y2h_rnn_sample(const float *out, int outputs, int n, int seqs, const float *u, const int *prev, int *next, float *x,
+                   float *probs, y2h_stream s);
+int y2h_rnn_feed(const int *tok, float *x, int rows, int inputs, y2h_stream s);
+int y2h_rnn_score(const float *out, int outputs, const int *next, int rows, float *p_next, float *probs, y2h_stream s);
+unsigned long y2h_rnn_sample_launches(void);     /* y2h_rnn_sample launches of this process */
 
 #ifdef __cplusplus
 }

@@ -118,6 +118,7 @@ void y2_engine_destroy(network *net)
         net->layers[i].dev = NULL;
     }
     y2h_free(e->arena);
+    y2_chargen_free(e);
     y2h_host_free(e->h_out_stage);
     y2h_host_free(e->h_reg_stage);
     if (e->ev_reg) y2h_event_destroy(e->ev_reg);

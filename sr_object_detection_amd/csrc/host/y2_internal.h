@@ -144,6 +144,11 @@ typedef struct y2_engine {
     y2h_event *feed_up, *feed_done;    /* per slot: H2D finished / the forward that read the device copy was enqueued and ran */
     int *feed_used;                    /* per slot: feed_done has been recorded at least once */
     y2h_stream feed_stream;            /* copies run here, next to the engine stream's kernels */
+    /* text generation / scoring (y2_chargen.c), grow-only: tokens [steps][B], one uniform per draw, one probability per
+     * scored row, the rows a caller asked to see */
+    int *d_gen_tok;
+    float *d_gen_u, *d_gen_p, *d_gen_probs;
+    size_t gen_tok_cap, gen_u_cap, gen_p_cap, gen_probs_cap;
     /* timing */
     y2h_event *ev;             /* n+1 events */
     int n_ev;
@@ -215,6 +220,9 @@ size_t y2_rec_layout(y2_ldev *d, const layer *l, size_t off);
 void y2_rec_pack(unsigned char *host, const y2_ldev *d, const layer *l);
 size_t y2_rec_workspace_bytes(const network *net);
 int y2_rec_forward(network *net, int i, const float *x);
+
+/* text generation / scoring (y2_chargen.c) */
+void y2_chargen_free(y2_engine *e);
 
 /* cfg helpers shared with other files */
 char *y2_fgetl(FILE *fp);

@@ -162,6 +162,76 @@ hipError_t launch_skinny(const y2h_rec_args &a, hipStream_t s)
     return hipSuccess;
 }
 
+// ---- character generation and scoring (include/y2_hip.h y2h_rnn_*) ----
+// The per-character loop of test_char_rnn (rnn.c:266-278) without a host round trip: the sampled character becomes the
+// next input row in HBM.  All three kernels are latency-bound; none waits on another workgroup.
+
+// One workgroup per sequence b: rnn.c:273-275 (threshold) and sample_array (utils.c:520-531) on row b of the network's
+// output.  The workgroup thresholds the row into LDS; the two ordered fp32 reductions -- sum_array's ascending sum from 0
+// (utils.c:407) and the running subtraction that decides the index -- are then walked by one thread in the reference's
+// order, eight values per LDS round trip (the walk is what this kernel costs: a dependent chain of n adds and n
+// subtractions).  scale_array's product a[i] * s is formed where the subtraction reads it: the same fp32 product, rounded
+// on its own (-ffp-contract=off).  The row itself is only read; `probs`, if set, gets it as the network produced it.
+#define Y2_DRAW(val, idx) do { r = r - (val) * s; if (c < 0 && r <= 0) c = (idx); } while (0)
+__global__ __launch_bounds__(256) void rec_sample_kernel(const float *out, int ld, int n, const float *u, const int *prev,
+                                                         int *next, float *x, float *probs)
+{
+    extern __shared__ float4 sv4[];
+    float *sv = (float *)sv4;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float *row = out + (size_t)b * ld;
+    for (int i = tid; i < n; i += 256) {
+        const float v = row[i];
+        sv[i] = ((double)v < .0001) ? 0.f : v;              // rnn.c:274, compared in double
+    }
+    if (probs)
+        for (int i = tid; i < ld; i += 256) probs[(size_t)b * ld + i] = row[i];
+    __syncthreads();
+    if (tid != 0) return;
+    float sum = 0;
+    int i = 0;
+    for (; i + 8 <= n; i += 8) {
+        const float4 p = sv4[i >> 2], q = sv4[(i >> 2) + 1];
+        sum += p.x; sum += p.y; sum += p.z; sum += p.w;
+        sum += q.x; sum += q.y; sum += q.z; sum += q.w;
+    }
+    for (; i < n; ++i) sum += sv[i];
+    const float s = (float)(1. / sum);                      // scale_array's float argument: the divide in double
+    float r = u[b];
+    int c = -1;                                             // the first i with r <= 0; later subtractions do not move it
+    for (i = 0; i + 8 <= n && c < 0; i += 8) {
+        const float4 p = sv4[i >> 2], q = sv4[(i >> 2) + 1];
+        Y2_DRAW(p.x, i); Y2_DRAW(p.y, i + 1); Y2_DRAW(p.z, i + 2); Y2_DRAW(p.w, i + 3);
+        Y2_DRAW(q.x, i + 4); Y2_DRAW(q.y, i + 5); Y2_DRAW(q.z, i + 6); Y2_DRAW(q.w, i + 7);
+    }
+    for (; i < n && c < 0; ++i) Y2_DRAW(sv[i], i);
+    if (c < 0) c = n - 1;                                   // nothing qualifies (a zero or NaN sum too): utils.c:530
+    x[(size_t)b * n + prev[b]] = 0.f;                       // rnn.c:269, 267: the one-hot row, in place
+    x[(size_t)b * n + c] = 1.f;
+    next[b] = c;
+}
+#undef Y2_DRAW
+
+// x[r][j] = (tok[r] == j): the one-hot input rows of one forward, step-major like tok
+__global__ __launch_bounds__(256) void rec_feed_kernel(const int *tok, float *x, int rows, int inputs)
+{
+    const long total = (long)rows * inputs;
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const int r = (int)(idx / inputs), j = (int)(idx - (long)r * inputs);
+        x[idx] = (tok[r] == j) ? 1.f : 0.f;
+    }
+}
+
+// p_next[r] = out[r][next[r]] (rnn.c:414 reads out[next]); probs, if set, gets every row
+__global__ __launch_bounds__(256) void rec_score_kernel(const float *out, int ld, const int *next, int rows, float *p_next, float *probs)
+{
+    const long total = probs ? (long)rows * ld : rows;
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        if (idx < rows) p_next[idx] = out[idx * ld + next[idx]];
+        if (probs) probs[idx] = out[idx];
+    }
+}
+
 }  // namespace
 
 // rows bounded by the accumulators a lane keeps (16 rows spill scalar registers), the staged rows by 64 KB of LDS
@@ -191,6 +261,38 @@ extern "C" int y2h_rec_step(const y2h_rec_args *a, int form, y2h_stream s)
     } else if (form == Y2H_REC_REF) {
         hipLaunchKernelGGL(rec_ref_kernel, dim3(y2h_grid((long)a->rows * a->n, 256)), dim3(256), 0, S(s), *a);
     } else return Y2H_EINVAL;
+    Y2H_LAUNCH_CHECK();
+    return Y2H_OK;
+}
+
+static unsigned long g_sample_launches = 0;
+extern "C" unsigned long y2h_rnn_sample_launches(void) { return g_sample_launches; }
+
+extern "C" int y2h_rnn_sample(const float *out, int outputs, int n, int seqs, const float *u, const int *prev, int *next,
+                              float *x, float *probs, y2h_stream s)
+{
+    const size_t lds = ((size_t)n + 3) / 4 * sizeof(float4);
+    if (!out || !u || !prev || !next || !x || seqs <= 0 || n <= 0 || n > outputs || lds > 65536) return Y2H_EINVAL;
+    Y2H_CHECK(y2h_lds_limit((const void *)rec_sample_kernel, lds));
+    hipLaunchKernelGGL(rec_sample_kernel, dim3((unsigned)seqs), dim3(256), lds, S(s), out, outputs, n, u, prev, next, x, probs);
+    Y2H_LAUNCH_CHECK();
+    ++g_sample_launches;
+    return Y2H_OK;
+}
+
+extern "C" int y2h_rnn_feed(const int *tok, float *x, int rows, int inputs, y2h_stream s)
+{
+    if (!tok || !x || rows <= 0 || inputs <= 0) return Y2H_EINVAL;
+    hipLaunchKernelGGL(rec_feed_kernel, dim3(y2h_grid((long)rows * inputs, 256)), dim3(256), 0, S(s), tok, x, rows, inputs);
+    Y2H_LAUNCH_CHECK();
+    return Y2H_OK;
+}
+
+extern "C" int y2h_rnn_score(const float *out, int outputs, const int *next, int rows, float *p_next, float *probs, y2h_stream s)
+{
+    if (!out || !next || !p_next || rows <= 0 || outputs <= 0) return Y2H_EINVAL;
+    hipLaunchKernelGGL(rec_score_kernel, dim3(y2h_grid(probs ? (long)rows * outputs : rows, 256)), dim3(256), 0, S(s), out, outputs,
+                       next, rows, p_next, probs);
     Y2H_LAUNCH_CHECK();
     return Y2H_OK;
 }

@@ -116,9 +116,11 @@ extern "C" int y2h_memcpy_h2d(void *dst, const void *src, size_t bytes, y2h_stre
     if (bytes) Y2H_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, S(s)));
     return Y2H_OK;
 }
+static unsigned long g_d2h_copies = 0;
+extern "C" unsigned long y2h_d2h_copies(void) { return g_d2h_copies; }
 extern "C" int y2h_memcpy_d2h(void *dst, const void *src, size_t bytes, y2h_stream s)
 {
-    if (bytes) Y2H_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, S(s)));
+    if (bytes) { Y2H_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, S(s))); ++g_d2h_copies; }
     return Y2H_OK;
 }
 extern "C" int y2h_memcpy_d2d(void *dst, const void *src, size_t bytes, y2h_stream s)

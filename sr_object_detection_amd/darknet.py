@@ -721,6 +721,64 @@ class Network:
             raise Y2Error("y2_pull_layer_output: " + _check())
         return out
 
+    # --- text generation and scoring (rnn.c; include/sr_yolo2.h y2_rnn_*) ---
+    @property
+    def sequences(self) -> int:
+        """B: sequences per forward of a recurrent network (net.batch / time_steps)"""
+        return self.net.batch // max(self.net.time_steps, 1)
+
+    @staticmethod
+    def rnn_uniforms(rseed: int, n: int) -> np.ndarray:
+        """srand(rseed), then n values of rand_uniform(0, 1) (utils.c:603): the reference's stream on libc rand"""
+        u = np.zeros(n, dtype=np.float32)
+        if lib().y2_rnn_uniforms(int(rseed), int(n), _ptr(u)) != 0:
+            raise Y2Error("y2_rnn_uniforms: " + _check())
+        return u
+
+    def rnn_generate(self, seed, num: int, uniforms, probs: bool = False):
+        """num characters per sequence, sampled on the device (test_char_rnn's loop, rnn.c:257-278): seed is [len][B] (or
+        [len] for one sequence; empty: token 0), uniforms [num][B].  Returns tokens [num][B], and with probs=True also the
+        rows each draw sampled from, [num][B][outputs].  Goes on from the network's current state and temperature."""
+        B = self.sequences
+        seed = np.ascontiguousarray(seed, dtype=np.int32).reshape(-1, B)
+        u = np.ascontiguousarray(uniforms, dtype=np.float32).reshape(-1)
+        if u.size != num * B:
+            raise ValueError("uniforms has %d values, %d draws x %d sequences need %d" % (u.size, num, B, num * B))
+        tokens = np.zeros((num, B), dtype=np.int32)
+        rows = np.zeros((num, B, self.output_size), dtype=np.float32) if probs else None
+        L = lib()
+        L.y2_rnn_generate.argtypes = [CNetwork, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        if L.y2_rnn_generate(self.net, _ptr(seed), seed.shape[0], num, _ptr(u), _ptr(tokens), _ptr(rows) if probs else None) != 0:
+            raise Y2Error("y2_rnn_generate: " + _check())
+        return (tokens, rows) if probs else tokens
+
+    def rnn_score(self, tokens, probs: bool = False):
+        """teacher-forced scoring of tokens [n][B] (or [n]): p_next [n-1][B], the probability given to the character that
+        followed; with probs=True also the rows, [n-1][B][outputs].  n-1 must be a multiple of time_steps."""
+        B = self.sequences
+        tokens = np.ascontiguousarray(tokens, dtype=np.int32).reshape(-1, B)
+        n = tokens.shape[0]
+        p = np.zeros((max(n - 1, 0), B), dtype=np.float32)
+        rows = np.zeros((max(n - 1, 0), B, self.output_size), dtype=np.float32) if probs else None
+        L = lib()
+        L.y2_rnn_score.argtypes = [CNetwork, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        if L.y2_rnn_score(self.net, _ptr(tokens), n, _ptr(p), _ptr(rows) if probs else None) != 0:
+            raise Y2Error("y2_rnn_score: " + _check())
+        return (p, rows) if probs else p
+
+    @staticmethod
+    def rnn_perplexity(p_next, text: bytes):
+        """valid_char_rnn's books (rnn.c:402-416) -> (perplexity, word perplexity) of a text and its len-1 scores"""
+        p = np.ascontiguousarray(p_next, dtype=np.float32).reshape(-1)
+        if p.size != len(text) - 1:
+            raise ValueError("%d scores for a text of %d characters" % (p.size, len(text)))
+        a, b = C.c_float(), C.c_float()
+        L = lib()
+        L.y2_rnn_perplexity.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        if L.y2_rnn_perplexity(_ptr(p), bytes(text), len(text), C.byref(a), C.byref(b)) != 0:
+            raise Y2Error("y2_rnn_perplexity: " + _check())
+        return a.value, b.value
+
     def sync(self) -> None:
         lib().y2_sync(self.net)
 
