@@ -112,6 +112,18 @@ class Region(C.Structure):   # include/sr_yolo2.h y2_region
                 ("x", C.c_int), ("y", C.c_int), ("rw", C.c_int), ("rh", C.c_int)]
 
 
+class RecArgs(C.Structure):  # include/y2_hip.h y2h_rec_args: one launch of y2h_rec_step
+    _fields_ = [("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("mean", C.c_void_p), ("scale", C.c_void_p),
+                ("rinv", C.c_void_p), ("bn", C.c_int), ("act", C.c_int), ("pre", C.c_void_p), ("rows", C.c_int), ("k", C.c_int),
+                ("n", C.c_int), ("h", C.c_int), ("mode", C.c_int), ("shortcut", C.c_int), ("proj", C.c_void_p),
+                ("state", C.c_void_p), ("out", C.c_void_p), ("out2", C.c_void_p), ("z", C.c_void_p), ("xcopy", C.c_void_p)]
+
+
+REC_DENSE, REC_RNN, REC_GRU_ZR, REC_GRU_H = 0, 1, 2, 3      # y2h_rec_args.mode
+REC_REF, REC_SKINNY = 0, 1                                  # y2h_rec_step's form
+REC_SKINNY_MAX_ROWS = 8
+Y2H_EINVAL = -2
+
 DET_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("w", "<f4"), ("h", "<f4"), ("prob", "<f4"), ("obj_id", "<i4")])
 
 LAYER_TYPES = ["CONVOLUTIONAL", "DECONVOLUTIONAL", "CONNECTED", "MAXPOOL", "SOFTMAX", "DETECTION", "DROPOUT", "CROP",
@@ -254,6 +266,10 @@ def lib():
     L.y2h_memcpy_d2d.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     L.y2h_stream_sync.argtypes = [C.c_void_p]
     L.y2h_set_device.argtypes = [C.c_int]
+    L.y2h_rec_skinny_ok.argtypes = [C.c_int, C.c_int]
+    L.y2h_rec_step.argtypes = [C.POINTER(RecArgs), C.c_int, C.c_void_p]
+    L.y2h_rnn_sample.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p]
     L.y2h_p8_stream_k_plan.argtypes = [C.c_long, C.c_int, C.c_long, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.y2h_stream_k_launches.restype = C.c_ulong
     L.y2h_tail_launches.restype = C.c_ulong

@@ -34,6 +34,13 @@ CASES = [
     ("gru_ref_b2_t8", "gru", 2, 8, 211, 311, True),
     ("rnn_mini_b3_t16", "rnn-mini", 3, 16, 221, 321, False),
     ("gru_mini_b3_t16", "gru-mini", 3, 16, 231, 331, False),
+    # the row counts of the step kernel's instantiations (4 and 8 rows, full and partly used) and the first count past it
+    ("rnn_mini_b4_t2", "rnn-mini", 4, 2, 241, 341, False),
+    ("gru_mini_b5_t3", "gru-mini", 5, 3, 251, 351, False),
+    ("rnn_mini_b8_t2", "rnn-mini", 8, 2, 261, 361, False),
+    ("gru_mini_b9_t2", "gru-mini", 9, 2, 271, 371, False),
+    ("gru_ref_b8_t2", "gru", 8, 2, 281, 381, True),
+    ("rnn_ref_b5_t2", "rnn", 5, 2, 291, 391, True),
 ]
 
 

@@ -14,9 +14,14 @@ from tests.helpers import load_golden
 
 pytestmark = pytest.mark.gpu
 
-CASES = {"rnn_ref_b2_t8": "rnn", "gru_ref_b2_t8": "gru", "rnn_mini_b3_t16": "rnn-mini", "gru_mini_b3_t16": "gru-mini"}
-MINI = ["rnn_mini_b3_t16", "gru_mini_b3_t16"]
+CASES = {"rnn_ref_b2_t8": "rnn", "gru_ref_b2_t8": "gru", "rnn_mini_b3_t16": "rnn-mini", "gru_mini_b3_t16": "gru-mini",
+         # the step kernel's other row counts: 4 and 8 rows in full, 5 of 8, 9 (the first count past the skinny kernel)
+         "rnn_mini_b4_t2": "rnn-mini", "gru_mini_b5_t3": "gru-mini", "rnn_mini_b8_t2": "rnn-mini", "gru_mini_b9_t2": "gru-mini",
+         "gru_ref_b8_t2": "gru", "rnn_ref_b5_t2": "rnn"}
+MINI = ["rnn_mini_b3_t16", "gru_mini_b3_t16"]              # the 16-step cases
 COST = 9
+RECURRENT = (15, 16)                                        # LAYER_TYPES: RNN, GRU
+SKINNY_ROWS = 8
 
 
 def _net(tmp, name, B, T, wseed, strict=False):
@@ -58,6 +63,9 @@ def test_golden(tmp_path, case, strict):
     for i in range(net.n):
         key = "layer_%02d" % i
         l = net.layer(i)
+        if l.type in RECURRENT and not strict:                  # the plan's choice: the skinny kernel while the rows fit it
+            name = net.layer_kernel(i)
+            assert ("step:skinny" in name) if B <= SKINNY_ROWS else ("skinny" not in name), name
         if key not in g or l.type == COST:
             continue
         got = net.pull_layer_output(i).reshape(B * T, -1)
@@ -73,6 +81,9 @@ def test_one_step_per_call(tmp_path, case, strict):
     net = _net(tmp_path, CASES[case], B, 1, ws, strict)
     for t in range(T):
         out = net.network_predict(g["x"][t * B:(t + 1) * B])
+        if not strict:                                          # at T = 1 the hoisted products have B rows as well
+            name = net.layer_kernel(0)
+            assert name.count("skinny") == (3 if B <= SKINNY_ROWS else 0), name      # the layer's three blocks
         _close(out, g["out"][t * B:(t + 1) * B], "%s step %d" % (case, t), strict)
     net.free()
 
@@ -122,7 +133,7 @@ def test_graph_replay_keeps_the_state(tmp_path, case, T):
     eager.free(); graph.free()
 
 
-@pytest.mark.parametrize("case", MINI)
+@pytest.mark.parametrize("case", MINI + ["rnn_mini_b8_t2"])     # 8 sequences: sequence 7 is the last accumulator of MB = 8
 def test_items_are_independent(tmp_path, case):
     g, B, T, ws = _golden(case)
     for strict in (True, False):
@@ -141,10 +152,15 @@ def test_step_forms(tmp_path, monkeypatch, case, form):
     g, B, T, ws = _golden(case)
     monkeypatch.setenv("Y2_RNN_STEP", form)
     net = _net(tmp_path, CASES[case], B, T, ws)
+    if form == "skinny" and B > SKINNY_ROWS:                    # a forced skinny step that does not fit is refused
+        with pytest.raises(darknet.Y2Error, match="skinny"):
+            net.network_predict(g["x"])
+        net.free()
+        return
     out = net.network_predict(g["x"])
     # the name says what runs: the matrix-core kernels do not take the mini nets' 30- / 36-wide rows, which then run on
     # the reference-order kernel
-    ran = form if (form == "skinny" or case.endswith("ref_b2_t8")) else "ref"
+    ran = form if (form == "skinny" or "_ref_" in case) else "ref"
     assert ("step:%s" % ran) in net.layer_kernel(0), net.layer_kernel(0)
     _close(out, g["out"], "%s step form %s" % (case, form), False)
     net.free()
