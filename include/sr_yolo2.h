@@ -278,6 +278,52 @@ int y2_validate_recall_frames(network net, float *frames, int n, const box *trut
 int y2_validate_classifier_frames(network net, float *frames, int n, const int *truth, int classes, int topk,
                                   float *top1_out, float *topk_out);
 
+/* ---- the reference's other three classifier evaluations, views built on the device (y2_tta.c) ----
+ * Frames are `image` structs of any size in host memory (CHW float, at least net.c planes; the first net.c are read);
+ * truth[f] as for y2_validate_classifier_frames.  Every view of a frame is predicted, the predictions are added into an
+ * accumulator that starts at 0 (fp32, one rounding per addition, in the order given below -- axpy_cpu, classifier.c:393,
+ * 577,580), and top_k is taken of the sum.  What a `mode` does per frame:
+ *   Y2_VIEWS_CROP10  validate_classifier_10, classifier.c:373-395.  The frame is resized to (net.w+32) x (net.h+32) unless
+ *       it has that size (load_image_color(path, w+shift, h+shift), image.c:2084).  Views, in this order: crop_image
+ *       (image.c:1512-1532) to net.w x net.h at shifts (-32,-32) (32,-32) (0,0) (-32,32) (32,32), then the same five of
+ *       the flip_image'd frame (image.c:1056-1070).  Two quirks are kept: (0,0) is the top-left window, not the centre,
+ *       and the other four reach 32 pixels past an edge, where crop_image's constrain_int repeats the edge pixel.
+ *   Y2_VIEWS_MULTI   validate_classifier_multi, classifier.c:572-582.  Per scale s, in the order given: (rw, rh) =
+ *       resize_min's dimensions (image.c:1662-1672: w < h ? (s, h*s/w) : (w*s/h, s), integers); the frame is resized to
+ *       them (not at all when equal, image.c:1673), the network is resized to (rw, rh), the whole image is predicted, then
+ *       its mirror image.  scales == NULL: the reference's 224, 288, 320, 352, 384 (classifier.c:550).
+ *   Y2_VIEWS_FULL    validate_classifier_full, classifier.c:436-452.  One scale, net.w as it was on entry; one unflipped
+ *       view of the whole resized image.
+ * How it runs: a block of consecutive frames goes up in ONE copy; the resizes, the views (one launch per forward), the
+ * forwards of net.batch views -- packed image-major, an image's views may straddle two forwards, unused slots are zero --
+ * and one accumulation launch per forward are enqueued on the engine's stream; the host syncs once per block and the
+ * block's sums come down in ONE copy.  MULTI and FULL go size-major inside a block: per scale the frames whose resized
+ * size is equal are grouped and the network is resized once per distinct size (y2_view_resizes counts these), not once
+ * per frame and scale; every accumulator still receives its rows in the order above, so the sums equal the image-major
+ * loop's bit for bit.  A block holds its sources, the largest scale's resized copies and its accumulators in at most
+ * Y2_VIEW_BLOCK_BYTES of HBM (one frame always goes); y2_set_view_block_bytes (0 = the default) or env
+ * Y2_VIEW_BLOCK_BYTES override it.  On return the network has the size and batch it had on entry; its plan is rebuilt at
+ * the next predict, as after any resize_network (hence the network * signatures).
+ * Refused before any device work, with a message naming the argument or the frame: n <= 0; NULL frames, sums or truth;
+ * a frame without data, with w or h <= 0 or with fewer than net.c planes; classes > outputs; topk > classes; nscales <= 0
+ * with a scale list; a scale <= 0; a hierarchical classifier (net.hierarchy); a recurrent network; for MULTI / FULL a
+ * network resize_network refuses (the layer is named: [connected] in alexnet.cfg) or a frame too small for it at some
+ * scale.  Strict mode, fp16 mode and y2_set_graph work as for network_predict. */
+enum { Y2_VIEWS_CROP10 = 0, Y2_VIEWS_MULTI = 1, Y2_VIEWS_FULL = 2 };
+#define Y2_VIEW_BLOCK_BYTES ((size_t)256 << 20)
+void y2_set_view_block_bytes(size_t bytes);
+unsigned long y2_view_resizes(void);             /* resize_network calls the view modes made for their size groups */
+/* sums: n x outputs, the summed predictions of each frame */
+int y2_classifier_view_sums(network *net, int mode, const image *frames, int n, const int *scales, int nscales, float *sums);
+/* The reference's loops around it: top_k of each sum, the running top-1 / top-k accuracy, the progress line
+ * "%d: top 1: %f, top %d: %f\n" per frame on stdout in frame order; the final averages are returned.  0 / -1. */
+int y2_validate_classifier_10_frames(network net, const image *frames, int n, const int *truth, int classes, int topk,
+                                     float *top1, float *topk_out);
+int y2_validate_classifier_multi_frames(network *net, const image *frames, int n, const int *scales, int nscales,
+                                        const int *truth, int classes, int topk, float *top1, float *topk_out);
+int y2_validate_classifier_full_frames(network *net, const image *frames, int n, const int *truth, int classes, int topk,
+                                       float *top1, float *topk_out);
+
 /* ---- small helpers the callers use (option_list.h:12-19, data.c:474, utils.c, tree.c, image.c) ---- */
 list *read_data_cfg(char *filename);
 char *option_find(list *l, char *key);

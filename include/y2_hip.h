@@ -385,6 +385,32 @@ typedef struct y2h_region {
 int y2h_regions_to_input(const y2h_region *desc, int n, const unsigned char *pixels, int batch, int planes, int swap_rb,
                          int h, int w, float *dst, y2h_stream s);
 
+/* ---- classifier views (classifier.c:336-593 valid10 / validmulti / validfull) ---- */
+/* One view of y2h_views_to_input: a w x h window of a CHW fp32 source image that becomes batch slot b of the network
+ * input.  The window's top-left corner sits at (dx, dy) of the source; both may be negative or reach past the source. */
+typedef struct y2h_view {
+    long long src;              /* float offset of the source image's first value from `src` */
+    int sw, sh;                 /* source size; its planes lie sw*sh floats apart */
+    int dx, dy;                 /* shift of the window */
+    int flip;                   /* 1: the window is taken of the mirrored source (flip_image) */
+    int pad_;
+} y2h_view;
+
+/* Fill the NCHW fp32 network input dst[batch][planes][h][w] in one launch from `n` views (table `desc` of n entries, in
+ * device memory, pointing into `src`).  Slot b < n equals, bit for bit, crop_image(source, dx, dy, w, h)
+ * (image.c:1512-1532), taken after flip_image (image.c:1056-1070) when flip is set:
+ *     r = clamp(j + dy, 0, sh-1);  c = clamp(i + dx, 0, sw-1);  if (flip) c = sw-1-c;  dst[b][k][j][i] = source[k][r][c]
+ * -- the reference's constrain_int: taps outside the source repeat its edge, they are not zero.  Slots n .. batch-1 are
+ * set to 0.  Data movement only: 4 bytes read and 4 written per output value. */
+int y2h_views_to_input(const y2h_view *desc, int n, const float *src, int batch, int planes, int h, int w, float *dst,
+                       y2h_stream s);
+/* acc[owner[s]][j] = acc[owner[s]][j] + rows[s][j] for the slots s = 0 .. nslots-1 in ascending order whose owner[s] >= 0
+ * (`owner` in device memory; a negative owner's row is not read), j < n.  rows has row stride ld >= n, acc is
+ * [..][n] contiguous.  One thread per column walks the slots in order: each sum is rounded once, in slot order, as
+ * axpy_cpu(classes, 1, p, 1, pred, 1) adds one prediction after another (classifier.c:393,577,580).  Per accumulated row
+ * 4 bytes read of `rows` and 4 read + 4 written of `acc` per value. */
+int y2h_accumulate_rows(float *acc, const float *rows, int ld, const int *owner, int nslots, int n, y2h_stream s);
+
 /* ---- recurrent layers ([rnn] / [gru], y2_recurrent.hip) ----
  * One launch computes n dense columns over `rows` (<= a few dozen) input rows, the sub-layer's epilogue (batch-norm with
  * the rolling statistics, bias, any activation, in the reference's order) and then the mode's combine:

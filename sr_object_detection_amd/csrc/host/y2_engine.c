@@ -121,6 +121,7 @@ void y2_engine_destroy(network *net)
     y2_chargen_free(e);
     y2h_host_free(e->h_out_stage);
     y2h_host_free(e->h_reg_stage);
+    y2h_host_free(e->h_tta); y2h_free(e->d_tta);
     if (e->ev_reg) y2h_event_destroy(e->ev_reg);
     if (e->h_out_pinned) y2h_host_free(e->h_out); else free(e->h_out);
     if (e->ev) { for (i = 0; i < e->n_ev; ++i) y2h_event_destroy(e->ev[i]); free(e->ev); }
@@ -456,6 +457,13 @@ static int stage_output(const network *net, int i, float *nchw, const float **sr
         HIP_OR_ERR(y2h_nhwc_to_nchw(d->out, d->out_ld, nchw, l->batch, l->out_c, l->out_h, l->out_w, e->stream));
     *src = nchw;
     return 0;
+}
+
+/* the output layer of the last forward in the reference's layout, in HBM: [batch][outputs] */
+int y2_output_device(network *net, const float **rows)
+{
+    y2_engine *e = y2_engine_of(net);
+    return stage_output(net, e->out_layer, e->d_out_nchw, rows);
 }
 
 /* copy the output layer to the pinned host buffer in the reference's layout */

@@ -149,6 +149,10 @@ typedef struct y2_engine {
     int *d_gen_tok;
     float *d_gen_u, *d_gen_p, *d_gen_probs;
     size_t gen_tok_cap, gen_u_cap, gen_p_cap, gen_probs_cap;
+    /* classifier views (y2_tta.c), grow-only: one pinned staging buffer (tables + the block's source planes) and one HBM
+     * arena (the same, the resized copies, the resize scratch, the block's accumulators) */
+    unsigned char *h_tta, *d_tta;
+    size_t h_tta_cap, d_tta_cap;
     /* timing */
     y2h_event *ev;             /* n+1 events */
     int n_ev;
@@ -191,6 +195,7 @@ int y2_enqueue_forward(network *net, const float *d_input_nchw);
 int y2_activate_after(y2_engine *e, ACTIVATION a, float *y, int ld, long rows, int n);
 int y2_engine_forward(network *net, const float *d_input_nchw);
 int y2_engine_fetch_output(network *net);
+int y2_output_device(network *net, const float **rows);
 int y2_ingest_u8_device(network net, const unsigned char *d_frames, int h, int w, int c, int step, int swap_rb, int letterbox);
 
 /* plan (y2_plan.c) */

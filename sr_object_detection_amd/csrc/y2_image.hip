@@ -198,6 +198,97 @@ extern "C" int y2h_regions_to_input(const y2h_region *desc, int n, const unsigne
     return Y2H_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Classifier views (classifier.c:336-593): a batch of crop_image windows (image.c:1512-1532, constrain_int taps: edge
+// pixels repeat) of CHW float images of any size, optionally taken after flip_image (image.c:1056-1070), in one
+// launch.  Pure data movement: one read and one write per value.  Each thread writes four consecutive pixels of one
+// output row in every plane -- one 16-byte store per plane when the rows allow it, and one 16-byte load when its four
+// taps are four consecutive, aligned source pixels (an unflipped window's interior); one block row of the grid per
+// batch slot, slots past n are zeroed.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void views_to_input_kernel(const y2h_view *__restrict__ desc, int n,
+                                                             const float *__restrict__ src, int planes, int h, int w,
+                                                             int vec, float *__restrict__ dst)
+{
+    const int b = blockIdx.y;
+    const long gw = (w + 3) / 4;
+    const long g = (long)blockIdx.x * 256 + threadIdx.x;
+    const int Y = (int)(g / gw), X0 = (int)(g - (long)Y * gw) * 4;
+    if (Y >= h) return;
+    const size_t plane = (size_t)h * w;
+    float *o = dst + (size_t)b * planes * plane + (size_t)Y * w + X0;
+    const int nx = min(4, w - X0);
+    if (b >= n) {                        // padded slot: deterministic zeros (uniform per block)
+        for (int k = 0; k < planes; ++k) {
+            if (vec) *(float4 *)(o + k * plane) = make_float4(0.f, 0.f, 0.f, 0.f);
+            else for (int i = 0; i < nx; ++i) o[k * plane + i] = 0.f;
+        }
+        return;
+    }
+    const y2h_view d = desc[b];
+    const size_t splane = (size_t)d.sh * d.sw;
+    const int r = min(max(Y + d.dy, 0), d.sh - 1);
+    const float *row = src + d.src + (size_t)r * d.sw;
+    int c[4];
+    for (int i = 0; i < 4; ++i) {
+        c[i] = min(max(X0 + i + d.dx, 0), d.sw - 1);
+        if (d.flip) c[i] = d.sw - 1 - c[i];
+    }
+    // four consecutive source pixels (no clamp hit, no flip): the clamped taps are then c[0] .. c[0] + 3
+    const bool run = !d.flip && X0 + d.dx >= 0 && X0 + 3 + d.dx <= d.sw - 1;
+    for (int k = 0; k < planes; ++k) {
+        const float *p = row + k * splane;
+        float v[4];
+        if (run && ((uintptr_t)(p + c[0]) % 16 == 0)) {
+            const float4 q = *(const float4 *)(p + c[0]);
+            v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+        } else {
+            for (int i = 0; i < 4; ++i) v[i] = p[c[i]];
+        }
+        if (vec) *(float4 *)(o + k * plane) = make_float4(v[0], v[1], v[2], v[3]);
+        else for (int i = 0; i < nx; ++i) o[k * plane + i] = v[i];
+    }
+}
+
+extern "C" int y2h_views_to_input(const y2h_view *desc, int n, const float *src, int batch, int planes, int h, int w,
+                                  float *dst, y2h_stream s)
+{
+    if (!dst || n < 0 || n > batch || batch <= 0 || planes <= 0 || h <= 0 || w <= 0 || (n > 0 && (!desc || !src)))
+        return Y2H_EINVAL;
+    const int vec = (w % 4 == 0) && ((uintptr_t)dst % 16 == 0);
+    const long groups = (long)h * ((w + 3) / 4);
+    hipLaunchKernelGGL(views_to_input_kernel, dim3((unsigned)((groups + 255) / 256), (unsigned)batch), dim3(256), 0, S(s),
+                       desc, n, src, planes, h, w, vec, dst);
+    Y2H_LAUNCH_CHECK();
+    return Y2H_OK;
+}
+
+// acc[owner[s]][j] = acc[owner[s]][j] + rows[s][j] for s ascending (axpy_cpu(classes, 1, p, 1, pred, 1),
+// classifier.c:393,577,580).  One thread per column j walks the slots in order, so no two threads touch the same value
+// and every accumulator receives its additions in slot order, one rounding each, whatever the launch shape.  A slot
+// whose owner is negative is not read.
+__global__ __launch_bounds__(256) void accumulate_rows_kernel(float *acc, const float *__restrict__ rows, int ld,
+                                                              const int *__restrict__ owner, int nslots, int n)
+{
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    for (int s = 0; s < nslots; ++s) {
+        const int o = owner[s];
+        if (o < 0) continue;
+        float *a = acc + (size_t)o * n + j;
+        *a = *a + rows[(size_t)s * ld + j];
+    }
+}
+
+extern "C" int y2h_accumulate_rows(float *acc, const float *rows, int ld, const int *owner, int nslots, int n, y2h_stream s)
+{
+    if (!acc || !rows || !owner || nslots <= 0 || n <= 0 || ld < n) return Y2H_EINVAL;
+    hipLaunchKernelGGL(accumulate_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(s), acc, rows, ld, owner,
+                       nslots, n);
+    Y2H_LAUNCH_CHECK();
+    return Y2H_OK;
+}
+
 // utils.c:420-432 mean_arrays on device buffers: avg = 0; for j: avg += frame j; avg /= n  (fp32, frame order)
 __global__ __launch_bounds__(256) void mean_frames_kernel(const float *__restrict__ frames, int n, long els, float *__restrict__ avg)
 {

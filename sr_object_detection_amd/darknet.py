@@ -112,6 +112,14 @@ class Region(C.Structure):   # include/sr_yolo2.h y2_region
                 ("x", C.c_int), ("y", C.c_int), ("rw", C.c_int), ("rh", C.c_int)]
 
 
+class View(C.Structure):     # include/y2_hip.h y2h_view: one view of y2h_views_to_input
+    _fields_ = [("src", C.c_longlong), ("sw", C.c_int), ("sh", C.c_int), ("dx", C.c_int), ("dy", C.c_int),
+                ("flip", C.c_int), ("pad_", C.c_int)]
+
+
+VIEWS_CROP10, VIEWS_MULTI, VIEWS_FULL = 0, 1, 2             # include/sr_yolo2.h Y2_VIEWS_*
+
+
 class RecArgs(C.Structure):  # include/y2_hip.h y2h_rec_args: one launch of y2h_rec_step
     _fields_ = [("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("mean", C.c_void_p), ("scale", C.c_void_p),
                 ("rinv", C.c_void_p), ("bn", C.c_int), ("act", C.c_int), ("pre", C.c_void_p), ("rows", C.c_int), ("k", C.c_int),
@@ -270,6 +278,18 @@ def lib():
     L.y2h_rec_step.argtypes = [C.POINTER(RecArgs), C.c_int, C.c_void_p]
     L.y2h_rnn_sample.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p]
+    L.y2h_views_to_input.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.y2h_accumulate_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.y2h_d2h_copies.restype = C.c_ulong
+    L.y2_set_view_block_bytes.argtypes = [C.c_size_t]
+    L.y2_view_resizes.restype = C.c_ulong
+    L.y2_classifier_view_sums.argtypes = [C.POINTER(CNetwork), C.c_int, C.POINTER(Image), C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    L.y2_validate_classifier_10_frames.argtypes = [CNetwork, C.POINTER(Image), C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                   C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.y2_validate_classifier_multi_frames.argtypes = [C.POINTER(CNetwork), C.POINTER(Image), C.c_int, C.c_void_p, C.c_int,
+                                                      C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.y2_validate_classifier_full_frames.argtypes = [C.POINTER(CNetwork), C.POINTER(Image), C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                     C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.y2h_p8_stream_k_plan.argtypes = [C.c_long, C.c_int, C.c_long, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.y2h_stream_k_launches.restype = C.c_ulong
     L.y2h_tail_launches.restype = C.c_ulong
@@ -309,6 +329,32 @@ def regions(items):
         x, y, rw, rh = rect if rect is not None else (0, 0, 0, 0)
         arr[i] = Region(f.ctypes.data, h, w, c, f.strides[0], x, y, rw, rh)
     return arr, keep
+
+
+def images(frames):
+    """frames: list of float32 [c][h][w] arrays of any size -> (Image array, arrays kept alive for the call)"""
+    keep = [np.ascontiguousarray(f, dtype=np.float32) for f in frames]
+    for f in keep:
+        if f.ndim != 3:
+            raise ValueError("a frame is [c][h][w]")
+    arr = (Image * max(len(keep), 1))()
+    for i, f in enumerate(keep):
+        arr[i] = Image(f.shape[1], f.shape[2], f.shape[0], f.ctypes.data_as(C.POINTER(C.c_float)))
+    return arr, keep
+
+
+def set_view_block_bytes(nbytes: int = 0) -> None:
+    """HBM budget of one block of frames in the classifier view modes (0: the default, Y2_VIEW_BLOCK_BYTES)"""
+    lib().y2_set_view_block_bytes(nbytes)
+
+
+def view_resizes() -> int:
+    """resize_network calls the classifier view modes made so far (one per distinct resized size per block)"""
+    return int(lib().y2_view_resizes())
+
+
+def d2h_copies() -> int:
+    return int(lib().y2h_d2h_copies())
 
 
 def region_box_to_frame(item, net_w: int, net_h: int, letterbox: bool, box):
@@ -729,6 +775,44 @@ class Network:
                                            C.byref(a), C.byref(b)) != 0:
             raise Y2Error("y2_validate_classifier_frames: " + _check())
         return a.value, b.value
+
+    # --- the reference's multi-view classifier evaluations (classifier.c:336-593; include/sr_yolo2.h Y2_VIEWS_*) ---
+    def classifier_view_sums(self, mode: int, frames, scales=None) -> np.ndarray:
+        """summed predictions [n][outputs] of every frame's views: VIEWS_CROP10 (valid10: ten crops of the frame at
+        net size + 32), VIEWS_MULTI (validmulti: whole image and mirror image at each scale, the network resized) or
+        VIEWS_FULL (validfull); frames: float32 [c][h][w] arrays of any size."""
+        arr, keep = images(frames)
+        sc = np.ascontiguousarray(scales, dtype=np.int32) if scales is not None else None
+        sums = np.zeros((len(keep), self.output_size), dtype=np.float32)
+        if lib().y2_classifier_view_sums(C.byref(self.net), mode, arr, len(keep), _ptr(sc) if sc is not None else None,
+                                         sc.size if sc is not None else 0, _ptr(sums)) != 0:
+            raise Y2Error(_check())
+        return sums
+
+    def _validate_views(self, fn, net_arg, frames, truth, classes: int, topk: int, scales=None, with_scales=False):
+        arr, keep = images(frames)
+        truth = np.ascontiguousarray(truth, dtype=np.int32)
+        a, b = C.c_float(), C.c_float()
+        args = [net_arg, arr, len(keep)]
+        if with_scales:
+            sc = np.ascontiguousarray(scales, dtype=np.int32) if scales is not None else None
+            args += [_ptr(sc) if sc is not None else None, sc.size if sc is not None else 0]
+        if fn(*args, _ptr(truth), classes, topk, C.byref(a), C.byref(b)) != 0:
+            raise Y2Error(_check())
+        return a.value, b.value
+
+    def validate_classifier_10(self, frames, truth, classes: int, topk: int):
+        """validate_classifier_10 (classifier.c:336) over in-memory frames -> (top-1 accuracy, top-k accuracy)"""
+        return self._validate_views(lib().y2_validate_classifier_10_frames, self.net, frames, truth, classes, topk)
+
+    def validate_classifier_multi(self, frames, truth, classes: int, topk: int, scales=None):
+        """validate_classifier_multi (classifier.c:531); scales=None: 224, 288, 320, 352, 384"""
+        return self._validate_views(lib().y2_validate_classifier_multi_frames, C.byref(self.net), frames, truth, classes, topk,
+                                    scales, True)
+
+    def validate_classifier_full(self, frames, truth, classes: int, topk: int):
+        """validate_classifier_full (classifier.c:408)"""
+        return self._validate_views(lib().y2_validate_classifier_full_frames, C.byref(self.net), frames, truth, classes, topk)
 
     def pull_layer_output(self, i: int) -> np.ndarray:
         l = self.net.layers[i]
