@@ -137,6 +137,8 @@ struct layer {
     int steps, hidden, shortcut;
     struct layer *input_layer, *self_layer, *output_layer;                  /* [rnn] */
     struct layer *input_z_layer, *state_z_layer, *input_r_layer, *state_r_layer, *input_h_layer, *state_h_layer;   /* [gru] */
+    /* [normalization] (normalization_layer.c:5-19): the window is `size` channels; y = x * (kappa + alpha * sum)^-beta */
+    float alpha, beta, kappa;
 };
 
 /* network.h:19-67, forward-path subset */

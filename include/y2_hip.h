@@ -242,6 +242,22 @@ int y2h_binarize(const float *x, int ldx, float *y, long rows, int c, y2h_stream
 /* activate_array (activations.c:95-101, the formulas of activations.h:21-54) in place on channels 0..c-1 of `rows`
  * pixels with channel stride ld; any Y2H_ACT_* code */
 int y2h_activate_array(float *x, int ld, long rows, int c, int activation, y2h_stream s);
+/* [activation] (activation_layer.c:39-43): y[row*ldy + k] = act(x[row*ldx + k]) out of place, the same formulas in strict
+ * and default mode, as y2h_activate_array.  _f16: half in and out, the function in fp32, Y2H_ACT_LINEAR .. _RELU only */
+int y2h_activate_copy(const float *x, int ldx, float *y, int ldy, long rows, int c, int activation, y2h_stream s);
+int y2h_activate_copy_f16(const void *x, int ldx, void *y, int ldy, long rows, int c, int activation, y2h_stream s);
+/* [normalization] (normalization_layer.c:65-94), cross-channel LRN on NHWC: y = norm^-beta * x with
+ * norm[k] = kappa + alpha * (sum of x[j]^2 over j in [k-(size-1)/2, k+size/2] within [0,c) - x[size/2]^2) -- the reference
+ * never adds channel size/2 but subtracts it once it leaves the window.  Needs c >= max(1, size/2), size >= 1, ldx, ldy >= c.
+ * strict = 0: one pass, squares staged in LDS, each window summed in ascending channel order, norm^-beta in fp32;
+ * strict = 1 (and any c, size for which y2h_lrn_fast_ok is 0: more than 1024 channels): one lane per pixel in the reference's channel order with
+ * pow in double, bit-identical to it.  A norm <= 0 gives a non-finite value, as in the reference.
+ * y2h_lrn_f16: the one-pass form with half in and out, fp32 arithmetic (ld in halves); Y2H_EINVAL without y2h_lrn_fast_ok */
+int y2h_lrn_fast_ok(int c, int size);
+int y2h_lrn(const float *x, int ldx, float *y, int ldy, long pixels, int c, int size, float alpha, float beta, float kappa,
+            int strict, y2h_stream s);
+int y2h_lrn_f16(const void *x, int ldx, void *y, int ldy, long pixels, int c, int size, float alpha, float beta, float kappa,
+                y2h_stream s);
 /* global average pool: [batch][h*w][ld] -> [batch][c] (sequential fp32 sum, avgpool_layer.c:40) */
 int y2h_avgpool(const float *x, int ldx, float *y, int batch, int h, int w, int c, y2h_stream s);
 /* rows of `n` floats: softmax with temperature (blas.c:205); in/out may alias */

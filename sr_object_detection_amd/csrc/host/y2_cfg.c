@@ -14,8 +14,8 @@
  * Sections built: the YOLOv2 / Darknet-19 forward path ([convolutional] [maxpool] [route] [reorg] [region] [avgpool]
  * [softmax], [cost] which does nothing at inference) plus the heads SURVEY 8(f)-4 admits ([shortcut], the YOLOv1
  * head [connected] [dropout] [detection]) and [crop] [local] [batchnorm], and the recurrent [rnn] / [gru]
- * (parser.c:188-212; rnn_layer.c:29-60, gru_layer.c:29-87) behind a flat input; any other section ([crnn], ...)
- * is an error rather than a silent skip.  No device memory is touched here:
+ * (parser.c:188-212; rnn_layer.c:29-60, gru_layer.c:29-87) behind a flat input, [normalization] and [activation]; any
+ * other section is an error rather than a silent skip ([crnn]: see the refusal in parse_network_cfg).  No device memory is touched here:
  * HBM buffers are planned at the first predict (y2_plan.c).
  */
 #include <stdarg.h>
@@ -687,6 +687,47 @@ static layer make_batchnorm(shape p)
     return l;
 }
 
+/* parser.c:399-407 parse_normalization + normalization_layer.c:5-19: cross-channel local response normalization.  The
+ * forward pass reads channels 0 .. size/2-1 before it looks at c (normalization_layer.c:78), so size/2 > c is refused */
+static layer make_normalization(list *o, shape p)
+{
+    layer l;
+    memset(&l, 0, sizeof l);
+    l.type = NORMALIZATION;
+    l.alpha = option_find_float(o, "alpha", .0001f);
+    l.beta = option_find_float(o, "beta", .75f);
+    l.kappa = option_find_float(o, "kappa", 1);
+    l.size = option_find_int(o, "size", 5);
+    if (!(p.h && p.w && p.c)) { y2_fail("Layer before normalization layer must output image."); return l; }
+    if (l.size < 1) { y2_fail("normalization layer: size=%d (must be at least 1)", l.size); return l; }
+    if (l.size / 2 > p.c) {
+        y2_fail("normalization layer: size=%d reads %d channels but the input has %d (the reference would read past it)", l.size, l.size / 2, p.c);
+        return l;
+    }
+    fprintf(stderr, "Local Response Normalization Layer: %d x %d x %d image, %d size\n", p.w, p.h, p.c, l.size);
+    l.batch = p.batch;
+    l.h = l.out_h = p.h; l.w = l.out_w = p.w; l.c = l.out_c = p.c;
+    l.inputs = l.outputs = p.w * p.h * p.c;
+    return l;
+}
+
+/* parser.c:433-448 parse_activation + activation_layer.c:12-37: a stand-alone activation behind an image or a vector */
+static layer make_activation(list *o, shape p)
+{
+    layer l;
+    memset(&l, 0, sizeof l);
+    l.type = ACTIVE;
+    l.activation = activation_by_name(option_find_str(o, "activation", "linear"));
+    if (p.inputs <= 0) { y2_fail("activation layer has no input"); return l; }
+    /* the engine hands layer 0 the network input as an image; a [net] with inputs= only is read by recurrent layers alone */
+    if (p.index == 0 && !(p.h && p.w && p.c)) { y2_fail("activation layer 0 needs an image-shaped network input (height, width, channels)"); return l; }
+    l.inputs = l.outputs = p.inputs;
+    l.batch = p.batch;
+    fprintf(stderr, "Activation Layer: %d inputs\n", l.inputs);
+    l.h = l.out_h = p.h; l.w = l.out_w = p.w; l.c = l.out_c = p.c;
+    return l;
+}
+
 /* parser.c:389-397: at inference a no-op whose output IS the previous layer's (parser.c:658-661) */
 static layer make_dropout(list *o, shape p)
 {
@@ -966,6 +1007,15 @@ network parse_network_cfg(char *filename)    /* parser.c:585-700 */
         else if (is_type(t, "[cost]", NULL)) l = make_cost(s->options, p);
         else if (is_type(t, "[rnn]", NULL)) l = make_rnn(s->options, p, &net, net.time_steps);
         else if (is_type(t, "[gru]", NULL)) l = make_gru(s->options, p, &net, net.time_steps);
+        else if (is_type(t, "[normalization]", "[lrn]")) l = make_normalization(s->options, p);
+        else if (is_type(t, "[activation]", NULL)) l = make_activation(s->options, p);
+        else if (is_type(t, "[crnn]", NULL)) {
+            /* crnn_layer.c:91-110 hands its convolutions a zeroed network_state: their im2col workspace is NULL and the
+             * compiled reference faults at the first step, on the CPU and on the GPU path alike */
+            memset(&l, 0, sizeof l);
+            y2_fail("layer type [crnn] is outside the forward path this engine implements: the reference's own forward pass "
+                    "of it faults (it runs its convolutions without a workspace), so there is no behaviour to reproduce");
+        }
         else {
             memset(&l, 0, sizeof l);
             y2_fail("layer type %s is outside the YOLOv2/Darknet-19 forward path this engine implements", t);

@@ -423,6 +423,20 @@ int y2_enqueue_forward(network *net, const float *d_input_nchw)
             HIP_OR_ERR(y2h_batchnorm(x, ldx, d->out, d->out_ld, (long)l->batch * l->h * l->w, l->c, (const float *)(e->arena + d->off_mean),
                                      (const double *)(e->arena + d->off_rinv), (const float *)(e->arena + d->off_scale), e->stream));
             break;
+        case NORMALIZATION:               /* normalization_layer.c:65-94 */
+            if (d->out_half)
+                HIP_OR_ERR(y2h_lrn_f16(x, ldx, d->out, d->out_ld, (long)l->batch * l->h * l->w, l->c, l->size, l->alpha, l->beta, l->kappa, e->stream));
+            else
+                HIP_OR_ERR(y2h_lrn(x, ldx, d->out, d->out_ld, (long)l->batch * l->h * l->w, l->c, l->size, l->alpha, l->beta, l->kappa,
+                                   e->strict, e->stream));
+            break;
+        case ACTIVE: {                    /* activation_layer.c:39-43: copy, then activate_array */
+            const int flat = y2_is_flat(net, i);
+            const long rows = flat ? (long)l->batch : (long)l->batch * l->out_h * l->out_w;
+            const int n = flat ? l->outputs : l->out_c;
+            if (d->out_half) HIP_OR_ERR(y2h_activate_copy_f16(x, ldx, d->out, d->out_ld, rows, n, y2_act_code(l->activation), e->stream));
+            else HIP_OR_ERR(y2h_activate_copy(x, ldx, d->out, d->out_ld, rows, n, y2_act_code(l->activation), e->stream));
+        } break;
         case LOCAL:
             if (y2_act_code(l->activation) < 0) { y2_fail("local layer %d: unknown activation %d", i, (int)l->activation); return -1; }
             HIP_OR_ERR(y2h_local(x, ldx, (const float *)(e->arena + d->off_w_packed), (const float *)(e->arena + d->off_bias), d->out,
@@ -671,6 +685,14 @@ int resize_network(network *net, int w, int h)   /* network.c:322-388 */
             y2_fail("resize_network: layer %d (%s) cannot be resized", i, get_layer_string(net->layers[i].type));
             return -1;
         }
+    /* [activation] has no resize (network.c:358-360); found before anything is changed, so the network stays usable.
+     * Layers behind an [avgpool] are not visited (network.c:367) */
+    for (i = 0; i < net->n && net->layers[i].type != AVGPOOL; ++i)
+        if (net->layers[i].type == ACTIVE) {
+            fprintf(stderr, "Resizing type %d \n", (int)ACTIVE);
+            y2_fail("Cannot resize this type of layer");
+            return -1;
+        }
     net->w = w; net->h = h;
     net->inputs = w * h * net->c;
     for (i = 0; i < net->n; ++i) {
@@ -728,6 +750,10 @@ int resize_network(network *net, int w, int h)   /* network.c:322-388 */
         case AVGPOOL:                        /* avgpool_layer.c:33-38 */
             l->w = w; l->h = h;
             l->inputs = h * w * l->c;
+            break;
+        case NORMALIZATION:                  /* normalization_layer.c:37-63 */
+            l->w = l->out_w = w; l->h = l->out_h = h;
+            l->inputs = l->outputs = w * h * l->c;
             break;
         case COST: case SOFTMAX:
             l->inputs = inputs; l->outputs = inputs;
@@ -832,6 +858,8 @@ char *get_layer_string(LAYER_TYPE a)         /* network.c:73-130 */
     case DETECTION: return "detection";
     case RNN: return "rnn";
     case GRU: return "gru";
+    case NORMALIZATION: return "normalization";
+    case ACTIVE: return "activation";
     default: return "none";
     }
 }

@@ -89,6 +89,13 @@ int y2_act_code(ACTIVATION a)
  * reference runs every activation -- a pass of their own over the stored output (activations.c:95) */
 int y2_act_in_kernel(ACTIVATION a) { const int c = y2_act_code(a); return c >= 0 && c <= Y2H_ACT_RELU; }
 int y2_act_for_kernel(ACTIVATION a) { return y2_act_in_kernel(a) ? y2_act_code(a) : Y2H_ACT_LINEAR; }
+/* the cfg name of an ACTIVATION (activations.c:8-38 get_activation_string) */
+static const char *act_name(ACTIVATION a)
+{
+    static const char *const names[] = { "logistic", "relu", "relie", "linear", "ramp", "tanh", "plse", "leaky", "elu", "loggy",
+                                         "stair", "hardtan", "lhtan" };
+    return ((int)a >= 0 && (int)a < (int)(sizeof names / sizeof names[0])) ? names[a] : "relu";
+}
 
 /* what the input form means: the size of the engine's NHWC input buffer and layer 0's descriptor fields */
 void y2_input_form(const network *net, y2_in_form *f)
@@ -196,7 +203,7 @@ int y2_is_flat(const network *net, int i)
 {
     switch (net->layers[i].type) {
     case REGION: case AVGPOOL: case SOFTMAX: case CONNECTED: case DETECTION: case RNN: case GRU: return 1;
-    case DROPOUT: case COST: return i > 0 ? y2_is_flat(net, i - 1) : 0;
+    case DROPOUT: case COST: case ACTIVE: return i > 0 ? y2_is_flat(net, i - 1) : 0;   /* as the layer in front */
     default: return 0;
     }
 }
@@ -459,6 +466,12 @@ static int plan_half(network *net)
         case REGION: case SOFTMAX:
             if (pd && pd->out_half) { y2_fail("fp16 mode: layer %d (%s) needs an fp32 producer (a convolutional or avgpool layer)", i, get_layer_string(l->type)); return -1; }
             break;
+        case NORMALIZATION: case ACTIVE:
+            if (!pd || !pd->out_half) { y2_fail("fp16 mode: layer %d (%s) needs a half-precision producer", i, get_layer_string(l->type)); return -1; }
+            if (l->type == ACTIVE && !y2_act_in_kernel(l->activation)) { y2_fail("fp16 mode: layer %d: activation %d has no half-precision form", i, (int)l->activation); return -1; }
+            if (l->type == NORMALIZATION && !y2h_lrn_fast_ok(l->c, l->size)) { y2_fail("fp16 mode: layer %d: a normalization over %d channels has no half-precision form", i, l->c); return -1; }
+            d->out_half = 1;
+            break;
         case COST: d->out_half = pd ? pd->out_half : 0; break;
         case SHORTCUT: case CONNECTED: case DETECTION: case DROPOUT: case CROP: case LOCAL: case BATCHNORM: case RNN: case GRU:
             y2_fail("fp16 mode: layer %d (%s) has no half-precision kernel", i, get_layer_string(l->type)); return -1;
@@ -520,6 +533,17 @@ static int plan_activations(network *net)
         case SHORTCUT: case CROP: case LOCAL: case BATCHNORM:
             if (alloc_activations(d, l) != 0) return -1;
             d->kernel = l->type == SHORTCUT ? "shortcut" : l->type == CROP ? "crop" : l->type == LOCAL ? (e->strict ? "local_ref" : "local") : "batchnorm";
+            break;
+        case NORMALIZATION:
+            if (alloc_activations(d, l) != 0) return -1;
+            /* a row too wide for a workgroup's tile runs the reference-order kernel in every mode */
+            d->kernel = d->out_half ? "lrn_nhwc_f16" : (e->strict || !y2h_lrn_fast_ok(l->c, l->size)) ? "lrn_ref" : "lrn_nhwc";
+            break;
+        case ACTIVE:
+            if (y2_act_code(l->activation) < 0) { y2_fail("activation layer %d: unknown activation %d", i, (int)l->activation); return -1; }
+            if ((y2_is_flat(net, i) ? alloc_flat(d, l) : alloc_activations(d, l)) != 0) return -1;
+            snprintf(d->kname, sizeof d->kname, d->out_half ? "activation_f16(%s)" : "activation(%s)", act_name(l->activation));
+            d->kernel = d->kname;
             break;
         case ROUTE:
             d->kernel = "route(zero-copy)";

@@ -85,6 +85,7 @@ Layer._fields_ = [
         ("input_layer", C.POINTER(Layer)), ("self_layer", C.POINTER(Layer)), ("output_layer", C.POINTER(Layer)),
         ("input_z_layer", C.POINTER(Layer)), ("state_z_layer", C.POINTER(Layer)), ("input_r_layer", C.POINTER(Layer)),
         ("state_r_layer", C.POINTER(Layer)), ("input_h_layer", C.POINTER(Layer)), ("state_h_layer", C.POINTER(Layer)),
+        ("alpha", C.c_float), ("beta", C.c_float), ("kappa", C.c_float),
     ]
 
 
@@ -280,6 +281,14 @@ def lib():
                                  C.c_void_p, C.c_void_p]
     L.y2h_views_to_input.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.y2h_accumulate_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.y2h_lrn_fast_ok.argtypes = [C.c_int, C.c_int]
+    L.y2h_lrn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
+                          C.c_int, C.c_void_p]
+    L.y2h_lrn_f16.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
+                              C.c_void_p]
+    L.y2h_activate_array.argtypes = [C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_int, C.c_void_p]
+    L.y2h_activate_copy.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_int, C.c_void_p]
+    L.y2h_activate_copy_f16.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_int, C.c_void_p]
     L.y2h_d2h_copies.restype = C.c_ulong
     L.y2_set_view_block_bytes.argtypes = [C.c_size_t]
     L.y2_view_resizes.restype = C.c_ulong

@@ -19,6 +19,7 @@ from __future__ import annotations
 #   ("max", size, stride[, padding]) | ("route", [idx...]) | ("reorg", stride)
 #   ("region", dict) | ("avg",) | ("softmax",) | ("cost",)
 #   ("crop", width, height, noadjust) | ("batchnorm",) | ("local", filters, size, stride, pad, activation)
+#   ("lrn", size[, alpha[, beta[, kappa]]])  (options left out take the parser's defaults) | ("activation", name)
 
 _D19_TRUNK = [
     ("conv", 32, 3, 1, "leaky"), ("max", 2, 2),
@@ -276,6 +277,10 @@ def cfg_text(name: str, width: int | None = None, height: int | None = None, bat
             out += ["[batchnorm]", ""]
         elif kind == "local":
             out += ["[local]", "filters=%d" % e[1], "size=%d" % e[2], "stride=%d" % e[3], "pad=%d" % e[4], "activation=%s" % e[5], ""]
+        elif kind == "lrn":
+            out += ["[normalization]", "size=%d" % e[1]] + ["%s=%r" % (k, v) for k, v in zip(("alpha", "beta", "kappa"), e[2:])] + [""]
+        elif kind == "activation":
+            out += ["[activation]", "activation=%s" % e[1], ""]
         elif kind == "avg":
             out += ["[avgpool]", ""]
         elif kind == "softmax":
@@ -339,6 +344,12 @@ def resolve(name_or_spec, width: int, height: int | None = None, channels: int =
             _, filters, size, stride, pad, act = e
             L.update(type="local", filters=filters, size=size, stride=stride, pad=pad, activation=act,
                      out_w=(w - (1 if pad else size)) // stride + 1, out_h=(h - (1 if pad else size)) // stride + 1, out_c=filters)
+        elif kind == "lrn":
+            a = dict(zip(("alpha", "beta", "kappa"), e[2:]))
+            L.update(type="normalization", size=e[1], alpha=a.get("alpha", .0001), beta=a.get("beta", .75), kappa=a.get("kappa", 1.0),
+                     out_w=w, out_h=h, out_c=c)
+        elif kind == "activation":
+            L.update(type="activation", activation=e[1], out_w=w, out_h=h, out_c=c, outputs=inputs)
         elif kind == "avg":
             L.update(type="avgpool", out_w=1, out_h=1, out_c=c)
         elif kind in ("softmax", "cost"):
@@ -406,3 +417,39 @@ def recurrent_records(name: str):
             recs.append((e[1], inputs, 0))
             inputs = e[1]
     return recs
+
+
+# Networks with [normalization] (cross-channel LRN) and [activation] layers.  Kept apart from SPECS, like RECURRENT.
+# name -> (width, height, batch, spec).
+LRN = {
+    # the AlexNet-era pattern conv -> LRN -> maxpool, an [activation] on an image, a classifier tail
+    "lrn_mini": (12, 10, 3, [
+        ("conv", 12, 3, 1, "leaky"), ("lrn", 5, .05), ("max", 2, 2), ("conv", 10, 1, 0, "linear"), ("activation", "hardtan"),
+        ("avg",), ("softmax",)]),
+    # layer 0 is placed in the route's buffer, so the first LRN reads 8 channels at a pixel stride of 14; size 4 has an
+    # asymmetric window; the second LRN takes every default but size
+    "lrn_route": (6, 5, 2, [
+        ("conv", 8, 3, 1, "leaky"), ("lrn", 4, .1), ("conv", 6, 3, 1, "leaky"), ("route", [0, 2]), ("lrn", 3),
+        ("activation", "logistic")]),
+    # an [activation] behind a flat layer
+    "act_flat": (8, 8, 2, [
+        ("conv", 4, 3, 1, "leaky"), ("connected", 20, 0, "linear"), ("activation", "elu"), ("connected", 7, 0, "linear"),
+        ("softmax",)]),
+    # lrn_mini as fp16 storage takes it: 32 filters in front (the half first-layer kernel) and an [activation] the half
+    # kernels have
+    "lrn_mini_f16": (12, 10, 3, [
+        ("conv", 32, 3, 1, "leaky"), ("lrn", 5, .05), ("max", 2, 2), ("conv", 10, 1, 0, "linear"), ("activation", "leaky"),
+        ("avg",), ("softmax",)]),
+}
+
+
+def lrn_cfg_text(name: str, batch: int | None = None, width: int | None = None, height: int | None = None, spec=None) -> str:
+    """cfg text of an LRN entry (or of `spec` with the entry's size), at its own size and batch unless given"""
+    w, h, b, own = LRN[name]
+    return cfg_text(name, width or w, height or h, batch or b, spec=own if spec is None else spec)
+
+
+def lrn_resolve(name: str, width: int | None = None, height: int | None = None, spec=None):
+    """the layer table (resolve) of an LRN entry"""
+    w, h, _, own = LRN[name]
+    return resolve(own if spec is None else spec, width or w, height or h)

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Per-layer device time of one zoo network (engine timing events, median over iterations).
-usage: layer_times.py <net> [size] [batch] [iters=20] [top=0]      top > 0: only the `top` slowest layers"""
+usage: layer_times.py <net> [size] [batch] [iters=20] [top=0]      top > 0: only the `top` slowest layers
+<net> is one of zoo.SPECS or of zoo.LRN (the [normalization] / [activation] networks; size then scales both sides)"""
 import os
 import sys
 import tempfile
@@ -14,14 +15,15 @@ from sr_object_detection_amd import darknet, synth, zoo  # noqa: E402
 
 def main():
     name = sys.argv[1]
-    size = int(sys.argv[2]) if len(sys.argv) > 2 else zoo.DEFAULT_SIZE.get(name, 416)
+    spec = zoo.LRN[name][3] if name in zoo.LRN else zoo.SPECS[name]
+    size = int(sys.argv[2]) if len(sys.argv) > 2 else (zoo.LRN[name][0] if name in zoo.LRN else zoo.DEFAULT_SIZE.get(name, 416))
     batch = int(sys.argv[3]) if len(sys.argv) > 3 else 1
     iters = int(sys.argv[4]) if len(sys.argv) > 4 else 20
     top = int(sys.argv[5]) if len(sys.argv) > 5 else 0
     tmp = tempfile.mkdtemp()
     cfg = os.path.join(tmp, "n.cfg")
-    open(cfg, "w").write(zoo.cfg_text(name, size, size, batch))
-    layers = zoo.resolve(name, size)
+    open(cfg, "w").write(zoo.cfg_text(name, size, size, batch, spec=spec))
+    layers = zoo.resolve(spec, size)
     wts = os.path.join(tmp, "n.weights")
     synth.write_weights(wts, layers, 7)
     net = darknet.Network.parse_network_cfg(cfg)
