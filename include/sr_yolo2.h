@@ -276,9 +276,27 @@ typedef struct { int total, correct, proposals; float avg_iou; } y2_recall;
 int y2_validate_recall_frames(network net, float *frames, int n, const box *truth, const int *truth_first, y2_recall *res);
 /* validate_classifier_single (classifier.c:469-529) over `n` network-sized CHW frames in memory: truth[f] is the class
  * the reference derives from the file path (-1 = none); per frame network_predict -> top_k -> running top-1 / top-k
- * accuracy, the reference's progress line on stdout; the final averages are returned.  Returns 0 / -1. */
+ * accuracy, the reference's progress line on stdout; the final averages are returned.  Returns 0 / -1.
+ * A hierarchical classifier ([softmax] tree=, net.hierarchy) follows classifier.c:514-520: hierarchy_predictions(pred,
+ * outputs, hierarchy, 1) runs on the device before the rows come down.  The device applies the hierarchy of its own head
+ * only: a net.hierarchy that is not the softmax_tree of the network's output [softmax] layer with n == outputs (a tree hung
+ * on a flat classifier, a head with groups > 1) is refused before any device work, here and in every entry point below
+ * that applies a hierarchy. */
 int y2_validate_classifier_frames(network net, float *frames, int n, const int *truth, int classes, int topk,
                                   float *top1_out, float *topk_out);
+/* The core of predict_classifier (classifier.c:716-718) over `n` network-sized CHW frames, net.batch at a time:
+ * network_predict, with a hierarchy hierarchy_predictions(pred, outputs, hierarchy, 0) on the device, then top_k over all
+ * net.outputs.  indexes[n][top], probs[n][top] (the values at those indexes).  A flat classifier has no hierarchy step.
+ * Returns 0 / -1. */
+int y2_classify_frames(network net, float *frames, int n, int top, int *indexes, float *probs);
+/* hierarchy_predictions(row, outputs, net.hierarchy, only_leaves) (tree.c:37-51) on all net.batch rows of the output
+ * layer's DEVICE copy, in place, on the engine's stream: for callers of y2_forward_device, before y2_output_enqueue /
+ * y2_output_fetch.  The leaf flags are read from net.hierarchy->leaf at the call and sent up only when they changed since
+ * the last call (change_leaves).  The rows are multiplied IN PLACE and nothing marks them as absolute: call it once per
+ * forward -- a second call after the same forward (graph replay included), or a call after y2_classify_frames /
+ * y2_validate_classifier_frames / a view mode, which have applied the hierarchy already, applies it twice.
+ * Refused without net.hierarchy, and before the first forward.  Returns 0 / -1. */
+int y2_hierarchy_enqueue(network net, int only_leaves);
 
 /* ---- the reference's other three classifier evaluations, views built on the device (y2_tta.c) ----
  * Frames are `image` structs of any size in host memory (CHW float, at least net.c planes; the first net.c are read);
@@ -296,6 +314,13 @@ int y2_validate_classifier_frames(network net, float *frames, int n, const int *
  *       its mirror image.  scales == NULL: the reference's 224, 288, 320, 352, 384 (classifier.c:550).
  *   Y2_VIEWS_FULL    validate_classifier_full, classifier.c:436-452.  One scale, net.w as it was on entry; one unflipped
  *       view of the whole resized image.
+ * A hierarchical classifier (net.hierarchy: the tree of the output [softmax] tree= layer) gets hierarchy_predictions(pred,
+ * outputs, hierarchy, 1) on a view's prediction before it is added, on the device (a row mask per forward, no copy and no
+ * wait): all ten views of CROP10 (classifier.c:392), FULL's one (:453), but of MULTI only the UNFLIPPED views (:576) -- the
+ * reference adds the flipped view's prediction as network_predict returned it, conditional probabilities and all
+ * (:579-580).  That quirk is kept.  The head's tree tables are derived again by every plan but sent up only when they differ
+ * from what the device holds, so the re-plans of MULTI / FULL cost a hierarchical network no copy and no wait either: per
+ * block it resizes, copies down and waits exactly as often as a flat classifier of the same shape.
  * How it runs: a block of consecutive frames goes up in ONE copy; the resizes, the views (one launch per forward), the
  * forwards of net.batch views -- packed image-major, an image's views may straddle two forwards, unused slots are zero --
  * and one accumulation launch per forward are enqueued on the engine's stream; the host syncs once per block and the
@@ -308,7 +333,7 @@ int y2_validate_classifier_frames(network net, float *frames, int n, const int *
  * the next predict, as after any resize_network (hence the network * signatures).
  * Refused before any device work, with a message naming the argument or the frame: n <= 0; NULL frames, sums or truth;
  * a frame without data, with w or h <= 0 or with fewer than net.c planes; classes > outputs; topk > classes; nscales <= 0
- * with a scale list; a scale <= 0; a hierarchical classifier (net.hierarchy); a recurrent network; for MULTI / FULL a
+ * with a scale list; a scale <= 0; a net.hierarchy that is not the output head's tree (above); a recurrent network; for MULTI / FULL a
  * network resize_network refuses (the layer is named: [connected] in alexnet.cfg) or a frame too small for it at some
  * scale.  Strict mode, fp16 mode and y2_set_graph work as for network_predict. */
 enum { Y2_VIEWS_CROP10 = 0, Y2_VIEWS_MULTI = 1, Y2_VIEWS_FULL = 2 };
@@ -338,6 +363,9 @@ void free_list(list *l);
 char **get_labels(char *filename);
 image **load_alphabet(void);               /* glyph PNGs are UI (image.c:212): returns NULL here */
 tree *read_tree(char *filename);           /* tree.c:53 */
+void change_leaves(tree *t, char *leaf_list);   /* tree.c:7: leaf[i] = t->name[i] is a line of the file; "Found %d leaves." on stderr */
+float get_hierarchy_probability(float *x, tree *hier, int c);   /* tree.c:27: x[c] times x of every ancestor */
+void hierarchy_predictions(float *predictions, int n, tree *hier, int only_leaves);   /* tree.c:37: on the host, in place */
 int *read_map(char *filename);             /* utils.c:17 */
 int max_index(float *a, int n);            /* utils.c:533 */
 void top_k(float *a, int n, int k, int *index);   /* utils.c:179 */

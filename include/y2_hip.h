@@ -78,6 +78,7 @@ int         y2h_host_unregister(void *ptr);
 int         y2h_memcpy_h2d(void *dst, const void *src, size_t bytes, y2h_stream s);
 int         y2h_memcpy_d2h(void *dst, const void *src, size_t bytes, y2h_stream s);
 unsigned long y2h_d2h_copies(void);      /* y2h_memcpy_d2h calls of this process that moved bytes */
+unsigned long y2h_stream_syncs(void);    /* y2h_stream_sync calls of this process: the host waits a test may count */
 int         y2h_memcpy_d2d(void *dst, const void *src, size_t bytes, y2h_stream s);
 int         y2h_memset(void *dst, int value, size_t bytes, y2h_stream s);
 int         y2h_stream_create(y2h_stream *s);
@@ -262,6 +263,20 @@ int y2h_lrn_f16(const void *x, int ldx, void *y, int ldy, long pixels, int c, in
 int y2h_avgpool(const float *x, int ldx, float *y, int batch, int h, int w, int c, y2h_stream s);
 /* rows of `n` floats: softmax with temperature (blas.c:205); in/out may alias */
 int y2h_softmax_rows(const float *x, float *y, long rows, int n, float temp, y2h_stream s);
+/* softmax_tree (softmax_layer.c:35-47): every row of `n` floats is `groups` sibling groups [goff[g], goff[g] + gsize[g]),
+ * each softmaxed on its own with y2h_softmax_rows' arithmetic (double exp, fp32 sum in index order); group_of[n] names
+ * every element's group (tree.group).  The tables are device pointers; in/out may alias.  One workgroup per row with the
+ * row in LDS while n + groups floats fit 64 KB, a thread per (row, group) in global memory beyond.
+ * rows, n or groups <= 0 or a NULL pointer: Y2H_EINVAL. */
+int y2h_softmax_tree_rows(const float *x, float *y, long rows, int n, float temp, int groups, const int *group_size,
+                          const int *group_offset, const int *group_of, y2h_stream s);
+/* hierarchy_predictions (tree.c:37-51) in place on `nrows` rows of `n` floats, `ld` floats apart: p[j] *= p[parent[j]] for j
+ * ascending, then p[j] = 0 where !leaf[j] (leaf == NULL: no such step).  levels > 0: order / level_off are the nodes sorted
+ * by depth and the level offsets (every parent precedes its child) and the row is walked level by level; levels == 0: the
+ * sequential walk, whatever the order of the nodes.  row_mask (one int per row, NULL = every row): rows whose entry is 0
+ * are left as they are. */
+int y2h_hierarchy_rows(float *rows, long ld, int nrows, int n, const int *parent, const int *order, const int *level_off,
+                       int levels, const int *leaf, const int *row_mask, y2h_stream s);
 
 /* ---- half-storage variants (engine extension: BASELINE configs[4]; void* = IEEE half, ld in halves) ---- */
 int y2h_maxpool_f16(const void *x, int ldx, void *y, int ldy, int batch, int h, int w, int c,

@@ -112,8 +112,9 @@ void y2_engine_destroy(network *net)
     for (i = 0; i < net->n; ++i) {
         y2_ldev *d = ld_of(&net->layers[i]);
         if (!d) continue;
-        y2h_free(d->d_anchors); y2h_free(d->d_tree_parent); y2h_free(d->d_tree_gsize); y2h_free(d->d_tree_goff); y2h_free(d->d_map);
-        y2h_free(d->d_tree_order); y2h_free(d->d_tree_loff); y2h_free(d->d_tree_best);
+        y2h_free(d->d_anchors); y2h_free(d->d_tree_block); free(d->h_tree_block); y2h_free(d->d_map);
+        y2h_free(d->d_tree_best);
+        y2h_free(d->d_tree_leaf); free(d->h_tree_leaf);
         free(d);
         net->layers[i].dev = NULL;
     }
@@ -398,8 +399,10 @@ int y2_enqueue_forward(network *net, const float *d_input_nchw)
                 y2_fail("softmax layer %d: input must be a flat vector (e.g. after avgpool)", i);
                 return -1;
             }
-            if (l->softmax_tree) { y2_fail("softmax layer with tree= is not implemented on the device"); return -1; }
-            HIP_OR_ERR(y2h_softmax_rows(x, d->d_flat, (long)l->batch * l->groups, l->inputs / l->groups, l->temperature, e->stream));
+            if (l->softmax_tree)          /* softmax_layer.c:54-55: every row is the tree's sibling groups, each softmaxed on its own */
+                HIP_OR_ERR(y2h_softmax_tree_rows(x, d->d_flat, (long)l->batch * l->groups, l->inputs / l->groups, l->temperature,
+                                                 l->softmax_tree->groups, d->d_tree_gsize, d->d_tree_goff, d->d_tree_group, e->stream));
+            else HIP_OR_ERR(y2h_softmax_rows(x, d->d_flat, (long)l->batch * l->groups, l->inputs / l->groups, l->temperature, e->stream));
         } break;
         case CONNECTED: rc = forward_connected(net, i, x, ldx); break;
         case RNN: case GRU: rc = y2_rec_forward(net, i, x); break;

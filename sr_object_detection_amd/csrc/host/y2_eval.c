@@ -105,14 +105,21 @@ static int det_arrays_make(det_arrays *d, int total, int classes)
 static void det_arrays_free(det_arrays *d) { free(d->boxes); free(d->probs); free(d->store); }
 
 /* One forward of up to net.batch frames (the tail of the last batch is zero padded). */
-static float *predict_chunk(network net, float *frames, int first, int n, float *staging)
+/* frames [first, first + net.batch) through the network, the last chunk zero padded.  only_leaves >= 0 on a network with
+ * a hierarchy: hierarchy_predictions(.., only_leaves) runs on the device before the rows come down; NO_HIERARCHY: plain
+ * network_predict */
+enum { NO_HIERARCHY = -1 };
+static float *predict_chunk(network net, float *frames, int first, int n, float *staging, int only_leaves)
 {
     const size_t per = (size_t)net.inputs;
     int cnt = n - first < net.batch ? n - first : net.batch;
-    if (cnt == net.batch) return network_predict(net, frames + per * first);
-    memset(staging, 0, per * net.batch * sizeof(float));
-    memcpy(staging, frames + per * first, per * cnt * sizeof(float));
-    return network_predict(net, staging);
+    float *in = frames + per * first;
+    if (cnt != net.batch) {
+        memset(staging, 0, per * net.batch * sizeof(float));
+        memcpy(staging, in, per * cnt * sizeof(float));
+        in = staging;
+    }
+    return (only_leaves != NO_HIERARCHY && net.hierarchy) ? y2_predict_hierarchy(&net, in, only_leaves) : network_predict(net, in);
 }
 
 /* yolo.c:95-114: the YOLOv1 writer -- corner form clipped to [0,w] x [0,h] (no +1 offset), one file per class */
@@ -178,7 +185,7 @@ int y2_validate_detector_frames(network net, float *frames, int n, char **paths,
     d.classes = classes;
     staging = calloc((size_t)net.inputs * net.batch, sizeof(float));
     for (i = 0; i < n; i += net.batch) {
-        float *out = predict_chunk(net, frames, i, n, staging);
+        float *out = predict_chunk(net, frames, i, n, staging, NO_HIERARCHY);
         if (!out) goto done;
         for (b = 0; b < net.batch && i + b < n; ++b) {
             layer lb = l;
@@ -223,7 +230,7 @@ int y2_validate_recall_frames(network net, float *frames, int n, const box *trut
     if (det_arrays_make(&d, total_boxes, l.classes)) { y2_fail("out of memory"); goto done; }
     staging = calloc((size_t)net.inputs * net.batch, sizeof(float));
     for (i = 0; i < n; i += net.batch) {
-        float *out = predict_chunk(net, frames, i, n, staging);
+        float *out = predict_chunk(net, frames, i, n, staging, NO_HIERARCHY);
         if (!out) goto done;
         for (b = 0; b < net.batch && i + b < n; ++b) {
             layer lb = l;
@@ -259,22 +266,24 @@ done:
 /* validate_classifier_single (classifier.c:469-529) with the image list replaced by `n` network-sized CHW frames in
  * memory and the label-from-path lookup (:502-507) by `truth[f]` (-1 = no label, as when no label string matches):
  * per frame network_predict -> top_k(pred, classes, topk, indexes) -> running top-1 / top-k accuracy, the reference's
- * progress line per frame on stdout.  Frames are processed net.batch at a time.  A hierarchical classifier
- * (net.hierarchy, softmax tree=) is refused: that head is not implemented on the device. */
+ * progress line per frame on stdout.  Frames are processed net.batch at a time.  With a hierarchy (net.hierarchy, the tree
+ * of the output [softmax] tree= layer) hierarchy_predictions(pred, outputs, hierarchy, 1) runs on the device before the
+ * rows come down (classifier.c:514-520); any other net.hierarchy is refused (y2_hierarchy_refusal). */
 int y2_validate_classifier_frames(network net, float *frames, int n, const int *truth, int classes, int topk,
                                   float *top1_out, float *topk_out)
 {
     float *staging = NULL, avg_acc = 0, avg_topk = 0;
     int *indexes = NULL, i, b, j, rc = -1, outputs;
+    char why[256];
     if (!frames || n <= 0 || !truth || classes <= 0 || topk <= 0) { y2_fail("y2_validate_classifier_frames: missing argument"); return -1; }
-    if (net.hierarchy) { y2_fail("y2_validate_classifier_frames: hierarchical classifiers (softmax tree=) are not implemented on the device"); return -1; }
+    if (net.hierarchy && y2_hierarchy_refusal(&net, why, sizeof why)) { y2_fail("y2_validate_classifier_frames: %s", why); return -1; }
     outputs = get_network_output_size(net);
     if (classes > outputs || topk > classes) { y2_fail("y2_validate_classifier_frames: classes %d / top %d against %d network outputs", classes, topk, outputs); return -1; }
     indexes = calloc(topk, sizeof(int));
     staging = calloc((size_t)net.inputs * net.batch, sizeof(float));
     if (!indexes || !staging) { y2_fail("out of memory"); goto done; }
     for (i = 0; i < n; i += net.batch) {
-        float *out = predict_chunk(net, frames, i, n, staging);
+        float *out = predict_chunk(net, frames, i, n, staging, 1);
         if (!out) goto done;
         for (b = 0; b < net.batch && i + b < n; ++b) {
             const int f = i + b;
@@ -289,6 +298,37 @@ int y2_validate_classifier_frames(network net, float *frames, int n, const int *
     rc = 0;
 done:
     free(indexes);
+    free(staging);
+    return rc;
+}
+
+/* The core of predict_classifier (classifier.c:716-718) over `n` network-sized CHW frames, net.batch at a time:
+ * network_predict, hierarchy_predictions(pred, outputs, hierarchy, 0) on the device when the network has a hierarchy,
+ * top_k over all outputs.  indexes / probs: [n][top]. */
+int y2_classify_frames(network net, float *frames, int n, int top, int *indexes, float *probs)
+{
+    float *staging = NULL;
+    int i, b, j, rc = -1, outputs;
+    char why[256];
+    if (!frames || n <= 0 || top <= 0 || !indexes || !probs) { y2_fail("y2_classify_frames: missing argument"); return -1; }
+    if (!net.layers || net.n <= 0) { y2_fail("y2_classify_frames: net is empty"); return -1; }
+    if (net.hierarchy && y2_hierarchy_refusal(&net, why, sizeof why)) { y2_fail("y2_classify_frames: %s", why); return -1; }
+    outputs = get_network_output_size(net);
+    if (top > outputs) { y2_fail("y2_classify_frames: top %d against %d network outputs", top, outputs); return -1; }
+    staging = calloc((size_t)net.inputs * net.batch, sizeof(float));
+    if (!staging) { y2_fail("out of memory"); goto done; }
+    for (i = 0; i < n; i += net.batch) {
+        float *out = predict_chunk(net, frames, i, n, staging, 0);
+        if (!out) goto done;
+        for (b = 0; b < net.batch && i + b < n; ++b) {
+            const float *row = out + (size_t)b * outputs;
+            int *idx = indexes + (size_t)(i + b) * top;
+            top_k((float *)row, outputs, top, idx);
+            for (j = 0; j < top; ++j) probs[(size_t)(i + b) * top + j] = row[idx[j]];
+        }
+    }
+    rc = 0;
+done:
     free(staging);
     return rc;
 }

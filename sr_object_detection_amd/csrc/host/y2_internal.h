@@ -31,9 +31,14 @@ typedef struct y2_ldev {
     int tile_bm, tile_bn, ksplit;   /* measured tile choice (y2_set_autotune), 0 = the host's cost model */
     /* region */
     float *d_anchors;
-    int *d_tree_parent, *d_tree_gsize, *d_tree_goff, *d_map;
+    int *d_tree_block, *h_tree_block;  /* the head's tree tables in one allocation and their host copy (y2_plan.c plan_tree_tables) */
+    size_t tree_block_ints;
+    int *d_tree_parent, *d_tree_gsize, *d_tree_goff, *d_map;     /* the d_tree_* tables point into d_tree_block */
     int *d_tree_order, *d_tree_loff;   /* nodes by depth level (only when parents precede children) */
     int tree_levels;
+    /* every node's group (tree.group), and for [softmax] tree= the leaf flags hierarchy_predictions(.., only_leaves = 1) reads;
+     * h_tree_leaf is the host copy of what d_tree_leaf holds, so a change_leaves between two calls is seen and sent up once */
+    int *d_tree_group, *d_tree_leaf, *h_tree_leaf;
     float *d_tree_best;                /* [2 * boxes]: the region layer's (score | class) per box for y2h_detect_tree_chain, or NULL */
     int tree_best_valid;               /* the last forward filled d_tree_best (it does unless the detection chain overlaps the next forward) */
     float *d_region;           /* [batch][outputs] flattened region output */
@@ -196,11 +201,16 @@ int y2_activate_after(y2_engine *e, ACTIVATION a, float *y, int ld, long rows, i
 int y2_engine_forward(network *net, const float *d_input_nchw);
 int y2_engine_fetch_output(network *net);
 int y2_output_device(network *net, const float **rows);
+const char *y2_hierarchy_refusal(const network *net, char *buf, size_t cap);
+float *y2_predict_hierarchy(network *net, float *input, int only_leaves);
+int y2_hierarchy_leaves(network *net);
+int y2_hierarchy_device(network *net, float *rows, int nrows, int only_leaves, const int *d_row_mask);
 int y2_ingest_u8_device(network net, const unsigned char *d_frames, int h, int w, int c, int step, int swap_rb, int letterbox);
 
 /* plan (y2_plan.c) */
 int y2_engine_build(network *net);
 void y2_free_plan(network *net);
+int y2_softmax_tree_check(const network *net);
 int y2_act_code(ACTIVATION a);
 int y2_act_in_kernel(ACTIVATION a);
 int y2_act_for_kernel(ACTIVATION a);

@@ -347,10 +347,40 @@ static int autotune_allowed(const y2_engine *e) { return e->autotune && !e->stri
 /* ------------------------------------------------------------------ */
 /* the passes, in the order y2_engine_build runs them                  */
 /* ------------------------------------------------------------------ */
+/* [softmax] tree=: the tree must cover the layer's rows exactly.  softmax_tree (softmax_layer.c:35-47) walks the tree's
+ * groups whatever inputs/groups is: a larger tree writes past the row, a smaller one leaves outputs unwritten.  Needs no
+ * device, and is the first thing a plan asks. */
+int y2_softmax_tree_check(const network *net)
+{
+    int i, g, j, count;
+    for (i = 0; i < net->n; ++i) {
+        const layer *l = &net->layers[i];
+        const tree *t = l->softmax_tree;
+        if (l->type != SOFTMAX || !t) continue;
+        if (l->groups <= 0 || t->n != l->inputs / l->groups) {
+            y2_fail("softmax layer %d: tree has %d nodes but the layer's rows have inputs/groups = %d (the reference would read or "
+                    "write out of bounds, softmax_layer.c:41-45)", i, t->n, l->groups > 0 ? l->inputs / l->groups : 0);
+            return -1;
+        }
+        for (g = 0, count = 0; g < t->groups; ++g) {
+            if (t->group_size[g] < 0 || t->group_offset[g] != count) { y2_fail("softmax layer %d: tree group %d is not contiguous", i, g); return -1; }
+            count += t->group_size[g];
+        }
+        if (count != t->n) { y2_fail("softmax layer %d: the tree's groups hold %d of its %d nodes", i, count, t->n); return -1; }
+        for (j = 0; j < t->n; ++j)
+            if (t->parent[j] >= t->n || t->group[j] < 0 || t->group[j] >= t->groups) {
+                y2_fail("softmax layer %d: tree node %d has parent %d, group %d (of %d nodes, %d groups)", i, j, t->parent[j], t->group[j], t->n, t->groups);
+                return -1;
+            }
+    }
+    return 0;
+}
+
 static int plan_checks(network *net)
 {
     y2_engine *e = y2_engine_of(net);
     if (!e) { y2_fail("network has no engine (was it built by parse_network_cfg?)"); return -1; }
+    if (y2_softmax_tree_check(net) != 0) return -1;
     if (net->gpu_index < 0) {
         y2_fail("gpu_index %d: this library has no CPU compute path; select a GPU (>= 0)", net->gpu_index);
         return -1;
@@ -560,7 +590,7 @@ static int plan_activations(network *net)
             break;
         case AVGPOOL: case SOFTMAX:
             if (alloc_flat(d, l) != 0) return -1;
-            d->kernel = l->type == AVGPOOL ? "avgpool" : "softmax_rows";
+            d->kernel = l->type == AVGPOOL ? "avgpool" : (l->softmax_tree ? "softmax_tree" : "softmax_rows");
             break;
         case CONNECTED: case DETECTION: {
             /* YOLOv1 family: flat fp32 vectors.  The producer of a dense layer must be contiguous (an image
@@ -701,46 +731,69 @@ static int plan_output(network *net)
     return 0;
 }
 
-/* depth levels for the level-parallel hierarchy walk; only valid when parents come first */
-static int tree_levels(y2_engine *e, y2_ldev *d, const layer *l)
+/* The tree tables of a [region] / [softmax] tree= head, in ONE block of ints:
+ *   parent[n] | group_size[groups] | group_offset[groups] | group[n] | order[n] | level_off[levels + 1]
+ * (order / level_off: the nodes by depth level for the level-parallel hierarchy walk, only when every parent precedes its
+ * child; tree_levels = 0 otherwise).  Every plan derives them again from the layer's tree; they depend on the tree alone,
+ * so they go up -- one copy, one wait -- only when they differ from what the device already holds: a re-plan after
+ * resize_network / set_batch_network costs a tree head no copy and no wait. */
+static int plan_tree_tables(y2_engine *e, y2_ldev *d, const layer *l)
 {
     const tree *t = l->softmax_tree;
-    int *depth = calloc(t->n, sizeof(int)), *order = calloc(t->n, sizeof(int)), *loff = NULL, j, ok = 1, maxd = 0, lv, pos = 0, rc = -1;
-    for (j = 0; j < t->n && ok; ++j) {
+    const int n = t->n, g = t->groups;
+    int *depth = calloc(n > 0 ? n : 1, sizeof(int)), *blk = NULL, *order, *loff, j, ok = 1, maxd = 0, lv, pos = 0, rc = -1;
+    size_t ints;
+    for (j = 0; j < n && ok; ++j) {
         int par = t->parent[j];
         if (par >= j) ok = 0;
         else depth[j] = par < 0 ? 0 : depth[par] + 1;
         if (ok && depth[j] > maxd) maxd = depth[j];
     }
-    d->tree_levels = 0;
-    if (!ok) { rc = 0; goto cleanup; }
-    loff = calloc(maxd + 2, sizeof(int));
-    for (lv = 0; lv <= maxd; ++lv) {
-        loff[lv] = pos;
-        for (j = 0; j < t->n; ++j) if (depth[j] == lv) order[pos++] = j;
+    ints = (size_t)2 * n + 2 * g + (ok ? (size_t)n + maxd + 2 : 0);
+    blk = calloc(ints ? ints : 1, sizeof(int));
+    if (!depth || !blk) { y2_fail("out of memory"); goto cleanup; }
+    memcpy(blk, t->parent, n * sizeof(int));
+    memcpy(blk + n, t->group_size, g * sizeof(int));
+    memcpy(blk + n + g, t->group_offset, g * sizeof(int));
+    memcpy(blk + n + 2 * g, t->group, n * sizeof(int));
+    order = blk + 2 * n + 2 * g; loff = order + n;
+    if (ok) {
+        for (lv = 0; lv <= maxd; ++lv) {
+            loff[lv] = pos;
+            for (j = 0; j < n; ++j) if (depth[j] == lv) order[pos++] = j;
+        }
+        loff[maxd + 1] = pos;
     }
-    loff[maxd + 1] = pos;
-    if (upload_small((void **)&d->d_tree_order, order, t->n * sizeof(int), e->stream) ||
-        upload_small((void **)&d->d_tree_loff, loff, (maxd + 2) * sizeof(int), e->stream)) {
-        y2_fail("tree upload: %s", y2h_last_error());
-        goto cleanup;
+    if (!d->d_tree_block || d->tree_block_ints != ints || memcmp(d->h_tree_block, blk, ints * sizeof(int)) != 0) {
+        free(d->h_tree_block); d->h_tree_block = blk; blk = NULL; d->tree_block_ints = ints;
+        if (upload_small((void **)&d->d_tree_block, d->h_tree_block, ints * sizeof(int), e->stream)) {
+            y2h_free(d->d_tree_block); d->d_tree_block = NULL;
+            y2_fail("tree upload: %s", y2h_last_error());
+            goto cleanup;
+        }
     }
-    d->tree_levels = maxd + 1;
+    d->d_tree_parent = d->d_tree_block;
+    d->d_tree_gsize = d->d_tree_block + n;
+    d->d_tree_goff = d->d_tree_block + n + g;
+    d->d_tree_group = d->d_tree_block + n + 2 * g;
+    d->d_tree_order = ok ? d->d_tree_block + 2 * n + 2 * g : NULL;
+    d->d_tree_loff = ok ? d->d_tree_order + n : NULL;
+    d->tree_levels = ok ? maxd + 1 : 0;
     /* detect mode's (score, class) per box as a by-product of the region layer (y2h_region_forward_tree) */
     y2h_free(d->d_tree_best); d->d_tree_best = NULL;
-    if (!l->map && l->coords == 4 && y2h_region_tree_best_ok(l->classes, d->tree_levels) &&
+    if (ok && l->type == REGION && !l->map && l->coords == 4 && y2h_region_tree_best_ok(l->classes, d->tree_levels) &&
         y2h_malloc((void **)&d->d_tree_best, (size_t)2 * l->batch * l->h * l->w * l->n * sizeof(float))) {
         y2_fail("tree scratch: %s", y2h_last_error());
         goto cleanup;
     }
     rc = 0;
 cleanup:
-    free(depth); free(order); free(loff);
+    free(depth); free(blk);
     return rc;
 }
 
-/* region constants */
-static int plan_region_constants(network *net)
+/* the constants of the heads: a region layer's anchors and class map, and the tree tables of a [region] or [softmax] tree= */
+static int plan_head_constants(network *net)
 {
     y2_engine *e = y2_engine_of(net);
     int i;
@@ -748,15 +801,9 @@ static int plan_region_constants(network *net)
         layer *l = &net->layers[i];
         y2_ldev *d = ld_of(l);
         tree *t = l->softmax_tree;
-        if (l->type != REGION) continue;
-        if (upload_small((void **)&d->d_anchors, l->biases, 2 * l->n * sizeof(float), e->stream)) { y2_fail("anchor upload: %s", y2h_last_error()); return -1; }
-        if (t && (upload_small((void **)&d->d_tree_parent, t->parent, t->n * sizeof(int), e->stream) ||
-                  upload_small((void **)&d->d_tree_gsize, t->group_size, t->groups * sizeof(int), e->stream) ||
-                  upload_small((void **)&d->d_tree_goff, t->group_offset, t->groups * sizeof(int), e->stream))) {
-            y2_fail("tree upload: %s", y2h_last_error());
-            return -1;
-        }
-        if (t && tree_levels(e, d, l) != 0) return -1;
+        if (l->type != REGION && !(l->type == SOFTMAX && t)) continue;
+        if (l->type == REGION && upload_small((void **)&d->d_anchors, l->biases, 2 * l->n * sizeof(float), e->stream)) { y2_fail("anchor upload: %s", y2h_last_error()); return -1; }
+        if (t && plan_tree_tables(e, d, l) != 0) return -1;
         if (l->map && upload_small((void **)&d->d_map, l->map, 200 * sizeof(int), e->stream)) { y2_fail("map upload: %s", y2h_last_error()); return -1; }
     }
     return 0;
@@ -815,7 +862,7 @@ int y2_engine_build(network *net)
     y2_free_plan(net);
     if (plan_batches(net) != 0 || plan_routes(net) != 0 || plan_pool_fusion(net) != 0 || plan_half(net) != 0 ||
         plan_activations(net) != 0 || plan_input_copies(net) != 0 || plan_input(net) != 0 || plan_output(net) != 0 ||
-        plan_region_constants(net) != 0 || plan_conv_kernels(net) != 0) return -1;
+        plan_head_constants(net) != 0 || plan_conv_kernels(net) != 0) return -1;
     y2_arena_layout(net);
     /* the arena commit: signature, reallocation, the refusal of a replicated rank whose layout changed */
     if (plan_workspace(net) != 0 || y2_arena_commit(net) != 0 || plan_timing_events(net) != 0) return -1;

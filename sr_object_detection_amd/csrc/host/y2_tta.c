@@ -98,6 +98,7 @@ static int views_check(const char *who, const network *net, int mode, const imag
                        int nscales, const float *sums)
 {
     int i, j;
+    char why[256];
     if (!net || !net->layers || net->n <= 0) { y2_fail("%s: net is NULL or empty", who); return -1; }
     if (mode != Y2_VIEWS_CROP10 && mode != Y2_VIEWS_MULTI && mode != Y2_VIEWS_FULL) { y2_fail("%s: mode %d is none of Y2_VIEWS_CROP10 / _MULTI / _FULL", who, mode); return -1; }
     if (n <= 0) { y2_fail("%s: n = %d frames", who, n); return -1; }
@@ -105,7 +106,7 @@ static int views_check(const char *who, const network *net, int mode, const imag
     if (!sums) { y2_fail("%s: sums is NULL", who); return -1; }
     if (scales && nscales <= 0) { y2_fail("%s: nscales = %d with a scale list", who, nscales); return -1; }
     if (scales) for (j = 0; j < nscales; ++j) if (scales[j] <= 0) { y2_fail("%s: scales[%d] = %d", who, j, scales[j]); return -1; }
-    if (net->hierarchy) { y2_fail("%s: hierarchical classifiers (softmax tree=) are not implemented on the device", who); return -1; }
+    if (net->hierarchy && y2_hierarchy_refusal(net, why, sizeof why)) { y2_fail("%s: %s", who, why); return -1; }
     for (i = 0; i < net->n; ++i)
         if (is_recurrent(&net->layers[i])) { y2_fail("%s: layer %d (%s): a recurrent network has no image views", who, i, get_layer_string(net->layers[i].type)); return -1; }
     if (net->w <= 0 || net->h <= 0 || net->c <= 0 || net->batch <= 0) { y2_fail("%s: the network input must be an image (h, w, c > 0)", who); return -1; }
@@ -147,8 +148,11 @@ static int grow_buffers(y2_engine *e, size_t host_bytes, size_t dev_bytes)
 }
 
 /* One block: frames [first, first+cnt).  Layout of the pinned staging buffer and of the front of the HBM arena:
- * [view table: forwards x batch][owner table: forwards x batch][source planes of the frames]; behind it in HBM the
- * current stage's resized copies, the resize scratch and the accumulators. */
+ * [view table: forwards x batch][owner table: forwards x batch][hierarchy table: forwards x batch, hierarchical networks
+ * only][source planes of the frames]; behind it in HBM the current stage's resized copies, the resize scratch and the
+ * accumulators.  The hierarchy table is the row mask of y2h_hierarchy_rows: 1 where hierarchy_predictions(.., 1) is applied
+ * to the slot's prediction before it is added -- every view of CROP10 (classifier.c:392) and FULL (:453), but of MULTI only
+ * the unflipped views (:576): the reference adds the flipped view's prediction as network_predict left it (:579-580). */
 static int run_block(network *net, int mode, const image *frames, int first, int cnt, const int *scales, int nstages,
                      int scale_full, int outputs, float *sums, unsigned char *done)
 {
@@ -157,12 +161,14 @@ static int run_block(network *net, int mode, const image *frames, int first, int
     const int crop_w = net->w, crop_h = net->h;         /* CROP10's window; the other modes' window is the whole image */
     const long forwards_max = ((long)cnt * per + batch - 1) / batch + (long)cnt;   /* every size group may end in a partial forward */
     const size_t slots = (size_t)forwards_max * nstages * batch;
+    const int hier = net->hierarchy != NULL;
     const size_t desc_bytes = align_up(slots * sizeof(y2h_view), 256), owner_bytes = align_up(slots * sizeof(int), 256);
+    const size_t mask_bytes = hier ? owner_bytes : 0, tables_bytes = desc_bytes + owner_bytes + mask_bytes;
     size_t src_floats = 0, res_floats = 0, tmp_floats = 0, acc_floats = (size_t)cnt * outputs, up_bytes, off;
     size_t *src_off = calloc(cnt, sizeof(size_t)), *res_off = calloc(cnt, sizeof(size_t));
     dims *sz = calloc(cnt, sizeof(dims));
     y2h_view *desc;
-    int *owner;
+    int *owner, *hmask;
     float *d_src, *d_res, *d_tmp, *d_acc;
     size_t slot = 0;
     int i, j, k, v, rc = -1;
@@ -184,18 +190,19 @@ static int run_block(network *net, int mode, const image *frames, int first, int
         }
         if (stage > res_floats) res_floats = stage;
     }
-    up_bytes = desc_bytes + owner_bytes + src_floats * sizeof(float);
+    up_bytes = tables_bytes + src_floats * sizeof(float);
     if (grow_buffers(e, up_bytes, up_bytes + (res_floats + align_up(tmp_floats, 4) + acc_floats) * sizeof(float)) != 0) goto cleanup;
     desc = (y2h_view *)e->h_tta;
     owner = (int *)(e->h_tta + desc_bytes);
-    d_src = (float *)(e->d_tta + desc_bytes + owner_bytes);
+    hmask = (int *)(e->h_tta + desc_bytes + owner_bytes);
+    d_src = (float *)(e->d_tta + tables_bytes);
     d_res = d_src + src_floats;
     d_tmp = d_res + res_floats;
     d_acc = d_tmp + align_up(tmp_floats, 4);
-    memset(e->h_tta, 0, desc_bytes + owner_bytes);
+    memset(e->h_tta, 0, tables_bytes);
     for (i = 0; i < cnt; ++i) {
         const image *f = &frames[first + i];
-        memcpy(e->h_tta + desc_bytes + owner_bytes + src_off[i] * sizeof(float), f->data, (size_t)c * f->h * f->w * sizeof(float));
+        memcpy(e->h_tta + tables_bytes + src_off[i] * sizeof(float), f->data, (size_t)c * f->h * f->w * sizeof(float));
     }
     /* pass 1 (host only): the view and owner tables of every forward of the block, in the order pass 2 launches them */
     for (j = 0; j < nstages; ++j) {
@@ -223,6 +230,7 @@ static int run_block(network *net, int mode, const image *frames, int first, int
                     d->dy = mode == Y2_VIEWS_CROP10 ? crop_dy[v % 5] : 0;
                     d->flip = mode == Y2_VIEWS_CROP10 ? v >= 5 : v;
                     owner[slot] = k;
+                    if (hier) hmask[slot] = !(mode == Y2_VIEWS_MULTI && d->flip);
                     ++slot;
                     if (++fill == batch) fill = 0;
                 }
@@ -262,6 +270,7 @@ static int run_block(network *net, int mode, const image *frames, int first, int
                 HIP_OR_CLEANUP(y2h_views_to_input((const y2h_view *)e->d_tta + slot, used, d_src, batch, c, net->h, net->w, e->d_in_nchw, e->stream));
                 if (y2_engine_forward(net, e->d_in_nchw) != 0) goto cleanup;
                 if (y2_output_device(net, &rows) != 0) goto cleanup;
+                if (hier && y2_hierarchy_device(net, (float *)rows, batch, 1, (const int *)(e->d_tta + desc_bytes + owner_bytes) + slot) != 0) goto cleanup;
                 HIP_OR_CLEANUP(y2h_accumulate_rows(d_acc, rows, outputs, (const int *)(e->d_tta + desc_bytes) + slot, batch, outputs, e->stream));
                 slot += batch;
             }
@@ -306,6 +315,7 @@ static int view_sums(const char *who, network *net, int mode, const image *frame
     w0 = net->w; h0 = net->h;
     if (y2_prepare(net) != 0) return -1;
     HIP_OR_ERR(y2h_set_device(y2_engine_of(net)->device));
+    if (net->hierarchy && y2_hierarchy_leaves(net) != 0) return -1;     /* the one wait the leaf flags may cost, before the blocks */
     outputs = get_network_output_size(*net);
     budget = block_budget();
     done = malloc(n);

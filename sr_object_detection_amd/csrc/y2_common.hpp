@@ -1,6 +1,7 @@
 // Shared helpers for the HIP translation units (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <float.h>
 #include <stdio.h>
 #include <string.h>
 #include <map>
@@ -56,6 +57,20 @@ inline hipError_t y2h_lds_limit(const void *fn, size_t bytes)
     e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e == hipSuccess) have = bytes;
     return e;
+}
+
+// softmax of one row or one tree group by one thread (src_yolo2/blas.c:205-221): max-subtract, exp in double, fp32 running
+// sum in index order, divide -- the summation order is the reference's.  in / out may be the same pointer.
+__device__ __forceinline__ void softmax_seq(const float *in, int n, float temp, float *out)
+{
+    float sum = 0.f, largest = -FLT_MAX;
+    for (int i = 0; i < n; ++i) if (in[i] > largest) largest = in[i];
+    for (int i = 0; i < n; ++i) {
+        const float e = (float)exp((double)(in[i] / temp - largest / temp));
+        sum += e;
+        out[i] = e;
+    }
+    for (int i = 0; i < n; ++i) out[i] /= sum;
 }
 
 // every activation of activations.h:21-54, with the reference's own promotion rules (float x, double constants, the

@@ -180,17 +180,7 @@ extern "C" int y2h_avgpool(const float *x, int ldx, float *y, int batch, int h, 
 // sum in index order, divide.  One thread walks one row (or one tree group) so
 // the summation order is the reference's.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void softmax_seq(const float *in, int n, float temp, float *out)
-{
-    float sum = 0.f, largest = -FLT_MAX;
-    for (int i = 0; i < n; ++i) if (in[i] > largest) largest = in[i];
-    for (int i = 0; i < n; ++i) {
-        const float e = (float)exp((double)(in[i] / temp - largest / temp));
-        sum += e;
-        out[i] = e;
-    }
-    for (int i = 0; i < n; ++i) out[i] /= sum;
-}
+// (softmax_seq itself is in y2_common.hpp: the tree softmax of y2_hier.hip walks its groups with it too)
 
 // The same walk with the single-precision exponential (expf, ~1 ulp) in place of the reference's double exp rounded to float
 // (blas.c:softmax): results differ by ~1e-7 relative, the order of the sums is the reference's.  9418 double exps per box are

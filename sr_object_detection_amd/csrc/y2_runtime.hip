@@ -2,6 +2,7 @@
 // (include/y2_hip.h).  Replaces the reference's cuda.c wrapper
 // (src_yolo2/cuda.c:12-160); unlike it, nothing here aborts -- errors come
 // back as codes and the text is kept for y2h_last_error().
+#include <atomic>
 #include "y2_common.hpp"
 #include <mutex>
 #include <unordered_map>
@@ -142,7 +143,11 @@ extern "C" int y2h_stream_create(y2h_stream *s)
     return Y2H_OK;
 }
 extern "C" int y2h_stream_destroy(y2h_stream s) { if (s) Y2H_CHECK(hipStreamDestroy(S(s))); return Y2H_OK; }
-extern "C" int y2h_stream_sync(y2h_stream s) { Y2H_CHECK(hipStreamSynchronize(S(s))); return Y2H_OK; }
+// counted for tests that hold an entry point to its promised number of host waits; atomic: the feed and detect paths
+// wait from more than one thread
+static std::atomic<unsigned long> g_stream_syncs{0};
+extern "C" unsigned long y2h_stream_syncs(void) { return g_stream_syncs.load(); }
+extern "C" int y2h_stream_sync(y2h_stream s) { g_stream_syncs.fetch_add(1, std::memory_order_relaxed); Y2H_CHECK(hipStreamSynchronize(S(s))); return Y2H_OK; }
 extern "C" int y2h_device_sync(void) { Y2H_CHECK(hipDeviceSynchronize()); return Y2H_OK; }
 
 // ---- hipGraph: a launch-bound kernel sequence (batch-1 inference: ~30 launches of 5-30 us) recorded once, replayed

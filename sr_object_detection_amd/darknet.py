@@ -290,6 +290,7 @@ def lib():
     L.y2h_activate_copy.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_int, C.c_void_p]
     L.y2h_activate_copy_f16.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_int, C.c_void_p]
     L.y2h_d2h_copies.restype = C.c_ulong
+    L.y2h_stream_syncs.restype = C.c_ulong
     L.y2_set_view_block_bytes.argtypes = [C.c_size_t]
     L.y2_view_resizes.restype = C.c_ulong
     L.y2_classifier_view_sums.argtypes = [C.POINTER(CNetwork), C.c_int, C.POINTER(Image), C.c_int, C.c_void_p, C.c_int, C.c_void_p]
@@ -299,6 +300,21 @@ def lib():
                                                       C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.y2_validate_classifier_full_frames.argtypes = [C.POINTER(CNetwork), C.POINTER(Image), C.c_int, C.c_void_p, C.c_int, C.c_int,
                                                      C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.y2_classify_frames.argtypes = [CNetwork, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.y2_hierarchy_enqueue.argtypes = [CNetwork, C.c_int]
+    L.read_tree.restype = C.POINTER(Tree)
+    L.read_tree.argtypes = [C.c_char_p]
+    L.hierarchy_predictions.restype = None
+    L.hierarchy_predictions.argtypes = [C.c_void_p, C.c_int, C.POINTER(Tree), C.c_int]
+    L.get_hierarchy_probability.restype = C.c_float
+    L.get_hierarchy_probability.argtypes = [C.c_void_p, C.POINTER(Tree), C.c_int]
+    L.change_leaves.restype = None
+    L.change_leaves.argtypes = [C.POINTER(Tree), C.c_char_p]
+    L.y2h_softmax_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_float, C.c_void_p]
+    L.y2h_softmax_tree_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]
+    L.y2h_hierarchy_rows.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]
     L.y2h_p8_stream_k_plan.argtypes = [C.c_long, C.c_int, C.c_long, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.y2h_stream_k_launches.restype = C.c_ulong
     L.y2h_tail_launches.restype = C.c_ulong
@@ -364,6 +380,11 @@ def view_resizes() -> int:
 
 def d2h_copies() -> int:
     return int(lib().y2h_d2h_copies())
+
+
+def stream_syncs() -> int:
+    """y2h_stream_sync calls so far: the host waits of this process"""
+    return int(lib().y2h_stream_syncs())
 
 
 def region_box_to_frame(item, net_w: int, net_h: int, letterbox: bool, box):
@@ -785,6 +806,28 @@ class Network:
             raise Y2Error("y2_validate_classifier_frames: " + _check())
         return a.value, b.value
 
+    def classify(self, frames: np.ndarray, top: int):
+        """predict_classifier's core (classifier.c:716-718) over network-sized frames [n][c][h][w]: forward, with a
+        hierarchy hierarchy_predictions(.., 0) on the device, top_k over all outputs -> (indexes [n][top], probs [n][top])."""
+        frames = np.ascontiguousarray(frames, dtype=np.float32)
+        n = frames.shape[0]
+        idx = np.zeros((n, top), dtype=np.int32)
+        probs = np.zeros((n, top), dtype=np.float32)
+        if lib().y2_classify_frames(self.net, _ptr(frames), n, top, _ptr(idx), _ptr(probs)) != 0:
+            raise Y2Error(_check())
+        return idx, probs
+
+    def hierarchy_enqueue(self, only_leaves: bool = False) -> None:
+        """hierarchy_predictions (tree.c:37) on the output rows of the last forward, in HBM, before output_enqueue /
+        output_fetch; the leaf flags are read from net.hierarchy at the call.  In place: once per forward"""
+        if lib().y2_hierarchy_enqueue(self.net, 1 if only_leaves else 0) != 0:
+            raise Y2Error(_check())
+
+    @property
+    def hierarchy(self):
+        """net.hierarchy (a POINTER(Tree); false when the network has none)"""
+        return self.net.hierarchy
+
     # --- the reference's multi-view classifier evaluations (classifier.c:336-593; include/sr_yolo2.h Y2_VIEWS_*) ---
     def classifier_view_sums(self, mode: int, frames, scales=None) -> np.ndarray:
         """summed predictions [n][outputs] of every frame's views: VIEWS_CROP10 (valid10: ten crops of the frame at
@@ -925,6 +968,35 @@ def do_nms(boxes: np.ndarray, probs: np.ndarray, thresh: float) -> np.ndarray:
     if L.y2_failed_and_clear():
         raise Y2Error("do_nms: " + _check())
     return probs
+
+
+def read_tree(path: str):
+    """tree.c:53 -> POINTER(Tree)"""
+    t = lib().read_tree(path.encode())
+    if not t:
+        raise Y2Error("read_tree: " + _check())
+    return t
+
+
+def hierarchy_predictions(predictions: np.ndarray, hier, only_leaves: bool = False) -> np.ndarray:
+    """tree.c:37 on a host row (hier: POINTER(Tree), e.g. Network.hierarchy or read_tree's); returns the new row"""
+    p = np.array(predictions, dtype=np.float32, order="C", copy=True)
+    lib().hierarchy_predictions(_ptr(p), p.size, hier, 1 if only_leaves else 0)
+    return p
+
+
+def get_hierarchy_probability(x: np.ndarray, hier, c: int) -> float:
+    """tree.c:27: x[c] times x of every ancestor of c"""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    return float(lib().get_hierarchy_probability(_ptr(x), hier, int(c)))
+
+
+def change_leaves(hier, leaf_list: str) -> None:
+    """tree.c:7: the tree's leaves become the names listed in the file, one per line"""
+    L = lib()
+    L.change_leaves(hier, leaf_list.encode())
+    if L.y2_failed_and_clear():
+        raise Y2Error("change_leaves: " + _check())
 
 
 def box_iou(a, b) -> float:

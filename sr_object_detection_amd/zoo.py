@@ -225,6 +225,37 @@ DEFAULT_SIZE = {"mini-cls": 75, "mini-xnor": 32, "resnet50": 256, "densenet201":
                 "strided": 256, "yolo-v1-small": 448, "mini-acts": 32, "yolo-v1": 448, "mini-v1-local": 40, "yolo": 416, "tiny-yolo-voc": 416, "yolo9000": 544, "darknet19": 448, "mini": 32, "mini-mfma": 64, "mini-res": 32, "tiny-yolo-v1": 448, "mini-v1": 32}
 
 
+# Hierarchical classifiers ([softmax] tree=), name -> (nominal size, spec); kept beside SPECS like LRN below, so that the
+# committed dispatch table of every SPECS network (tests/golden/conv_plan_table.txt) stays what it is.
+# darknet19_9k: the WordTree classifier YOLO9000's detector was trained from -- the Darknet-19 trunk, a 1x1 conv to 9418
+# outputs, avgpool, a tree softmax over synth.write_tree's 9418-node tree.
+HIER = {
+    "darknet19_9k": (448, _D19_TRUNK + [("conv", 9418, 1, 0, "linear"), ("avg",), ("softmax", {"tree": "synth:9418"}), ("cost",)]),
+}
+
+
+def synth_tree(path: str) -> str:
+    """A ("softmax", {"tree": path}) spec names a tree file, or "synth:<nodes>" for synth.write_tree's tree of that many
+    nodes, written once per process into a temporary directory that is removed when the process ends."""
+    if not path.startswith("synth:"):
+        return path
+    if path not in _SYNTH_TREES:
+        import atexit
+        import os
+        import shutil
+        import tempfile
+        from . import synth
+        tmp = tempfile.mkdtemp(prefix="zoo_tree_")
+        atexit.register(shutil.rmtree, tmp, ignore_errors=True)
+        f = os.path.join(tmp, "%s.tree" % path[6:])
+        synth.write_tree(f, int(path[6:]))
+        _SYNTH_TREES[path] = f
+    return _SYNTH_TREES[path]
+
+
+_SYNTH_TREES: dict = {}
+
+
 def cfg_text(name: str, width: int | None = None, height: int | None = None, batch: int = 1,
              tree_path: str | None = None, map_path: str | None = None, spec=None) -> str:
     """Darknet cfg text for one of SPECS (or an explicit spec list)."""
@@ -284,7 +315,13 @@ def cfg_text(name: str, width: int | None = None, height: int | None = None, bat
         elif kind == "avg":
             out += ["[avgpool]", ""]
         elif kind == "softmax":
-            out += ["[softmax]", "groups=1", ""]
+            o = e[1] if len(e) > 1 else {}
+            out += ["[softmax]", "groups=%d" % o.get("groups", 1)]
+            if "temperature" in o:
+                out.append("temperature=%r" % o["temperature"])
+            if o.get("tree"):                    # the hierarchical head: ("softmax", {"tree": path})
+                out.append("tree=%s" % (tree_path or synth_tree(o["tree"])))
+            out.append("")
         elif kind == "cost":
             out += ["[cost]", "type=sse", ""]
         else:

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-layer device time of one zoo network (engine timing events, median over iterations).
 usage: layer_times.py <net> [size] [batch] [iters=20] [top=0]      top > 0: only the `top` slowest layers
-<net> is one of zoo.SPECS or of zoo.LRN (the [normalization] / [activation] networks; size then scales both sides)"""
+<net> is one of zoo.SPECS, of zoo.LRN (the [normalization] / [activation] networks; size then scales both sides) or of
+zoo.HIER (the hierarchical classifiers, [softmax] tree=)"""
 import os
 import sys
 import tempfile
@@ -15,8 +16,9 @@ from sr_object_detection_amd import darknet, synth, zoo  # noqa: E402
 
 def main():
     name = sys.argv[1]
-    spec = zoo.LRN[name][3] if name in zoo.LRN else zoo.SPECS[name]
-    size = int(sys.argv[2]) if len(sys.argv) > 2 else (zoo.LRN[name][0] if name in zoo.LRN else zoo.DEFAULT_SIZE.get(name, 416))
+    spec = zoo.LRN[name][3] if name in zoo.LRN else (zoo.HIER[name][1] if name in zoo.HIER else zoo.SPECS[name])
+    size = int(sys.argv[2]) if len(sys.argv) > 2 else (zoo.LRN[name][0] if name in zoo.LRN else
+                                                       (zoo.HIER[name][0] if name in zoo.HIER else zoo.DEFAULT_SIZE.get(name, 416)))
     batch = int(sys.argv[3]) if len(sys.argv) > 3 else 1
     iters = int(sys.argv[4]) if len(sys.argv) > 4 else 20
     top = int(sys.argv[5]) if len(sys.argv) > 5 else 0
