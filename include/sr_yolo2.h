@@ -531,6 +531,66 @@ void y2_region_box_to_frame(const y2_region *item, int net_w, int net_h, int let
  * RecObjects[i] holds room for l.w*l.h*l.n objects.  net.batch >= n (set_batch_network). */
 void test_detector_regions(char **names, network net, const y2_region *items, int n, float thresh,
                            object **RecObjects, int *objectNumPerRegion);
+/* ------------------------------------------------------------------------- */
+/* The depth stage of the Kinect RGB-D loop, on the device behind the detect  */
+/* chain (KinectUtil_with_cam.cpp:394-442 drawDepth, :1866-1888                */
+/* colorImgFilterbyDistance, :1482-1562 caculateXYZinCameraSpace, :1632-1706   */
+/* objectBelong2Person).  All sums are integer sums (depth in 64 bits: the     */
+/* reference's `int` overflows on a full-frame box at ordinary ranges, which   */
+/* is not reproduced); the float steps are single IEEE operations.             */
+/* ------------------------------------------------------------------------- */
+typedef struct {
+    const uint16_t *depth;   /* dh x dw, millimetres */
+    const uint8_t  *body;    /* dh x dw, 1..6 = a tracked person, anything else none; NULL = no bodies */
+    const float    *map;     /* H x W x 2: (X, Y) in the depth frame for every colour pixel (MapColorFrameToDepthSpace);
+                                NULL = already registered: needs H == dh, W == dw, identity */
+    int dh, dw, H, W;
+} y2_depth_frame;
+/* One H2D copy (pinned staging, grow-only) + the alignment kernel, on the engine's stream.  Per colour pixel (:407-423):
+ * dx = (int)(X + 0.5f), dy likewise (truncation toward zero: X = -0.7 lands on column 0); inside [0,dw) x [0,dh):
+ * depth16 = depth, depth8 = (uint8_t)(depth >> 5), person = body (255 without a body frame); otherwise 0, 0, 255.  A
+ * coordinate that is not finite or outside int range is unmapped.  The planes stay in HBM until the next upload.
+ * dh, dw <= 32767. */
+int y2_depth_upload(network net, const y2_depth_frame *f);
+/* GetDepthFrameToCameraSpaceTable: dh x dw x 2 floats, sent once.  The SDK's MapDepthPointToCameraSpace is closed; this
+ * library DEFINES a depth-space point (px, py) at z metres to map to (tab[iy][ix].x * z, tab[iy][ix].y * z, z) with
+ * ix = (int)(px + 0.5f), iy likewise, and to (-inf, -inf, -inf) outside the table.  Without a table the camera fields
+ * of y2_det3d are (0, 0, -1, 0, 0).  tab == NULL drops the table. */
+int y2_depth_set_camera_table(network net, const float *tab, int dh, int dw);
+/* Fetch the aligned planes (H x W each; any pointer may be NULL). */
+int y2_depth_aligned(network net, uint16_t *depth16, uint8_t *depth8, uint8_t *person);
+
+/* Per-box result.  ROI (:1501-1504, y2_depth_roi); otsu = otsuThreshold of depth8 in the ROI (y2_otsu_threshold);
+ * mean_all_mm = sum(depth16) / n (KinectUtil.cpp:489-501); avg_mm = GetImgAvg(depth16, otsu * 32) - 16 (:1526, integer
+ * division); owner = the body label 1..6 with the most pixels (a tie goes to the lower label; the reference's answer
+ * depends on which label it meets first), belongs = (float)count / n > 0.5, body_id = that label or 255 (:1684-1703);
+ * pts = centre, top, bottom, left, right depth-space points of caculateXY (:1366-1452; the centre test compares depth8
+ * with otsu * 32 as the reference does); cam_* = :1540-1559 through the camera table.  An empty ROI (the reference
+ * would hit an OpenCV assertion) gives valid = 0, zeros and cam_z = -1. */
+typedef struct { int valid, left, top, right, bot, otsu, mean_all_mm; float avg_mm; int body_id, belongs;
+                 float cam_x, cam_y, cam_z, cam_w, cam_h; float pts[5][2]; } y2_det3d;
+/* otsuThreshold (:1564-1630) of a 256-bin histogram, the very code the kernel runs (include/y2_depth_rule.h). */
+int y2_otsu_threshold(const int hist[256]);
+/* The ROI of a frame-relative box in a W x H frame; returns 1 when it is not empty. */
+int y2_depth_roi(box b, int W, int H, int *left, int *top, int *right, int *bot);
+/* Statistics of n caller-given frame-relative boxes against the uploaded planes. */
+int y2_depth_boxes(network net, const box *boxes, int n, y2_det3d *out);
+/* y2_ingest_regions with the hand-crop distance filter fused into the source read: item i with far_m[i] > 0 (the caller
+ * passes jointDistance + 0.3) reads a source pixel at frame position (r, c) as 255 in every plane when
+ * depth8[r][c] <= 15 || (float)depth8[r][c] >= far_m * 1000 / 32 (fp32, that order, :1879).  far_m[i] <= 0: no filter;
+ * with every far_m <= 0 the input is bit-identical to y2_ingest_regions.  Refused before any device work, besides what
+ * y2_ingest_regions refuses: a filtered item with fewer than 3 channels, no uploaded depth frame, a filtered item whose
+ * frame is not the uploaded H x W. */
+int y2_ingest_regions_depth(network net, const y2_region *items, int n, const float *far_m, int swap_rb, int letterbox);
+/* y2_detect_regions with that ingest (far_m == NULL: no filter), and behind the detect chain, on the same stream with no
+ * host synchronisation in between, the statistics of every kept detection (its box mapped into its frame on the
+ * device): d3[i*max_per_item + j] belongs to dets[i*max_per_item + j].  Needs an uploaded depth frame. */
+int y2_detect_regions_depth(network net, const y2_region *items, int n, const float *far_m, int swap_rb, int letterbox,
+                            float thresh, float nms, y2_det *dets, y2_det3d *d3, int *counts, int max_per_item);
+/* test_detector_regions + the eight depth fields of `object`: CameraX/Y/Z, CameraWidth, CameraHeight,
+ * flagBelong2Person, bodyId (far_m == NULL: no filter). */
+void test_detector_regions_depth(char **names, network net, const y2_region *items, int n, const float *far_m, float thresh,
+                                 object **RecObjects, int *objectNumPerRegion);
 /* Copy layer i's activations to host as NCHW [batch][out_c][out_h][out_w] (or [batch][outputs]). */
 int y2_pull_layer_output(network net, int i, float *dst);
 /* Per-layer device time of the last forward in ms (needs y2_set_timing(net,1)); returns layers written. */

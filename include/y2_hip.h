@@ -416,6 +416,63 @@ typedef struct y2h_region {
 int y2h_regions_to_input(const y2h_region *desc, int n, const unsigned char *pixels, int batch, int planes, int swap_rb,
                          int h, int w, float *dst, y2h_stream s);
 
+/* One item of y2h_regions_to_input_filtered: a y2h_region plus where its first pixel sits in the frame the aligned
+ * depth8 plane belongs to, and the hand-crop distance filter of KinectUtil_with_cam.cpp:1866-1888.  filter == 0: the
+ * item is read exactly as y2h_regions_to_input reads it. */
+typedef struct y2h_region_f {
+    y2h_region r;
+    int fx, fy;                 /* frame position of the region's pixel (0, 0) */
+    int filter;                 /* 1: a source pixel reads as 255 in every plane where y2_depth_whitens(depth8, far_limit) */
+    float far_limit;            /* y2_far_limit(far_m), computed on the host in fp32 */
+} y2h_region_f;
+
+/* y2h_regions_to_input with that filter on the source read; depth8 is the H x W plane of y2h_depth_align (may be NULL
+ * when no item filters), W its row length.  With every filter == 0 the result is bit-identical to y2h_regions_to_input. */
+int y2h_regions_to_input_filtered(const y2h_region_f *desc, int n, const unsigned char *pixels, const unsigned char *depth8,
+                                  int W, int batch, int planes, int swap_rb, int h, int w, float *dst, y2h_stream s);
+
+/* ---- depth stage of the Kinect loop (y2_depth.hip; KinectUtil_with_cam.cpp:394-442, :1482-1706) ---- */
+/* Register a dh x dw depth frame (and body-index frame, or NULL) to the H x W colour frame: for every colour pixel
+ * (dx, dy) = y2_depth_coord of map[pixel] (NULL map: the pixel's own position, H == dh and W == dw); inside the depth
+ * frame depth16 = depth, depth8 = depth >> 5, person = body (255 without one), dxy = (dx, dy); otherwise 0, 0, 255,
+ * (-1, -1).  Streams 8 bytes of map in and 8 bytes of planes out per colour pixel. */
+int y2h_depth_align(const unsigned short *depth, const unsigned char *body, const float *map, int dh, int dw, int H, int W,
+                    unsigned short *depth16, unsigned char *depth8, unsigned char *person, short *dxy, y2h_stream s);
+
+/* How the boxes of y2h_depth_boxes reach their frame: item b's boxes are mapped with these values by the expressions
+ * of y2_region_box_to_frame in fp32 in the same order.  letterbox == 0 skips the first step, whole != 0 the second. */
+typedef struct y2h_box_map {
+    int letterbox, whole;
+    int net_w, net_h, nw, nh;
+    int rx, ry, rw, rh, fw, fh;
+} y2h_box_map;
+
+/* what y2h_depth_boxes writes per box: sr_yolo2.h y2_det3d, field for field */
+typedef struct y2h_det3d {
+    int valid, left, top, right, bot, otsu, mean_all_mm; float avg_mm; int body_id, belongs;
+    float cam_x, cam_y, cam_z, cam_w, cam_h; float pts[5][2];
+} y2h_det3d;
+
+typedef struct y2h_depth_planes {
+    const unsigned short *depth16; const unsigned char *depth8, *person;
+    const short *dxy;           /* NULL: identity (the frame was registered already) */
+    const float *cam_table;     /* dh x dw x 2, or NULL */
+    int H, W, dh, dw;
+} y2h_depth_planes;
+
+unsigned long y2h_depth_acc_bytes(void);     /* bytes of accumulator scratch per box */
+/* Statistics of `items * per_item` box slots.  Slot (b, j) holds a box when j < min(counts[b], per_item) (counts == NULL:
+ * every slot does); its box is the first four floats of boxes[(b * stride_item + j) * stride_box ...], mapped by maps[b]
+ * (maps == NULL: used as it is).  The launch needs no count on the host: its size does not grow with the slots (up to 64
+ * workgroups share a box, 128 rows of them walk the slots and skip the empty ones after one read of the count).  Results
+ * are written DENSELY: item b's records follow item b-1's, out[sum_{i<b} min(counts[i], per_item) + j]; with counts ==
+ * NULL that is out[b * per_item + j].  acc: items * per_item * y2h_depth_acc_bytes() of scratch.  `stages` selects what
+ * is enqueued (Y2H_DEPTH_ALL for a result; single stages exist to be timed): clear the scratch, pass 1 over each ROI,
+ * pass 2, finalise.  No synchronisation. */
+enum { Y2H_DEPTH_CLEAR = 1, Y2H_DEPTH_PASS1 = 2, Y2H_DEPTH_PASS2 = 4, Y2H_DEPTH_FINALISE = 8, Y2H_DEPTH_ALL = 15 };
+int y2h_depth_boxes(const y2h_depth_planes *p, const float *boxes, int stride_box, long stride_item, const int *counts,
+                    const y2h_box_map *maps, int items, int per_item, void *acc, y2h_det3d *out, int stages, y2h_stream s);
+
 /* ---- classifier views (classifier.c:336-593 valid10 / validmulti / validfull) ---- */
 /* One view of y2h_views_to_input: a w x h window of a CHW fp32 source image that becomes batch slot b of the network
  * input.  The window's top-left corner sits at (dx, dy) of the source; both may be negative or reach past the source. */

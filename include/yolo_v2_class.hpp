@@ -39,6 +39,27 @@ struct frame_region_t {
     int x, y, rw, rh;
 };
 
+// One detection of Detector::detect_regions_depth: the box as detect_regions returns it, and where it is in depth
+// (sr_yolo2.h y2_det3d: camera-space centre, width and height in metres, the thresholded mean depth, the owner).
+struct bbox3d_t {
+    bbox_t box;
+    bool valid;                  // false: the box's ROI in the colour frame is empty
+    float x, y, z;               // CameraX / CameraY / CameraZ, (0, 0, -1) when the point cannot be mapped
+    float width, height;         // CameraWidth / CameraHeight
+    float avg_mm;                // thresholded mean depth - 16 (millimetres)
+    int otsu;                    // Otsu threshold of the 8-bit depth inside the box
+    bool belongs_to_person;      // flagBelong2Person
+    int body_id;                 // bodyId: 1..6, or 255
+};
+
+// A depth frame for Detector::upload_depth (sr_yolo2.h y2_depth_frame).
+struct depth_frame_t {
+    const unsigned short *depth;     // dh x dw, millimetres
+    const unsigned char *body;       // dh x dw body index, or nullptr
+    const float *map;                // H x W x 2 colour -> depth coordinates, or nullptr for a registered frame
+    int dh, dw, H, W;
+};
+
 struct image_t {
     int h, w, c;                 // CHW planes
     float *data;                 // values in [0,1]
@@ -74,6 +95,16 @@ public:
     // while in use, and detect / detect_frame / use_mean / tracking keep their own batch-1 network untouched.
     YOLODLL_API std::vector<std::vector<bbox_t>> detect_regions(const std::vector<frame_region_t> &items,
                                                                 float thresh = 0.2f, bool bgr = true);
+
+    // Extension: the depth stage of the Kinect loop behind detect_regions (y2_depth_upload / y2_depth_set_camera_table /
+    // y2_detect_regions_depth).  upload_depth registers the depth and body-index frames to the colour frame on the device;
+    // detect_regions_depth is detect_regions with the hand-crop distance filter on the items whose far_m is > 0 (far_m
+    // empty: none) and, for every box, its depth statistics, computed on the device behind the detect chain.
+    YOLODLL_API void upload_depth(const depth_frame_t &frame, int max_items = 3);
+    YOLODLL_API void set_camera_table(const float *table, int dh, int dw);
+    YOLODLL_API std::vector<std::vector<bbox3d_t>> detect_regions_depth(const std::vector<frame_region_t> &items,
+                                                                        const std::vector<float> &far_m = std::vector<float>(),
+                                                                        float thresh = 0.2f, bool bgr = true);
 
 #ifdef OPENCV
     // The OpenCV convenience surface of the reference (yolo_v2_class.hpp:59-92), same names, signatures and results, so

@@ -16,6 +16,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "y2_internal.h"
+#include "y2_depth_rule.h"
 
 /* get_region_boxes: l.output is a HOST pointer the caller may have replaced
  * (yolo_v2_class.cpp:211 substitutes the 3-frame mean).  When it still is the
@@ -666,17 +667,21 @@ static int regions_check(const char *who, network net, const y2_region *items, i
     return 0;
 }
 
-static int ingest_regions(const char *who, network net, const y2_region *items, int n, int swap_rb, int letterbox)
+/* far_m == NULL: the plain ingest.  Otherwise the table holds y2h_region_f entries and the kernel with the hand-crop
+ * distance filter on its source read runs (item i is filtered when far_m[i] > 0, against the aligned depth8 plane of the
+ * last y2_depth_upload). */
+static int ingest_regions(const char *who, network net, const y2_region *items, int n, const float *far_m, int swap_rb, int letterbox)
 {
     y2_engine *e;
-    y2h_region *desc;
+    const size_t desc_size = far_m ? sizeof(y2h_region_f) : sizeof(y2h_region);
     size_t desc_bytes, pix_bytes = 0, off, need;
     int i, r;
     if (regions_check(who, net, items, n, letterbox) != 0) return -1;
+    if (far_m && y2_depth_filter_check(who, net, items, n, far_m) != 0) return -1;
     if (y2_prepare(&net) != 0) return -1;
     e = y2_engine_of(&net);
     HIP_OR_ERR(y2h_set_device(e->device));
-    desc_bytes = ((size_t)n * sizeof(y2h_region) + 63) & ~(size_t)63;
+    desc_bytes = ((size_t)n * desc_size + 63) & ~(size_t)63;
     for (i = 0; i < n; ++i) {
         int x, y, rw, rh;
         region_rect(&items[i], &x, &y, &rw, &rh);
@@ -692,12 +697,11 @@ static int ingest_regions(const char *who, network net, const y2_region *items, 
     }
     if (grow((void **)&e->d_reg, &e->reg_cap, need)) { y2_fail("%s: %s", who, y2h_last_error()); return -1; }
     if (!e->ev_reg) HIP_OR_ERR(y2h_event_create(&e->ev_reg));
-    desc = (y2h_region *)e->h_reg_stage;
-    memset(desc, 0, desc_bytes);
+    memset(e->h_reg_stage, 0, desc_bytes);
     off = 0;
     for (i = 0; i < n; ++i) {
         const y2_region *it = &items[i];
-        y2h_region *d = &desc[i];
+        y2h_region *d = (y2h_region *)(e->h_reg_stage + (size_t)i * desc_size);     /* y2h_region_f starts with one */
         int x, y, rw, rh, nw = net.w, nh = net.h;
         size_t row;
         region_rect(it, &x, &y, &rw, &rh);
@@ -711,6 +715,12 @@ static int ingest_regions(const char *who, network net, const y2_region *items, 
         d->dx = (net.w - nw) / 2; d->dy = (net.h - nh) / 2;
         d->w_scale = (float)(rw - 1) / (nw - 1);           /* as y2h_resize_chw */
         d->h_scale = (float)(rh - 1) / (nh - 1);
+        if (far_m) {
+            y2h_region_f *f = (y2h_region_f *)d;
+            f->fx = x; f->fy = y;
+            f->filter = far_m[i] > 0;
+            f->far_limit = y2_far_limit(far_m[i]);
+        }
         for (r = 0; r < rh; ++r)
             memcpy(e->h_reg_stage + desc_bytes + off + (size_t)r * row, it->data + (size_t)(y + r) * it->step + (size_t)x * it->c, row);
         off += row * rh;
@@ -718,6 +728,13 @@ static int ingest_regions(const char *who, network net, const y2_region *items, 
     HIP_OR_ERR(y2h_memcpy_h2d(e->d_reg, e->h_reg_stage, need, e->stream));
     HIP_OR_ERR(y2h_event_record(e->ev_reg, e->stream));
     e->reg_pending = 1;
+    if (far_m) {
+        int W = 0;
+        const unsigned char *depth8 = y2_depth_plane8(e, &W);
+        HIP_OR_ERR(y2h_regions_to_input_filtered((const y2h_region_f *)e->d_reg, n, e->d_reg + desc_bytes, depth8, W, net.batch, net.c,
+                                                swap_rb, net.h, net.w, e->d_in_nchw, e->stream));
+        return 0;
+    }
     HIP_OR_ERR(y2h_regions_to_input((const y2h_region *)e->d_reg, n, e->d_reg + desc_bytes, net.batch, net.c, swap_rb, net.h, net.w,
                                    e->d_in_nchw, e->stream));
     return 0;
@@ -725,7 +742,33 @@ static int ingest_regions(const char *who, network net, const y2_region *items, 
 
 int y2_ingest_regions(network net, const y2_region *items, int n, int swap_rb, int letterbox)
 {
-    return ingest_regions("y2_ingest_regions", net, items, n, swap_rb, letterbox);
+    return ingest_regions("y2_ingest_regions", net, items, n, NULL, swap_rb, letterbox);
+}
+
+/* what y2_depth.c needs of this file */
+int y2_ingest_regions_far(const char *who, network net, const y2_region *items, int n, const float *far_m, int swap_rb, int letterbox)
+{
+    return ingest_regions(who, net, items, n, far_m, swap_rb, letterbox);
+}
+void y2_region_rect(const y2_region *it, int *x, int *y, int *rw, int *rh) { region_rect(it, x, y, rw, rh); }
+int y2_regions_check(const char *who, network net, const y2_region *items, int n, int letterbox) { return regions_check(who, net, items, n, letterbox); }
+int y2_detect_chain_enqueue(network net, float thresh, float nms) { return detect_enqueue(net, NULL, thresh, nms, 1, 1); }
+int y2_detect_chain_fetch(network net, y2_det *dets, int *counts, int max_per_item, int items) { return detect_fetch_items(net, dets, counts, max_per_item, items); }
+/* draw_detections_test (image.c:662-738) for one detection: what test_detector_regions and test_detector_regions_depth
+ * put into an `object` */
+void y2_fill_object(object *o, const y2_det *d, char **names, int classes)
+{
+    int cls = d->obj_id;
+    int offset = cls * 123457 % classes;
+    if (names) printf("%s: %.0f%%\n", names[cls], d->prob * 100);
+    o->x = d->x; o->y = d->y; o->w = d->w; o->h = d->h;
+    o->prob = d->prob;
+    o->objClass = cls;
+    if (names && names[cls]) { strncpy(o->name, names[cls], sizeof o->name - 1); o->name[sizeof o->name - 1] = 0; }
+    else o->name[0] = 0;
+    o->boxRGB[0] = get_color(2, offset, classes);
+    o->boxRGB[1] = get_color(1, offset, classes);
+    o->boxRGB[2] = get_color(0, offset, classes);
 }
 
 void y2_region_box_to_frame(const y2_region *item, int net_w, int net_h, int letterbox, float *x, float *y, float *w, float *h)
@@ -752,7 +795,7 @@ int y2_detect_regions(network net, const y2_region *items, int n, int swap_rb, i
 {
     int i, j;
     if (!dets || !counts || max_per_item < 1) { y2_fail("y2_detect_regions: needs dets, counts and max_per_item >= 1"); return -1; }
-    if (ingest_regions("y2_detect_regions", net, items, n, swap_rb, letterbox) != 0) return -1;
+    if (ingest_regions("y2_detect_regions", net, items, n, NULL, swap_rb, letterbox) != 0) return -1;
     if (y2_forward_device(net, NULL) != 0) return -1;
     if (detect_enqueue(net, NULL, thresh, nms, 1, 1) != 0 || detect_fetch_items(net, dets, counts, max_per_item, n) != 0) return -1;
     for (i = 0; i < n; ++i) {
@@ -783,19 +826,7 @@ void test_detector_regions(char **names, network net, const y2_region *items, in
     for (i = 0; i < n; ++i) {
         const int kept = counts[i] < total ? counts[i] : total;
         for (j = 0; j < kept; ++j) {
-            const y2_det *d = &dets[(size_t)i * total + j];
-            object *o = &RecObjects[i][objectNumPerRegion[i]];
-            int cls = d->obj_id;
-            int offset = cls * 123457 % l.classes;
-            if (names) printf("%s: %.0f%%\n", names[cls], d->prob * 100);
-            o->x = d->x; o->y = d->y; o->w = d->w; o->h = d->h;
-            o->prob = d->prob;
-            o->objClass = cls;
-            if (names && names[cls]) { strncpy(o->name, names[cls], sizeof o->name - 1); o->name[sizeof o->name - 1] = 0; }
-            else o->name[0] = 0;
-            o->boxRGB[0] = get_color(2, offset, l.classes);
-            o->boxRGB[1] = get_color(1, offset, l.classes);
-            o->boxRGB[2] = get_color(0, offset, l.classes);
+            y2_fill_object(&RecObjects[i][objectNumPerRegion[i]], &dets[(size_t)i * total + j], names, l.classes);
             objectNumPerRegion[i]++;
         }
     }

@@ -158,6 +158,7 @@ typedef struct y2_engine {
      * arena (the same, the resized copies, the resize scratch, the block's accumulators) */
     unsigned char *h_tta, *d_tta;
     size_t h_tta_cap, d_tta_cap;
+    struct y2_depth_state *depth;      /* the depth stage's planes and scratch (y2_depth.c), NULL until the first upload */
     /* timing */
     y2h_event *ev;             /* n+1 events */
     int n_ev;
@@ -238,6 +239,17 @@ int y2_rec_forward(network *net, int i, const float *x);
 
 /* text generation / scoring (y2_chargen.c) */
 void y2_chargen_free(y2_engine *e);
+
+/* regions (y2_detect.c) and the depth stage behind them (y2_depth.c) */
+int y2_ingest_regions_far(const char *who, network net, const y2_region *items, int n, const float *far_m, int swap_rb, int letterbox);
+void y2_region_rect(const y2_region *it, int *x, int *y, int *rw, int *rh);
+int y2_regions_check(const char *who, network net, const y2_region *items, int n, int letterbox);
+int y2_detect_chain_enqueue(network net, float thresh, float nms);
+int y2_detect_chain_fetch(network net, y2_det *dets, int *counts, int max_per_item, int items);
+void y2_fill_object(object *o, const y2_det *d, char **names, int classes);
+int y2_depth_filter_check(const char *who, network net, const y2_region *items, int n, const float *far_m);
+const unsigned char *y2_depth_plane8(const y2_engine *e, int *W);
+void y2_depth_free(y2_engine *e);
 
 /* cfg helpers shared with other files */
 char *y2_fgetl(FILE *fp);

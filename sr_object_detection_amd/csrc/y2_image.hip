@@ -8,6 +8,7 @@
 // the layout allows.  The arithmetic (a single double division rounded to fp32, copies) is
 // bit-identical to the C code.
 #include "y2_common.hpp"
+#include "y2_depth_rule.h"
 
 // dst[k][y][x] = (float)( src[y*step + x*c + sk] / 255. ), sk = k with planes 0 and 2 exchanged when swap_rb.
 // One thread per output pixel; the c source bytes of a pixel are read once and fanned out to the planes.
@@ -131,6 +132,8 @@ __device__ __forceinline__ float region_col(const RegionPix &p, int col, int iw,
     return (1 - dx) * p.at(ix) + dx * p.at(ix + 1);
 }
 
+// NOTE: regions_to_input_filtered_kernel below is this kernel with one changed source read and must stay so, expression
+// for expression (tests/test_gpu_depth.py::test_filter_off_is_ingest_regions compares them): edit both together.
 __global__ __launch_bounds__(256) void regions_to_input_kernel(const y2h_region *__restrict__ desc, int n,
                                                                const unsigned char *__restrict__ pixels, int planes,
                                                                int swap_rb, int h, int w, int vec, float *__restrict__ dst)
@@ -194,6 +197,109 @@ extern "C" int y2h_regions_to_input(const y2h_region *desc, int n, const unsigne
     const long groups = (long)h * ((w + 3) / 4);
     hipLaunchKernelGGL(regions_to_input_kernel, dim3((unsigned)((groups + 255) / 256), (unsigned)batch), dim3(256), 0, S(s),
                        desc, n, pixels, planes, swap_rb, h, w, vec, dst);
+    Y2H_LAUNCH_CHECK();
+    return Y2H_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The same chain with the hand-crop distance filter (KinectUtil_with_cam.cpp:1866-1888, applied at :1022 / :1066 before
+// the crop goes to the detector) on the source read: a pixel whose aligned 8-bit depth says "no depth" or "farther than
+// the hand" reads as 255 in every plane.  Only the read differs, so an item without a filter -- and the padded slots --
+// are formed by exactly the expressions of regions_to_input_kernel.
+// ---------------------------------------------------------------------------
+struct RegionPixF {                      // one source row of a region, one plane, with the row of depth8 under it
+    const unsigned char *row;
+    int c;
+    const float *lut;
+    const unsigned char *depth;          // depth8 under the region's pixel (row, 0), or NULL: no filter
+    float far_limit;
+    __device__ float at(int j) const
+    {
+        if (depth && y2_depth_whitens(depth[j], far_limit)) return lut[255];
+        return lut[row[(size_t)j * c]];
+    }
+};
+
+__device__ __forceinline__ float region_col_f(const RegionPixF &p, int col, int iw, int nw, float w_scale)
+{
+    if (col == nw - 1 || iw == 1) return p.at(iw - 1);
+    const float sx = col * w_scale;
+    const float dx = sx - (int)sx;
+    const int ix = min((int)sx, iw - 2);
+    return (1 - dx) * p.at(ix) + dx * p.at(ix + 1);
+}
+
+__global__ __launch_bounds__(256) void regions_to_input_filtered_kernel(const y2h_region_f *__restrict__ desc, int n,
+                                                                        const unsigned char *__restrict__ pixels,
+                                                                        const unsigned char *__restrict__ depth8, int W,
+                                                                        int planes, int swap_rb, int h, int w, int vec,
+                                                                        float *__restrict__ dst)
+{
+    __shared__ float lut[256];
+    const int b = blockIdx.y;
+    const long gw = (w + 3) / 4;
+    const long g = (long)blockIdx.x * 256 + threadIdx.x;
+    const int Y = (int)(g / gw), X0 = (int)(g - (long)Y * gw) * 4;
+    const size_t plane = (size_t)h * w;
+    float *o = dst + (size_t)b * planes * plane + (size_t)Y * w + X0;
+    const int nx = min(4, w - X0);
+    if (b >= n) {                        // padded slot: deterministic zeros (uniform per block)
+        if (Y >= h) return;
+        for (int k = 0; k < planes; ++k) {
+            if (vec) *(float4 *)(o + k * plane) = make_float4(0.f, 0.f, 0.f, 0.f);
+            else for (int i = 0; i < nx; ++i) o[k * plane + i] = 0.f;
+        }
+        return;
+    }
+    lut[threadIdx.x] = (float)((double)threadIdx.x / 255.);
+    __syncthreads();
+    if (Y >= h) return;
+    const y2h_region_f df = desc[b];
+    const y2h_region d = df.r;
+    const unsigned char *src = pixels + d.src;
+    const int y = Y - d.dy;
+    const bool row_in = y >= 0 && y < d.nh;
+    int iy = 0;
+    float dy = 0.f;
+    bool two = false;
+    if (row_in) {
+        const float sy = y * d.h_scale;
+        iy = min(max((int)sy, 0), d.ih - 1);
+        dy = sy - (int)sy;
+        two = !(y == d.nh - 1 || d.ih == 1);
+    }
+    const int iy1 = min(iy + 1, d.ih - 1);
+    const bool filt = df.filter && depth8;
+    const unsigned char *z0 = filt ? depth8 + (size_t)(df.fy + iy) * W + df.fx : nullptr;
+    const unsigned char *z1 = filt ? depth8 + (size_t)(df.fy + iy1) * W + df.fx : nullptr;
+    for (int k = 0; k < planes; ++k) {
+        int sk = k;
+        if (swap_rb && d.c >= 3) sk = (k == 0) ? 2 : (k == 2 ? 0 : k);
+        const RegionPixF p0{src + (size_t)iy * d.pitch + sk, d.c, lut, z0, df.far_limit};
+        const RegionPixF p1{src + (size_t)iy1 * d.pitch + sk, d.c, lut, z1, df.far_limit};
+        float v[4];
+        for (int i = 0; i < 4; ++i) {
+            const int x = X0 + i - d.dx;
+            if (i >= nx || !row_in || x < 0 || x >= d.nw) { v[i] = .5f; continue; }
+            float val = (1 - dy) * region_col_f(p0, x, d.iw, d.nw, d.w_scale);
+            if (two) val = val + dy * region_col_f(p1, x, d.iw, d.nw, d.w_scale);
+            v[i] = val;
+        }
+        if (vec) *(float4 *)(o + k * plane) = make_float4(v[0], v[1], v[2], v[3]);
+        else for (int i = 0; i < nx; ++i) o[k * plane + i] = v[i];
+    }
+}
+
+extern "C" int y2h_regions_to_input_filtered(const y2h_region_f *desc, int n, const unsigned char *pixels,
+                                             const unsigned char *depth8, int W, int batch, int planes, int swap_rb, int h,
+                                             int w, float *dst, y2h_stream s)
+{
+    if (!desc || !pixels || !dst || n < 0 || n > batch || batch <= 0 || planes <= 0 || h <= 0 || w <= 0 || (depth8 && W <= 0))
+        return Y2H_EINVAL;
+    const int vec = (w % 4 == 0) && ((uintptr_t)dst % 16 == 0);
+    const long groups = (long)h * ((w + 3) / 4);
+    hipLaunchKernelGGL(regions_to_input_filtered_kernel, dim3((unsigned)((groups + 255) / 256), (unsigned)batch), dim3(256), 0,
+                       S(s), desc, n, pixels, depth8, W, planes, swap_rb, h, w, vec, dst);
     Y2H_LAUNCH_CHECK();
     return Y2H_OK;
 }

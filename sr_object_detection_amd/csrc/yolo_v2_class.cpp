@@ -175,12 +175,10 @@ std::vector<bbox_t> Detector::detect_frame(const unsigned char *data, int w, int
     return out;
 }
 
-std::vector<std::vector<bbox_t>> Detector::detect_regions(const std::vector<frame_region_t> &items, float thresh, bool bgr)
+namespace {
+// the second network detect_regions runs on, with room for n items (created at the first use, grows only)
+void regions_net_for(DetectorState &st, int n)
 {
-    DeviceGuard guard;
-    DetectorState &st = state_of(detector_gpu_ptr);
-    const int n = (int)items.size();
-    if (n < 1) throw std::runtime_error("detect_regions: no items");
     if (st.regions_batch == 0) {
         const int saved = gpu_index;
         gpu_index = st.gpu_id;
@@ -190,10 +188,20 @@ std::vector<std::vector<bbox_t>> Detector::detect_regions(const std::vector<fram
         st.regions_net.gpu_index = st.gpu_id;
         if (!st.weights.empty()) load_weights(&st.regions_net, const_cast<char *>(st.weights.c_str()));
     }
-    if (n > st.regions_batch) {                  // grows only: the plan is rebuilt at the next call into the engine
+    if (n > st.regions_batch) {
         set_batch_network(&st.regions_net, n);
         st.regions_batch = n;
     }
+}
+}  // namespace
+
+std::vector<std::vector<bbox_t>> Detector::detect_regions(const std::vector<frame_region_t> &items, float thresh, bool bgr)
+{
+    DeviceGuard guard;
+    DetectorState &st = state_of(detector_gpu_ptr);
+    const int n = (int)items.size();
+    if (n < 1) throw std::runtime_error("detect_regions: no items");
+    regions_net_for(st, n);
     std::vector<y2_region> r(n);
     for (int i = 0; i < n; ++i) {
         const frame_region_t &f = items[i];
@@ -212,6 +220,64 @@ std::vector<std::vector<bbox_t>> Detector::detect_regions(const std::vector<fram
         for (int j = 0; j < std::min(st.regions_counts[i], total); ++j) {
             const y2_det &d = st.regions_dets[(size_t)i * total + j];
             out[i].push_back(to_bbox(d.x, d.y, d.w, d.h, d.prob, d.obj_id, items[i].w, items[i].h));
+        }
+    return out;
+}
+
+void Detector::upload_depth(const depth_frame_t &frame, int max_items)
+{
+    DeviceGuard guard;
+    DetectorState &st = state_of(detector_gpu_ptr);
+    regions_net_for(st, std::max(max_items, 1));
+    y2_depth_frame f;
+    f.depth = frame.depth; f.body = frame.body; f.map = frame.map;
+    f.dh = frame.dh; f.dw = frame.dw; f.H = frame.H; f.W = frame.W;
+    if (y2_depth_upload(st.regions_net, &f) != 0) throw std::runtime_error(y2_last_error());
+}
+
+void Detector::set_camera_table(const float *table, int dh, int dw)
+{
+    DeviceGuard guard;
+    DetectorState &st = state_of(detector_gpu_ptr);
+    regions_net_for(st, 1);
+    if (y2_depth_set_camera_table(st.regions_net, table, dh, dw) != 0) throw std::runtime_error(y2_last_error());
+}
+
+std::vector<std::vector<bbox3d_t>> Detector::detect_regions_depth(const std::vector<frame_region_t> &items,
+                                                                  const std::vector<float> &far_m, float thresh, bool bgr)
+{
+    DeviceGuard guard;
+    DetectorState &st = state_of(detector_gpu_ptr);
+    const int n = (int)items.size();
+    if (n < 1) throw std::runtime_error("detect_regions_depth: no items");
+    if (!far_m.empty() && (int)far_m.size() != n) throw std::runtime_error("detect_regions_depth: far_m needs one value per item");
+    regions_net_for(st, n);              // the depth planes belong to this network's engine and survive its growth
+    std::vector<y2_region> r(n);
+    for (int i = 0; i < n; ++i) {
+        const frame_region_t &f = items[i];
+        r[i].data = f.data; r[i].h = f.h; r[i].w = f.w; r[i].c = f.c; r[i].step = f.step;
+        r[i].x = f.x; r[i].y = f.y; r[i].rw = f.rw; r[i].rh = f.rh;
+    }
+    const layer &last = st.regions_net.layers[st.regions_net.n - 1];
+    const int total = std::max(last.w * last.h * last.n, 1);
+    st.regions_dets.resize((size_t)n * total);
+    st.regions_counts.assign(n, 0);
+    std::vector<y2_det3d> d3((size_t)n * total);
+    if (y2_detect_regions_depth(st.regions_net, r.data(), n, far_m.empty() ? nullptr : far_m.data(), bgr ? 1 : 0, 0, thresh, nms,
+                                st.regions_dets.data(), d3.data(), st.regions_counts.data(), total) != 0)
+        throw std::runtime_error(y2_last_error());
+    std::vector<std::vector<bbox3d_t>> out(n);
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < std::min(st.regions_counts[i], total); ++j) {
+            const y2_det &d = st.regions_dets[(size_t)i * total + j];
+            const y2_det3d &t = d3[(size_t)i * total + j];
+            bbox3d_t b;
+            b.box = to_bbox(d.x, d.y, d.w, d.h, d.prob, d.obj_id, items[i].w, items[i].h);
+            b.valid = t.valid != 0;
+            b.x = t.cam_x; b.y = t.cam_y; b.z = t.cam_z; b.width = t.cam_w; b.height = t.cam_h;
+            b.avg_mm = t.avg_mm; b.otsu = t.otsu;
+            b.belongs_to_person = t.belongs != 0; b.body_id = t.body_id;
+            out[i].push_back(b);
         }
     return out;
 }

@@ -113,6 +113,18 @@ class Region(C.Structure):   # include/sr_yolo2.h y2_region
                 ("x", C.c_int), ("y", C.c_int), ("rw", C.c_int), ("rh", C.c_int)]
 
 
+class DepthFrame(C.Structure):   # include/sr_yolo2.h y2_depth_frame
+    _fields_ = [("depth", C.c_void_p), ("body", C.c_void_p), ("map", C.c_void_p), ("dh", C.c_int), ("dw", C.c_int),
+                ("H", C.c_int), ("W", C.c_int)]
+
+
+class Det3d(C.Structure):        # include/sr_yolo2.h y2_det3d
+    _fields_ = [("valid", C.c_int), ("left", C.c_int), ("top", C.c_int), ("right", C.c_int), ("bot", C.c_int),
+                ("otsu", C.c_int), ("mean_all_mm", C.c_int), ("avg_mm", C.c_float), ("body_id", C.c_int),
+                ("belongs", C.c_int), ("cam_x", C.c_float), ("cam_y", C.c_float), ("cam_z", C.c_float),
+                ("cam_w", C.c_float), ("cam_h", C.c_float), ("pts", (C.c_float * 2) * 5)]
+
+
 class View(C.Structure):     # include/y2_hip.h y2h_view: one view of y2h_views_to_input
     _fields_ = [("src", C.c_longlong), ("sw", C.c_int), ("sh", C.c_int), ("dx", C.c_int), ("dy", C.c_int),
                 ("flip", C.c_int), ("pad_", C.c_int)]
@@ -134,6 +146,10 @@ REC_SKINNY_MAX_ROWS = 8
 Y2H_EINVAL = -2
 
 DET_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("w", "<f4"), ("h", "<f4"), ("prob", "<f4"), ("obj_id", "<i4")])
+
+DET3D_DTYPE = np.dtype([("valid", "<i4"), ("left", "<i4"), ("top", "<i4"), ("right", "<i4"), ("bot", "<i4"), ("otsu", "<i4"),
+                        ("mean_all_mm", "<i4"), ("avg_mm", "<f4"), ("body_id", "<i4"), ("belongs", "<i4"), ("cam_x", "<f4"),
+                        ("cam_y", "<f4"), ("cam_z", "<f4"), ("cam_w", "<f4"), ("cam_h", "<f4"), ("pts", "<f4", (5, 2))])
 
 LAYER_TYPES = ["CONVOLUTIONAL", "DECONVOLUTIONAL", "CONNECTED", "MAXPOOL", "SOFTMAX", "DETECTION", "DROPOUT", "CROP",
                "ROUTE", "COST", "NORMALIZATION", "AVGPOOL", "LOCAL", "SHORTCUT", "ACTIVE", "RNN", "GRU", "CRNN",
@@ -205,6 +221,17 @@ def lib():
     L.y2_region_box_to_frame.argtypes = [C.POINTER(Region), C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_float)] * 4
     L.test_detector_regions.argtypes = [C.POINTER(C.c_char_p), CNetwork, C.POINTER(Region), C.c_int, C.c_float,
                                         C.POINTER(C.POINTER(Object)), C.POINTER(C.c_int)]
+    L.y2_depth_upload.argtypes = [CNetwork, C.POINTER(DepthFrame)]
+    L.y2_depth_set_camera_table.argtypes = [CNetwork, C.c_void_p, C.c_int, C.c_int]
+    L.y2_depth_aligned.argtypes = [CNetwork, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.y2_otsu_threshold.argtypes = [C.c_void_p]
+    L.y2_depth_roi.argtypes = [Box, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 4
+    L.y2_depth_boxes.argtypes = [CNetwork, C.c_void_p, C.c_int, C.c_void_p]
+    L.y2_ingest_regions_depth.argtypes = [CNetwork, C.POINTER(Region), C.c_int, C.c_void_p, C.c_int, C.c_int]
+    L.y2_detect_regions_depth.argtypes = [CNetwork, C.POINTER(Region), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float,
+                                          C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.test_detector_regions_depth.argtypes = [C.POINTER(C.c_char_p), CNetwork, C.POINTER(Region), C.c_int, C.c_void_p,
+                                              C.c_float, C.POINTER(C.c_void_p), C.c_void_p]
     L.y2h_u8_to_planes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int,
                                    C.c_void_p, C.c_void_p]
     L.top_predictions.argtypes = [CNetwork, C.c_int, C.c_void_p]
@@ -385,6 +412,21 @@ def d2h_copies() -> int:
 def stream_syncs() -> int:
     """y2h_stream_sync calls so far: the host waits of this process"""
     return int(lib().y2h_stream_syncs())
+
+
+def otsu_threshold(hist) -> int:
+    """y2_otsu_threshold: otsuThreshold (KinectUtil_with_cam.cpp:1564-1630) of a 256-bin histogram, on the host"""
+    h = np.ascontiguousarray(hist, dtype=np.int32)
+    if h.shape != (256,):
+        raise ValueError("a histogram has 256 bins")
+    return int(lib().y2_otsu_threshold(_ptr(h)))
+
+
+def depth_roi(box, W: int, H: int):
+    """y2_depth_roi: (valid, left, top, right, bot) of a frame-relative (x, y, w, h) box in a W x H frame"""
+    v = [C.c_int(0) for _ in range(4)]
+    ok = lib().y2_depth_roi(Box(*[float(np.float32(b)) for b in box]), W, H, *[C.byref(t) for t in v])
+    return (int(ok),) + tuple(t.value for t in v)
 
 
 def region_box_to_frame(item, net_w: int, net_h: int, letterbox: bool, box):
@@ -763,6 +805,79 @@ class Network:
                                    cap) != 0:
             raise Y2Error(_check())
         return [dets[i, :min(int(counts[i]), cap)].copy() for i in range(n)], counts[:n]
+
+    # --- the depth stage of the Kinect loop (include/sr_yolo2.h y2_depth_*) ---
+    def depth_upload(self, depth, body=None, map_=None, color_hw=None) -> None:
+        """y2_depth_upload: depth uint16 [dh][dw], body uint8 [dh][dw] | None, map_ float32 [H][W][2] | None (then the
+        depth frame is already registered and H x W = dh x dw)"""
+        depth = np.ascontiguousarray(depth, dtype=np.uint16)
+        dh, dw = depth.shape
+        body = np.ascontiguousarray(body, dtype=np.uint8) if body is not None else None
+        if body is not None and body.shape != depth.shape:
+            raise ValueError("the body-index frame has the depth frame's size")
+        map_ = np.ascontiguousarray(map_, dtype=np.float32) if map_ is not None else None
+        H, W = map_.shape[:2] if map_ is not None else (color_hw or (dh, dw))
+        f = DepthFrame(depth.ctypes.data, body.ctypes.data if body is not None else None,
+                       map_.ctypes.data if map_ is not None else None, dh, dw, H, W)
+        if lib().y2_depth_upload(self.net, C.byref(f)) != 0:
+            raise Y2Error(_check())
+        self._depth_hw = (H, W)
+
+    def depth_set_camera_table(self, table) -> None:
+        """y2_depth_set_camera_table: float32 [dh][dw][2] (GetDepthFrameToCameraSpaceTable), or None to drop it"""
+        if table is None:
+            rc = lib().y2_depth_set_camera_table(self.net, None, 0, 0)
+        else:
+            t = np.ascontiguousarray(table, dtype=np.float32)
+            rc = lib().y2_depth_set_camera_table(self.net, _ptr(t), t.shape[0], t.shape[1])
+        if rc != 0:
+            raise Y2Error(_check())
+
+    def depth_aligned(self):
+        """y2_depth_aligned -> (depth16 [H][W] uint16, depth8 [H][W] uint8, person [H][W] uint8)"""
+        H, W = getattr(self, "_depth_hw", (0, 0))
+        if H * W == 0:
+            raise Y2Error("depth_aligned: no depth frame has been uploaded")
+        d16, d8, per = np.zeros((H, W), np.uint16), np.zeros((H, W), np.uint8), np.zeros((H, W), np.uint8)
+        if lib().y2_depth_aligned(self.net, _ptr(d16), _ptr(d8), _ptr(per)) != 0:
+            raise Y2Error(_check())
+        return d16, d8, per
+
+    def depth_boxes(self, boxes) -> np.ndarray:
+        """y2_depth_boxes: frame-relative (x, y, w, h) boxes [n][4] -> DET3D_DTYPE [n]"""
+        b = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 4)
+        out = np.zeros(max(len(b), 1), dtype=DET3D_DTYPE)
+        if lib().y2_depth_boxes(self.net, _ptr(b), len(b), _ptr(out)) != 0:
+            raise Y2Error(_check())
+        return out[:len(b)]
+
+    def ingest_regions_depth(self, items, far_m, swap_rb: bool = True, letterbox: bool = False) -> None:
+        """y2_ingest_regions_depth: ingest_regions with the hand-crop distance filter on the items whose far_m is > 0"""
+        arr, keep = regions(items)
+        far = np.ascontiguousarray(far_m, dtype=np.float32)
+        if len(far) != len(items):
+            raise ValueError("far_m needs one value per item")
+        if lib().y2_ingest_regions_depth(self.net, arr, len(items), _ptr(far), int(swap_rb), int(letterbox)) != 0:
+            raise Y2Error(_check())
+
+    def detect_regions_depth(self, items, far_m, thresh: float, nms: float, swap_rb: bool = True, letterbox: bool = False,
+                             max_per_item: int | None = None):
+        """y2_detect_regions_depth -> ([dets of item i], [DET3D_DTYPE of item i], counts[n]); far_m None: no filter"""
+        arr, keep = regions(items)
+        n = len(items)
+        far = np.ascontiguousarray(far_m, dtype=np.float32) if far_m is not None else None
+        if far is not None and len(far) != n:
+            raise ValueError("far_m needs one value per item")
+        l = self.last
+        cap = max_per_item or l.w * l.h * l.n
+        dets = np.zeros((max(n, 1), cap), dtype=DET_DTYPE)
+        d3 = np.zeros((max(n, 1), cap), dtype=DET3D_DTYPE)
+        counts = np.zeros(max(n, 1), dtype=np.int32)
+        if lib().y2_detect_regions_depth(self.net, arr, n, _ptr(far) if far is not None else None, int(swap_rb), int(letterbox),
+                                         thresh, nms, _ptr(dets), _ptr(d3), _ptr(counts), cap) != 0:
+            raise Y2Error(_check())
+        keep_n = [min(int(counts[i]), cap) for i in range(n)]
+        return [dets[i, :keep_n[i]].copy() for i in range(n)], [d3[i, :keep_n[i]].copy() for i in range(n)], counts[:n]
 
     def validate_detector_frames(self, frames: np.ndarray, paths, orig_w, orig_h, prefix: str, eval: str = "voc",
                                  names=None, map_: np.ndarray | None = None) -> None:
