@@ -252,6 +252,10 @@ box float_to_box(float *f);                                                     
 /* ---- Kinect-pipeline entry (test_detector.h:2, detector.c:558) ---- */
 void test_detector_img(char **names, image **alphabet, network net, image im, float thresh,
                        object *RecObects, int *objectNumPerFrame);
+/* test_detector.h / detector.c:514-554: the detection runs on imFilter (the frame with everything but the graspable
+ * objects whitened); `im` is only what the reference would draw on.  Objects are filled as test_detector_img fills them. */
+void test_detector_img_for_grasping(char **names, image **alphabet, network net, image im, image imFilter, float thresh,
+                                    object *RecObects, int *objectNumPerFrame);
 
 /* ---- evaluation writers (detector.c:169-243) and the validate loops over in-memory frames ---- */
 int get_coco_image_id(char *filename);                                                    /* detector.c:169 */
@@ -591,6 +595,50 @@ int y2_detect_regions_depth(network net, const y2_region *items, int n, const fl
  * flagBelong2Person, bodyId (far_m == NULL: no filter). */
 void test_detector_regions_depth(char **names, network net, const y2_region *items, int n, const float *far_m, float thresh,
                                  object **RecObjects, int *objectNumPerRegion);
+/* ------------------------------------------------------------------------- */
+/* The Grasp branch of the Kinect loop: the table plane removed on the device  */
+/* behind y2_depth_upload (KinectUtil_with_cam.cpp:364-377 updateDepth ->      */
+/* :1931-1974 desk_seg -> plane_seg.cpp:157-213).  PCL's sampler is seeded from */
+/* the clock and the SDK's camera mapping is closed, so this library DEFINES a */
+/* deterministic RANSAC: include/y2_plane_rule.h is its one statement, compiled */
+/* by the host and the kernels alike.  All hypotheses are evaluated (no         */
+/* adaptive early stop).                                                        */
+/* ------------------------------------------------------------------------- */
+/* far_m: depth beyond it is clipped to 0 (:1944-1950); dist_m: the inlier distance; iters: hypotheses (<= 256); seed: the
+ * sampler's start state, restarted at every upload; samples: NULL, or iters triples of depth-pixel indices to use instead
+ * of the sampler (copied).  The reference's values are 1.0, 0.02, 50. */
+typedef struct { float far_m, dist_m; int iters; unsigned seed; const int *samples; } y2_plane_opts;
+/* NULL or iters <= 0 turns the removal off, which is the default: y2_depth_upload then enqueues what it always did.
+ * Refused: iters > 256, far_m or dist_m not finite or <= 0.  Takes effect at the next y2_depth_upload, which with the
+ * removal on refuses, before any copy, a missing camera table or one whose size is not the depth frame's. */
+int y2_depth_set_plane_removal(network net, const y2_plane_opts *o);
+/* found = 0: no plane (fewer than 3 valid points, every hypothesis void, or a best count below 3); then best = -1,
+ * best_count = 0, the coefficients are 0 and nothing is removed.  best: the winning hypothesis (largest inlier count, a
+ * tie to the lowest index); valid_points: pixels with 0 < depth <= far_m; removed: valid pixels within dist_m of the
+ * refitted plane a*x + b*y + c*z + d = 0 (unit normal, d >= 0: oriented towards the camera). */
+typedef struct { int found, best, valid_points, best_count, removed; double a, b, c, d; } y2_plane;
+int y2_depth_plane(network net, y2_plane *out);
+/* grasp_depth (dh x dw): the clipped depth with the plane's pixels zeroed (depthBufferGrasping); grasp16 (H x W): that
+ * registered to the colour frame (i_RgbTodepthForGrasping, :402-438), 0 where unmapped.  Either pointer may be NULL. */
+int y2_depth_grasp_aligned(network net, uint16_t *grasp_depth, uint16_t *grasp16);
+/* Which branch of caculateXYZinCameraSpace (:1508-1527) y2_depth_boxes, y2_detect_regions_depth,
+ * test_detector_regions_depth and Detector::detect_regions_depth compute.  GRASP: avg_mm = GetImgAvg(grasp16 ROI, 255*32)
+ * with nothing subtracted, otsu reported as 255 (so the centre point takes every mapped pixel); every other field as in
+ * DEMO_WHAT, the default.  GRASP on a frame uploaded without plane removal is refused when the statistics are asked for. */
+enum { Y2_EVENT_DEMO_WHAT = 0, Y2_EVENT_GRASP = 1 };
+int y2_depth_set_event(network net, int event);
+/* on: a filtered item (far_m[i] > 0) of the *_depth ingests also reads a source pixel as 255 in every plane where grasp16
+ * is 0 -- the imFilter of test_detector_img_for_grasping, formed on the device.  Off (the default): the ingest is
+ * bit-identical to what it was. */
+int y2_depth_set_grasp_filter(network net, int on);
+/* The rule itself, host-callable: the very code the kernels run (include/y2_plane_rule.h).
+ * y2_plane_samples: the sampler over a depth frame -> iters triples of depth-pixel indices ((-1,-1,-1) = void); returns the
+ *   number of filled triples, -1 on bad arguments.
+ * y2_plane_from_points: the fp32 plane (nx, ny, nz, d) through three points; 0 = degenerate.
+ * y2_plane_fit: the refit from the ten sums n, x, y, z, xx, xy, xz, yy, yz, zz -> (a, b, c, d); 0 = no plane. */
+int y2_plane_samples(const uint16_t *depth, int dh, int dw, float far_m, int iters, unsigned seed, int *triples);
+int y2_plane_from_points(const float *p0, const float *p1, const float *p2, float *plane);
+int y2_plane_fit(const double *sums, double *plane);
 /* Copy layer i's activations to host as NCHW [batch][out_c][out_h][out_w] (or [batch][outputs]). */
 int y2_pull_layer_output(network net, int i, float *dst);
 /* Per-layer device time of the last forward in ms (needs y2_set_timing(net,1)); returns layers written. */

@@ -430,6 +430,12 @@ typedef struct y2h_region_f {
  * when no item filters), W its row length.  With every filter == 0 the result is bit-identical to y2h_regions_to_input. */
 int y2h_regions_to_input_filtered(const y2h_region_f *desc, int n, const unsigned char *pixels, const unsigned char *depth8,
                                   int W, int batch, int planes, int swap_rb, int h, int w, float *dst, y2h_stream s);
+/* The same with the grasp filter on top: where grasp16 (the H x W plane of y2h_plane_register, rows of W) is not NULL, a
+ * filtered item also reads a source pixel as 255 in every plane when grasp16 is 0 under it.  grasp16 == NULL is
+ * y2h_regions_to_input_filtered. */
+int y2h_regions_to_input_grasp(const y2h_region_f *desc, int n, const unsigned char *pixels, const unsigned char *depth8,
+                               const unsigned short *grasp16, int W, int batch, int planes, int swap_rb, int h, int w,
+                               float *dst, y2h_stream s);
 
 /* ---- depth stage of the Kinect loop (y2_depth.hip; KinectUtil_with_cam.cpp:394-442, :1482-1706) ---- */
 /* Register a dh x dw depth frame (and body-index frame, or NULL) to the H x W colour frame: for every colour pixel
@@ -458,6 +464,8 @@ typedef struct y2h_depth_planes {
     const short *dxy;           /* NULL: identity (the frame was registered already) */
     const float *cam_table;     /* dh x dw x 2, or NULL */
     int H, W, dh, dw;
+    const unsigned short *grasp16;  /* NULL: the Demo_what statistics.  Otherwise the Grasp branch (:1508-1518): avg_mm =
+                                       GetImgAvg(grasp16 ROI, 255 * 32) with no "- 16", otsu reported as 255 */
 } y2h_depth_planes;
 
 unsigned long y2h_depth_acc_bytes(void);     /* bytes of accumulator scratch per box */
@@ -472,6 +480,33 @@ unsigned long y2h_depth_acc_bytes(void);     /* bytes of accumulator scratch per
 enum { Y2H_DEPTH_CLEAR = 1, Y2H_DEPTH_PASS1 = 2, Y2H_DEPTH_PASS2 = 4, Y2H_DEPTH_FINALISE = 8, Y2H_DEPTH_ALL = 15 };
 int y2h_depth_boxes(const y2h_depth_planes *p, const float *boxes, int stride_box, long stride_item, const int *counts,
                     const y2h_box_map *maps, int items, int per_item, void *acc, y2h_det3d *out, int stages, y2h_stream s);
+
+/* ---- table-plane removal of the Grasp branch (y2_plane.hip; KinectUtil_with_cam.cpp:1931-1974, plane_seg.cpp:157-213;
+ * the rule is include/y2_plane_rule.h) ---- */
+/* the plane record: sr_yolo2.h y2_plane, field for field */
+typedef struct y2h_plane { int found, best, valid_points, best_count, removed, pad_; double a, b, c, d; } y2h_plane;
+#define Y2H_PLANE_COUNTS 260    /* ints of `counts`: one per hypothesis (256), the valid points at [256] */
+typedef struct y2h_plane_job {
+    const unsigned short *depth;    /* dh*dw, millimetres, as uploaded */
+    const float *tab;               /* dh*dw*2, the camera table */
+    const int *triples;             /* iters*3 depth-pixel indices; a void hypothesis is (-1, -1, -1) */
+    long n;                         /* dh*dw */
+    int iters;                      /* 1 .. 256 */
+    float far_mm, dist_m;           /* y2_plane_far_mm(far_m); the inlier distance */
+    int *counts;                    /* [Y2H_PLANE_COUNTS] */
+    double *slab;                   /* [y2h_plane_chunks(n)][10]: one partial of the ten sums per chunk of the tree */
+    y2h_plane *rec;
+    unsigned short *grasp_depth;    /* dh*dw out: the clipped depth with the plane's pixels zeroed */
+} y2h_plane_job;
+unsigned long y2h_plane_chunks(long n);
+/* Enqueue the stages selected (Y2H_PLANE_ALL for a result; single stages exist to be timed): clear the counts, count
+ * every hypothesis' inliers, the refit sums of the best one, the fit and the record, the grasp depth.  No synchronisation,
+ * no floating-point atomics: the result does not depend on the launch shape or on arrival order. */
+enum { Y2H_PLANE_CLEAR = 1, Y2H_PLANE_COUNT = 2, Y2H_PLANE_SUMS = 4, Y2H_PLANE_FIT = 8, Y2H_PLANE_APPLY = 16, Y2H_PLANE_ALL = 31 };
+int y2h_plane_remove(const y2h_plane_job *j, int stages, y2h_stream s);
+/* grasp16[H][W] = grasp_depth under the (dx, dy) that y2h_depth_align wrote for the colour pixel, 0 where unmapped */
+int y2h_plane_register(const unsigned short *grasp_depth, const short *dxy, int H, int W, int dw, unsigned short *grasp16,
+                       y2h_stream s);
 
 /* ---- classifier views (classifier.c:336-593 valid10 / validmulti / validfull) ---- */
 /* One view of y2h_views_to_input: a w x h window of a CHW fp32 source image that becomes batch slot b of the network

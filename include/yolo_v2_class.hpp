@@ -60,6 +60,13 @@ struct depth_frame_t {
     int dh, dw, H, W;
 };
 
+// The table plane of Detector::plane (sr_yolo2.h y2_plane): a*x + b*y + c*z + d = 0 in camera space, unit normal, d >= 0.
+struct plane_t {
+    bool found;                      // false: no plane in the frame; nothing was removed
+    int best, valid_points, best_count, removed;
+    double a, b, c, d;
+};
+
 struct image_t {
     int h, w, c;                 // CHW planes
     float *data;                 // values in [0,1]
@@ -105,6 +112,15 @@ public:
     YOLODLL_API std::vector<std::vector<bbox3d_t>> detect_regions_depth(const std::vector<frame_region_t> &items,
                                                                         const std::vector<float> &far_m = std::vector<float>(),
                                                                         float thresh = 0.2f, bool bgr = true);
+
+    // Extension: the Grasp event of the Kinect loop (sr_yolo2.h y2_depth_set_plane_removal / y2_depth_set_event /
+    // y2_depth_plane).  With the removal on, every upload_depth also finds the table plane on the device, zeroes it in the
+    // grasp depth and registers that to the colour frame; set_depth_event(1) makes detect_regions_depth report the Grasp
+    // branch's average depth (0 = Demo_what, the default).  iters <= 0 turns the removal off, which is the default.
+    YOLODLL_API void set_plane_removal(float far_m = 1.0f, float dist_m = 0.02f, int iters = 50, unsigned seed = 1,
+                                       const int *samples = nullptr);
+    YOLODLL_API void set_depth_event(int event);
+    YOLODLL_API plane_t plane();
 
 #ifdef OPENCV
     // The OpenCV convenience surface of the reference (yolo_v2_class.hpp:59-92), same names, signatures and results, so

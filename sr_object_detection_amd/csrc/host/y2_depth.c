@@ -10,8 +10,10 @@
 #include <string.h>
 #include "y2_internal.h"
 #include "y2_depth_rule.h"
+#include "y2_plane_rule.h"
 
 _Static_assert(sizeof(y2_det3d) == sizeof(y2h_det3d), "y2_det3d and y2h_det3d are one layout");
+_Static_assert(sizeof(y2_plane) == sizeof(y2h_plane), "y2_plane and y2h_plane are one layout");
 
 #define Y2_DEPTH_EAGER 256               /* records of y2_detect_regions_depth fetched before the counts are known (25 KB) */
 
@@ -34,6 +36,13 @@ typedef struct y2_depth_state {
     unsigned char *h_box, *d_box;
     size_t h_box_cap, d_box_cap;
     y2h_event ev_box;
+    /* table-plane removal (the Grasp branch): off unless plane.iters > 0 */
+    y2_plane_opts plane;
+    int *plane_samples;                  /* the caller's triples (plane.samples points here), or NULL: the sampler */
+    unsigned short *grasp_depth, *grasp16;   /* dh x dw and H x W; one plane for an identity frame */
+    y2h_plane *plane_rec;
+    int have_grasp;                      /* the uploaded frame went through the removal */
+    int event, grasp_filter;
 } y2_depth_state;
 
 static int grow_dev(void **p, size_t *cap, size_t need)
@@ -70,6 +79,7 @@ void y2_depth_free(y2_engine *e)
     y2h_host_free(s->h_box); y2h_free(s->d_box);
     if (s->ev_up) y2h_event_destroy(s->ev_up);
     if (s->ev_box) y2h_event_destroy(s->ev_box);
+    free(s->plane_samples);
     free(s);
     e->depth = NULL;
 }
@@ -80,6 +90,54 @@ const unsigned char *y2_depth_plane8(const y2_engine *e, int *W)
     if (!s || !s->have) { *W = 0; return NULL; }
     *W = s->W;
     return s->d8;
+}
+
+/* the grasp16 plane the filtered ingest also reads, or NULL while the grasp filter is off */
+const unsigned short *y2_depth_plane_grasp(const y2_engine *e)
+{
+    const y2_depth_state *s = e->depth;
+    return s && s->have && s->have_grasp && s->grasp_filter ? s->grasp16 : NULL;
+}
+
+/* ------------------------------------------------------------------ */
+/* the rule of the plane removal, host-callable: include/y2_plane_rule.h */
+/* ------------------------------------------------------------------ */
+int y2_plane_samples(const uint16_t *depth, int dh, int dw, float far_m, int iters, unsigned seed, int *triples)
+{
+    const float far_mm = y2_plane_far_mm(far_m);
+    unsigned state = seed, n;
+    int k, filled = 0;
+    if (!depth || !triples || dh <= 0 || dw <= 0 || dh > 32767 || dw > 32767 || iters < 0) return -1;
+    n = (unsigned)dh * (unsigned)dw;
+    for (k = 0; k < iters; ++k) {
+        int *t = triples + 3 * k, have = 0, draw;
+        for (draw = 0; draw < Y2_PLANE_MAX_DRAWS && have < 3; ++draw) {
+            int idx;
+            state = y2_plane_lcg(state);
+            idx = (int)((state >> 8) % n);
+            if (!(y2_plane_clip(depth[idx], far_mm) > 0)) continue;
+            if ((have > 0 && t[0] == idx) || (have > 1 && t[1] == idx)) continue;
+            t[have++] = idx;
+        }
+        if (have < 3) t[0] = t[1] = t[2] = -1;
+        else ++filled;
+    }
+    return filled;
+}
+
+int y2_plane_from_points(const float *p0, const float *p1, const float *p2, float *plane)
+{
+    y2_plane_hyp h;
+    if (!p0 || !p1 || !p2 || !plane) return 0;
+    y2_plane_of_points(p0, p1, p2, &h);
+    plane[0] = h.nx; plane[1] = h.ny; plane[2] = h.nz; plane[3] = h.d;
+    return h.ok;
+}
+
+int y2_plane_fit(const double *sums, double *plane)
+{
+    if (!sums || !plane) return 0;
+    return y2_plane_fit_sums(sums, plane);
 }
 
 int y2_otsu_threshold(const int hist[256])
@@ -115,6 +173,10 @@ int y2_depth_filter_check(const char *who, network net, const y2_region *items, 
     }
     if (!any) return 0;
     if (!s || !s->have) { y2_fail("%s: the distance filter needs a depth frame: call y2_depth_upload first", who); return -1; }
+    if (s->grasp_filter && !s->have_grasp) {
+        y2_fail("%s: the grasp filter needs a depth frame uploaded with plane removal on (y2_depth_set_plane_removal)", who);
+        return -1;
+    }
     for (i = 0; i < n; ++i)
         if (far_m[i] > 0 && (items[i].h != s->H || items[i].w != s->W)) {
             y2_fail("%s: item %d: the filtered frame is %d x %d, the uploaded depth frame is aligned to %d x %d", who, i,
@@ -140,29 +202,50 @@ int y2_depth_upload(network net, const y2_depth_frame *f)
 {
     y2_engine *e;
     y2_depth_state *s;
-    size_t npix, ndep, off_map, off_body, need, o16, oxy, o8, op, pneed;
+    size_t npix, ndep, off_map, off_body, off_tri = 0, need, o16, oxy, o8, op, pneed, ogd = 0, og16 = 0, ocnt = 0, oslab = 0, orec = 0;
+    int removal;
     if (depth_frame_check(f) != 0) return -1;
     if (y2_prepare(&net) != 0) return -1;
     e = y2_engine_of(&net);
     HIP_OR_ERR(y2h_set_device(e->device));
     s = state_of(e, 1);
     if (!s) { y2_fail("y2_depth_upload: out of memory"); return -1; }
+    removal = s->plane.iters > 0;
+    if (removal && (!s->d_tab || s->tab_dh != f->dh || s->tab_dw != f->dw)) {     /* before any copy */
+        if (!s->d_tab) y2_fail("y2_depth_upload: plane removal needs the camera table (y2_depth_set_camera_table)");
+        else y2_fail("y2_depth_upload: plane removal: the camera table is %d x %d, the depth frame %d x %d", s->tab_dw, s->tab_dh, f->dw, f->dh);
+        return -1;
+    }
     npix = (size_t)f->H * f->W; ndep = (size_t)f->dh * f->dw;
     off_map = align_up(ndep * 2, 256);
     off_body = off_map + (f->map ? align_up(npix * 8, 256) : 0);
     need = off_body + (f->body ? ndep : 0);
     o16 = 0; oxy = align_up(npix * 2, 256); o8 = oxy + align_up(npix * 4, 256); op = o8 + align_up(npix, 256);
     pneed = op + align_up(npix, 256);
+    if (removal) {                       /* the triples ride behind the frame; the grasp planes and the work area behind the planes */
+        off_tri = align_up(need, 256);
+        need = off_tri + (size_t)s->plane.iters * 3 * sizeof(int);
+        ogd = pneed; og16 = ogd + (f->map ? align_up(ndep * 2, 256) : 0);
+        ocnt = og16 + align_up(npix * 2, 256);
+        oslab = ocnt + align_up(Y2H_PLANE_COUNTS * sizeof(int), 256);
+        orec = oslab + align_up(y2h_plane_chunks((long)ndep) * 10 * sizeof(double), 256);
+        pneed = orec + align_up(sizeof(y2h_plane), 256);
+    }
     if (s->up_pending) { HIP_OR_ERR(y2h_event_sync(s->ev_up)); s->up_pending = 0; }
     if (grow_pinned((void **)&s->h_stage, &s->h_stage_cap, need) || grow_dev((void **)&s->d_stage, &s->d_stage_cap, need) ||
         grow_dev((void **)&s->d_planes, &s->planes_cap, pneed)) {
         y2_fail("y2_depth_upload: %s", y2h_last_error()); return -1;
     }
     if (!s->ev_up) HIP_OR_ERR(y2h_event_create(&s->ev_up));
-    s->have = 0;
+    s->have = 0; s->have_grasp = 0;
     memcpy(s->h_stage, f->depth, ndep * 2);
     if (f->map) memcpy(s->h_stage + off_map, f->map, npix * 8);
     if (f->body) memcpy(s->h_stage + off_body, f->body, ndep);
+    if (removal) {                       /* the sampler runs here, on the caller's frame: only the triples go up */
+        int *tri = (int *)(s->h_stage + off_tri);
+        if (s->plane.samples) memcpy(tri, s->plane.samples, (size_t)s->plane.iters * 3 * sizeof(int));
+        else y2_plane_samples(f->depth, f->dh, f->dw, s->plane.far_m, s->plane.iters, s->plane.seed, tri);
+    }
     HIP_OR_ERR(y2h_memcpy_h2d(s->d_stage, s->h_stage, need, e->stream));
     HIP_OR_ERR(y2h_event_record(s->ev_up, e->stream));
     s->up_pending = 1;
@@ -172,7 +255,73 @@ int y2_depth_upload(network net, const y2_depth_frame *f)
                               f->map ? (const float *)(s->d_stage + off_map) : NULL, f->dh, f->dw, f->H, f->W, s->d16, s->d8,
                               s->person, s->dxy, e->stream));
     s->H = f->H; s->W = f->W; s->dh = f->dh; s->dw = f->dw; s->has_map = f->map != NULL;
+    if (removal) {                       /* behind the align kernel on the same stream; nothing is left for the host */
+        y2h_plane_job j;
+        s->grasp_depth = (unsigned short *)(s->d_planes + ogd); s->grasp16 = (unsigned short *)(s->d_planes + og16);
+        s->plane_rec = (y2h_plane *)(s->d_planes + orec);
+        j.depth = (const unsigned short *)s->d_stage; j.tab = s->d_tab; j.triples = (const int *)(s->d_stage + off_tri);
+        j.n = (long)ndep; j.iters = s->plane.iters;
+        j.far_mm = y2_plane_far_mm(s->plane.far_m); j.dist_m = s->plane.dist_m;
+        j.counts = (int *)(s->d_planes + ocnt); j.slab = (double *)(s->d_planes + oslab);
+        j.rec = s->plane_rec; j.grasp_depth = s->grasp_depth;
+        HIP_OR_ERR(y2h_plane_remove(&j, Y2H_PLANE_ALL, e->stream));
+        if (f->map) HIP_OR_ERR(y2h_plane_register(s->grasp_depth, s->dxy, f->H, f->W, f->dw, s->grasp16, e->stream));
+        s->have_grasp = 1;
+    }
     s->have = 1;
+    return 0;
+}
+
+int y2_depth_set_plane_removal(network net, const y2_plane_opts *o)
+{
+    static const char *who = "y2_depth_set_plane_removal";
+    y2_engine *e;
+    y2_depth_state *s;
+    int *samples = NULL;
+    const int on = o && o->iters > 0;
+    if (on) {
+        if (o->iters > Y2_PLANE_MAX_ITERS) { y2_fail("%s: %d hypotheses, at most %d", who, o->iters, Y2_PLANE_MAX_ITERS); return -1; }
+        if (!(o->far_m > 0) || !(o->far_m <= 3.402823466e+38f)) { y2_fail("%s: far_m must be finite and > 0", who); return -1; }
+        if (!(o->dist_m > 0) || !(o->dist_m <= 3.402823466e+38f)) { y2_fail("%s: dist_m must be finite and > 0", who); return -1; }
+    }
+    if (y2_prepare(&net) != 0) return -1;
+    e = y2_engine_of(&net);
+    s = state_of(e, 1);
+    if (!s) { y2_fail("%s: out of memory", who); return -1; }
+    if (on && o->samples) {
+        samples = malloc((size_t)o->iters * 3 * sizeof(int));
+        if (!samples) { y2_fail("%s: out of memory", who); return -1; }
+        memcpy(samples, o->samples, (size_t)o->iters * 3 * sizeof(int));
+    }
+    free(s->plane_samples);
+    s->plane_samples = samples;
+    memset(&s->plane, 0, sizeof s->plane);
+    if (on) { s->plane = *o; s->plane.samples = samples; }
+    return 0;
+}
+
+int y2_depth_set_event(network net, int event)
+{
+    y2_engine *e;
+    y2_depth_state *s;
+    if (event != Y2_EVENT_DEMO_WHAT && event != Y2_EVENT_GRASP) { y2_fail("y2_depth_set_event: unknown event %d", event); return -1; }
+    if (y2_prepare(&net) != 0) return -1;
+    e = y2_engine_of(&net);
+    s = state_of(e, 1);
+    if (!s) { y2_fail("y2_depth_set_event: out of memory"); return -1; }
+    s->event = event;
+    return 0;
+}
+
+int y2_depth_set_grasp_filter(network net, int on)
+{
+    y2_engine *e;
+    y2_depth_state *s;
+    if (y2_prepare(&net) != 0) return -1;
+    e = y2_engine_of(&net);
+    s = state_of(e, 1);
+    if (!s) { y2_fail("y2_depth_set_grasp_filter: out of memory"); return -1; }
+    s->grasp_filter = on != 0;
     return 0;
 }
 
@@ -220,8 +369,45 @@ int y2_depth_aligned(network net, uint16_t *depth16, uint8_t *depth8, uint8_t *p
     return 0;
 }
 
+/* the Grasp statistics read the grasp16 plane of the uploaded frame: refused when that frame has none */
+static int event_check(const char *who, const y2_depth_state *s)
+{
+    if (s->event == Y2_EVENT_GRASP && !s->have_grasp) {
+        y2_fail("%s: the Grasp event needs a depth frame uploaded with plane removal on (y2_depth_set_plane_removal)", who);
+        return -1;
+    }
+    return 0;
+}
+
+int y2_depth_plane(network net, y2_plane *out)
+{
+    y2_engine *e;
+    y2_depth_state *s = uploaded("y2_depth_plane", net, &e);
+    if (!s) return -1;
+    if (!out) { y2_fail("y2_depth_plane: out is NULL"); return -1; }
+    if (!s->have_grasp) { y2_fail("y2_depth_plane: the uploaded frame did not go through plane removal (y2_depth_set_plane_removal)"); return -1; }
+    HIP_OR_ERR(y2h_set_device(e->device));
+    HIP_OR_ERR(y2h_memcpy_d2h(out, s->plane_rec, sizeof *out, e->stream));
+    HIP_OR_ERR(y2h_stream_sync(e->stream));
+    return 0;
+}
+
+int y2_depth_grasp_aligned(network net, uint16_t *grasp_depth, uint16_t *grasp16)
+{
+    y2_engine *e;
+    y2_depth_state *s = uploaded("y2_depth_grasp_aligned", net, &e);
+    if (!s) return -1;
+    if (!s->have_grasp) { y2_fail("y2_depth_grasp_aligned: the uploaded frame did not go through plane removal (y2_depth_set_plane_removal)"); return -1; }
+    HIP_OR_ERR(y2h_set_device(e->device));
+    if (grasp_depth) HIP_OR_ERR(y2h_memcpy_d2h(grasp_depth, s->grasp_depth, (size_t)s->dh * s->dw * 2, e->stream));
+    if (grasp16) HIP_OR_ERR(y2h_memcpy_d2h(grasp16, s->grasp16, (size_t)s->H * s->W * 2, e->stream));
+    HIP_OR_ERR(y2h_stream_sync(e->stream));
+    return 0;
+}
+
 static void planes_of(const y2_depth_state *s, y2h_depth_planes *p)
 {
+    p->grasp16 = s->event == Y2_EVENT_GRASP ? s->grasp16 : NULL;
     p->depth16 = s->d16; p->depth8 = s->d8; p->person = s->person;
     p->dxy = s->has_map ? s->dxy : NULL;
     p->cam_table = s->d_tab;
@@ -254,7 +440,7 @@ int y2_depth_boxes(network net, const box *boxes, int n, y2_det3d *out)
     box_layout L;
     if (!boxes || !out || n < 1 || n > 65535) { y2_fail("y2_depth_boxes: needs boxes, out and 1 <= n <= 65535"); return -1; }
     s = uploaded("y2_depth_boxes", net, &e);
-    if (!s) return -1;
+    if (!s || event_check("y2_depth_boxes", s) != 0) return -1;
     HIP_OR_ERR(y2h_set_device(e->device));
     if (box_scratch("y2_depth_boxes", s, (size_t)n * sizeof(box), n, &L) != 0) return -1;
     planes_of(s, &p);
@@ -291,7 +477,7 @@ int y2_detect_regions_depth(network net, const y2_region *items, int n, const fl
     if (y2_regions_check(who, net, items, n, letterbox) != 0) return -1;
     if (far_m && y2_depth_filter_check(who, net, items, n, far_m) != 0) return -1;
     s = uploaded(who, net, &e);
-    if (!s) return -1;
+    if (!s || event_check(who, s) != 0) return -1;
     if (y2_prepare(&net) != 0) return -1;                   /* det_cap belongs to the plan */
     e = y2_engine_of(&net);
     s = e->depth;

@@ -627,6 +627,14 @@ void test_detector_img(char **names, image **alphabet, network net, image im, fl
     free(dets);
 }
 
+/* detector.c:514-554: the same on imFilter; `im` is what the reference draws on */
+void test_detector_img_for_grasping(char **names, image **alphabet, network net, image im, image imFilter, float thresh,
+                                    object *RecObects, int *objectNumPerFrame)
+{
+    (void)im;
+    test_detector_img(names, alphabet, net, imFilter, thresh, RecObects, objectNumPerFrame);
+}
+
 /* ------------------------------------------------------------------ */
 /* regions of frames of any size in one batch                          */
 /* ------------------------------------------------------------------ */
@@ -731,8 +739,8 @@ static int ingest_regions(const char *who, network net, const y2_region *items, 
     if (far_m) {
         int W = 0;
         const unsigned char *depth8 = y2_depth_plane8(e, &W);
-        HIP_OR_ERR(y2h_regions_to_input_filtered((const y2h_region_f *)e->d_reg, n, e->d_reg + desc_bytes, depth8, W, net.batch, net.c,
-                                                swap_rb, net.h, net.w, e->d_in_nchw, e->stream));
+        HIP_OR_ERR(y2h_regions_to_input_grasp((const y2h_region_f *)e->d_reg, n, e->d_reg + desc_bytes, depth8, y2_depth_plane_grasp(e), W,
+                                             net.batch, net.c, swap_rb, net.h, net.w, e->d_in_nchw, e->stream));
         return 0;
     }
     HIP_OR_ERR(y2h_regions_to_input((const y2h_region *)e->d_reg, n, e->d_reg + desc_bytes, net.batch, net.c, swap_rb, net.h, net.w,

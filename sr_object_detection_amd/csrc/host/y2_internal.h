@@ -249,6 +249,7 @@ int y2_detect_chain_fetch(network net, y2_det *dets, int *counts, int max_per_it
 void y2_fill_object(object *o, const y2_det *d, char **names, int classes);
 int y2_depth_filter_check(const char *who, network net, const y2_region *items, int n, const float *far_m);
 const unsigned char *y2_depth_plane8(const y2_engine *e, int *W);
+const unsigned short *y2_depth_plane_grasp(const y2_engine *e);
 void y2_depth_free(y2_engine *e);
 
 /* cfg helpers shared with other files */

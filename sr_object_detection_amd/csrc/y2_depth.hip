@@ -95,6 +95,7 @@ struct DepthAcc {                        // one box's accumulators, zeroed befor
     u64 sum, idx;                        // depth16 and count of pixels with 0 < d < thr
     u64 pt[5][3];                        // centre, top, bottom, left, right: sum dx, sum dy, count
     int otsu, pad_;
+    u64 sum_all_g;                       // Grasp event: grasp16 over the ROI (GetImgAvg's own sumAll)
 };
 
 struct DepthJob {
@@ -146,7 +147,7 @@ __global__ __launch_bounds__(256) void depth_pass1_kernel(DepthJob q, int slots)
 {
     __shared__ int hist[4][256];
     __shared__ int lperson[8];
-    __shared__ u64 lsum;
+    __shared__ u64 lsum, lsumg;
     const int tid = threadIdx.x, wave = tid >> 6;
     for (int slot = blockIdx.y; slot < slots; slot += gridDim.y) {
     Roi r; bool valid;
@@ -155,12 +156,12 @@ __global__ __launch_bounds__(256) void depth_pass1_kernel(DepthJob q, int slots)
     __syncthreads();                                    // the last box's merge has read the LDS
     for (int k = 0; k < 4; ++k) hist[k][tid] = 0;
     if (tid < 8) lperson[tid] = 0;
-    if (tid == 0) lsum = 0;
+    if (tid == 0) { lsum = 0; lsumg = 0; }
     __syncthreads();
     const int rw = r.right - r.left;
     const long n = (long)rw * (r.bot - r.top);
     const long nround = (n + 255) / 256 * 256;          // whole waves stay in the loop: the ballots below need every lane
-    u64 s = 0;
+    u64 s = 0, sg = 0;
     int pc[7] = {0, 0, 0, 0, 0, 0, 0};                  // wave-uniform label counts
     for (long i = (long)blockIdx.x * 256 + tid; i < nround; i += (long)gridDim.x * 256) {
         int lab = 0;
@@ -169,6 +170,7 @@ __global__ __launch_bounds__(256) void depth_pass1_kernel(DepthJob q, int slots)
             const size_t at = (size_t)(r.top + rr) * q.p.W + r.left + cc;
             atomicAdd(&hist[wave][q.p.depth8[at]], 1);
             s += q.p.depth16[at];
+            if (q.p.grasp16) sg += q.p.grasp16[at];
             lab = q.p.person[at];
         }
         const bool is_person = lab >= 1 && lab <= 6;
@@ -176,6 +178,7 @@ __global__ __launch_bounds__(256) void depth_pass1_kernel(DepthJob q, int slots)
             for (int l = 1; l <= 6; ++l) pc[l] += __popcll(__ballot(lab == l));
     }
     if (s) atomicAdd(&lsum, s);
+    if (sg) atomicAdd(&lsumg, sg);
     if ((tid & 63) == 0) for (int l = 1; l <= 6; ++l) if (pc[l]) atomicAdd(&lperson[l], pc[l]);
     __syncthreads();
     DepthAcc *a = q.acc + slot;
@@ -183,12 +186,14 @@ __global__ __launch_bounds__(256) void depth_pass1_kernel(DepthJob q, int slots)
     if (hsum) atomicAdd(&a->hist[tid], hsum);
     if (tid >= 1 && tid <= 6 && lperson[tid]) atomicAdd(&a->person[tid], lperson[tid]);
     if (tid == 0 && lsum) atomicAdd(&a->sum_all, lsum);
+    if (tid == 0 && lsumg) atomicAdd(&a->sum_all_g, lsumg);
     }
 }
 
 // pass 2: every block of a slot recomputes the Otsu threshold from the finished histogram (one lane per candidate i,
 // each with its own 255-step loop, as the association of the running sums differs per i), then the thresholded depth sum
-// and the five point sums.
+// and the five point sums.  In the Grasp event (:1508-1518) there is no Otsu step: the threshold is 255 * 32 and the
+// thresholded sum reads grasp16.
 __global__ __launch_bounds__(256) void depth_pass2_kernel(DepthJob q, int slots)
 {
     __shared__ float pro[256];
@@ -204,15 +209,23 @@ __global__ __launch_bounds__(256) void depth_pass2_kernel(DepthJob q, int slots)
     __syncthreads();                                    // the last box's merge has read the LDS
     const int rw = r.right - r.left, rh = r.bot - r.top;
     const long n = (long)rw * rh;
-    const int hist0 = a->hist[0];
-    pro[tid] = y2_otsu_prob(a->hist[tid], tid, (int)n - hist0);
+    const unsigned short *avg_src = q.p.grasp16 ? q.p.grasp16 : q.p.depth16;
     if (tid < 17) l[tid] = 0;
-    __syncthreads();
-    delta[tid] = tid ? y2_otsu_delta(pro, tid) : 0.f;
-    __syncthreads();
-    if (tid == 0) {
-        s_otsu = y2_otsu_mostly_empty(hist0, (int)n) ? 0 : y2_otsu_pick(delta);
-        if (blockIdx.x == 0) a->otsu = s_otsu;
+    if (q.p.grasp16) {
+        if (tid == 0) {
+            s_otsu = 255;
+            if (blockIdx.x == 0) a->otsu = s_otsu;
+        }
+    } else {
+        const int hist0 = a->hist[0];
+        pro[tid] = y2_otsu_prob(a->hist[tid], tid, (int)n - hist0);
+        __syncthreads();
+        delta[tid] = tid ? y2_otsu_delta(pro, tid) : 0.f;
+        __syncthreads();
+        if (tid == 0) {
+            s_otsu = y2_otsu_mostly_empty(hist0, (int)n) ? 0 : y2_otsu_pick(delta);
+            if (blockIdx.x == 0) a->otsu = s_otsu;
+        }
     }
     __syncthreads();
     const int thr = s_otsu * 32;
@@ -221,7 +234,7 @@ __global__ __launch_bounds__(256) void depth_pass2_kernel(DepthJob q, int slots)
         const int rr = (int)(i / rw), cc = (int)(i - (long)rr * rw);
         const int Y = r.top + rr, X = r.left + cc;
         const size_t at = (size_t)Y * q.p.W + X;
-        const int d = q.p.depth16[at];
+        const int d = avg_src[at];
         if (d > 0 && d < thr) { sum += d; ++idx; }
         int dx = X, dy = Y;
         if (q.p.dxy) { const short2 v = *(const short2 *)(q.p.dxy + 2 * at); dx = v.x; dy = v.y; }
@@ -283,8 +296,9 @@ __global__ __launch_bounds__(64) void depth_finalise_kernel(DepthJob q, int slot
     o.valid = 1; o.left = r.left; o.top = r.top; o.right = r.right; o.bot = r.bot;
     o.otsu = a->otsu;
     o.mean_all_mm = (int)(a->sum_all / (u64)n);                                 // KinectUtil.cpp:489-501
-    const float res = (float)(a->idx ? a->sum / a->idx : a->sum_all / (u64)n);   // :1340-1345, integer division
-    o.avg_mm = res - 16;                                                        // :1526
+    const u64 all = q.p.grasp16 ? a->sum_all_g : a->sum_all;
+    const float res = (float)(a->idx ? a->sum / a->idx : all / (u64)n);          // :1340-1345, integer division
+    o.avg_mm = q.p.grasp16 ? res : res - 16;                                    // :1526; :1516 subtracts nothing
     for (int k = 0; k < 5; ++k) {
         const u64 c = a->pt[k][2];
         o.pts[k][0] = c ? (float)a->pt[k][0] / (float)c : 0.f;                  // :1403-1452

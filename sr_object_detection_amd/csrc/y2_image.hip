@@ -204,7 +204,8 @@ extern "C" int y2h_regions_to_input(const y2h_region *desc, int n, const unsigne
 // ---------------------------------------------------------------------------
 // The same chain with the hand-crop distance filter (KinectUtil_with_cam.cpp:1866-1888, applied at :1022 / :1066 before
 // the crop goes to the detector) on the source read: a pixel whose aligned 8-bit depth says "no depth" or "farther than
-// the hand" reads as 255 in every plane.  Only the read differs, so an item without a filter -- and the padded slots --
+// the hand" reads as 255 in every plane; with the grasp filter (y2_depth_set_grasp_filter) so does a pixel whose grasp16
+// is 0, i.e. one on the removed table plane or without depth.  Only the read differs, so an item without a filter -- and the padded slots --
 // are formed by exactly the expressions of regions_to_input_kernel.
 // ---------------------------------------------------------------------------
 struct RegionPixF {                      // one source row of a region, one plane, with the row of depth8 under it
@@ -213,9 +214,11 @@ struct RegionPixF {                      // one source row of a region, one plan
     const float *lut;
     const unsigned char *depth;          // depth8 under the region's pixel (row, 0), or NULL: no filter
     float far_limit;
+    const unsigned short *grasp;         // grasp16 under the region's pixel (row, 0), or NULL: no grasp filter
     __device__ float at(int j) const
     {
         if (depth && y2_depth_whitens(depth[j], far_limit)) return lut[255];
+        if (grasp && grasp[j] == 0) return lut[255];
         return lut[row[(size_t)j * c]];
     }
 };
@@ -231,7 +234,8 @@ __device__ __forceinline__ float region_col_f(const RegionPixF &p, int col, int 
 
 __global__ __launch_bounds__(256) void regions_to_input_filtered_kernel(const y2h_region_f *__restrict__ desc, int n,
                                                                         const unsigned char *__restrict__ pixels,
-                                                                        const unsigned char *__restrict__ depth8, int W,
+                                                                        const unsigned char *__restrict__ depth8,
+                                                                        const unsigned short *__restrict__ grasp16, int W,
                                                                         int planes, int swap_rb, int h, int w, int vec,
                                                                         float *__restrict__ dst)
 {
@@ -272,11 +276,14 @@ __global__ __launch_bounds__(256) void regions_to_input_filtered_kernel(const y2
     const bool filt = df.filter && depth8;
     const unsigned char *z0 = filt ? depth8 + (size_t)(df.fy + iy) * W + df.fx : nullptr;
     const unsigned char *z1 = filt ? depth8 + (size_t)(df.fy + iy1) * W + df.fx : nullptr;
+    const bool gfilt = filt && grasp16;
+    const unsigned short *g0 = gfilt ? grasp16 + (size_t)(df.fy + iy) * W + df.fx : nullptr;
+    const unsigned short *g1 = gfilt ? grasp16 + (size_t)(df.fy + iy1) * W + df.fx : nullptr;
     for (int k = 0; k < planes; ++k) {
         int sk = k;
         if (swap_rb && d.c >= 3) sk = (k == 0) ? 2 : (k == 2 ? 0 : k);
-        const RegionPixF p0{src + (size_t)iy * d.pitch + sk, d.c, lut, z0, df.far_limit};
-        const RegionPixF p1{src + (size_t)iy1 * d.pitch + sk, d.c, lut, z1, df.far_limit};
+        const RegionPixF p0{src + (size_t)iy * d.pitch + sk, d.c, lut, z0, df.far_limit, g0};
+        const RegionPixF p1{src + (size_t)iy1 * d.pitch + sk, d.c, lut, z1, df.far_limit, g1};
         float v[4];
         for (int i = 0; i < 4; ++i) {
             const int x = X0 + i - d.dx;
@@ -290,18 +297,26 @@ __global__ __launch_bounds__(256) void regions_to_input_filtered_kernel(const y2
     }
 }
 
-extern "C" int y2h_regions_to_input_filtered(const y2h_region_f *desc, int n, const unsigned char *pixels,
-                                             const unsigned char *depth8, int W, int batch, int planes, int swap_rb, int h,
-                                             int w, float *dst, y2h_stream s)
+extern "C" int y2h_regions_to_input_grasp(const y2h_region_f *desc, int n, const unsigned char *pixels,
+                                          const unsigned char *depth8, const unsigned short *grasp16, int W, int batch,
+                                          int planes, int swap_rb, int h, int w, float *dst, y2h_stream s)
 {
-    if (!desc || !pixels || !dst || n < 0 || n > batch || batch <= 0 || planes <= 0 || h <= 0 || w <= 0 || (depth8 && W <= 0))
+    if (!desc || !pixels || !dst || n < 0 || n > batch || batch <= 0 || planes <= 0 || h <= 0 || w <= 0 || (depth8 && W <= 0) ||
+        (grasp16 && !depth8))
         return Y2H_EINVAL;
     const int vec = (w % 4 == 0) && ((uintptr_t)dst % 16 == 0);
     const long groups = (long)h * ((w + 3) / 4);
     hipLaunchKernelGGL(regions_to_input_filtered_kernel, dim3((unsigned)((groups + 255) / 256), (unsigned)batch), dim3(256), 0,
-                       S(s), desc, n, pixels, depth8, W, planes, swap_rb, h, w, vec, dst);
+                       S(s), desc, n, pixels, depth8, grasp16, W, planes, swap_rb, h, w, vec, dst);
     Y2H_LAUNCH_CHECK();
     return Y2H_OK;
+}
+
+extern "C" int y2h_regions_to_input_filtered(const y2h_region_f *desc, int n, const unsigned char *pixels,
+                                             const unsigned char *depth8, int W, int batch, int planes, int swap_rb, int h,
+                                             int w, float *dst, y2h_stream s)
+{
+    return y2h_regions_to_input_grasp(desc, n, pixels, depth8, nullptr, W, batch, planes, swap_rb, h, w, dst, s);
 }
 
 // ---------------------------------------------------------------------------

@@ -243,6 +243,37 @@ void Detector::set_camera_table(const float *table, int dh, int dw)
     if (y2_depth_set_camera_table(st.regions_net, table, dh, dw) != 0) throw std::runtime_error(y2_last_error());
 }
 
+void Detector::set_plane_removal(float far_m, float dist_m, int iters, unsigned seed, const int *samples)
+{
+    DeviceGuard guard;
+    DetectorState &st = state_of(detector_gpu_ptr);
+    regions_net_for(st, 1);
+    y2_plane_opts o;
+    o.far_m = far_m; o.dist_m = dist_m; o.iters = iters; o.seed = seed; o.samples = samples;
+    if (y2_depth_set_plane_removal(st.regions_net, iters > 0 ? &o : nullptr) != 0) throw std::runtime_error(y2_last_error());
+}
+
+void Detector::set_depth_event(int event)
+{
+    DeviceGuard guard;
+    DetectorState &st = state_of(detector_gpu_ptr);
+    regions_net_for(st, 1);
+    if (y2_depth_set_event(st.regions_net, event) != 0) throw std::runtime_error(y2_last_error());
+}
+
+plane_t Detector::plane()
+{
+    DeviceGuard guard;
+    DetectorState &st = state_of(detector_gpu_ptr);
+    regions_net_for(st, 1);
+    y2_plane p;
+    if (y2_depth_plane(st.regions_net, &p) != 0) throw std::runtime_error(y2_last_error());
+    plane_t out;
+    out.found = p.found != 0; out.best = p.best; out.valid_points = p.valid_points; out.best_count = p.best_count;
+    out.removed = p.removed; out.a = p.a; out.b = p.b; out.c = p.c; out.d = p.d;
+    return out;
+}
+
 std::vector<std::vector<bbox3d_t>> Detector::detect_regions_depth(const std::vector<frame_region_t> &items,
                                                                   const std::vector<float> &far_m, float thresh, bool bgr)
 {

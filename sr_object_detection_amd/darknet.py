@@ -125,6 +125,18 @@ class Det3d(C.Structure):        # include/sr_yolo2.h y2_det3d
                 ("cam_w", C.c_float), ("cam_h", C.c_float), ("pts", (C.c_float * 2) * 5)]
 
 
+class PlaneOpts(C.Structure):    # include/sr_yolo2.h y2_plane_opts
+    _fields_ = [("far_m", C.c_float), ("dist_m", C.c_float), ("iters", C.c_int), ("seed", C.c_uint), ("samples", C.c_void_p)]
+
+
+class Plane(C.Structure):        # include/sr_yolo2.h y2_plane
+    _fields_ = [("found", C.c_int), ("best", C.c_int), ("valid_points", C.c_int), ("best_count", C.c_int),
+                ("removed", C.c_int), ("a", C.c_double), ("b", C.c_double), ("c", C.c_double), ("d", C.c_double)]
+
+
+EVENT_DEMO_WHAT, EVENT_GRASP = 0, 1                         # include/sr_yolo2.h Y2_EVENT_*
+
+
 class View(C.Structure):     # include/y2_hip.h y2h_view: one view of y2h_views_to_input
     _fields_ = [("src", C.c_longlong), ("sw", C.c_int), ("sh", C.c_int), ("dx", C.c_int), ("dy", C.c_int),
                 ("flip", C.c_int), ("pad_", C.c_int)]
@@ -232,6 +244,16 @@ def lib():
                                           C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.test_detector_regions_depth.argtypes = [C.POINTER(C.c_char_p), CNetwork, C.POINTER(Region), C.c_int, C.c_void_p,
                                               C.c_float, C.POINTER(C.c_void_p), C.c_void_p]
+    L.y2_depth_set_plane_removal.argtypes = [CNetwork, C.POINTER(PlaneOpts)]
+    L.y2_depth_plane.argtypes = [CNetwork, C.POINTER(Plane)]
+    L.y2_depth_grasp_aligned.argtypes = [CNetwork, C.c_void_p, C.c_void_p]
+    L.y2_depth_set_event.argtypes = [CNetwork, C.c_int]
+    L.y2_depth_set_grasp_filter.argtypes = [CNetwork, C.c_int]
+    L.y2_plane_samples.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_uint, C.c_void_p]
+    L.y2_plane_from_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.y2_plane_fit.argtypes = [C.c_void_p, C.c_void_p]
+    L.test_detector_img_for_grasping.argtypes = [C.POINTER(C.c_char_p), C.c_void_p, CNetwork, Image, Image, C.c_float,
+                                                 C.POINTER(Object), C.POINTER(C.c_int)]
     L.y2h_u8_to_planes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int,
                                    C.c_void_p, C.c_void_p]
     L.top_predictions.argtypes = [CNetwork, C.c_int, C.c_void_p]
@@ -422,6 +444,31 @@ def otsu_threshold(hist) -> int:
     return int(lib().y2_otsu_threshold(_ptr(h)))
 
 
+def plane_samples(depth, far_m: float, iters: int, seed: int) -> np.ndarray:
+    """y2_plane_samples: the sampler of include/y2_plane_rule.h over a depth frame -> int32 [iters][3], -1 = void"""
+    depth = np.ascontiguousarray(depth, dtype=np.uint16)
+    out = np.zeros((max(iters, 1), 3), np.int32)
+    if lib().y2_plane_samples(_ptr(depth), depth.shape[0], depth.shape[1], far_m, iters, seed & 0xFFFFFFFF, _ptr(out)) < 0:
+        raise Y2Error("y2_plane_samples: bad arguments")
+    return out[:iters]
+
+
+def plane_from_points(p0, p1, p2):
+    """y2_plane_from_points: three float32 points -> (ok, float32 [4] = nx, ny, nz, d)"""
+    pts = [np.ascontiguousarray(p, dtype=np.float32) for p in (p0, p1, p2)]
+    out = np.zeros(4, np.float32)
+    ok = lib().y2_plane_from_points(_ptr(pts[0]), _ptr(pts[1]), _ptr(pts[2]), _ptr(out))
+    return int(ok), out
+
+
+def plane_fit(sums):
+    """y2_plane_fit: float64 [10] = n, x, y, z, xx, xy, xz, yy, yz, zz -> (ok, float64 [4] = a, b, c, d)"""
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    out = np.zeros(4, np.float64)
+    ok = lib().y2_plane_fit(_ptr(sums), _ptr(out))
+    return int(ok), out
+
+
 def depth_roi(box, W: int, H: int):
     """y2_depth_roi: (valid, left, top, right, bot) of a frame-relative (x, y, w, h) box in a W x H frame"""
     v = [C.c_int(0) for _ in range(4)]
@@ -592,6 +639,22 @@ class Network:
             out.append(dict(x=o.x, y=o.y, w=o.w, h=o.h, prob=o.prob, objClass=o.objClass, name=o.name.decode(),
                             boxRGB=tuple(o.boxRGB)))
         return out
+
+    def test_detector_img_for_grasping(self, im: np.ndarray, im_filter: np.ndarray, thresh: float, names=None):
+        """detector.c:514: test_detector_img on im_filter; im is what the reference draws on"""
+        L = lib()
+        im = np.ascontiguousarray(im, dtype=np.float32)
+        imf = np.ascontiguousarray(im_filter, dtype=np.float32)
+        cim = Image(im.shape[1], im.shape[2], im.shape[0], im.ctypes.data_as(C.POINTER(C.c_float)))
+        cimf = Image(imf.shape[1], imf.shape[2], imf.shape[0], imf.ctypes.data_as(C.POINTER(C.c_float)))
+        objs = (Object * 2048)()
+        cnt = C.c_int(0)
+        cnames = (C.c_char_p * len(names))(*[n.encode() for n in names]) if names else None
+        L.test_detector_img_for_grasping(cnames, None, self.net, cim, cimf, thresh, objs, C.byref(cnt))
+        if L.y2_failed_and_clear():
+            raise Y2Error("test_detector_img_for_grasping: " + _check())
+        return [dict(x=o.x, y=o.y, w=o.w, h=o.h, prob=o.prob, objClass=o.objClass, name=o.name.decode(), boxRGB=tuple(o.boxRGB))
+                for o in objs[:cnt.value]]
 
     # --- extensions ---
     def prepare(self) -> None:
@@ -842,6 +905,43 @@ class Network:
         if lib().y2_depth_aligned(self.net, _ptr(d16), _ptr(d8), _ptr(per)) != 0:
             raise Y2Error(_check())
         return d16, d8, per
+
+    # --- the Grasp branch: the table plane removed behind depth_upload (include/sr_yolo2.h y2_plane_*) ---
+    def depth_set_plane_removal(self, far_m: float = 1.0, dist_m: float = 0.02, iters: int = 50, seed: int = 1,
+                                samples=None) -> None:
+        """y2_depth_set_plane_removal; iters <= 0 turns it off.  samples: int32 [iters][3] depth-pixel indices, or None"""
+        smp = np.ascontiguousarray(samples, dtype=np.int32).reshape(-1, 3) if samples is not None else None
+        if smp is not None and len(smp) != iters:
+            raise ValueError("samples needs one triple per hypothesis")
+        o = PlaneOpts(far_m, dist_m, iters, seed & 0xFFFFFFFF, smp.ctypes.data if smp is not None else None)
+        if lib().y2_depth_set_plane_removal(self.net, C.byref(o) if iters > 0 else None) != 0:
+            raise Y2Error(_check())
+
+    def depth_plane(self) -> dict:
+        """y2_depth_plane -> dict of the fields of y2_plane"""
+        p = Plane()
+        if lib().y2_depth_plane(self.net, C.byref(p)) != 0:
+            raise Y2Error(_check())
+        return {k: getattr(p, k) for k, _ in Plane._fields_}
+
+    def depth_grasp_aligned(self, dhw):
+        """y2_depth_grasp_aligned -> (grasp_depth [dh][dw] uint16, grasp16 [H][W] uint16); dhw = the depth frame's shape"""
+        H, W = getattr(self, "_depth_hw", (0, 0))
+        if H * W == 0:
+            raise Y2Error("depth_grasp_aligned: no depth frame has been uploaded")
+        gd, g16 = np.zeros(tuple(dhw), np.uint16), np.zeros((H, W), np.uint16)
+        if lib().y2_depth_grasp_aligned(self.net, _ptr(gd), _ptr(g16)) != 0:
+            raise Y2Error(_check())
+        return gd, g16
+
+    def depth_set_event(self, event: int) -> None:
+        """y2_depth_set_event: EVENT_DEMO_WHAT or EVENT_GRASP"""
+        if lib().y2_depth_set_event(self.net, event) != 0:
+            raise Y2Error(_check())
+
+    def depth_set_grasp_filter(self, on: bool) -> None:
+        if lib().y2_depth_set_grasp_filter(self.net, int(on)) != 0:
+            raise Y2Error(_check())
 
     def depth_boxes(self, boxes) -> np.ndarray:
         """y2_depth_boxes: frame-relative (x, y, w, h) boxes [n][4] -> DET3D_DTYPE [n]"""

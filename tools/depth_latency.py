@@ -33,7 +33,8 @@ FAR = [0.0, 1.3, 1.4]                                      # jointDistance + 0.3
 
 class Planes(C.Structure):     # include/y2_hip.h y2h_depth_planes
     _fields_ = [("depth16", C.c_void_p), ("depth8", C.c_void_p), ("person", C.c_void_p), ("dxy", C.c_void_p),
-                ("cam_table", C.c_void_p), ("H", C.c_int), ("W", C.c_int), ("dh", C.c_int), ("dw", C.c_int)]
+                ("cam_table", C.c_void_p), ("H", C.c_int), ("W", C.c_int), ("dh", C.c_int), ("dw", C.c_int),
+                ("grasp16", C.c_void_p)]                   # NULL: the Demo_what statistics
 
 
 class Timer:
