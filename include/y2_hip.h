@@ -291,6 +291,31 @@ int y2h_nchw_to_nhwc4_halo_f16(const float *src, void *dst, int n, int c, int h,
 int y2h_f32_to_f16(const float *src, void *dst, long n, y2h_stream s);
 int y2h_f16_to_f32(const void *src, float *dst, long n, y2h_stream s);
 
+/* ---- dense heads in fp16 storage mode (y2_dense_f16.hip) ---- */
+/* The K ranges of y2h_connected_f16 for `rows` x `inputs` x `outputs` (host arithmetic only, no GPU): *ranges K ranges,
+ * each a whole number of 32-steps except the last, which ends at `inputs`; range r is [bounds[r], bounds[r + 1]) (bounds:
+ * room for max_bounds ints, or NULL).  forced > 0 sets the count, clamped to the number of 32-steps; forced <= 0 lets the
+ * cost model choose.  *ws_bytes = ranges * 16 * roundup(outputs, 16) * sizeof(float) of raw partial sums
+ * ([range][16 rows][roundup(outputs, 16)]), 0 with one range. */
+int y2h_connected_f16_plan(int rows, int inputs, int outputs, int forced, int *ranges, size_t *ws_bytes, int *bounds,
+                           int max_bounds);
+/* y[r][n] = act((sum_k x[r][k] * w[n][k]) * alpha[n] + beta[n]): x half [rows][ldx], w half [outputs][inputs], y fp32 or
+ * half (y_f16) [rows][ldy], fp32 accumulation on the fp16 matrix cores, Y2H_ACT_LINEAR .. _RELU.  ranges / ws / ws_bytes as
+ * y2h_connected_f16_plan gives them; partial sums are added in ascending K order (no atomics).  More than 16 rows run in
+ * passes of 16. */
+int y2h_connected_f16(const void *x, long ldx, const void *w, const float *alpha, const float *beta, void *y, int ldy,
+                      int y_f16, int rows, int inputs, int outputs, int activation, int ranges, float *ws, size_t ws_bytes,
+                      y2h_stream s);
+/* y2h_local with half weights (same [location][filter][kh][kw][c] order), half input and output, fp32 accumulation and
+ * fp32 biases; Y2H_ACT_LINEAR .. _RELU */
+int y2h_local_f16(const void *x, int ldx, const void *w_packed, const float *bias_packed, void *y, int ldy, int batch,
+                  int h, int w, int c, int n, int size, int stride, int pad, int out_h, int out_w, int activation,
+                  y2h_stream s);
+/* y2h_crop reading fp32 and writing half NHWC; y4 (or NULL; c <= 4): also the interior of half [batch][out_h+2][out_w+2][4],
+ * the input form of the fp16 first-layer kernel (the caller zeroes it once) */
+int y2h_crop_f16(const float *x, int ldx, void *y, int ldy, void *y4, int batch, int h, int w, int c, int out_h, int out_w,
+                 int noadjust, y2h_stream s);
+
 /* ---- region head ---- */
 /* x: last conv output NHWC [batch][h*w][ldx] holding num*(coords+1+classes) channels.
  * y: [batch][h*w*num][coords+1+classes] (the reference's flattened layout).

@@ -15,9 +15,6 @@ static int owns_arena(const layer *l)
     return l->type == CONVOLUTIONAL || l->type == CONNECTED || l->type == LOCAL || l->type == BATCHNORM || is_recurrent(l);
 }
 
-/* half input -> half weights */
-static int half_weights(const network *net, int i) { return (i > 0) && ld_of(&net->layers[i - 1])->out_half; }
-
 /* the batch-norm constants of n filters: mean, scale, and the reciprocal divisor in double */
 void y2_bn_slots(size_t *off, int n, size_t *mean, size_t *scale, size_t *rinv)
 {
@@ -81,12 +78,12 @@ void y2_arena_layout(network *net)
         const layer *l = &net->layers[i];
         y2_ldev *d = ld_of(l);
         const size_t wbytes = (size_t)l->n * l->size * l->size * l->c * sizeof(float);
-        const int w_half = half_weights(net, i);
+        const int w_half = y2_half_weights(net, i);
         if (!owns_arena(l)) continue;
         if (l->type == BATCHNORM) { y2_bn_slots(&off, l->c, &d->off_mean, &d->off_scale, &d->off_rinv); continue; }
         if (is_recurrent(l)) { off = y2_rec_layout(d, l, off); continue; }
         if (l->type == LOCAL) {
-            d->off_w_packed = off; off = align_up(off + (size_t)l->out_h * l->out_w * l->n * l->size * l->size * l->c * sizeof(float), 256);
+            d->off_w_packed = off; off = align_up(off + (size_t)l->out_h * l->out_w * l->n * l->size * l->size * l->c * (w_half ? 2 : sizeof(float)), 256);
             d->off_bias = off; off = align_up(off + (size_t)l->outputs * sizeof(float), 64);
             continue;
         }
@@ -119,7 +116,7 @@ static uint64_t arena_signature(const network *net)
             continue;
         }
         SIG_MIX(i); SIG_MIX(d->off_w_packed); SIG_MIX(d->has_w_ref ? d->off_w_ref + 1 : 0); SIG_MIX(d->off_bias);
-        SIG_MIX(d->uses_mfma); SIG_MIX(half_weights(net, i));
+        SIG_MIX(d->uses_mfma); SIG_MIX(y2_half_weights(net, i));
         SIG_MIX(l->batch_normalize ? d->off_rinv + 1 : 0);
     }
     SIG_MIX(e->strict); SIG_MIX(e->half); SIG_MIX(e->arena_need);
@@ -157,8 +154,8 @@ int y2_arena_commit(network *net)
 }
 
 /* reference: weights [location][filter][c][kh][kw], biases [filter][location] (local_layer.c:100,111-121);
- * kernel: weights [location][filter][kh][kw][c], biases [location][filter] */
-static void pack_local(unsigned char *host, const y2_ldev *d, const layer *l)
+ * kernel: weights [location][filter][kh][kw][c] in fp32 or half, biases [location][filter] in fp32 */
+static void pack_local(unsigned char *host, const y2_ldev *d, const layer *l, int w_half)
 {
     const int locations = l->out_h * l->out_w, kk = l->size * l->size, K = kk * l->c;
     float *wp = (float *)(host + d->off_w_packed), *b = (float *)(host + d->off_bias);
@@ -168,7 +165,10 @@ static void pack_local(unsigned char *host, const y2_ldev *d, const layer *l)
             const float *src = l->weights + ((size_t)loc * l->n + co) * K;
             float *dst = wp + ((size_t)loc * l->n + co) * K;
             for (ci = 0; ci < l->c; ++ci)
-                for (t = 0; t < kk; ++t) dst[(size_t)t * l->c + ci] = src[(size_t)ci * kk + t];
+                for (t = 0; t < kk; ++t) {
+                    if (w_half) ((unsigned short *)wp)[((size_t)loc * l->n + co) * K + (size_t)t * l->c + ci] = f32_to_f16_rne(src[(size_t)ci * kk + t]);
+                    else dst[(size_t)t * l->c + ci] = src[(size_t)ci * kk + t];
+                }
             b[(size_t)loc * l->n + co] = l->biases[(size_t)co * locations + loc];
         }
 }
@@ -188,8 +188,12 @@ static void pack_filters(float *wp, const network *net, int i, int w_half)
         int pix;
         for (co = 0; co < l->n; ++co)
             for (ci = 0; ci < C; ++ci)
-                for (pix = 0; pix < hw; ++pix)
-                    wp[(size_t)co * K + (size_t)pix * C + ci] = l->weights[(size_t)co * K + (size_t)ci * hw + pix];
+                for (pix = 0; pix < hw; ++pix) {
+                    const size_t dst = (size_t)co * K + (size_t)pix * C + ci;
+                    const float v = l->weights[(size_t)co * K + (size_t)ci * hw + pix];
+                    if (w_half) ((unsigned short *)wp)[dst] = f32_to_f16_rne(v);
+                    else wp[dst] = v;
+                }
         return;
     }
     /* reference layout [n][c][kh][kw] (im2col.c:24-27) -> kernel layout [n][kh][kw][c] */
@@ -212,7 +216,7 @@ static void pack_dense(unsigned char *host, const network *net, int i)
 {
     const layer *l = &net->layers[i];
     const y2_ldev *d = ld_of(l);
-    const int K = l->size * l->size * l->c, w_half = half_weights(net, i);
+    const int K = l->size * l->size * l->c, w_half = y2_half_weights(net, i);
     int co, f, q;
     pack_filters((float *)(host + d->off_w_packed), net, i, w_half);
     if (w_half) {
@@ -262,7 +266,7 @@ int y2_upload_weights(network *net)
             memcpy(host + d->off_scale, l->scales, l->c * sizeof(float));
             y2_fill_rinv((double *)(host + d->off_rinv), l->rolling_variance, l->c);
         }
-        else if (l->type == LOCAL) pack_local(host, d, l);
+        else if (l->type == LOCAL) pack_local(host, d, l, y2_half_weights(net, i));
         else pack_dense(host, net, i);
     }
     if (y2h_memcpy_h2d(e->arena, host, e->arena_bytes, e->stream) != 0 || y2h_stream_sync(e->stream) != 0) {

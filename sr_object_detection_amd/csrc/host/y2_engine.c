@@ -329,6 +329,12 @@ static int forward_connected(network *net, int i, const float *x, int ldx)
     const y2_ldev *d = ld_of(l);
     y2h_conv c;
     y2_conv_desc(net, i, &c, x, ldx);
+    if (d->conn_ranges && !e->strict) {
+        /* fp16 mode: the weight-streaming form; its epilogue applies the activation (the plan admits no other) */
+        HIP_OR_ERR(y2h_connected_f16(x, (long)l->inputs, c.w_packed, c.alpha, c.beta, d->d_flat, l->outputs, d->out_half, l->batch,
+                                     l->inputs, l->outputs, c.activation, d->conn_ranges, e->d_ws, e->ws_bytes, e->stream));
+        return 0;
+    }
     if (d->uses_mfma && !e->strict) HIP_OR_ERR(y2h_conv_forward(&c, 0, e->stream));
     else {
         const int pi = y2_producer_of(net, i);
@@ -419,6 +425,10 @@ int y2_enqueue_forward(network *net, const float *d_input_nchw)
             rc = y2_activate_after(e, l->activation, d->out, d->out_ld, (long)l->batch * l->out_h * l->out_w, l->out_c);
         } break;
         case CROP:
+            if (d->out_half) {            /* fp16 mode: half NHWC, and the first-layer kernel's [h+2][w+2][4] form beside it */
+                HIP_OR_ERR(y2h_crop_f16(x, ldx, d->out, d->out_ld, d->d_halo, l->batch, l->h, l->w, l->c, l->out_h, l->out_w, l->noadjust, e->stream));
+                break;
+            }
             HIP_OR_ERR(y2h_crop(x, ldx, d->out, d->out_ld, l->batch, l->h, l->w, l->c, l->out_h, l->out_w, l->noadjust, 0, e->stream));
             if (d->d_halo)
                 HIP_OR_ERR(y2h_crop(x, ldx, d->d_halo, l->out_c, l->batch, l->h, l->w, l->c, l->out_h, l->out_w, l->noadjust, d->halo_px, e->stream));
@@ -443,6 +453,12 @@ int y2_enqueue_forward(network *net, const float *d_input_nchw)
         } break;
         case LOCAL:
             if (y2_act_code(l->activation) < 0) { y2_fail("local layer %d: unknown activation %d", i, (int)l->activation); return -1; }
+            if (d->out_half) {
+                HIP_OR_ERR(y2h_local_f16(x, ldx, e->arena + d->off_w_packed, (const float *)(e->arena + d->off_bias), d->out, d->out_ld,
+                                         l->batch, l->h, l->w, l->c, l->n, l->size, l->stride, l->pad, l->out_h, l->out_w,
+                                         y2_act_for_kernel(l->activation), e->stream));
+                break;
+            }
             HIP_OR_ERR(y2h_local(x, ldx, (const float *)(e->arena + d->off_w_packed), (const float *)(e->arena + d->off_bias), d->out,
                                  d->out_ld, l->batch, l->h, l->w, l->c, l->n, l->size, l->stride, l->pad, l->out_h, l->out_w,
                                  y2_act_for_kernel(l->activation), e->strict, e->stream));
@@ -468,6 +484,11 @@ static int stage_output(const network *net, int i, float *nchw, const float **sr
     const layer *l = &net->layers[i];
     const y2_ldev *d = ld_of(l);
     *src = d->out;
+    if (y2_is_flat(net, i) && d->out_half) {      /* a dense layer that feeds another one in fp16 mode */
+        HIP_OR_ERR(y2h_f16_to_f32(d->out, nchw, (long)l->batch * l->outputs, e->stream));
+        *src = nchw;
+        return 0;
+    }
     if (y2_is_flat(net, i)) return 0;
     if (d->out_half)
         HIP_OR_ERR(y2h_nhwc_f16_to_nchw(d->out, d->out_ld, nchw, l->batch, l->out_c, l->out_h, l->out_w, e->stream));
@@ -646,7 +667,7 @@ int y2_pull_layer_output(network net, int i, float *dst)
         return -1;
     }
     HIP_OR_ERR(y2h_set_device(e->device));
-    if (!y2_is_flat(&net, i)) HIP_OR_ERR(y2h_malloc((void **)&tmp, n * sizeof(float)));
+    if (!y2_is_flat(&net, i) || d->out_half) HIP_OR_ERR(y2h_malloc((void **)&tmp, n * sizeof(float)));
     rc = stage_output(&net, i, tmp, &src);
     if (rc == 0 && (y2h_memcpy_d2h(dst, src, n * sizeof(float), e->stream) != 0 || y2h_stream_sync(e->stream) != 0)) {
         y2_fail("y2_pull_layer_output: %s", y2h_last_error());

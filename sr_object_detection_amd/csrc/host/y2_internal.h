@@ -29,6 +29,7 @@ typedef struct y2_ldev {
     size_t off_alpha, off_beta; /* fp16 mode: folded batch-norm, y = act(acc*alpha + beta) */
     char kname[80];
     int tile_bm, tile_bn, ksplit;   /* measured tile choice (y2_set_autotune), 0 = the host's cost model */
+    int conn_ranges;           /* fp16 mode [connected]: K ranges of connected_f16, 0 = the layer does not run it */
     /* region */
     float *d_anchors;
     int *d_tree_block, *h_tree_block;  /* the head's tree tables in one allocation and their host copy (y2_plan.c plan_tree_tables) */
@@ -218,6 +219,7 @@ int y2_act_for_kernel(ACTIVATION a);
 int y2_flat_input(const network *net);
 int y2_producer_of(const network *net, int i);
 int y2_is_flat(const network *net, int i);
+int y2_half_weights(const network *net, int i);
 void y2_input_form(const network *net, y2_in_form *f);
 void y2_input_view(const network *net, int i, const float **x, int *ldx);
 void y2_conv_desc(const network *net, int i, y2h_conv *c, const float *x, int ldx);

@@ -33,6 +33,7 @@ void y2_free_plan(network *net)
         d->fused_pool = 0; d->fused_into = -1;
         d->out_half = 0;
         d->tile_bm = d->tile_bn = d->ksplit = 0;
+        d->conn_ranges = 0;
     }
     y2_drop_graphs(e);
     y2h_free(e->d_in_nchw); e->d_in_nchw = NULL;
@@ -143,7 +144,7 @@ void y2_conv_desc(const network *net, int i, y2h_conv *c, const float *x, int ld
         c->w_packed = (const float *)(e->arena + d->off_w_packed);
         c->w_ref = d->has_w_ref ? (const float *)(e->arena + d->off_w_ref) : NULL;
         c->bias = (const float *)(e->arena + d->off_bias);
-        if (c->x_f16 && i > 0) {
+        if (y2_half_weights(net, i)) {
             c->alpha = (const float *)(e->arena + d->off_alpha);
             c->beta = (const float *)(e->arena + d->off_beta);
         }
@@ -180,7 +181,8 @@ void y2_input_view(const network *net, int i, const float **x, int *ldx)
     } else {
         const y2_ldev *p = ld_of(&net->layers[i - 1]);
         *x = p->out; *ldx = p->out_ld;
-        if (p->d_halo && net->layers[i].type == CONVOLUTIONAL) { *x = p->d_halo; *ldx = net->layers[i - 1].out_c; }
+        /* (a half [crop] keeps the [h+2][w+2][4] form of the fp16 first-layer kernel there) */
+        if (p->d_halo && net->layers[i].type == CONVOLUTIONAL) { *x = p->d_halo; *ldx = p->out_half ? 4 : net->layers[i - 1].out_c; }
     }
     /* an xnor convolution reads the binarized copy of its input */
     if (net->layers[i].type == CONVOLUTIONAL && net->layers[i].xnor && ld_of(&net->layers[i])->d_bin) {
@@ -206,6 +208,24 @@ int y2_is_flat(const network *net, int i)
     case DROPOUT: case COST: case ACTIVE: return i > 0 ? y2_is_flat(net, i - 1) : 0;   /* as the layer in front */
     default: return 0;
     }
+}
+
+/* 1: layer i holds half weights -- its input is half.  A [connected] layer looks through [dropout]; the convolution
+ * behind a half [crop] that runs the fp16 first-layer kernel keeps fp32 [n][27] weights, as that kernel does at layer 0 */
+int y2_half_weights(const network *net, int i)
+{
+    const y2_ldev *pd;
+    if (i <= 0) return 0;
+    pd = ld_of(&net->layers[net->layers[i].type == CONNECTED ? y2_producer_of(net, i) : i - 1]);
+    if (!pd->out_half) return 0;
+    return !(net->layers[i].type == CONVOLUTIONAL && pd->d_halo);
+}
+
+/* Y2_CONN_KSPLIT=n forces the K ranges of connected_f16 (tests; clamped by y2h_connected_f16_plan) */
+static int conn_forced_ranges(void)
+{
+    const char *ks = getenv("Y2_CONN_KSPLIT");
+    return (ks && atoi(ks) > 0) ? atoi(ks) : 0;
 }
 
 static int upload_small(void **dst, const void *src, size_t bytes, y2h_stream s)
@@ -238,6 +258,11 @@ static int plan_workspace(network *net)
         const float *x; int ldx;
         size_t b;
         if ((net->layers[i].type != CONVOLUTIONAL && net->layers[i].type != CONNECTED) || e->strict) continue;
+        if (ld_of(&net->layers[i])->conn_ranges) {         /* connected_f16: the raw sums of its K ranges */
+            const layer *l = &net->layers[i];
+            if (y2h_connected_f16_plan(l->batch, l->inputs, l->outputs, ld_of(l)->conn_ranges, NULL, &b, NULL, 0) == 0 && b > need) need = b;
+            continue;
+        }
         y2_input_view(net, i, &x, &ldx);
         conv_query(net, i, &c, x, ldx);
         b = y2h_conv_workspace_bytes(&c);
@@ -493,9 +518,34 @@ static int plan_half(network *net)
                 d->out_half = 1;
             }
             break;
-        case REGION: case SOFTMAX:
+        case REGION: case SOFTMAX: case DETECTION:
             if (pd && pd->out_half) { y2_fail("fp16 mode: layer %d (%s) needs an fp32 producer (a convolutional or avgpool layer)", i, get_layer_string(l->type)); return -1; }
             break;
+        case CONNECTED: {
+            /* reads a half image or a half flat vector; like the conv in front of [region], the last dense layer of a
+             * head writes fp32: a dense layer stores half only for another dense layer */
+            const int pi = y2_producer_of(net, i);
+            int nx = i + 1;
+            if (i == 0) { y2_fail("layer %d (%s) cannot be the first layer", i, get_layer_string(l->type)); return -1; }
+            if (!y2_act_in_kernel(l->activation)) { y2_fail("fp16 mode: layer %d (connected): activation %d has no half-precision form", i, (int)l->activation); return -1; }
+            if (!ld_of(&net->layers[pi])->out_half) {
+                y2_fail("fp16 mode: layer %d (connected) needs a half-precision producer, layer %d (%s) stores fp32", i, pi, get_layer_string(net->layers[pi].type));
+                return -1;
+            }
+            while (nx < net->n && (net->layers[nx].type == DROPOUT || net->layers[nx].type == COST)) ++nx;
+            d->out_half = nx < net->n && net->layers[nx].type == CONNECTED;
+        } break;
+        case LOCAL:
+            if (!pd || !pd->out_half || y2_is_flat(net, i - 1)) { y2_fail("fp16 mode: layer %d (local) needs a half-precision image producer", i); return -1; }
+            if (!y2_act_in_kernel(l->activation)) { y2_fail("fp16 mode: layer %d (local): activation %d has no half-precision form", i, (int)l->activation); return -1; }
+            d->out_half = 1;
+            break;
+        case CROP:
+            /* reads the fp32 network input and writes half */
+            if (i != 0) { y2_fail("fp16 mode: layer %d (crop) has a half-precision form only as the first layer", i); return -1; }
+            d->out_half = 1;
+            break;
+        case DROPOUT: d->out_half = pd ? pd->out_half : 0; break;
         case NORMALIZATION: case ACTIVE:
             if (!pd || !pd->out_half) { y2_fail("fp16 mode: layer %d (%s) needs a half-precision producer", i, get_layer_string(l->type)); return -1; }
             if (l->type == ACTIVE && !y2_act_in_kernel(l->activation)) { y2_fail("fp16 mode: layer %d: activation %d has no half-precision form", i, (int)l->activation); return -1; }
@@ -503,12 +553,12 @@ static int plan_half(network *net)
             d->out_half = 1;
             break;
         case COST: d->out_half = pd ? pd->out_half : 0; break;
-        case SHORTCUT: case CONNECTED: case DETECTION: case DROPOUT: case CROP: case LOCAL: case BATCHNORM: case RNN: case GRU:
+        case SHORTCUT: case BATCHNORM: case RNN: case GRU:
             y2_fail("fp16 mode: layer %d (%s) has no half-precision kernel", i, get_layer_string(l->type)); return -1;
         default: break;
         }
     }
-    if (net->n > 0 && net->layers[0].type != CONVOLUTIONAL) { y2_fail("fp16 mode: the first layer must be convolutional"); return -1; }
+    if (net->n > 0 && net->layers[0].type != CONVOLUTIONAL && net->layers[0].type != CROP) { y2_fail("fp16 mode: the first layer must be convolutional or crop"); return -1; }
     return 0;
 }
 
@@ -522,10 +572,10 @@ static int alloc_activations(y2_ldev *d, const layer *l)
     return 0;
 }
 
-/* a flat [batch][outputs] fp32 vector */
+/* a flat [batch][outputs] vector: fp32, or half for a dense layer that feeds another one in fp16 mode */
 static int alloc_flat(y2_ldev *d, const layer *l)
 {
-    HIP_OR_ERR(y2h_malloc((void **)&d->d_flat, (size_t)l->batch * l->outputs * sizeof(float)));
+    HIP_OR_ERR(y2h_malloc((void **)&d->d_flat, (size_t)l->batch * l->outputs * (d->out_half ? 2 : sizeof(float))));
     d->out = d->d_flat; d->out_ld = l->outputs;
     return 0;
 }
@@ -562,7 +612,8 @@ static int plan_activations(network *net)
             break;
         case SHORTCUT: case CROP: case LOCAL: case BATCHNORM:
             if (alloc_activations(d, l) != 0) return -1;
-            d->kernel = l->type == SHORTCUT ? "shortcut" : l->type == CROP ? "crop" : l->type == LOCAL ? (e->strict ? "local_ref" : "local") : "batchnorm";
+            d->kernel = l->type == SHORTCUT ? "shortcut" : l->type == CROP ? (d->out_half ? "crop_f16" : "crop") :
+                        l->type == LOCAL ? (d->out_half ? "local_f16" : e->strict ? "local_ref" : "local") : "batchnorm";
             break;
         case NORMALIZATION:
             if (alloc_activations(d, l) != 0) return -1;
@@ -649,6 +700,22 @@ static int plan_input_copies(network *net)
         HIP_OR_ERR(y2h_malloc((void **)&d->d_halo, fl * sizeof(float)));
         HIP_OR_ERR(y2h_memset(d->d_halo, 0, fl * sizeof(float), e->stream));
         d->halo_px = px;
+    }
+    /* fp16 mode: the half counterpart for a first-layer [crop] -- the [b][h+2][w+2][4] form with a zero halo that the fp16
+     * first-layer kernel reads (vgg-16.cfg, yolov1/yolo-small.cfg) */
+    if (net->n > 1 && !e->strict && net->layers[0].type == CROP && ld_of(&net->layers[0])->out_half) {
+        const layer *l = &net->layers[0], *nl = &net->layers[1];
+        y2_ldev *d = ld_of(l);
+        y2h_conv c0;
+        if (nl->type == CONVOLUTIONAL && nl->c <= 4 && !ld_of(nl)->fused_pool) {
+            conv_query(net, 1, &c0, NULL, nl->c);
+            if (y2h_conv_first_layer_f16_ok(&c0)) {
+                const size_t bytes = (size_t)l->batch * (l->out_h + 2) * (l->out_w + 2) * 4 * 2;
+                HIP_OR_ERR(y2h_malloc((void **)&d->d_halo, bytes));
+                HIP_OR_ERR(y2h_memset(d->d_halo, 0, bytes, e->stream));
+                d->halo_px = 1;
+            }
+        }
     }
     for (i = 0; i < net->n; ++i) {
         layer *l = &net->layers[i];
@@ -824,6 +891,26 @@ static int plan_conv_kernels(network *net)
         if (y2_act_code(l->activation) < 0) { y2_fail("layer %d: unknown activation %d", i, (int)l->activation); return -1; }
         y2_input_view(net, i, &x, &ldx);
         conv_query(net, i, &c, x, ldx);
+        if (l->type == CONNECTED && y2_half_weights(net, i)) {
+            /* fp16 mode.  Up to 16 rows: connected_f16.  More: the fp16 matrix-core conv tile on a 1x1 image where its own
+             * query takes the descriptor, else connected_f16 in passes of 16.  Y2_CONN_F16=skinny|mfma forces the form
+             * where both are possible.  One half copy of the weights either way, no reference-layout copy. */
+            const char *form = getenv("Y2_CONN_F16");
+            const int tile_ok = y2h_conv_uses_mfma(&c) && strncmp(y2h_conv_variant(&c, 0), "conv_mfma_f16", 13) == 0;
+            int tile = tile_ok && l->batch > 16;
+            if (form && strcmp(form, "skinny") == 0) tile = 0;
+            if (form && strcmp(form, "mfma") == 0) tile = tile_ok;
+            d->uses_mfma = tile;
+            d->has_w_ref = 0;
+            if (tile) { d->kernel = y2h_conv_variant(&c, 0); continue; }
+            if (y2h_connected_f16_plan(l->batch, l->inputs, l->outputs, conn_forced_ranges(), &d->conn_ranges, NULL, NULL, 0) != 0) {
+                y2_fail("fp16 mode: layer %d (connected): %d inputs x %d outputs cannot be planned", i, l->inputs, l->outputs);
+                return -1;
+            }
+            snprintf(d->kname, sizeof d->kname, d->conn_ranges > 1 ? "connected_f16+ksplit%d" : "connected_f16", d->conn_ranges);
+            d->kernel = d->kname;
+            continue;
+        }
         d->uses_mfma = !e->strict && y2h_conv_uses_mfma(&c);
         if (d->fused_pool && !d->uses_mfma) {
             /* the shape test of the fusion pass was optimistic (e.g. misaligned input view): give the conv its own buffer back */

@@ -251,6 +251,8 @@ def lib():
     L.y2_depth_set_grasp_filter.argtypes = [CNetwork, C.c_int]
     L.y2_plane_samples.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_uint, C.c_void_p]
     L.y2_plane_from_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.y2h_connected_f16_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_size_t),
+                                         C.c_void_p, C.c_int]
     L.y2_plane_fit.argtypes = [C.c_void_p, C.c_void_p]
     L.test_detector_img_for_grasping.argtypes = [C.POINTER(C.c_char_p), C.c_void_p, CNetwork, Image, Image, C.c_float,
                                                  C.POINTER(Object), C.POINTER(C.c_int)]
@@ -451,6 +453,16 @@ def plane_samples(depth, far_m: float, iters: int, seed: int) -> np.ndarray:
     if lib().y2_plane_samples(_ptr(depth), depth.shape[0], depth.shape[1], far_m, iters, seed & 0xFFFFFFFF, _ptr(out)) < 0:
         raise Y2Error("y2_plane_samples: bad arguments")
     return out[:iters]
+
+
+def connected_f16_plan(rows: int, inputs: int, outputs: int, forced: int = 0):
+    """y2h_connected_f16_plan: how fp16 mode cuts a dense layer of `inputs` x `outputs` along K, on the host (no GPU) ->
+    (K ranges, bytes of partial-sum workspace, int32 [ranges + 1] range bounds); forced > 0 sets the number of ranges"""
+    n, ws = C.c_int(0), C.c_size_t(0)
+    bounds = np.zeros((inputs + 31) // 32 + 1, np.int32)
+    if lib().y2h_connected_f16_plan(rows, inputs, outputs, forced, C.byref(n), C.byref(ws), _ptr(bounds), bounds.size) != 0:
+        raise Y2Error("y2h_connected_f16_plan: bad arguments")
+    return n.value, ws.value, bounds[:n.value + 1].copy()
 
 
 def plane_from_points(p0, p1, p2):
