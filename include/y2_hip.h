@@ -291,7 +291,7 @@ int y2h_nchw_to_nhwc4_halo_f16(const float *src, void *dst, int n, int c, int h,
 int y2h_f32_to_f16(const float *src, void *dst, long n, y2h_stream s);
 int y2h_f16_to_f32(const void *src, float *dst, long n, y2h_stream s);
 
-/* ---- dense heads in fp16 storage mode (y2_dense_f16.hip) ---- */
+/* ---- dense heads in fp16 storage mode ---- */
 /* The K ranges of y2h_connected_f16 for `rows` x `inputs` x `outputs` (host arithmetic only, no GPU): *ranges K ranges,
  * each a whole number of 32-steps except the last, which ends at `inputs`; range r is [bounds[r], bounds[r + 1]) (bounds:
  * room for max_bounds ints, or NULL).  forced > 0 sets the count, clamped to the number of 32-steps; forced <= 0 lets the

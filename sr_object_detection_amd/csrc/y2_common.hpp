@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <float.h>
+#include <stdint.h>
 #include <stdio.h>
 #include <string.h>
 #include <map>
@@ -38,6 +39,28 @@ static inline unsigned y2h_grid(long n, int block, int max_blocks = 256 * 16)
     if (g > max_blocks) g = max_blocks;
     if (g < 1) g = 1;
     return (unsigned)g;
+}
+
+// The two storage types of an activation, fp32 and IEEE half (fp16 mode), for the layer kernels that have one body for
+// both: the vector of one 16-byte access, how many elements it holds, and the most negative finite value.
+template <typename T> struct storage;
+template <> struct storage<float> {
+    typedef float vec __attribute__((ext_vector_type(4)));
+    static constexpr int VEC = 4;
+    static constexpr float LOWEST = -FLT_MAX;
+};
+template <> struct storage<_Float16> {
+    typedef _Float16 vec __attribute__((ext_vector_type(8)));
+    static constexpr int VEC = 8;
+    static constexpr float LOWEST = -65504.f;
+};
+
+// 16-byte accesses to rows of c elements at leading dimensions ldx, ldy (counted in elements) are possible
+template <typename T>
+static inline bool y2h_vec_ok(int c, int ldx, int ldy, const void *x, const void *y)
+{
+    constexpr int V = storage<T>::VEC;
+    return (c % V == 0) && (ldx % V == 0) && (ldy % V == 0) && (((uintptr_t)x | (uintptr_t)y) % 16 == 0);
 }
 
 // Dynamic LDS above the default needs hipFuncAttributeMaxDynamicSharedMemorySize on the kernel, per device.  The attribute

@@ -1,7 +1,7 @@
-// fp16 storage mode for the dense heads (engine extension; the reference is fp32 only): [connected], [local] and [crop]
-// with half weights and half activations, fp32 accumulation.  At the batches these heads run at they are weight streams
-// (vgg-16's first dense layer: 25088 x 4096, yolov1/yolo.cfg's [local]: 49 x 256 x 9216), so half storage halves the
-// bytes that bound them.
+// fp16 storage mode for the dense heads (engine extension; the reference is fp32 only): [connected] and [crop] with half
+// weights and half activations, fp32 accumulation ([local] in half is local_kernel<_Float16, ...> of y2_layers.hip).  At
+// the batches these heads run at they are weight streams (vgg-16's first dense layer: 25088 x 4096, yolov1/yolo.cfg's
+// [local]: 49 x 256 x 9216), so half storage halves the bytes that bound them.
 //
 // connected_f16: y[r][n] = act((sum_k x[r][k] * w[n][k]) * alpha[n] + beta[n]) for up to 16 rows per pass on
 // v_mfma_f32_16x16x32_f16.  The A fragment is 16 rows of x (rows past the batch are zero), the B fragment 16 weight rows:
@@ -171,129 +171,6 @@ extern "C" int y2h_connected_f16(const void *x, long ldx, const void *w, const f
             Y2H_LAUNCH_CHECK();
         }
     }
-    return Y2H_OK;
-}
-
-// ---------------------------------------------------------------------------
-// local_f16: local_kernel's decomposition (y2_layers.hip) on half weights [location][filter][kh][kw][c] and a half NHWC
-// input: a wave owns (location, 4 filters), lanes stride over the K = size*size*c taps, 8 values per 16-byte load
-// (VEC: c % 8 == 0, so a load never leaves its tap), fp32 accumulation, the weights read once per up to NB images, a
-// wave reduction, y = act(sum + bias) stored as half.
-// ---------------------------------------------------------------------------
-struct LocalH {
-    const _Float16 *x; int ldx;
-    const _Float16 *wp;
-    const float *bias;              // [loc][n]
-    _Float16 *y; int ldy;
-    int batch, h, w, c, n, size, stride, pad, oh, ow, act;
-};
-
-template <int NB, bool VEC>
-__global__ __launch_bounds__(256) void local_f16_kernel(LocalH a)
-{
-    const int lane = threadIdx.x & 63;
-    const int groups = (a.n + 3) >> 2;
-    const long wave = ((long)blockIdx.x * 256 + threadIdx.x) >> 6;
-    const long nwork = (long)a.oh * a.ow * groups;
-    if (wave >= nwork) return;
-    const int loc = (int)(wave / groups), m0 = (int)(wave - (long)loc * groups) * 4;
-    const int oy = loc / a.ow, ox = loc - oy * a.ow;
-    const int K = a.size * a.size * a.c;
-    const _Float16 *w0 = a.wp + ((size_t)loc * a.n + m0) * K;
-    const int nf = (a.n - m0 < 4) ? a.n - m0 : 4;
-    constexpr int STEP = VEC ? 8 : 1;
-    for (int b0 = 0; b0 < a.batch; b0 += NB) {
-        float acc[NB][4];
-#pragma unroll
-        for (int i = 0; i < NB; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
-        for (int k = lane * STEP; k < K; k += 64 * STEP) {
-            const int tap = k / a.c, ci = k - tap * a.c;
-            const int kh = tap / a.size, kw = tap - kh * a.size;
-            const int iy = oy * a.stride + kh - a.pad, ix = ox * a.stride + kw - a.pad;
-            const bool in = iy >= 0 && iy < a.h && ix >= 0 && ix < a.w;
-            float wv[4][STEP];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-#pragma unroll
-                for (int q = 0; q < STEP; ++q) wv[j][q] = 0.f;
-                if (j < nf) {
-                    if constexpr (VEC) {
-                        const f16x8 t = *(const f16x8 *)(w0 + (size_t)j * K + k);
-#pragma unroll
-                        for (int q = 0; q < STEP; ++q) wv[j][q] = (float)t[q];
-                    } else wv[j][0] = (float)w0[(size_t)j * K + k];
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < NB; ++i) {
-                float xv[STEP];
-#pragma unroll
-                for (int q = 0; q < STEP; ++q) xv[q] = 0.f;
-                if (in && b0 + i < a.batch) {
-                    const _Float16 *xp = a.x + (((size_t)(b0 + i) * a.h + iy) * a.w + ix) * a.ldx + ci;
-                    if constexpr (VEC) {
-                        const f16x8 t = *(const f16x8 *)xp;
-#pragma unroll
-                        for (int q = 0; q < STEP; ++q) xv[q] = (float)t[q];
-                    } else xv[0] = (float)*xp;
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int q = 0; q < STEP; ++q) acc[i][j] = __builtin_fmaf(wv[j][q], xv[q], acc[i][j]);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < NB; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float v = acc[i][j];
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-                acc[i][j] = v;
-            }
-        if (lane < nf) {
-            const float bias = a.bias[(size_t)loc * a.n + m0 + lane];
-#pragma unroll
-            for (int i = 0; i < NB; ++i) {
-                if (b0 + i >= a.batch) break;
-                float v = 0.f;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v = (lane == j) ? acc[i][j] : v;
-                a.y[((size_t)(b0 + i) * a.oh * a.ow + loc) * a.ldy + m0 + lane] = (_Float16)epilogue_fast(v, 1.f, bias, a.act);
-            }
-        }
-    }
-}
-
-extern "C" int y2h_local_f16(const void *x, int ldx, const void *w_packed, const float *bias_packed, void *y, int ldy, int batch,
-                             int h, int w, int c, int n, int size, int stride, int pad, int out_h, int out_w, int activation,
-                             y2h_stream s)
-{
-    if (!x || !w_packed || !bias_packed || !y || batch <= 0 || h <= 0 || w <= 0 || c <= 0 || n <= 0 || size <= 0 || stride <= 0 ||
-        pad < 0 || out_h <= 0 || out_w <= 0 || ldx < c || ldy < n) return Y2H_EINVAL;
-    if ((out_h - 1) * stride + size - pad > h + pad || (out_w - 1) * stride + size - pad > w + pad) return Y2H_EINVAL;
-    if (activation < Y2H_ACT_LINEAR || activation > Y2H_ACT_RELU) return Y2H_EINVAL;
-    LocalH a;
-    a.x = (const _Float16 *)x; a.ldx = ldx; a.wp = (const _Float16 *)w_packed; a.bias = bias_packed; a.y = (_Float16 *)y; a.ldy = ldy;
-    a.batch = batch; a.h = h; a.w = w; a.c = c; a.n = n; a.size = size; a.stride = stride; a.pad = pad; a.oh = out_h; a.ow = out_w;
-    a.act = activation;
-    const long waves = (long)out_h * out_w * ((n + 3) / 4);
-    const unsigned blocks = (unsigned)((waves + 3) / 4);
-    const bool vec = (c % 8 == 0) && (ldx % 8 == 0) && (((uintptr_t)x | (uintptr_t)w_packed) % 16 == 0);
-    if (batch == 1) {
-        if (vec) hipLaunchKernelGGL((local_f16_kernel<1, true>), dim3(blocks), dim3(256), 0, S(s), a);
-        else hipLaunchKernelGGL((local_f16_kernel<1, false>), dim3(blocks), dim3(256), 0, S(s), a);
-    } else if (batch <= 4) {
-        if (vec) hipLaunchKernelGGL((local_f16_kernel<4, true>), dim3(blocks), dim3(256), 0, S(s), a);
-        else hipLaunchKernelGGL((local_f16_kernel<4, false>), dim3(blocks), dim3(256), 0, S(s), a);
-    } else {        // eight images per pass over the weights
-        if (vec) hipLaunchKernelGGL((local_f16_kernel<8, true>), dim3(blocks), dim3(256), 0, S(s), a);
-        else hipLaunchKernelGGL((local_f16_kernel<8, false>), dim3(blocks), dim3(256), 0, S(s), a);
-    }
-    Y2H_LAUNCH_CHECK();
     return Y2H_OK;
 }
 

@@ -1,10 +1,14 @@
-// Non-convolution layers of the forward path, NHWC fp32 (include/y2_hip.h).
+// Non-convolution layers of the forward path, NHWC (include/y2_hip.h).
 // All of these are HBM-bound copies/reductions; the arithmetic follows the
 // reference CPU order exactly so results are bit-identical to it.
+// maxpool, reorg, the average pool and [local] also run on half activations (fp16 storage mode, an engine extension: the
+// reference has no half path): one kernel body templated on the element type T, `ld` arguments count elements of T.
+// max / copy / permutation are exact in half.
 // Compiled with -ffp-contract=off.
-#include "y2_common.hpp"
+#include "y2_conv_shared.hpp"       // epilogue_fast: the half [local]'s epilogue is the half convolutions'
 #include <float.h>
 #include <stdlib.h>
+#include <type_traits>
 
 // the four in-kernel activations, with the reference's arithmetic (activations.h:35-41: leaky and logistic in double)
 __device__ __forceinline__ float activate_ref(float v, int act)
@@ -17,13 +21,15 @@ __device__ __forceinline__ float activate_ref(float v, int act)
 
 // ---------------------------------------------------------------------------
 // maxpool  (src_yolo2/maxpool_layer.c:79-114; CUDA twin maxpool_layer_kernels.cu:10)
-// window origin = -pad + o*stride, out-of-image taps read as -FLT_MAX, strict '>'
+// window origin = -pad + o*stride, out-of-image taps read as the lowest finite value of T, strict '>'
+// V = storage<T>::VEC: a lane takes V channels with one 16-byte access; V = 1: one channel
 // ---------------------------------------------------------------------------
-template <int V>
-__global__ __launch_bounds__(256) void maxpool_kernel(const float *__restrict__ x, int ldx, float *__restrict__ y, int ldy,
+template <typename T, int V>
+__global__ __launch_bounds__(256) void maxpool_kernel(const T *__restrict__ x, int ldx, T *__restrict__ y, int ldy,
                                                       int h, int w, int c, int size, int stride, int pad,
                                                       int out_h, int out_w, long total)
 {
+    typedef typename storage<T>::vec vec;
     const int cv = c / V;
     for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
         const int cg = (int)(idx % cv);
@@ -31,52 +37,62 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const float *__restrict__ 
         const int ox = (int)(op % out_w);
         const int oy = (int)((op / out_w) % out_h);
         const long n = op / ((long)out_w * out_h);
-        float m[V];
+        T m[V];
 #pragma unroll
-        for (int v = 0; v < V; ++v) m[v] = -FLT_MAX;
+        for (int v = 0; v < V; ++v) m[v] = (T)storage<T>::LOWEST;
         for (int kh = 0; kh < size; ++kh) {
             const int iy = -pad + oy * stride + kh;
             for (int kw = 0; kw < size; ++kw) {
                 const int ix = -pad + ox * stride + kw;
                 if (iy >= 0 && iy < h && ix >= 0 && ix < w) {
-                    const float *src = x + ((n * h + iy) * (long)w + ix) * ldx + cg * V;
-                    if (V == 4) {
-                        const float4 q = *(const float4 *)src;
-                        m[0] = (q.x > m[0]) ? q.x : m[0];
-                        m[1 % V] = (q.y > m[1 % V]) ? q.y : m[1 % V];
-                        m[2 % V] = (q.z > m[2 % V]) ? q.z : m[2 % V];
-                        m[3 % V] = (q.w > m[3 % V]) ? q.w : m[3 % V];
+                    const T *src = x + ((n * h + iy) * (long)w + ix) * ldx + cg * V;
+                    if constexpr (V > 1) {
+                        const vec q = *(const vec *)src;
+#pragma unroll
+                        for (int v = 0; v < V; ++v) m[v] = (q[v] > m[v]) ? q[v] : m[v];
                     } else {
-                        const float q = *src;
+                        const T q = *src;
                         m[0] = (q > m[0]) ? q : m[0];
                     }
                 }
             }
         }
-        float *dst = y + op * ldy + cg * V;
-        if (V == 4) *(float4 *)dst = make_float4(m[0], m[1 % V], m[2 % V], m[3 % V]);
-        else *dst = m[0];
+        T *dst = y + op * ldy + cg * V;
+        if constexpr (V > 1) {
+            vec o;
+#pragma unroll
+            for (int v = 0; v < V; ++v) o[v] = m[v];
+            *(vec *)dst = o;
+        } else *dst = m[0];
     }
+}
+
+template <typename T>
+static int maxpool_launch(const T *x, int ldx, T *y, int ldy, int batch, int h, int w, int c, int size, int stride, int pad,
+                          int out_h, int out_w, y2h_stream s)
+{
+    if (!x || !y || batch <= 0 || h <= 0 || w <= 0 || c <= 0 || size <= 0 || stride <= 0 || ldx < c || ldy < c) return Y2H_EINVAL;
+    if (out_h != (h + 2 * pad) / stride || out_w != (w + 2 * pad) / stride) return Y2H_EINVAL;
+    constexpr int V = storage<T>::VEC;
+    const bool vec = y2h_vec_ok<T>(c, ldx, ldy, x, y);
+    const long total = (long)batch * out_h * out_w * (vec ? c / V : c);
+    void (*fn)(const T *, int, T *, int, int, int, int, int, int, int, int, int, long) = vec ? maxpool_kernel<T, V> : maxpool_kernel<T, 1>;
+    hipLaunchKernelGGL(fn, dim3(y2h_grid(total, 256, 256 * 32)), dim3(256), 0, S(s), x, ldx, y, ldy, h, w, c, size, stride, pad,
+                       out_h, out_w, total);
+    Y2H_LAUNCH_CHECK();
+    return Y2H_OK;
 }
 
 extern "C" int y2h_maxpool(const float *x, int ldx, float *y, int ldy, int batch, int h, int w, int c,
                            int size, int stride, int pad, int out_h, int out_w, y2h_stream s)
 {
-    if (batch <= 0 || h <= 0 || w <= 0 || c <= 0 || size <= 0 || stride <= 0 || ldx < c || ldy < c) return Y2H_EINVAL;
-    if (out_h != (h + 2 * pad) / stride || out_w != (w + 2 * pad) / stride) return Y2H_EINVAL;
-    const bool v4 = (c % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && (((uintptr_t)x | (uintptr_t)y) % 16 == 0);
-    const long npix = (long)batch * out_h * out_w;
-    if (v4) {
-        const long total = npix * (c / 4);
-        hipLaunchKernelGGL(maxpool_kernel<4>, dim3(y2h_grid(total, 256, 256 * 32)), dim3(256), 0, S(s),
-                           x, ldx, y, ldy, h, w, c, size, stride, pad, out_h, out_w, total);
-    } else {
-        const long total = npix * c;
-        hipLaunchKernelGGL(maxpool_kernel<1>, dim3(y2h_grid(total, 256, 256 * 32)), dim3(256), 0, S(s),
-                           x, ldx, y, ldy, h, w, c, size, stride, pad, out_h, out_w, total);
-    }
-    Y2H_LAUNCH_CHECK();
-    return Y2H_OK;
+    return maxpool_launch<float>(x, ldx, y, ldy, batch, h, w, c, size, stride, pad, out_h, out_w, s);
+}
+
+extern "C" int y2h_maxpool_f16(const void *x, int ldx, void *y, int ldy, int batch, int h, int w, int c,
+                               int size, int stride, int pad, int out_h, int out_w, y2h_stream s)
+{
+    return maxpool_launch<_Float16>((const _Float16 *)x, ldx, (_Float16 *)y, ldy, batch, h, w, c, size, stride, pad, out_h, out_w, s);
 }
 
 // ---------------------------------------------------------------------------
@@ -92,7 +108,8 @@ extern "C" int y2h_maxpool(const float *x, int ldx, float *y, int ldy, int batch
 // in the output's label geometry to find where it lives in NHWC, and the flat
 // source index is decoded in the input's [c][h][w] geometry.
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void reorg_kernel(const float *__restrict__ x, int ldx, float *__restrict__ y, int ldy,
+template <typename T>
+__global__ __launch_bounds__(256) void reorg_kernel(const T *__restrict__ x, int ldx, T *__restrict__ y, int ldy,
                                                     int h, int w, int c, int s, int reverse, long total)
 {
     const int oc_small = c / (s * s);
@@ -100,7 +117,6 @@ __global__ __launch_bounds__(256) void reorg_kernel(const float *__restrict__ x,
     const int lo_c = reverse ? oc_small : c * s * s;
     const int lo_h = reverse ? h * s : h / s;
     const int lo_w = reverse ? w * s : w / s;
-    const long per = (long)c * h * w;
     for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
         // idx enumerates NHWC output elements: (b, yo, xo, co), co fastest
         const int co = (int)(idx % lo_c);
@@ -130,49 +146,117 @@ __global__ __launch_bounds__(256) void reorg_kernel(const float *__restrict__ x,
         const int xi = (int)(q % w);
         const int yi = (int)((q / w) % h);
         const int ci = (int)(q / ((long)w * h));
-        (void)per;
         y[opix * ldy + co] = x[((b * h + yi) * (long)w + xi) * ldx + ci];
     }
 }
 
-extern "C" int y2h_reorg(const float *x, int ldx, float *y, int ldy, int batch, int h, int w, int c,
-                         int stride, int reverse, y2h_stream s)
+template <typename T>
+static int reorg_launch(const T *x, int ldx, T *y, int ldy, int batch, int h, int w, int c, int stride, int reverse, y2h_stream s)
 {
-    if (batch <= 0 || h <= 0 || w <= 0 || c <= 0 || stride <= 0 || ldx < c) return Y2H_EINVAL;
+    if (!x || !y || batch <= 0 || h <= 0 || w <= 0 || c <= 0 || stride <= 0 || ldx < c) return Y2H_EINVAL;
     if (c % (stride * stride) != 0) return Y2H_EINVAL;
     if (!reverse && (h % stride != 0 || w % stride != 0)) return Y2H_EINVAL;
     const int oc = reverse ? c / (stride * stride) : c * stride * stride;
     if (ldy < oc) return Y2H_EINVAL;
     const long total = (long)batch * h * w * c;
-    hipLaunchKernelGGL(reorg_kernel, dim3(y2h_grid(total, 256)), dim3(256), 0, S(s), x, ldx, y, ldy, h, w, c, stride,
+    hipLaunchKernelGGL(reorg_kernel<T>, dim3(y2h_grid(total, 256)), dim3(256), 0, S(s), x, ldx, y, ldy, h, w, c, stride,
                        reverse ? 1 : 0, total);
     Y2H_LAUNCH_CHECK();
     return Y2H_OK;
 }
 
+extern "C" int y2h_reorg(const float *x, int ldx, float *y, int ldy, int batch, int h, int w, int c,
+                         int stride, int reverse, y2h_stream s)
+{
+    return reorg_launch<float>(x, ldx, y, ldy, batch, h, w, c, stride, reverse, s);
+}
+
+extern "C" int y2h_reorg_f16(const void *x, int ldx, void *y, int ldy, int batch, int h, int w, int c,
+                             int stride, int reverse, y2h_stream s)
+{
+    return reorg_launch<_Float16>((const _Float16 *)x, ldx, (_Float16 *)y, ldy, batch, h, w, c, stride, reverse, s);
+}
+
 // ---------------------------------------------------------------------------
-// global average pool (src_yolo2/avgpool_layer.c:40-54): sequential fp32 sum, one divide
+// global average pool (src_yolo2/avgpool_layer.c:40-54): sequential fp32 sum in pixel order, one divide, fp32 result
+// (fp16 mode has no reference arithmetic to mirror; its input is half, the sum and the result are fp32 all the same)
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void avgpool_kernel(const float *__restrict__ x, int ldx, float *__restrict__ y,
+template <typename T>
+__global__ __launch_bounds__(256) void avgpool_kernel(const T *__restrict__ x, int ldx, float *__restrict__ y,
                                                       int hw, int c, long total)
 {
     for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
         const int k = (int)(idx % c);
         const long b = idx / c;
-        const float *src = x + b * hw * (long)ldx + k;
+        const T *src = x + b * hw * (long)ldx + k;
         float sum = 0.f;
-        for (int i = 0; i < hw; ++i) sum += src[(long)i * ldx];
+        for (int i = 0; i < hw; ++i) sum += (float)src[(long)i * ldx];
         y[idx] = sum / hw;
     }
 }
 
-extern "C" int y2h_avgpool(const float *x, int ldx, float *y, int batch, int h, int w, int c, y2h_stream s)
+// Half input with 16-byte loads: block = (image, 64 groups of 8 channels), a lane owns 8 channels, the block's four waves each
+// sum a contiguous quarter of the pixels in pixel order and wave 0 adds the four partial sums in order.  (The scalar form
+// above issues one 2-byte load per lane and pixel: 0.9 TB/s on the 50 MB of darknet19_448 b128, 1.6 % of that step.)  On
+// integer data both forms are exact.
+typedef float avg_f32x4 __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(256) void avgpool_f16_v8_kernel(const _Float16 *__restrict__ x, int ldx, float *__restrict__ y, int hw, int c)
 {
-    if (batch <= 0 || h <= 0 || w <= 0 || c <= 0 || ldx < c) return Y2H_EINVAL;
+    typedef storage<_Float16>::vec avg_f16x8;
+    __shared__ float part[4][64][9];
+    const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
+    const int c0 = (blockIdx.x * 64 + lane) * 8;
+    const long b = blockIdx.y;
+    float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (c0 < c) {
+        const int p0 = (int)((long)q * hw / 4), p1 = (int)((long)(q + 1) * hw / 4);
+        const _Float16 *src = x + (b * hw + p0) * (long)ldx + c0;
+#pragma unroll 7
+        for (int p = p0; p < p1; ++p, src += ldx) {
+            const avg_f16x8 v = *(const avg_f16x8 *)src;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) s[k] += (float)v[k];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) part[q][lane][k] = s[k];
+    __syncthreads();
+    if (q == 0 && c0 < c) {
+        float r[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) r[k] = (((part[0][lane][k] + part[1][lane][k]) + part[2][lane][k]) + part[3][lane][k]) / hw;
+        avg_f32x4 *dst = (avg_f32x4 *)(y + b * c + c0);
+        dst[0] = avg_f32x4{r[0], r[1], r[2], r[3]};
+        dst[1] = avg_f32x4{r[4], r[5], r[6], r[7]};
+    }
+}
+
+template <typename T>
+static int avgpool_launch(const T *x, int ldx, float *y, int batch, int h, int w, int c, y2h_stream s)
+{
+    if (!x || !y || batch <= 0 || h <= 0 || w <= 0 || c <= 0 || ldx < c) return Y2H_EINVAL;
+    if constexpr (std::is_same<T, _Float16>::value) {
+        if (c % 8 == 0 && ldx % 8 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0 && h * w >= 4 && !getenv("Y2_AVGPOOL_SCALAR")) {
+            hipLaunchKernelGGL(avgpool_f16_v8_kernel, dim3((unsigned)((c / 8 + 63) / 64), (unsigned)batch), dim3(256), 0, S(s),
+                               x, ldx, y, h * w, c);
+            Y2H_LAUNCH_CHECK();
+            return Y2H_OK;
+        }
+    }
     const long total = (long)batch * c;
-    hipLaunchKernelGGL(avgpool_kernel, dim3(y2h_grid(total, 256)), dim3(256), 0, S(s), x, ldx, y, h * w, c, total);
+    hipLaunchKernelGGL(avgpool_kernel<T>, dim3(y2h_grid(total, 256)), dim3(256), 0, S(s), x, ldx, y, h * w, c, total);
     Y2H_LAUNCH_CHECK();
     return Y2H_OK;
+}
+
+extern "C" int y2h_avgpool(const float *x, int ldx, float *y, int batch, int h, int w, int c, y2h_stream s)
+{
+    return avgpool_launch<float>(x, ldx, y, batch, h, w, c, s);
+}
+
+extern "C" int y2h_avgpool_f16(const void *x, int ldx, float *y, int batch, int h, int w, int c, y2h_stream s)
+{
+    return avgpool_launch<_Float16>((const _Float16 *)x, ldx, y, batch, h, w, c, s);
 }
 
 // ---------------------------------------------------------------------------
@@ -607,6 +691,8 @@ extern "C" int y2h_batchnorm(const float *x, int ldx, float *y, int ldy, long pi
 // (re-ordered at upload to [location][filter][kh][kw][c], matching the NHWC activations) and of the input, up to
 // eight images per pass so the weights are read once per eight images; a wave reduction finishes the dot products.
 //   y = act(bias + sum_k w*x)         (the reference adds the bias first; same value to rounding)
+// In fp16 mode the same kernel runs on half weights and activations (eight values per 16-byte load): the layer is a
+// weight stream, so half storage halves the bytes that bound it.
 // local_ref_kernel is the strict-mode form: one thread per output value, bias first, taps in the reference's
 // k = (c, kh, kw) order, product and sum rounded separately -- the arithmetic of gemm_nn (gemm.c:74-88).
 // ---------------------------------------------------------------------------
@@ -647,17 +733,22 @@ extern "C" int y2h_activate_array(float *x, int ld, long rows, int c, int activa
     return Y2H_OK;
 }
 
+template <typename T>          // activations and weights are both T (fp32, or half in fp16 mode); the bias is fp32
 struct LocalK {
-    const float *x; int ldx;
-    const float *wp;            // [loc][n][kh][kw][c]
+    const T *x; int ldx;
+    const T *wp;                // [loc][n][kh][kw][c]
     const float *bias;          // [loc][n]
-    float *y; int ldy;
+    T *y; int ldy;
     int batch, h, w, c, n, size, stride, pad, oh, ow, act;
 };
 
-template <int NB, bool VEC>
-__global__ __launch_bounds__(256) void local_kernel(LocalK a)
+// VEC: 16-byte loads of storage<T>::VEC values (c is a multiple of that, so a load never leaves its tap).  fp32
+// accumulation for both T.  fp32: y = act(bias + sum) in the reference's arithmetic; half: the half convolutions'
+// epilogue, rounded to half once.
+template <typename T, int NB, bool VEC>
+__global__ __launch_bounds__(256) void local_kernel(LocalK<T> a)
 {
+    typedef typename storage<T>::vec vec;
     const int lane = threadIdx.x & 63;
     const int groups = (a.n + 3) >> 2;
     const long wave = ((long)blockIdx.x * 256 + threadIdx.x) >> 6;
@@ -666,15 +757,15 @@ __global__ __launch_bounds__(256) void local_kernel(LocalK a)
     const int loc = (int)(wave / groups), m0 = (int)(wave - (long)loc * groups) * 4;
     const int oy = loc / a.ow, ox = loc - oy * a.ow;
     const int K = a.size * a.size * a.c;
-    const float *w0 = a.wp + ((size_t)loc * a.n + m0) * K;
+    const T *w0 = a.wp + ((size_t)loc * a.n + m0) * K;
     const int nf = (a.n - m0 < 4) ? a.n - m0 : 4;
+    constexpr int STEP = VEC ? storage<T>::VEC : 1;
     for (int b0 = 0; b0 < a.batch; b0 += NB) {
         float acc[NB][4];
 #pragma unroll
         for (int i = 0; i < NB; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
-        constexpr int STEP = VEC ? 4 : 1;
         for (int k = lane * STEP; k < K; k += 64 * STEP) {
             const int tap = k / a.c, ci = k - tap * a.c;
             const int kh = tap / a.size, kw = tap - kh * a.size;
@@ -683,12 +774,14 @@ __global__ __launch_bounds__(256) void local_kernel(LocalK a)
             float wv[4][STEP];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                if (j < nf) {
-                    if constexpr (VEC) { const float4 t = *(const float4 *)(w0 + (size_t)j * K + k); wv[j][0] = t.x; wv[j][1] = t.y; wv[j][2] = t.z; wv[j][3] = t.w; }
-                    else wv[j][0] = w0[(size_t)j * K + k];
-                } else {
 #pragma unroll
-                    for (int q = 0; q < STEP; ++q) wv[j][q] = 0.f;
+                for (int q = 0; q < STEP; ++q) wv[j][q] = 0.f;
+                if (j < nf) {
+                    if constexpr (VEC) {
+                        const vec t = *(const vec *)(w0 + (size_t)j * K + k);
+#pragma unroll
+                        for (int q = 0; q < STEP; ++q) wv[j][q] = (float)t[q];
+                    } else wv[j][0] = (float)w0[(size_t)j * K + k];
                 }
             }
 #pragma unroll
@@ -697,9 +790,12 @@ __global__ __launch_bounds__(256) void local_kernel(LocalK a)
 #pragma unroll
                 for (int q = 0; q < STEP; ++q) xv[q] = 0.f;
                 if (in && b0 + i < a.batch) {
-                    const float *xp = a.x + (((size_t)(b0 + i) * a.h + iy) * a.w + ix) * a.ldx + ci;
-                    if constexpr (VEC) { const float4 t = *(const float4 *)xp; xv[0] = t.x; xv[1] = t.y; xv[2] = t.z; xv[3] = t.w; }
-                    else xv[0] = *xp;
+                    const T *xp = a.x + (((size_t)(b0 + i) * a.h + iy) * a.w + ix) * a.ldx + ci;
+                    if constexpr (VEC) {
+                        const vec t = *(const vec *)xp;
+#pragma unroll
+                        for (int q = 0; q < STEP; ++q) xv[q] = (float)t[q];
+                    } else xv[0] = (float)*xp;
                 }
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
@@ -716,21 +812,23 @@ __global__ __launch_bounds__(256) void local_kernel(LocalK a)
                 for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
                 acc[i][j] = v;
             }
-        if (lane < 4 && lane < nf) {
+        if (lane < nf) {
+            const float bias = a.bias[(size_t)loc * a.n + m0 + lane];
 #pragma unroll
             for (int i = 0; i < NB; ++i) {
                 if (b0 + i >= a.batch) break;
                 float v = 0.f;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) v = (lane == j) ? acc[i][j] : v;
-                v = a.bias[(size_t)loc * a.n + m0 + lane] + v;
-                a.y[((size_t)(b0 + i) * a.oh * a.ow + loc) * a.ldy + m0 + lane] = activate_ref(v, a.act);
+                if constexpr (std::is_same<T, float>::value) v = activate_ref(bias + v, a.act);
+                else v = epilogue_fast(v, 1.f, bias, a.act);
+                a.y[((size_t)(b0 + i) * a.oh * a.ow + loc) * a.ldy + m0 + lane] = (T)v;
             }
         }
     }
 }
 
-__global__ __launch_bounds__(256) void local_ref_kernel(LocalK a)
+__global__ __launch_bounds__(256) void local_ref_kernel(LocalK<float> a)
 {
     const long total = (long)a.batch * a.oh * a.ow * a.n;
     const int K = a.size * a.size * a.c;
@@ -754,34 +852,46 @@ __global__ __launch_bounds__(256) void local_ref_kernel(LocalK a)
     }
 }
 
-extern "C" int y2h_local(const float *x, int ldx, const float *w_packed, const float *bias_packed, float *y, int ldy, int batch,
-                         int h, int w, int c, int n, int size, int stride, int pad, int out_h, int out_w, int activation,
-                         int strict, y2h_stream s)
+// strict (fp32 only): local_ref_kernel
+template <typename T>
+static int local_launch(const T *x, int ldx, const T *w_packed, const float *bias_packed, T *y, int ldy, int batch, int h, int w,
+                        int c, int n, int size, int stride, int pad, int out_h, int out_w, int activation, int strict, y2h_stream s)
 {
     if (!x || !w_packed || !bias_packed || !y || batch <= 0 || h <= 0 || w <= 0 || c <= 0 || n <= 0 || size <= 0 || stride <= 0 ||
         pad < 0 || out_h <= 0 || out_w <= 0 || ldx < c || ldy < n) return Y2H_EINVAL;
     if ((out_h - 1) * stride + size - pad > h + pad || (out_w - 1) * stride + size - pad > w + pad) return Y2H_EINVAL;
-    LocalK a;
-    a.x = x; a.ldx = ldx; a.wp = w_packed; a.bias = bias_packed; a.y = y; a.ldy = ldy; a.batch = batch; a.h = h; a.w = w; a.c = c;
-    a.n = n; a.size = size; a.stride = stride; a.pad = pad; a.oh = out_h; a.ow = out_w; a.act = activation;
-    if (strict) {
-        hipLaunchKernelGGL(local_ref_kernel, dim3(y2h_grid((long)batch * out_h * out_w * n, 256)), dim3(256), 0, S(s), a);
-        Y2H_LAUNCH_CHECK();
-        return Y2H_OK;
+    const LocalK<T> a = {x, ldx, w_packed, bias_packed, y, ldy, batch, h, w, c, n, size, stride, pad, out_h, out_w, activation};
+    if constexpr (std::is_same<T, float>::value) {
+        if (strict) {
+            hipLaunchKernelGGL(local_ref_kernel, dim3(y2h_grid((long)batch * out_h * out_w * n, 256)), dim3(256), 0, S(s), a);
+            Y2H_LAUNCH_CHECK();
+            return Y2H_OK;
+        }
     }
     const long waves = (long)out_h * out_w * ((n + 3) / 4);
     const unsigned blocks = (unsigned)((waves + 3) / 4);
-    const bool vec = (c % 4 == 0) && (ldx % 4 == 0) && (((uintptr_t)x | (uintptr_t)w_packed) % 16 == 0);
-    if (batch == 1) {
-        if (vec) hipLaunchKernelGGL((local_kernel<1, true>), dim3(blocks), dim3(256), 0, S(s), a);
-        else hipLaunchKernelGGL((local_kernel<1, false>), dim3(blocks), dim3(256), 0, S(s), a);
-    } else if (batch <= 4) {
-        if (vec) hipLaunchKernelGGL((local_kernel<4, true>), dim3(blocks), dim3(256), 0, S(s), a);
-        else hipLaunchKernelGGL((local_kernel<4, false>), dim3(blocks), dim3(256), 0, S(s), a);
-    } else {        // eight images per pass over the weights
-        if (vec) hipLaunchKernelGGL((local_kernel<8, true>), dim3(blocks), dim3(256), 0, S(s), a);
-        else hipLaunchKernelGGL((local_kernel<8, false>), dim3(blocks), dim3(256), 0, S(s), a);
-    }
+    constexpr int V = storage<T>::VEC;
+    const bool vec = (c % V == 0) && (ldx % V == 0) && (((uintptr_t)x | (uintptr_t)w_packed) % 16 == 0);
+    void (*fn)(LocalK<T>) = batch == 1 ? (vec ? local_kernel<T, 1, true> : local_kernel<T, 1, false>) :
+                            batch <= 4 ? (vec ? local_kernel<T, 4, true> : local_kernel<T, 4, false>) :
+                                         (vec ? local_kernel<T, 8, true> : local_kernel<T, 8, false>);   // eight images per pass over the weights
+    hipLaunchKernelGGL(fn, dim3(blocks), dim3(256), 0, S(s), a);
     Y2H_LAUNCH_CHECK();
     return Y2H_OK;
+}
+
+extern "C" int y2h_local(const float *x, int ldx, const float *w_packed, const float *bias_packed, float *y, int ldy, int batch,
+                         int h, int w, int c, int n, int size, int stride, int pad, int out_h, int out_w, int activation,
+                         int strict, y2h_stream s)
+{
+    return local_launch<float>(x, ldx, w_packed, bias_packed, y, ldy, batch, h, w, c, n, size, stride, pad, out_h, out_w, activation, strict, s);
+}
+
+extern "C" int y2h_local_f16(const void *x, int ldx, const void *w_packed, const float *bias_packed, void *y, int ldy, int batch,
+                             int h, int w, int c, int n, int size, int stride, int pad, int out_h, int out_w, int activation,
+                             y2h_stream s)
+{
+    if (activation < Y2H_ACT_LINEAR || activation > Y2H_ACT_RELU) return Y2H_EINVAL;
+    return local_launch<_Float16>((const _Float16 *)x, ldx, (const _Float16 *)w_packed, bias_packed, (_Float16 *)y, ldy, batch, h, w, c, n,
+                                  size, stride, pad, out_h, out_w, activation, 0, s);
 }

@@ -222,20 +222,22 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float *__restri
     }
 }
 
-__global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const float *__restrict__ src, int ld, float *__restrict__ dst,
+// NHWC [n][hw][ld] of fp32 or half -> fp32 NCHW [n][c][hw] (what network_predict / y2_pull_layer_output hand to the host)
+template <typename T>
+__global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const T *__restrict__ src, int ld, float *__restrict__ dst,
                                                            int c, long hw)
 {
     __shared__ float tile[32][65];
     const long p0 = (long)blockIdx.x * 64;
     const int c0 = blockIdx.y * 32;
     const int n = blockIdx.z;
-    const float *s = src + (long)n * hw * ld;
+    const T *s = src + (long)n * hw * ld;
     float *d = dst + (long)n * c * hw;
     const int cx = threadIdx.x & 31, py = threadIdx.x >> 5;
     for (int pp = py; pp < 64; pp += 8) {
         const long p = p0 + pp;
         const int ch = c0 + cx;
-        tile[cx][pp] = (ch < c && p < hw) ? s[p * ld + ch] : 0.f;
+        tile[cx][pp] = (ch < c && p < hw) ? (float)s[p * ld + ch] : 0.f;
     }
     __syncthreads();
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
@@ -256,14 +258,25 @@ extern "C" int y2h_nchw_to_nhwc(const float *src, float *dst, int n, int c, int 
     return Y2H_OK;
 }
 
-extern "C" int y2h_nhwc_to_nchw(const float *src, int ld, float *dst, int n, int c, int h, int w, y2h_stream s)
+template <typename T>
+static int nhwc_to_nchw_launch(const T *src, int ld, float *dst, int n, int c, int h, int w, y2h_stream s)
 {
-    if (n <= 0 || c <= 0 || h <= 0 || w <= 0 || ld < c) return Y2H_EINVAL;
+    if (!src || !dst || n <= 0 || c <= 0 || h <= 0 || w <= 0 || ld < c) return Y2H_EINVAL;
     const long hw = (long)h * w;
     dim3 grid((unsigned)((hw + 63) / 64), (unsigned)((c + 31) / 32), (unsigned)n);
-    hipLaunchKernelGGL(nhwc_to_nchw_kernel, grid, dim3(256), 0, S(s), src, ld, dst, c, hw);
+    hipLaunchKernelGGL(nhwc_to_nchw_kernel<T>, grid, dim3(256), 0, S(s), src, ld, dst, c, hw);
     Y2H_LAUNCH_CHECK();
     return Y2H_OK;
+}
+
+extern "C" int y2h_nhwc_to_nchw(const float *src, int ld, float *dst, int n, int c, int h, int w, y2h_stream s)
+{
+    return nhwc_to_nchw_launch<float>(src, ld, dst, n, c, h, w, s);
+}
+
+extern "C" int y2h_nhwc_f16_to_nchw(const void *src, int ld, float *dst, int n, int c, int h, int w, y2h_stream s)
+{
+    return nhwc_to_nchw_launch<_Float16>((const _Float16 *)src, ld, dst, n, c, h, w, s);
 }
 
 // few-channel NCHW -> NHWC with a `halo`-pixel border: one thread per pixel reads its c planes
@@ -291,43 +304,97 @@ extern "C" int y2h_nchw_to_nhwc_halo(const float *src, float *dst, int n, int c,
     return Y2H_OK;
 }
 
-__global__ __launch_bounds__(256) void copy_channels_kernel(const float *__restrict__ src, int ld_src,
-                                                            float *__restrict__ dst, int ld_dst, int c, long total)
+// network input for the fp16 first-layer kernel: fp32 NCHW (<= 4 planes) -> half [n][h+2][w+2][4], interior only;
+// one thread per pixel reads its planes (coalesced along x) and writes one 8-byte pixel
+typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(256) void nchw_to_nhwc4_halo_f16_kernel(const float *__restrict__ src, _Float16 *__restrict__ dst,
+                                                                     int c, int h, int w, long total)
 {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-        const long p = i / c;
-        const int ch = (int)(i - p * c);
-        dst[p * ld_dst + ch] = src[p * ld_src + ch];
+    const long hw = (long)h * w;
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const int x = (int)(idx % w);
+        const int y = (int)((idx / w) % h);
+        const long n = idx / hw;
+        const float *s = src + n * c * hw + (long)y * w + x;
+        h4 px;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) px[k] = (k < c) ? (_Float16)s[k * hw] : (_Float16)0.f;
+        *(h4 *)&dst[((n * (h + 2) + (y + 1)) * (long)(w + 2) + (x + 1)) * 4] = px;
     }
 }
 
-__global__ __launch_bounds__(256) void copy_channels4_kernel(const float4 *__restrict__ src, int ld_src4,
-                                                             float4 *__restrict__ dst, int ld_dst4, int c4, long total)
+extern "C" int y2h_nchw_to_nhwc4_halo_f16(const float *src, void *dst, int n, int c, int h, int w, y2h_stream s)
 {
+    if (!src || !dst || n <= 0 || c <= 0 || c > 4 || h <= 0 || w <= 0 || ((uintptr_t)dst % 8) != 0) return Y2H_EINVAL;
+    const long total = (long)n * h * w;
+    hipLaunchKernelGGL(nchw_to_nhwc4_halo_f16_kernel, dim3(y2h_grid(total, 256)), dim3(256), 0, S(s), src, (_Float16 *)dst,
+                       c, h, w, total);
+    Y2H_LAUNCH_CHECK();
+    return Y2H_OK;
+}
+
+// array conversions (weights are converted on the host; these serve the kernel-level tests)
+__global__ __launch_bounds__(256) void f32_to_f16_kernel(const float *__restrict__ src, _Float16 *__restrict__ dst, long n)
+{
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) dst[i] = (_Float16)src[i];
+}
+__global__ __launch_bounds__(256) void f16_to_f32_kernel(const _Float16 *__restrict__ src, float *__restrict__ dst, long n)
+{
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) dst[i] = (float)src[i];
+}
+extern "C" int y2h_f32_to_f16(const float *src, void *dst, long n, y2h_stream s)
+{
+    if (!src || !dst || n <= 0) return Y2H_EINVAL;
+    hipLaunchKernelGGL(f32_to_f16_kernel, dim3(y2h_grid(n, 256)), dim3(256), 0, S(s), src, (_Float16 *)dst, n);
+    Y2H_LAUNCH_CHECK();
+    return Y2H_OK;
+}
+extern "C" int y2h_f16_to_f32(const void *src, float *dst, long n, y2h_stream s)
+{
+    if (!src || !dst || n <= 0) return Y2H_EINVAL;
+    hipLaunchKernelGGL(f16_to_f32_kernel, dim3(y2h_grid(n, 256)), dim3(256), 0, S(s), (const _Float16 *)src, dst, n);
+    Y2H_LAUNCH_CHECK();
+    return Y2H_OK;
+}
+
+// [route] fallback copy of c channels per pixel between two leading dimensions; V = storage<T>::VEC: one 16-byte access
+// per lane, V = 1: one element
+template <typename T, int V>
+__global__ __launch_bounds__(256) void copy_channels_kernel(const T *__restrict__ src, int ld_src, T *__restrict__ dst, int ld_dst,
+                                                            int c, long total)
+{
+    typedef typename storage<T>::vec vec;
+    const int cv = c / V;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-        const long p = i / c4;
-        const int ch = (int)(i - p * c4);
-        dst[p * ld_dst4 + ch] = src[p * ld_src4 + ch];
+        const long p = i / cv;
+        const int ch = (int)(i - p * cv) * V;
+        if constexpr (V > 1) *(vec *)&dst[p * ld_dst + ch] = *(const vec *)&src[p * ld_src + ch];
+        else dst[p * ld_dst + ch] = src[p * ld_src + ch];
     }
+}
+
+template <typename T>
+static int copy_channels_launch(const T *src, int ld_src, T *dst, int ld_dst, int c, long npix, y2h_stream s)
+{
+    if (c <= 0 || npix <= 0) return Y2H_OK;
+    if (!src || !dst || ld_src < c || ld_dst < c) return Y2H_EINVAL;
+    constexpr int V = storage<T>::VEC;
+    const bool vec = y2h_vec_ok<T>(c, ld_src, ld_dst, src, dst);
+    const long total = npix * (vec ? c / V : c);
+    void (*fn)(const T *, int, T *, int, int, long) = vec ? copy_channels_kernel<T, V> : copy_channels_kernel<T, 1>;
+    hipLaunchKernelGGL(fn, dim3(y2h_grid(total, 256)), dim3(256), 0, S(s), src, ld_src, dst, ld_dst, c, total);
+    Y2H_LAUNCH_CHECK();
+    return Y2H_OK;
 }
 
 extern "C" int y2h_copy_channels(const float *src, int ld_src, float *dst, int ld_dst, int c, long npix, y2h_stream s)
 {
-    if (c <= 0 || npix <= 0) return Y2H_OK;
-    if (ld_src < c || ld_dst < c) return Y2H_EINVAL;
-    const bool v4 = (c % 4 == 0) && (ld_src % 4 == 0) && (ld_dst % 4 == 0) &&
-                    (((uintptr_t)src | (uintptr_t)dst) % 16 == 0);
-    if (v4) {
-        const long total = npix * (c / 4);
-        hipLaunchKernelGGL(copy_channels4_kernel, dim3(y2h_grid(total, 256)), dim3(256), 0, S(s),
-                           (const float4 *)src, ld_src / 4, (float4 *)dst, ld_dst / 4, c / 4, total);
-    } else {
-        const long total = npix * c;
-        hipLaunchKernelGGL(copy_channels_kernel, dim3(y2h_grid(total, 256)), dim3(256), 0, S(s),
-                           src, ld_src, dst, ld_dst, c, total);
-    }
-    Y2H_LAUNCH_CHECK();
-    return Y2H_OK;
+    return copy_channels_launch<float>(src, ld_src, dst, ld_dst, c, npix, s);
+}
+
+extern "C" int y2h_copy_channels_f16(const void *src, int ld_src, void *dst, int ld_dst, int c, long npix, y2h_stream s)
+{
+    return copy_channels_launch<_Float16>((const _Float16 *)src, ld_src, (_Float16 *)dst, ld_dst, c, npix, s);
 }
 
 // ---------------------------------------------------------------------------

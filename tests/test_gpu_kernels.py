@@ -63,6 +63,16 @@ def to_nchw(x):
     return np.ascontiguousarray(np.transpose(x, (0, 3, 1, 2)))
 
 
+def _both_storages(ident, *case):
+    """One case for the fp32 entry under `ident` and for the half-storage entry (y2h_*_f16) under `ident`-f16.  Half data
+    is chosen exactly representable in half, where max, copy and permutation are exact: both legs compare bit for bit."""
+    return [pytest.param(np.float32, *case, id=ident), pytest.param(np.float16, *case, id=ident + "-f16")]
+
+
+def _offset(p, elements, dtype):
+    return C.c_void_p(p.value + elements * np.dtype(dtype).itemsize)
+
+
 @pytest.mark.parametrize("n,c,h,w", [(1, 3, 5, 7), (2, 32, 19, 19), (3, 425, 13, 13), (1, 1, 1, 1), (2, 70, 33, 65)])
 def test_layout_round_trip(dev, n, c, h, w):
     L = dev.L
@@ -76,42 +86,118 @@ def test_layout_round_trip(dev, n, c, h, w):
     assert np.array_equal(dev.get(dy, (n, h, w, c)), to_nhwc(x))
     assert L.y2h_nhwc_to_nchw(dy, c, dz, n, c, h, w, None) == 0
     assert np.array_equal(dev.get(dz, (n, c, h, w)), x)
+    # half storage on the device, fp32 NCHW for the host: the conversion to fp32 is exact
+    L.y2h_nhwc_f16_to_nchw.argtypes = L.y2h_nhwc_to_nchw.argtypes
+    dh = dev.put(to_nhwc(x).astype(np.float16))
+    assert L.y2h_nhwc_f16_to_nchw(dh, c, dz, n, c, h, w, None) == 0
+    assert np.array_equal(dev.get(dz, (n, c, h, w)), x.astype(np.float16).astype(np.float32))
 
 
-@pytest.mark.parametrize("h,w,c,size,stride,pad", [(8, 8, 16, 2, 2, 0), (13, 13, 512, 2, 1, 0), (7, 9, 3, 2, 2, 0),
-                                                   (9, 9, 8, 3, 2, 1), (5, 5, 4, 3, 1, 1), (6, 6, 5, 2, 1, 0)])
-def test_maxpool_matches_oracle_bitwise(dev, oracle, h, w, c, size, stride, pad):
+# (h, w, c, size, stride, pad, ld, off): ld = leading dimension of x and y (0: c), off = elements by which x is moved into
+# its buffer.  c = 8 at ld 12 is a 16-byte layout for fp32 and not for half; off = 1 takes the pointer off 16 bytes.
+MAXPOOL_CASES = sum((_both_storages("%d-%d-%d-%d-%d-%d" % k, *k, 0, 0) for k in [
+    (8, 8, 16, 2, 2, 0), (13, 13, 512, 2, 1, 0), (7, 9, 3, 2, 2, 0), (9, 9, 8, 3, 2, 1), (5, 5, 4, 3, 1, 1), (6, 6, 5, 2, 1, 0),
+    (4, 4, 8, 3, 2, 1)]), []) + _both_storages("5-5-8-2-2-0-ld12", 5, 5, 8, 2, 2, 0, 12, 0) + \
+    _both_storages("5-5-8-2-2-0-off1", 5, 5, 8, 2, 2, 0, 0, 1)
+
+
+@pytest.mark.parametrize("dtype,h,w,c,size,stride,pad,ld,off", MAXPOOL_CASES)
+def test_maxpool_matches_oracle_bitwise(dev, oracle, dtype, h, w, c, size, stride, pad, ld, off):
     L = dev.L
     n = 2
+    ld = ld or c
+    half = dtype == np.float16
     x = synth.uniform(3, n * c * h * w, -2, 2).reshape(n, c, h, w)
-    x[0, 0, 0, 0] = np.float32(-3.0e38)
+    if half:          # multiples of 1/64, and the lowest finite half below
+        x = (np.round(x * 64) / 64).astype(np.float32)
+    x[0, 0, 0, 0] = np.float32(-65504 if half else -3.0e38)
     oh, ow = (h + 2 * pad) // stride, (w + 2 * pad) // stride
     want = oracle.maxpool(x, n, h, w, c, size, stride, pad).reshape(n, c, oh, ow)
-    dx = dev.put(to_nhwc(x))
-    dy = dev.empty(n * oh * ow * c * 4)
-    L.y2h_maxpool.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 10 + [C.c_void_p]
-    assert L.y2h_maxpool(dx, c, dy, c, n, h, w, c, size, stride, pad, oh, ow, None) == 0
-    assert np.array_equal(to_nchw(dev.get(dy, (n, oh, ow, c))), want)
+    if half:
+        # a window with no tap inside the image (5-5-4-3-1-1: the last row and column) keeps the starting value, which
+        # is -FLT_MAX in fp32 and the lowest finite half, -65504, in half: no input is below it
+        want = np.maximum(want, np.float32(-65504)).astype(np.float16)
+    rows = np.zeros((n, h, w, ld), dtype)
+    rows[..., :c] = to_nhwc(x)
+    dx = dev.put(np.concatenate([np.zeros(off, dtype), rows.reshape(-1)]))
+    sentinel = dtype(-7)
+    dy = dev.put(np.full(n * oh * ow * ld, sentinel, dtype))
+    fn = L.y2h_maxpool_f16 if half else L.y2h_maxpool
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 10 + [C.c_void_p]
+    assert fn(_offset(dx, off, dtype), ld, dy, ld, n, h, w, c, size, stride, pad, oh, ow, None) == 0
+    got = dev.get(dy, (n, oh, ow, ld), dtype)
+    assert np.array_equal(to_nchw(got[..., :c]), want)
+    assert np.all(got[..., c:] == sentinel)           # the padding columns of y are not written
 
 
-@pytest.mark.parametrize("w,h,c,s", [(2, 2, 4, 2), (2, 2, 8, 2), (4, 2, 4, 2), (38, 38, 64, 2), (6, 6, 9, 3)])
+@pytest.mark.parametrize("dtype,w,h,c,s", sum((_both_storages("%d-%d-%d-%d" % k, *k) for k in [
+    (2, 2, 4, 2), (2, 2, 8, 2), (4, 2, 4, 2), (38, 38, 64, 2), (6, 6, 9, 3)]), []))
 @pytest.mark.parametrize("reverse", [0, 1])
-def test_reorg_quirk_matches_oracle_bitwise(dev, oracle, w, h, c, s, reverse):
+def test_reorg_quirk_matches_oracle_bitwise(dev, oracle, dtype, w, h, c, s, reverse):
     L = dev.L
     n = 2
     if reverse:
         h, w = max(h // s, 1), max(w // s, 1)
     x = np.arange(n * c * h * w, dtype=np.float32).reshape(n, c, h, w)
-    want = oracle.reorg(x, w, h, c, n, s, forward=reverse)
+    if dtype == np.float16:
+        x = x % 2039          # integers below 2048 are exact in half; a prime period, so a wrong permutation still shows
+    want = oracle.reorg(x, w, h, c, n, s, forward=reverse).astype(dtype)
     oc, oh, ow = (c // (s * s), h * s, w * s) if reverse else (c * s * s, h // s, w // s)
-    dx = dev.put(to_nhwc(x))
+    dx = dev.put(to_nhwc(x).astype(dtype))
     dy = dev.empty(x.nbytes)
-    L.y2h_reorg.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]
-    assert L.y2h_reorg(dx, c, dy, oc, n, h, w, c, s, reverse, None) == 0
-    got = to_nchw(dev.get(dy, (n, oh, ow, oc))).reshape(-1)
+    fn = L.y2h_reorg_f16 if dtype == np.float16 else L.y2h_reorg
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]
+    assert fn(dx, c, dy, oc, n, h, w, c, s, reverse, None) == 0
+    got = to_nchw(dev.get(dy, (n, oh, ow, oc), dtype)).reshape(-1)
     assert np.array_equal(got, want.reshape(-1))
     if (w, h, c, s, reverse) == (2, 2, 4, 2, 0):      # SURVEY.md appendix C known answer (batch item 0)
         assert got[:16].tolist() == [0, 2, 8, 10, 1, 3, 9, 11, 4, 6, 12, 14, 5, 7, 13, 15]
+
+
+@pytest.mark.parametrize("c", [8, 12, 5])
+@pytest.mark.parametrize("dtype", [np.float32, np.float16], ids=["f32", "f16"])
+def test_copy_channels_both_storages(dev, dtype, c):
+    """The [route] fallback copy: c = 8 is one 16-byte access in half and two in fp32, 12 is 16-byte in fp32 only, 5 in
+    neither; a source row of c + 3 elements, or a destination that starts 3 channels into its row, breaks the 16-byte
+    layout and takes the element form.  Only the c copied columns of the destination change."""
+    L = dev.L
+    npix, ld_dst = 7, 24
+    fn = L.y2h_copy_channels_f16 if dtype == np.float16 else L.y2h_copy_channels
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_long, C.c_void_p]
+    sentinel = dtype(-7)
+    for ld_src in (c + 3, c):
+        src = (np.arange(npix * ld_src) % 2039).astype(dtype).reshape(npix, ld_src)       # exact in half
+        dsrc = dev.put(src)
+        for at in (0, 3):
+            ddst = dev.put(np.full((npix, ld_dst), sentinel, dtype))
+            assert fn(dsrc, ld_src, _offset(ddst, at, dtype), ld_dst, c, npix, None) == 0
+            got = dev.get(ddst, (npix, ld_dst), dtype)
+            assert np.array_equal(got[:, at:at + c], src[:, :c]), (ld_src, at)
+            assert np.all(got[:, :at] == sentinel) and np.all(got[:, at + c:] == sentinel), (ld_src, at)
+
+
+@pytest.mark.parametrize("hw,c", [(49, 8), (3, 8), (49, 5), (1, 16)])
+@pytest.mark.parametrize("entry", ["y2h_avgpool", "y2h_avgpool_f16"])
+def test_avgpool_scalar_and_vector_agree(dev, monkeypatch, entry, hw, c):
+    """avgpool_layer.c:40-54 on small integers, where every sum is exact in any order: the fp32 entry, and the half
+    entry in its 16-byte form (c % 8 == 0 and at least four pixels) and, with Y2_AVGPOOL_SCALAR set or where that form
+    does not apply, in the scalar form, all give sum / hw rounded to fp32 once."""
+    L = dev.L
+    n = 2
+    half = entry.endswith("_f16")
+    x = np.round(synth.uniform(5, n * hw * c, -8, 8)).astype(np.float32).reshape(n, hw, c)
+    want = (x.astype(np.float64).sum(axis=1) / hw).astype(np.float32)
+    dx = dev.put(x.astype(np.float16 if half else np.float32))
+    fn = getattr(L, entry)
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]
+    for scalar in ((False, True) if half else (False,)):
+        if scalar:
+            monkeypatch.setenv("Y2_AVGPOOL_SCALAR", "1")
+        else:
+            monkeypatch.delenv("Y2_AVGPOOL_SCALAR", raising=False)
+        dy = dev.put(np.full((n, c), -7, np.float32))
+        assert fn(dx, c, dy, n, 1, hw, c, None) == 0
+        assert np.array_equal(dev.get(dy, (n, c)), want), scalar
 
 
 def test_softmax_rows_matches_oracle(dev, oracle):
