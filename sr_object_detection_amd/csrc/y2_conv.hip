@@ -1815,6 +1815,7 @@ static int stem_launch(const y2h_conv *d, ConvK &a, y2h_stream s)
     if (bpc > 4) bpc = 4;
     long blocks = (ntiles + 3) / 4;
     if (blocks > 256L * bpc) blocks = 256L * bpc;
+    if (const char *g = getenv("Y2_CONV_GRID")) { if (atol(g) > 0 && atol(g) < blocks) blocks = atol(g); }   // tests: several tiles per wave on small shapes
     hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(256), lds, S(s), a);
     Y2H_LAUNCH_CHECK();
     return Y2H_OK;

@@ -258,14 +258,19 @@ def test_resize_image_matches_oracle_bitwise(oracle):
         assert np.array_equal(darknet.resize_image(x, w, h), oracle.resize_image(x, w, h))
 
 
-def _small_int_conv_case(workdir, spec, size, batch, seed, neg_scale=False):
+def _small_int_conv_case(workdir, spec, size, batch, seed, neg_scale=False, height=None, channels=3):
     """cfg + integer-valued weights/inputs so that every fp32 partial sum is exact in any order.
-    neg_scale: batch-norm scales alternate +1, -1.5 (a negative scale turns the epilogue into a DEcreasing function)."""
+    neg_scale: batch-norm scales alternate +1, -1.5 (a negative scale turns the epilogue into a DEcreasing function).
+    size is the input width; height (default: square) and channels (default 3) describe the rest of the network input."""
     import os
     import struct
-    layers = zoo.resolve(spec, size)
+    height = height or size
+    layers = zoo.resolve(spec, size, height, channels)
     cfg = os.path.join(workdir, "intconv_%d.cfg" % seed)
-    open(cfg, "w").write(zoo.cfg_text("x", size, size, batch, spec=spec))
+    text = zoo.cfg_text("x", size, height, batch, spec=spec)
+    if channels != 3:
+        text = text.replace("\nchannels=3\n", "\nchannels=%d\n" % channels, 1)
+    open(cfg, "w").write(text)
     wts = os.path.join(workdir, "intconv_%d.weights" % seed)
     with open(wts, "wb") as f:
         f.write(struct.pack("<iiii", 0, 1, 0, 0))
@@ -284,7 +289,8 @@ def _small_int_conv_case(workdir, spec, size, batch, seed, neg_scale=False):
                 f.write(np.round(synth.uniform(s + 100, n, -2, 2)).astype(np.float32).tobytes())  # mean
                 f.write(np.full(n, 1, np.float32).tobytes())                                      # variance
             f.write(np.round(synth.uniform(s + 200, n * K, -1.49, 1.49)).astype(np.float32).tobytes())
-    x = np.round(synth.uniform(seed + 999, batch * 3 * size * size, -2, 2)).astype(np.float32).reshape(batch, 3, size, size)
+    x = np.round(synth.uniform(seed + 999, batch * channels * height * size, -2, 2)).astype(np.float32)
+    x = x.reshape(batch, channels, height, size)
     return cfg, wts, x
 
 

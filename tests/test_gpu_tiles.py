@@ -7,7 +7,8 @@ straddle two images), with the persistent grid capped (Y2_CONV_GRID) so that eve
 the cross-tile prefetch of the staging side runs, with 1x1 and 3x3 filters, both K-slice depths, with and without the
 fused 2x2 maxpool, and K-split for the tiles that use it.  Integer-valued data make every fp32 partial sum exact in
 any order, so the result must EQUAL the oracle's (convolutional_layer.c:435-474, gemm.c:74-88 restated in
-oracle/y2_oracle.c); the fp16 kernels must equal it rounded once to half.
+oracle/y2_oracle.c); the fp16 kernels must equal it rounded once to half.  The four 5x5 tiles, strides above 1, the stem
+kernel and the direct kernel are held to the same standard in tests/test_gpu_conv_forms.py; the 5x5 names are listed here.
 
 TESTED_F32 / TESTED_F16 are also what tests/test_gpu_configs.py holds the BASELINE workloads to: a kernel name the
 benchmark times must be in these sets."""
@@ -28,8 +29,12 @@ F32_TILES_BK16 = [(128, 128), (128, 64), (64, 64), (128, 32)]
 F16_TILES = [(256, 256, True), (256, 256, False), (256, 128, False), (256, 64, False), (128, 128, False), (128, 64, False),
              (64, 64, False)]
 
+# (BM, BN): the 5x5 instantiations, at both K-slice depths; forced and compared in tests/test_gpu_conv_forms.py
+F32_TILES_K5 = [(128, 128), (64, 64)]
+
 TESTED_F32 = {"conv_mfma_f32_%dx%dx%d_k%d" % (bm, bn, bk, ks) for bk, tiles in ((32, F32_TILES_BK32), (16, F32_TILES_BK16))
               for (bm, bn) in tiles for ks in (1, 3)}
+TESTED_F32 |= {"conv_mfma_f32_%dx%dx%d_k5" % (bm, bn, bk) for (bm, bn) in F32_TILES_K5 for bk in (32, 16)}
 TESTED_F16 = {"conv_mfma_f16_%dx%dx%d_k%d" % (bm, bn, bk, ks) for (bm, bn, _) in F16_TILES for bk in (64, 32) for ks in (1, 3)}
 
 
@@ -507,4 +512,4 @@ def test_f32_c32_weights_stationary_kernel_is_exact(oracle, workdir, monkeypatch
 
 def test_kernel_name_pattern():
     for n in sorted(TESTED_F32 | TESTED_F16):
-        assert re.fullmatch(r"conv_mfma_f(32|16)_\d+x\d+x\d+_k[13]", n)
+        assert re.fullmatch(r"conv_mfma_f(32|16)_\d+x\d+x\d+_k[135]", n)
