@@ -328,7 +328,7 @@ int y2h_region_forward(const float *x, int ldx, float *y, int batch, int hw, int
  *   without a map; tree.c:37-44): best[0 .. boxes) = hierarchy probability of the deepest class above .5 (0: none),
  *   best[boxes .. 2 boxes) = that class as int.  Independent of the detection threshold; y is written exactly as without.
  *   parent / order / level_off / levels: the tree with its nodes listed by depth level (parents precede children);
- *   y2h_region_tree_best_ok: 1 when the row fits the LDS kernel.
+ *   y2h_region_tree_best_ok: 1 when the row fits the LDS kernel (classes <= 16383: the row and one word in 64 KB).
  * flags & Y2H_REGION_FAST_EXP: the group softmax takes expf (single precision, ~1 ulp) where the reference rounds a double
  *   exp to float (blas.c softmax): outputs differ by ~1e-7 relative, sums run in the reference's order.  The double exps are
  *   what the layer costs (9418 per box in yolo9000).  Env Y2_REGION_EXP_DOUBLE=1 overrides the flag. */
@@ -388,7 +388,7 @@ int y2h_detect_chain(const y2h_decode *q, float nms, float *probs_nms, int *clas
 int y2h_detect_tree_chain_ok(const y2h_decode *q);
 int y2h_detect_tree_chain(const y2h_decode *q, float nms, float *records, int *counts, int max_per_image, float *best_scratch,
                           const float *tree_best /* y2h_region_forward_tree's `best` for q->pred, or 0 */, y2h_stream s);
-/* class-agnostic variant, box.c:279-298 */
+/* class-agnostic variant, box.c:279-298; total <= 16384 (one flag byte per box in LDS), Y2H_EINVAL beyond */
 int y2h_nms(const float *boxes, float *probs, int batch, int total, int classes, int stride,
             float thresh, y2h_stream s);
 

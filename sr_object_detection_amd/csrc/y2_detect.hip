@@ -426,7 +426,9 @@ extern "C" int y2h_nms(const float *boxes, float *probs, int batch, int total, i
                        float thresh, y2h_stream s)
 {
     if (!boxes || !probs || batch <= 0 || total <= 0 || classes <= 0 || stride < classes) return Y2H_EINVAL;
-    if (total > 65536) return Y2H_EINVAL;
+    // one flag byte per box in dynamic LDS next to the static word s_any: 16384 (y2h_nms_sort's bound, and the largest total
+    // the suite runs) stays far inside the 64 KB a launch gets without hipFuncAttributeMaxDynamicSharedMemorySize
+    if (total > 16384) return Y2H_EINVAL;
     hipLaunchKernelGGL(nms_plain_kernel, dim3((unsigned)batch), dim3(256), (size_t)((total + 15) / 16 * 16), S(s),
                        boxes, probs, total, classes, stride, thresh);
     Y2H_LAUNCH_CHECK();

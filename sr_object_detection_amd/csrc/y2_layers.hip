@@ -489,9 +489,11 @@ __global__ __launch_bounds__(RT_NT) void region_tree_lds_kernel(const float *__r
     }
 }
 
+// The row (dynamic LDS) and the kernel's static word (s_best) together must fit the 64 KB a launch gets without
+// hipFuncAttributeMaxDynamicSharedMemorySize: 16383 classes is the last row, 16384 goes to region_tree_kernel.
 static bool region_tree_lds_ok(int classes, long boxes)
 {
-    return (size_t)classes * sizeof(float) <= 64 * 1024 && boxes < 0x7fffffffL && !getenv("Y2_REGION_TREE_SIMPLE");
+    return (size_t)classes * sizeof(float) + sizeof(int) <= 64 * 1024 && boxes < 0x7fffffffL && !getenv("Y2_REGION_TREE_SIMPLE");
 }
 
 extern "C" int y2h_region_tree_best_ok(int classes, int levels)

@@ -337,6 +337,7 @@ def test_split_k_conv_is_exact_on_integer_data(oracle, workdir, monkeypatch, cin
 
 
 def test_region_kernel_matches_oracle(oracle, workdir):
+    """the region head inside a network; every kernel form of it by itself: tests/test_gpu_head_kernels.py"""
     cfg, wts, x = materialize(workdir, "mini", 32, 2, 3)
     net = darknet.Network.parse_network_cfg(cfg)
     net.load_weights(wts)
