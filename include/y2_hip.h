@@ -104,11 +104,11 @@ int  y2h_graph_launch(y2h_graph g, y2h_stream s);
 int  y2h_graph_destroy(y2h_graph g);
 
 /* ---- layout ---- */
-/* [n][c][h][w] -> [n][h][w][ld] (channels 0..c-1 of each pixel row) and back */
+/* [n][c][h][w] -> [n][h][w][ld] (channels 0..c-1 of each pixel row) and back; a NULL pointer or ld < c: Y2H_EINVAL */
 int y2h_nchw_to_nhwc(const float *src, float *dst, int n, int c, int h, int w, int ld, y2h_stream s);
 int y2h_nhwc_to_nchw(const float *src, int ld, float *dst, int n, int c, int h, int w, y2h_stream s);
 /* [n][c][h][w] -> interior of [n][h+2*halo][w+2*halo][ld]; the border is not written
- * (the caller zeroes the buffer once) */
+ * (the caller zeroes the buffer once); a NULL pointer, ld < c or halo < 0: Y2H_EINVAL */
 int y2h_nchw_to_nhwc_halo(const float *src, float *dst, int n, int c, int h, int w, int ld, int halo, y2h_stream s);
 /* copy `c` channels of `npix` pixels between two NHWC buffers ([route] fallback) */
 int y2h_copy_channels(const float *src, int ld_src, float *dst, int ld_dst, int c, long npix, y2h_stream s);
@@ -221,7 +221,9 @@ int y2h_connected_ref(const float *x, long x_batch_stride, int ld, int hw, int c
 int y2h_detection_boxes(const float *pred, long pred_stride, int batch, int side, int num, int classes, int sqrt_flag,
                         int w, int h, float thresh, int only_objectness, float *boxes, float *probs, y2h_stream s);
 /* residual add (shortcut_layer.c:38-43, blas.c:57-81): out = act(in + add) where the shapes overlap; `add` is
- * w1 x h1 x c1, in/out are w2 x h2 x c2; stride = w1/w2 and sample = w2/w1 (each >= 1) as in shortcut_cpu */
+ * w1 x h1 x c1, in/out are w2 x h2 x c2; stride = w1/w2 and sample = w2/w1 (each >= 1) as in shortcut_cpu.
+ * activation: Y2H_ACT_LINEAR .. _RELU, the four evaluated inside the kernel (any other code: Y2H_EINVAL -- the engine passes
+ * y2_act_for_kernel() and runs y2h_activate_array behind); w1/w2 != h1/h2 or w2/w1 != h2/h1 (blas.c:61-62): Y2H_EINVAL */
 int y2h_shortcut(const float *in, int ld_in, const float *add, int ld_add, float *out, int ld_out, int batch,
                  int w1, int h1, int c1, int w2, int h2, int c2, int activation, y2h_stream s);
 /* [crop] at inference (crop_layer.c:69-105, !state.train): centred out_h x out_w window, x*2-1 unless noadjust.
@@ -234,7 +236,9 @@ int y2h_batchnorm(const float *x, int ldx, float *y, int ldy, long pixels, int c
                   const float *scale, y2h_stream s);
 /* [local] (local_layer.c:95-126): per-location filter banks.  w_packed [location][filter][kh][kw][c], bias_packed
  * [location][filter] (the engine re-orders the reference's [location][filter][c][kh][kw] / [filter][location]);
- * strict = 1 runs the reference's summation order (bias first, taps in c,kh,kw order, one rounding per step) */
+ * strict = 1 runs the reference's summation order (bias first, taps in c,kh,kw order, one rounding per step).
+ * activation: Y2H_ACT_LINEAR .. _RELU in both forms, any other code: Y2H_EINVAL (as y2h_shortcut); a last window that leaves
+ * the padded image, (out_h - 1) * stride + size - pad > h + pad (or the same in w): Y2H_EINVAL */
 int y2h_local(const float *x, int ldx, const float *w_packed, const float *bias_packed, float *y, int ldy, int batch,
               int h, int w, int c, int n, int size, int stride, int pad, int out_h, int out_w, int activation,
               int strict, y2h_stream s);
@@ -261,7 +265,8 @@ int y2h_lrn_f16(const void *x, int ldx, void *y, int ldy, long pixels, int c, in
                 y2h_stream s);
 /* global average pool: [batch][h*w][ld] -> [batch][c] (sequential fp32 sum, avgpool_layer.c:40) */
 int y2h_avgpool(const float *x, int ldx, float *y, int batch, int h, int w, int c, y2h_stream s);
-/* rows of `n` floats: softmax with temperature (blas.c:205); in/out may alias */
+/* rows of `n` floats: softmax with temperature (blas.c:205); in/out may alias.  One workgroup per row, the exponentials in
+ * LDS up to n = 12288 (48 KB), in the output row beyond.  A NULL pointer, rows or n <= 0, temp == 0: Y2H_EINVAL */
 int y2h_softmax_rows(const float *x, float *y, long rows, int n, float temp, y2h_stream s);
 /* softmax_tree (softmax_layer.c:35-47): every row of `n` floats is `groups` sibling groups [goff[g], goff[g] + gsize[g]),
  * each softmaxed on its own with y2h_softmax_rows' arithmetic (double exp, fp32 sum in index order); group_of[n] names
@@ -307,7 +312,7 @@ int y2h_connected_f16(const void *x, long ldx, const void *w, const float *alpha
                       int y_f16, int rows, int inputs, int outputs, int activation, int ranges, float *ws, size_t ws_bytes,
                       y2h_stream s);
 /* y2h_local with half weights (same [location][filter][kh][kw][c] order), half input and output, fp32 accumulation and
- * fp32 biases; Y2H_ACT_LINEAR .. _RELU */
+ * fp32 biases; Y2H_ACT_LINEAR .. _RELU, any other code: Y2H_EINVAL */
 int y2h_local_f16(const void *x, int ldx, const void *w_packed, const float *bias_packed, void *y, int ldy, int batch,
                   int h, int w, int c, int n, int size, int stride, int pad, int out_h, int out_w, int activation,
                   y2h_stream s);

@@ -322,7 +322,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float *x, float
 
 extern "C" int y2h_softmax_rows(const float *x, float *y, long rows, int n, float temp, y2h_stream s)
 {
-    if (rows <= 0 || n <= 0) return Y2H_EINVAL;
+    if (!x || !y || rows <= 0 || n <= 0 || temp == 0.f) return Y2H_EINVAL;
     if ((size_t)n * sizeof(float) <= 48 * 1024)
         hipLaunchKernelGGL(softmax_rows_kernel<true>, dim3((unsigned)rows), dim3(256), (size_t)n * sizeof(float), S(s), x, y, rows, n, temp);
     else
@@ -607,6 +607,7 @@ extern "C" int y2h_shortcut(const float *in, int ld_in, const float *add, int ld
 {
     if (!in || !add || !out || batch <= 0 || w1 <= 0 || h1 <= 0 || c1 <= 0 || w2 <= 0 || h2 <= 0 || c2 <= 0) return Y2H_EINVAL;
     if (ld_in < c2 || ld_out < c2 || ld_add < c1) return Y2H_EINVAL;
+    if (activation < Y2H_ACT_LINEAR || activation > Y2H_ACT_RELU) return Y2H_EINVAL;     /* the four in-kernel activations */
     if (w1 == w2 && h1 == h2 && c1 == c2 && c2 % 4 == 0 && ld_in % 4 == 0 && ld_add % 4 == 0 && ld_out % 4 == 0 &&
         (((uintptr_t)in | (uintptr_t)add | (uintptr_t)out) & 15) == 0) {
         const long total4 = (long)batch * h2 * w2 * (c2 / 4);
@@ -862,6 +863,7 @@ static int local_launch(const T *x, int ldx, const T *w_packed, const float *bia
     if (!x || !w_packed || !bias_packed || !y || batch <= 0 || h <= 0 || w <= 0 || c <= 0 || n <= 0 || size <= 0 || stride <= 0 ||
         pad < 0 || out_h <= 0 || out_w <= 0 || ldx < c || ldy < n) return Y2H_EINVAL;
     if ((out_h - 1) * stride + size - pad > h + pad || (out_w - 1) * stride + size - pad > w + pad) return Y2H_EINVAL;
+    if (activation < Y2H_ACT_LINEAR || activation > Y2H_ACT_RELU) return Y2H_EINVAL;     /* the four in-kernel activations */
     const LocalK<T> a = {x, ldx, w_packed, bias_packed, y, ldy, batch, h, w, c, n, size, stride, pad, out_h, out_w, activation};
     if constexpr (std::is_same<T, float>::value) {
         if (strict) {
@@ -893,7 +895,6 @@ extern "C" int y2h_local_f16(const void *x, int ldx, const void *w_packed, const
                              int h, int w, int c, int n, int size, int stride, int pad, int out_h, int out_w, int activation,
                              y2h_stream s)
 {
-    if (activation < Y2H_ACT_LINEAR || activation > Y2H_ACT_RELU) return Y2H_EINVAL;
     return local_launch<_Float16>((const _Float16 *)x, ldx, (const _Float16 *)w_packed, bias_packed, (_Float16 *)y, ldy, batch, h, w, c, n,
                                   size, stride, pad, out_h, out_w, activation, 0, s);
 }

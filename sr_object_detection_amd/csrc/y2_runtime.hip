@@ -250,7 +250,7 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const T *__restrict__
 
 extern "C" int y2h_nchw_to_nhwc(const float *src, float *dst, int n, int c, int h, int w, int ld, y2h_stream s)
 {
-    if (n <= 0 || c <= 0 || h <= 0 || w <= 0 || ld < c) return Y2H_EINVAL;
+    if (!src || !dst || n <= 0 || c <= 0 || h <= 0 || w <= 0 || ld < c) return Y2H_EINVAL;
     const long hw = (long)h * w;
     dim3 grid((unsigned)((hw + 63) / 64), (unsigned)((c + 31) / 32), (unsigned)n);
     hipLaunchKernelGGL(nchw_to_nhwc_kernel, grid, dim3(256), 0, S(s), src, dst, c, hw, ld);
@@ -297,7 +297,7 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_halo_kernel(const float *__r
 
 extern "C" int y2h_nchw_to_nhwc_halo(const float *src, float *dst, int n, int c, int h, int w, int ld, int halo, y2h_stream s)
 {
-    if (n <= 0 || c <= 0 || h <= 0 || w <= 0 || ld < c || halo < 0) return Y2H_EINVAL;
+    if (!src || !dst || n <= 0 || c <= 0 || h <= 0 || w <= 0 || ld < c || halo < 0) return Y2H_EINVAL;
     const long total = (long)n * h * w;
     hipLaunchKernelGGL(nchw_to_nhwc_halo_kernel, dim3(y2h_grid(total, 256)), dim3(256), 0, S(s), src, dst, c, h, w, ld, halo, total);
     Y2H_LAUNCH_CHECK();

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from sr_object_detection_amd import darknet, synth, zoo
+from tests import layer_rule
 from tests.helpers import materialize
 
 pytestmark = pytest.mark.gpu
@@ -198,6 +199,122 @@ def test_avgpool_scalar_and_vector_agree(dev, monkeypatch, entry, hw, c):
         dy = dev.put(np.full((n, c), -7, np.float32))
         assert fn(dx, c, dy, n, 1, hw, c, None) == 0
         assert np.array_equal(dev.get(dy, (n, c)), want), scalar
+
+
+def _maxpool_run(dev, oracle, dtype, n, h, w, c, size, stride, pad, ldx, ldy, seed=3):
+    """-> (got [n][oh][ow][ldy], want [n][c][oh][ow]); y pre-filled with -7 and followed by 64 more of them"""
+    half = dtype == np.float16
+    x = synth.uniform(seed, n * c * h * w, -2, 2).reshape(n, c, h, w)
+    if half:
+        x = (np.round(x * 64) / 64).astype(np.float32)
+    oh, ow = (h + 2 * pad) // stride, (w + 2 * pad) // stride
+    want = oracle.maxpool(x, n, h, w, c, size, stride, pad).reshape(n, c, oh, ow)
+    if half:
+        want = np.maximum(want, np.float32(-65504)).astype(np.float16)
+    rows = np.zeros((n, h, w, ldx), dtype)
+    rows[..., :c] = to_nhwc(x)
+    dy = dev.put(np.full(n * oh * ow * ldy + 64, -7, dtype))
+    fn = dev.L.y2h_maxpool_f16 if half else dev.L.y2h_maxpool
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 10 + [C.c_void_p]
+    assert fn(dev.put(rows), ldx, dy, ldy, n, h, w, c, size, stride, pad, oh, ow, None) == 0
+    got = dev.get(dy, (n * oh * ow * ldy + 64,), dtype)
+    assert np.all(got[-64:] == dtype(-7))
+    return got[:-64].reshape(n, oh, ow, ldy), want
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float16], ids=["f32", "f16"])
+@pytest.mark.parametrize("h,w,c,size,stride,pad,ldx,ldy", layer_rule.MAXPOOL_LD)
+def test_maxpool_with_two_leading_dimensions(dev, oracle, dtype, h, w, c, size, stride, pad, ldx, ldy):
+    """ldx != ldy, as between a placed route and a layer of its own: 16-byte forms (c = 8 at 12 / 16 in fp32, at 8 / 24 in
+    half) and element forms"""
+    got, want = _maxpool_run(dev, oracle, dtype, 2, h, w, c, size, stride, pad, ldx, ldy)
+    assert np.array_equal(to_nchw(got[..., :c]), want)
+    assert np.all(got[..., c:] == dtype(-7))
+
+
+@pytest.mark.parametrize("key", sorted(layer_rule.MAXPOOL_BIG))
+def test_maxpool_second_grid_stride_trip(dev, oracle, key):
+    """more than 2^21 work items: the grid is capped at 8192 workgroups, so some threads walk their loop twice"""
+    n, h, w, c, size, stride, pad = layer_rule.MAXPOOL_BIG[key]
+    dtype = np.float16 if key == "f16" else np.float32
+    assert n * ((h + 2 * pad) // stride) * ((w + 2 * pad) // stride) * (c // (8 if key == "f16" else 4)) > 2 ** 21
+    got, want = _maxpool_run(dev, oracle, dtype, n, h, w, c, size, stride, pad, c, c)
+    assert np.array_equal(to_nchw(got), want)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float16], ids=["f32", "f16"])
+@pytest.mark.parametrize("reverse", [0, 1])
+@pytest.mark.parametrize("w,h,c,s", [(4, 2, 4, 2), (6, 6, 9, 3), (10, 6, 8, 2)])
+def test_reorg_with_leading_dimensions_and_a_guarded_output(dev, oracle, dtype, w, h, c, s, reverse):
+    """ldx = c + 2, ldy = oc + 3; the padding columns of y and what lies behind it keep their -7"""
+    n = 2
+    x = (np.arange(n * c * h * w, dtype=np.float32) % 2039).reshape(n, c, h, w)
+    want = oracle.reorg(x, w, h, c, n, s, forward=reverse).astype(dtype)
+    oc, oh, ow = (c // (s * s), h * s, w * s) if reverse else (c * s * s, h // s, w // s)
+    ldx, ldy = c + 2, oc + 3
+    rows = np.full((n, h, w, ldx), 60000, dtype)
+    rows[..., :c] = to_nhwc(x)
+    dy = dev.put(np.full(n * oh * ow * ldy + 64, -7, dtype))
+    fn = dev.L.y2h_reorg_f16 if dtype == np.float16 else dev.L.y2h_reorg
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]
+    assert fn(dev.put(rows), ldx, dy, ldy, n, h, w, c, s, reverse, None) == 0
+    got = dev.get(dy, (n * oh * ow * ldy + 64,), dtype)
+    body = got[:-64].reshape(n, oh, ow, ldy)
+    assert np.array_equal(to_nchw(body[..., :oc]).reshape(-1), want.reshape(-1))
+    assert np.all(body[..., oc:] == dtype(-7)) and np.all(got[-64:] == dtype(-7))
+
+
+def test_copy_channels_second_grid_stride_trip(dev):
+    """2^20 + 300 elements of the element form (c = 5): the grid is capped at 4096 workgroups"""
+    c, ld_src, ld_dst = 5, 6, 8
+    npix = (layer_rule.PAST + c - 1) // c
+    src = (np.arange(npix * ld_src) % 8191).astype(np.float32).reshape(npix, ld_src)
+    ddst = dev.put(np.full(npix * ld_dst + 64, -7, np.float32))
+    dev.L.y2h_copy_channels.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_long, C.c_void_p]
+    assert dev.L.y2h_copy_channels(dev.put(src), ld_src, ddst, ld_dst, c, npix, None) == 0
+    got = dev.get(ddst, (npix * ld_dst + 64,))
+    body = got[:-64].reshape(npix, ld_dst)
+    assert np.array_equal(body[:, :c], src[:, :c]) and np.all(body[:, c:] == -7) and np.all(got[-64:] == -7)
+
+
+def _avgpool_f16(dev, x, ldx):
+    """y2h_avgpool_f16 on x [n][hw][c] (half values) stored with row stride ldx -> [n][c]"""
+    n, hw, c = x.shape
+    rows = np.full((n, hw, ldx), 60000, np.float16)
+    rows[..., :c] = x
+    dy = dev.put(np.full(n * c + 64, -7, np.float32))
+    fn = dev.L.y2h_avgpool_f16
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]
+    assert fn(dev.put(rows), ldx, dy, n, 1, hw, c, None) == 0
+    got = dev.get(dy, (n * c + 64,))
+    assert np.all(got[-64:] == -7)
+    return got[:-64].reshape(n, c)
+
+
+@pytest.mark.parametrize("hw", layer_rule.AVGPOOL_HW + (3,))
+@pytest.mark.parametrize("c,ldx", [(8, 8), (8, 16), (16, 24), (8, 12), (layer_rule.AVGPOOL_WIDE_C, layer_rule.AVGPOOL_WIDE_C)])
+def test_avgpool_f16_quarters_and_leading_dimensions(dev, monkeypatch, hw, c, ldx):
+    """hw = 4..7: the quarter boundaries p0 = q * hw / 4 of the 16-byte form just above its hw >= 4 limit (hw = 3, and
+    ldx = 12: the scalar form); c = 1000: 125 lane groups in two workgroups, the second partly idle; ldx > c.  Integer data:
+    exact in either form.  Real-valued half data: the 16-byte form, which adds four partial sums, within
+    hw * 2^-24 * sum |x| / hw of the float64 mean (hw - 1 additions and a divide, each within 2^-24 relative of a partial
+    result no larger than sum |x|); the scalar form equals the sequential fp32 rule of avgpool_layer.c:40-54."""
+    n = 2
+    vector = layer_rule.avgpool_form(True, c, ldx, hw) == "avgpool_f16_v8_kernel"
+    monkeypatch.delenv("Y2_AVGPOOL_SCALAR", raising=False)
+    xi = np.round(synth.uniform(50 + hw, n * hw * c, -8, 8)).astype(np.float16).reshape(n, hw, c)
+    assert np.array_equal(_avgpool_f16(dev, xi, ldx), (xi.astype(np.float64).sum(axis=1) / hw).astype(np.float32))
+    xr = synth.uniform(60 + hw, n * hw * c, -2, 2).astype(np.float16).reshape(n, hw, c)
+    got = _avgpool_f16(dev, xr, ldx)
+    seq = layer_rule.avgpool_seq(xr.astype(np.float32))
+    if vector:
+        x64 = xr.astype(np.float64)
+        frac = np.abs(got - x64.mean(axis=1)) / (hw * 2.0 ** -24 * np.abs(x64).sum(axis=1) / hw)
+        print("avgpool_f16_v8 hw %d c %d: at most %.3f of the bound" % (hw, c, float(frac.max())))
+        assert frac.max() <= 1
+        monkeypatch.setenv("Y2_AVGPOOL_SCALAR", "1")
+        got = _avgpool_f16(dev, xr, ldx)
+    assert np.array_equal(got, seq)
 
 
 def test_softmax_rows_matches_oracle(dev, oracle):
