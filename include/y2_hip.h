@@ -172,6 +172,14 @@ size_t y2h_conv_workspace_bytes(const y2h_conv *d);
  * workgroups, the last *sk_tiles are cut along K into equal shares for workgroups 0 .. *sk_wgs - 1 and finished by a
  * fix-up launch.  Returns 1 when the plan splits, 0 when every tile is walked whole.  Host arithmetic only (no GPU). */
 int y2h_p8_stream_k_plan(long ntiles, int nk, long grid, int *sk_tiles, int *sk_wgs);
+/* The stream-K share rule as every kernel compiles it (include/y2_streamk_rule.h: `tiles` tiles of nk K-steps dealt to G
+ * workgroups), one call for all workgroups / tiles.  Host arithmetic only.  Each returns -1 unless 1 <= tiles <= G, nk >= 1.
+ * y2h_sk_shares: out[5 w ..] = pieces (0, 1, 2), tile, kb0, ke0, ke1 of workgroup w.  y2h_sk_first: out[t] = the first share
+ * that reaches into tile t.  y2h_sk_walk: the walk of every tile in turn, out[3 i ..] = tile, workgroup, piece (1: the share
+ * began in the previous tile); returns the number of visits (at most tiles + G; -1 if `max` triples do not hold them). */
+int y2h_sk_shares(long tiles, int nk, long G, int *out);
+int y2h_sk_first(long tiles, int nk, long G, int *out);
+int y2h_sk_walk(long tiles, int nk, long G, int *out, int max);
 /* number of stream-K launches (main + fix-up pairs) issued by this process so far (tests, benchmark reports) */
 unsigned long y2h_stream_k_launches(void);
 /* number of small-tile tail launches behind the fp16 256x256 kernel (the other way to finish a partial last round) */

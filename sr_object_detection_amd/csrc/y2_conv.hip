@@ -35,6 +35,10 @@
 //    CPU path (separately rounded mul+add, ci-major k order) only by ordinary
 //    fp32 summation noise (~1e-6 relative).
 //
+//    The tap mask, the slice address and the stream-K share rule are one statement shared with the fp16 kernels
+//    (y2_conv_shared.hpp, include/y2_streamk_rule.h); the row decode and the slice loads / stores are this kernel's own copy
+//    of what conv_mfma_f16_kernel takes from there.
+//
 //    Strides are free (the GEMM rows enumerate the output grid; taps are centred on input (oy*s, ox*s)); sizes 1, 3
 //    and 5 are instantiated (one tap-validity mask bit per tap, pad = size/2).
 //
@@ -57,7 +61,7 @@
 // MFMA implicit GEMM
 // ---------------------------------------------------------------------------
 __device__ int g_skh_timeouts = 0;     // hybrid stream-K: flag waits that gave up (a bug or a lost workgroup; results of that launch are wrong)
-template <int BM, int BN, int BK, int KS, int WM, int WN, bool PIPE, bool XO = false, int SKMODE = 0>
+template <int BM, int BN, int BK, int KS, int WM, int WN, bool XO = false, int SKMODE = 0>
 __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
 {
     constexpr bool SKM = SKMODE == 1;     // stream-K over ALL tiles, pieces finished by sk_reduce_kernel (grids smaller than the machine)
@@ -76,7 +80,6 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
     // 8-wave tiles (one workgroup per CU, LDS to spare): outputs leave as 16-byte stores through a wave-private LDS
     // transpose.  A lane of the accumulator layout owns ONE filter of 16 pixels -- sixteen 4-byte stores per 32x32 tile,
     // 96 per lane and tile, each with its own 64-bit address; transposed, a lane stores 4 consecutive filters of a pixel.
-    constexpr bool VST = true;
     constexpr bool ES_OWN = (WM * WN == 8);   // 8-wave tiles: 18 KB of LDS of their own; 4-wave tiles (two workgroups per
                                               // CU, no LDS to spare): the staging buffer the last K-step has just
                                               // released, and a barrier behind the epilogue before it is written again
@@ -111,16 +114,6 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
     // at most two work items = pieces (tile, K range); work item v in {0, 1} is piece v, its raw sums go to workspace slot
     // 2 * wg + v in tile-local layout [BM][BN], and sk_reduce_kernel adds a tile's pieces in ascending K order.  Against
     // the integer split-K above every workgroup gets the same number of K-steps whatever the tile count.
-    int n_sk = 0, sk_t0 = 0, sk_kb0 = 0, sk_ke0 = 0, sk_ke1 = 0;
-    if constexpr (SKM) {
-        const long I = (long)a.sk_tiles * nk;
-        const long lo = (long)blockIdx.x * I / a.sk_wgs, hi = (long)(blockIdx.x + 1) * I / a.sk_wgs;
-        if (hi > lo) {
-            const int t0 = (int)(lo / nk), k0 = (int)(lo - (long)t0 * nk), len = (int)(hi - lo);
-            sk_t0 = t0; sk_kb0 = k0; sk_ke0 = k0 + len < nk ? k0 + len : nk; n_sk = 1;
-            if (k0 + len > nk) { sk_ke1 = k0 + len - nk; n_sk = 2; }
-        }
-    }
     // SKH (hybrid stream-K, grids of several rounds: batch 32): the first ndp = ntiles - sk_tiles output tiles are walked whole
     // (b, b + G, ...); the K loops of the last sk_tiles tiles -- the partial last round -- are dealt in equal contiguous
     // shares to ALL G workgroups, again at most two pieces each.  A piece that does not reach the end of its tile's K loop
@@ -132,14 +125,10 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
     // same moment with a piece no longer than the finisher's share, have published.  Work-item codes in SKH: 0 .. ndp - 1 a
     // whole tile, ntiles + v piece v of this workgroup (v = 0: in tile sk_t0, from sk_kb0; v = 1: the head of tile sk_t0 + 1).
     const int ndp = SKH ? a.ntiles - a.sk_tiles : 0;
-    if constexpr (SKH) {
-        const long I = (long)a.sk_tiles * nk;
-        const long lo = (long)blockIdx.x * I / a.sk_wgs, hi = (long)(blockIdx.x + 1) * I / a.sk_wgs;
-        if (hi > lo) {
-            const int t0 = (int)(lo / nk), k0 = (int)(lo - (long)t0 * nk), len = (int)(hi - lo);
-            sk_t0 = ndp + t0; sk_kb0 = k0; sk_ke0 = k0 + len < nk ? k0 + len : nk; n_sk = 1;
-            if (k0 + len > nk) { sk_ke1 = k0 + len - nk; n_sk = 2; }
-        }
+    int n_sk = 0, sk_t0 = 0, sk_kb0 = 0, sk_ke0 = 0, sk_ke1 = 0;
+    if constexpr (SKM || SKH) {       // this workgroup's share of the sk_tiles cut tiles, which follow the ndp whole ones
+        const y2_sk_share sh = y2_sk_share_of(blockIdx.x, a.sk_tiles, nk, a.sk_wgs);
+        n_sk = sh.n; sk_t0 = ndp + sh.tile; sk_kb0 = sh.kb0; sk_ke0 = sh.ke0; sk_ke1 = sh.ke1;
     }
     const int END = SKM ? 2 : SKH ? a.ntiles + 2 : a.ntiles;       // work-item number that means "past the end"
     auto setup_tile = [&](int vtile) {
@@ -162,6 +151,8 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
     // row pattern.  The setup runs on the VALU while the matrix pipe waits, so its length matters on short-K layers.
     // (a.out_h x a.out_w is the output grid the GEMM rows enumerate, a.H x a.W the input the taps are read from:
     // output (oy, ox) is centred on input (oy*stride, ox*stride) for the pad = size/2 shapes this kernel takes)
+    // (this kernel's own copy of conv_stage_rows / conv_stage_filters, y2_conv_shared.hpp, on the strided output grid: at the
+    // 256-register ceiling the shared form moved the 192x256 streams and yolo608_b32 by -0.2 %, profiles/conv_staging_ab.txt)
     const int Wu = a.pool ? a.out_w >> 1 : a.out_w, Hu = a.pool ? a.out_h >> 1 : a.out_h;
     const int r0 = p0 + sr;
     const int u0 = a.pool ? r0 >> 2 : r0, tc = r0 & 3;        // RP % 4 == 0: the corner is the same for every q
@@ -173,27 +164,7 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
         const int r = r0 + q * RP;                            // GEMM row
         const int py = (a.pool ? 2 * cy + (tc >> 1) : cy) * a.stride, px = (a.pool ? 2 * cx + (tc & 1) : cx) * a.stride;
         a_off[q] = ((unsigned)((cn * a.H + py) * a.W + px) * (unsigned)a.ldx + (unsigned)sc * 4u) * 4u;
-        unsigned m = 0;
-        if (live && r < a.npix && (BM % RP == 0 || sr + q * RP < BM)) {
-            if (KS == 1) m = 1u;
-            else if (KS == 3) {
-                // bit kh*3+kw = tap inside the image: (column pattern) x (row pattern spread 3 bits apart), no carries
-                const unsigned xm = (px > 0 ? 1u : 0u) | 2u | (px < a.W - 1 ? 4u : 0u);
-                const unsigned ym = (py > 0 ? 1u : 0u) | 8u | (py < a.H - 1 ? 64u : 0u);
-                m = xm * ym;
-            } else {
-                // same product for any odd size with KS*KS <= 32 taps (5x5: alexnet.cfg)
-                static_assert(KS * KS <= 32, "one mask bit per tap");
-                unsigned xm = 0, ym = 0;
-#pragma unroll
-                for (int k = 0; k < KS; ++k) {
-                    if (px + k - KS / 2 >= 0 && px + k - KS / 2 < a.W) xm |= 1u << k;
-                    if (py + k - KS / 2 >= 0 && py + k - KS / 2 < a.H) ym |= 1u << (k * KS);
-                }
-                m = xm * ym;
-            }
-        }
-        a_msk[q] = m;
+        a_msk[q] = (live && r < a.npix && (BM % RP == 0 || sr + q * RP < BM)) ? conv_tap_mask<KS>(px, py, a.W, a.H) : 0u;
         cx += a.pool ? RP / 4 : RP;
         while (cx >= Wu) { cx -= Wu; if (++cy >= Hu) { cy = 0; ++cn; } }
     }
@@ -250,28 +221,21 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
     // "tile" past the end whose rows are all masked: those loads are out-of-range buffer accesses
     // (zeros, no memory traffic) -- cheaper than a branch, which would split the scheduling region.
     auto load_slice = [&]() {
-        int delta = 0;        // float offset of the tap relative to the centre pixel
-        if (KS > 1) {
-            const int kh = tap / KS, kw = tap - kh * KS;
-            delta = ((kh - KS / 2) * a.W + (kw - KS / 2)) * a.ldx;
-        }
-        const unsigned add = (unsigned)((delta + c0) * 4);
+        // (its own copy of conv_load_slice / conv_store_slice, for the same reason as the row loop above)
+        const unsigned add = conv_slice_a<KS, 4>(tap, c0, a.W, a.ldx);
 #pragma unroll
         for (int q = 0; q < PA; ++q) {
             const bool ok = (a_msk[q] >> tap) & 1u;
             const unsigned off = ok ? a_off[q] + add : a.xbytes;
             ra[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, off, 0, 0));
         }
-        const unsigned kadd = (unsigned)((tap * a.Cin + c0) * 4);
+        const unsigned kadd = conv_slice_b<4>(tap, c0, a.Cin);
 #pragma unroll
         for (int q = 0; q < PB; ++q) {
             const unsigned off = (b_off[q] == a.wbytes) ? a.wbytes : b_off[q] + kadd;
             rb[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wr, off, 0, 0));
         }
-        // K order: channel chunk outermost, the KS*KS taps innermost.  The nine taps of one
-        // 32-channel chunk touch the same (neighbouring) 128-byte pixel lines, so eight of the
-        // nine A-slice reads hit L1/L2 instead of going back to the Infinity Cache / HBM.
-        if (++tap == KS * KS) { tap = 0; c0 += BK; }     // the hop to the next tile is done by the K loop
+        conv_slice_next<KS, BK>(tap, c0);                // the hop to the next tile is done by the K loop
         ++s_k;
     };
     auto store_slice = [&](int buf) {
@@ -285,13 +249,9 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
             if (BN % RP == 0 || sr + q * RP < BN) *(f32x4 *)&Bs[(sr + q * RP) * LS + sc * 4] = rb[q];
     };
 
-#ifdef Y2_NO_EARLYB
-    constexpr bool EB = false;
-#else
     // (not the 64x64 tile: it is what batch-1 grids run, one short work item per workgroup, where the longer prologue of
     // the two-slices-ahead staging costs 1-2 us per layer and buys nothing)
-    constexpr bool EB = PIPE && BK >= 32 && !(BM == 64 && BN == 64);
-#endif
+    constexpr bool EB = BK >= 32 && !(BM == 64 && BN == 64);
     load_slice();
     store_slice(0);
     if (EB) {
@@ -325,7 +285,7 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
         for (int j = 0; j < TN; ++j) bf[0][j] = *(const f32x4 *)&Bs0[j * 32 * LS];
     }
 
-    // One K-step = BK/8 groups of 4*TM*TN MFMAs.  Software pipeline (PIPE): the operand fragments
+    // One K-step = BK/8 groups of 4*TM*TN MFMAs.  Software pipeline: the operand fragments
     // of group g+1 are read from LDS while group g multiplies (two register sets), the global
     // loads of the next slice are issued under group 0 and written to the other LDS buffer
     // before the last group, so that when the workgroup reaches the barrier only the barrier is
@@ -378,94 +338,74 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
         }
         const float *As = smem + cur * BUF + (wm * (BM / WM) + li) * LS + lh * 4;
         const float *Bs = smem + cur * BUF + BM * LS + (wn * (BN / WN) + li) * LS + lh * 4;
-        if (!PIPE) {
-            load_slice();                            // global loads in flight under the MFMAs
+        if (!EB) {
 #pragma unroll
-            for (int kg = 0; kg < NG; ++kg) {
-                f32x4 af[TM], bf[TN];
+            for (int i = 0; i < TM; ++i) af[0][i] = *(const f32x4 *)&As[i * 32 * LS];
 #pragma unroll
-                for (int i = 0; i < TM; ++i) af[i] = *(const f32x4 *)&As[i * 32 * LS + kg * 8];
-#pragma unroll
-                for (int j = 0; j < TN; ++j) bf[j] = *(const f32x4 *)&Bs[j * 32 * LS + kg * 8];
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int j = 0; j < TN; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][s], bf[j][s], acc[i][j], 0, 0, 0);
-            }
-            store_slice(cur ^ 1);
-        } else {
-            if (!EB) {
-#pragma unroll
-                for (int i = 0; i < TM; ++i) af[0][i] = *(const f32x4 *)&As[i * 32 * LS];
-#pragma unroll
-                for (int j = 0; j < TN; ++j) bf[0][j] = *(const f32x4 *)&Bs[j * 32 * LS];
-            }
-            constexpr int SG = EB ? NG - 2 : NG - 1;      // group under which the fetched slice is written to LDS
-            constexpr int BG = EB ? NG - 2 : NG - 1;                  // group behind which the workgroup barrier sits
-            constexpr int LG = EB ? NG - 1 : 0;                       // group under which the next global loads are issued
-#pragma unroll
-            for (int kg = 0; kg < NG; ++kg) {
-                const int c = kg & 1, n = c ^ 1;
-                if (kg + 1 < NG) {
-#pragma unroll
-                    for (int i = 0; i < TM; ++i) af[n][i] = *(const f32x4 *)&As[i * 32 * LS + (kg + 1) * 8];
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) bf[n][j] = *(const f32x4 *)&Bs[j * 32 * LS + (kg + 1) * 8];
-                } else if (EB) {
-                    // group 0 of the next K-step, from the buffer published by the barrier behind group NG-2
-                    const float *An = smem + (cur ^ 1) * BUF + (wm * (BM / WM) + li) * LS + lh * 4;
-                    const float *Bn = smem + (cur ^ 1) * BUF + BM * LS + (wn * (BN / WN) + li) * LS + lh * 4;
-#pragma unroll
-                    for (int i = 0; i < TM; ++i) af[n][i] = *(const f32x4 *)&An[i * 32 * LS];
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) bf[n][j] = *(const f32x4 *)&Bn[j * 32 * LS];
-                }
-                if (kg == SG) store_slice(cur ^ 1);
-                if (kg == LG) load_slice();               // (after the store when both fall into one group: same registers)
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int j = 0; j < TN; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[c][i][s], bf[c][j][s], acc[i][j], 0, 0, 0);
-                // issue order inside the group: one MFMA first (the pipe is busy from here on), then the
-                // fragment reads of the next group, then the staging work one piece per MFMA
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                if (kg + 1 < NG || EB) __builtin_amdgcn_sched_group_barrier(0x100, TM + TN, 0);
-                if (kg == LG) {
-#pragma unroll
-                    for (int q = 0; q < PA + PB; ++q) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                    }
-                }
-                if (kg == SG) {
-#pragma unroll
-                    for (int q = 0; q < PA + PB; ++q) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#ifdef Y2_F32_STAMPS
-                if (EB && kg == BG) { const unsigned long long b0 = __builtin_amdgcn_s_memtime(); __syncthreads(); st_bar += __builtin_amdgcn_s_memtime() - b0; }
-#else
-                if (EB && kg == BG) {
-                    // raw barrier: only this wave's LDS traffic has to be complete (its slice stores and its reads of the
-                    // current buffer); __syncthreads() would also wait for the global loads that may already be in flight
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_s_barrier();
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-#endif
-            }
+            for (int j = 0; j < TN; ++j) bf[0][j] = *(const f32x4 *)&Bs[j * 32 * LS];
         }
-        if (!EB || !PIPE) __syncthreads();
+        constexpr int SG = EB ? NG - 2 : NG - 1;      // group under which the fetched slice is written to LDS
+        constexpr int BG = EB ? NG - 2 : NG - 1;                  // group behind which the workgroup barrier sits
+        constexpr int LG = EB ? NG - 1 : 0;                       // group under which the next global loads are issued
+#pragma unroll
+        for (int kg = 0; kg < NG; ++kg) {
+            const int c = kg & 1, n = c ^ 1;
+            if (kg + 1 < NG) {
+#pragma unroll
+                for (int i = 0; i < TM; ++i) af[n][i] = *(const f32x4 *)&As[i * 32 * LS + (kg + 1) * 8];
+#pragma unroll
+                for (int j = 0; j < TN; ++j) bf[n][j] = *(const f32x4 *)&Bs[j * 32 * LS + (kg + 1) * 8];
+            } else if (EB) {
+                // group 0 of the next K-step, from the buffer published by the barrier behind group NG-2
+                const float *An = smem + (cur ^ 1) * BUF + (wm * (BM / WM) + li) * LS + lh * 4;
+                const float *Bn = smem + (cur ^ 1) * BUF + BM * LS + (wn * (BN / WN) + li) * LS + lh * 4;
+#pragma unroll
+                for (int i = 0; i < TM; ++i) af[n][i] = *(const f32x4 *)&An[i * 32 * LS];
+#pragma unroll
+                for (int j = 0; j < TN; ++j) bf[n][j] = *(const f32x4 *)&Bn[j * 32 * LS];
+            }
+            if (kg == SG) store_slice(cur ^ 1);
+            if (kg == LG) load_slice();               // (after the store when both fall into one group: same registers)
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j)
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[c][i][s], bf[c][j][s], acc[i][j], 0, 0, 0);
+            // issue order inside the group: one MFMA first (the pipe is busy from here on), then the
+            // fragment reads of the next group, then the staging work one piece per MFMA
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            if (kg + 1 < NG || EB) __builtin_amdgcn_sched_group_barrier(0x100, TM + TN, 0);
+            if (kg == LG) {
+#pragma unroll
+                for (int q = 0; q < PA + PB; ++q) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+                }
+            }
+            if (kg == SG) {
+#pragma unroll
+                for (int q = 0; q < PA + PB; ++q) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#ifdef Y2_F32_STAMPS
+            if (EB && kg == BG) { const unsigned long long b0 = __builtin_amdgcn_s_memtime(); __syncthreads(); st_bar += __builtin_amdgcn_s_memtime() - b0; }
+#else
+            if (EB && kg == BG) {
+                // raw barrier: only this wave's LDS traffic has to be complete (its slice stores and its reads of the
+                // current buffer); __syncthreads() would also wait for the global loads that may already be in flight
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#endif
+        }
+        if (!EB) __syncthreads();
         cur ^= 1;
     }
     __builtin_amdgcn_s_setprio(0);
@@ -515,7 +455,7 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
                     if (a.pool) {
 #pragma unroll
                         for (int g = 0; g < 4; ++g) {
-                            const float m = epilogue_f32(pool_pick(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3],
+                            const float m = epilogue(pool_pick(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3],
                                                                  !BN_ || scale >= 0.f), BN_, mean, rinv, scale, bias, ACT_);
                             es[(2 * g + lh) * ES + li] = m;               // pooled row (pb + 8g + 4lh) / 4 - pb / 4
                         }
@@ -530,7 +470,7 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
 #pragma unroll
                             for (int r = 0; r < 8; ++r)
                                 es[((r & 3) + 8 * (r >> 2) + 4 * lh) * ES + li] =
-                                    epilogue_f32(acc[i][j][8 * h2 + r], BN_, mean, rinv, scale, bias, ACT_);
+                                    epilogue(acc[i][j][8 * h2 + r], BN_, mean, rinv, scale, bias, ACT_);
 #pragma unroll
                             for (int u = 0; u < 2; ++u) {
                                 const u32x4 v = *(const u32x4 *)&es[(rrow + 8 * u) * ES + rch];
@@ -546,7 +486,7 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
                         const int r0 = prow + 8 * g;              // first of the window's four rows
-                        const float m = epilogue_f32(pool_pick(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3],
+                        const float m = epilogue(pool_pick(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3],
                                                                  !BN_ || scale >= 0.f), BN_, mean, rinv, scale, bias, ACT_);
                         // buffer store, 32-bit offset, out-of-range = dropped (no exec masking, no 64-bit address per store)
                         const unsigned off = (cok && r0 < a.npix) ? ((unsigned)(r0 >> 2) * (unsigned)a.ldy + (unsigned)co) * 4u : 0xffffffffu;
@@ -557,7 +497,7 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int dr = (r & 3) + 8 * (r >> 2);
-                        const float v = epilogue_f32(acc[i][j][r], BN_, mean, rinv, scale, bias, ACT_);
+                        const float v = epilogue(acc[i][j][r], BN_, mean, rinv, scale, bias, ACT_);
                         const unsigned off = (cok && prow + dr < a.npix) ? base + (unsigned)dr * (unsigned)a.ldy * 4u : 0xffffffffu;
                         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), yr, off, 0, 0);
                     }
@@ -624,14 +564,13 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
         }
         if (piece && kb > 0) {
             // finisher: the earlier pieces of this tile belong to the workgroups below this one whose shares reach into it
-            const long I = (long)a.sk_tiles * nk, G = a.sk_wgs, tb = (long)(ct - ndp) * nk;
-            long w0 = tb * G / I;
-            while (w0 > 0 && w0 * I / G > tb) --w0;
-            while (w0 + 1 < G && (w0 + 1) * I / G <= tb) ++w0;
+            // (y2_sk_walk of y2_streamk_rule.h from the tile's first share, stopped at this workgroup's own share -- written out on
+            // y2_sk_begin, empty shares skipped: through y2_sk_walk the 128x128 form spills one register more; slot = producer workgroup)
+            const long w0 = y2_sk_first(ct - ndp, a.sk_tiles, nk, a.sk_wgs);
+            const long I = (long)a.sk_tiles * nk, G = a.sk_wgs;
             if (t == 0) {
                 for (long w = w0; w < (long)blockIdx.x; ++w) {
-                    const long lo = w * I / G, hi = (w + 1) * I / G;
-                    if (hi <= lo) continue;
+                    if (y2_sk_begin(w + 1, I, G) <= y2_sk_begin(w, I, G)) continue;
                     int *fl = a.sk_flags + w;
                     int spins = 0;
                     while (__hip_atomic_load(fl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 1) {
@@ -644,8 +583,7 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");                          // no payload load may be scheduled in front of the barrier
             for (long w = w0; w < (long)blockIdx.x; ++w) {
-                const long lo = w * I / G, hi = (w + 1) * I / G;
-                if (hi <= lo) continue;
+                if (y2_sk_begin(w + 1, I, G) <= y2_sk_begin(w, I, G)) continue;
                 const size_t slot = (size_t)w;
                 const __amdgpu_buffer_rsrc_t pr = __builtin_amdgcn_make_buffer_rsrc((void *)(a.ws + slot * (BM * BN)), 0, (unsigned)(BM * BN * 4), 0x00020000);
 #pragma unroll
@@ -668,7 +606,7 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
         }
-    } else if (VST && a.vec_store && a.bn && a.act == Y2H_ACT_LEAKY) {        // (every conv of the target cfgs but the last)
+    } else if (a.vec_store && a.bn && a.act == Y2H_ACT_LEAKY) {        // (every conv of the target cfgs but the last)
         epilogue_pass(std::integral_constant<int, 1>{}, std::true_type{});
         if (!ES_OWN) {            // the scratch lies in the buffer the next K-step stores its slice into
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -709,25 +647,25 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(ConvK a)
                 for (int s = 1; s < a.ksplit; ++s) sum += a.ws[(size_t)s * slab + off];
                 sums[t] = sum;
             }
-            a.y[(size_t)p * a.ldy + co] = epilogue_f32(pool_pick(sums[0], sums[1], sums[2], sums[3], !a.bn || scale >= 0.f), a.bn, mean,
+            a.y[(size_t)p * a.ldy + co] = epilogue(pool_pick(sums[0], sums[1], sums[2], sums[3], !a.bn || scale >= 0.f), a.bn, mean,
                                                       rinv, scale, bias, a.act);
             continue;
         }
         float sum = a.ws[idx];
         for (int s = 1; s < a.ksplit; ++s) sum += a.ws[(size_t)s * slab + idx];
-        a.y[(size_t)p * a.ldy + co] = epilogue_f32(sum, a.bn, mean, rinv, scale, bias, a.act);
+        a.y[(size_t)p * a.ldy + co] = epilogue(sum, a.bn, mean, rinv, scale, bias, a.act);
     }
 }
 
 // second pass of a stream-K convolution (conv_mfma_kernel<..., SKM>): y[p][co .. co+3] = epilogue(sum of the pieces of the
 // output's tile, ascending K = ascending workgroup).  A piece slot holds a whole tile in tile-local layout [bm][bn]; the
-// pieces of tile t are those of the workgroups whose share [w * I / G, (w + 1) * I / G) reaches into [t * nk, (t + 1) * nk):
-// slot 2 w + (1 if the share began in the previous tile).  Cout and ldy multiples of 4 (the host checks).
+// pieces of tile t are those the walk of y2_streamk_rule.h visits: slot 2 w + (1 if share w began in the previous tile).
+// Cout and ldy multiples of 4 (the host checks).
 __global__ __launch_bounds__(256) void sk_reduce_kernel(ConvK a, int bm, int bn, int nk)
 {
     const int c4 = a.Cout >> 2;
     const long rows = a.pool ? (long)a.npix >> 2 : (long)a.npix;
-    const long total = rows * c4, I = (long)a.sk_tiles * nk, G = a.sk_wgs;
+    const long total = rows * c4;
     const int nt = a.pool ? 4 : 1;
     for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
         const int q = (int)(idx % c4), co = q * 4;
@@ -735,18 +673,12 @@ __global__ __launch_bounds__(256) void sk_reduce_kernel(ConvK a, int bm, int bn,
         const long g0 = a.pool ? 4 * p : p;                     // first GEMM row of this output (a pooling window's four rows share a tile: bm % 4 == 0)
         const int tile = (int)(g0 / bm) * a.tiles_n + co / bn;
         const int r0 = (int)(g0 % bm), c = co % bn;
-        const long tb = (long)tile * nk, te = tb + nk;
-        long w = tb * G / I;
-        while (w > 0 && w * I / G > tb) --w;
-        while (w + 1 < G && (w + 1) * I / G <= tb) ++w;
         f32x4 sums[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) sums[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (; w < G; ++w) {
-            const long lo = w * I / G, hi = (w + 1) * I / G;
-            if (lo >= te) break;
-            if (hi <= lo) continue;
-            const float *slot = a.ws + (size_t)(2 * w + (lo < tb ? 1 : 0)) * ((size_t)bm * bn);
+        int piece;
+        for (long w = y2_sk_first(tile, a.sk_tiles, nk, a.sk_wgs); y2_sk_walk(&w, &piece, tile, a.sk_tiles, nk, a.sk_wgs); ++w) {
+            const float *slot = a.ws + (size_t)(2 * w + piece) * ((size_t)bm * bn);
             for (int t = 0; t < nt; ++t) sums[t] = sums[t] + *(const f32x4 *)&slot[(size_t)(r0 + t) * bn + c];
         }
         f32x4 out;
@@ -756,7 +688,7 @@ __global__ __launch_bounds__(256) void sk_reduce_kernel(ConvK a, int bm, int bn,
             double rinv = 1.0;
             if (a.bn) { mean = a.mean[co + k]; rinv = a.rinv[co + k]; scale = a.scale[co + k]; }
             const float v = a.pool ? pool_pick(sums[0][k], sums[1][k], sums[2][k], sums[3][k], !a.bn || scale >= 0.f) : sums[0][k];
-            out[k] = epilogue_f32(v, a.bn, mean, rinv, scale, a.bias[co + k], a.act);
+            out[k] = epilogue(v, a.bn, mean, rinv, scale, a.bias[co + k], a.act);
         }
         *(f32x4 *)&a.y[(size_t)p * a.ldy + co] = out;
     }
@@ -889,7 +821,7 @@ __global__ __launch_bounds__(256, Y2_FIRST_MINB) void conv_first_kernel(ConvK a)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const long r0 = prow + 8 * g;
-                    const float m = epilogue_f32(pool_pick(acc[j][4 * g], acc[j][4 * g + 1], acc[j][4 * g + 2], acc[j][4 * g + 3], !a.bn || scale[j] >= 0.f),
+                    const float m = epilogue(pool_pick(acc[j][4 * g], acc[j][4 * g + 1], acc[j][4 * g + 2], acc[j][4 * g + 3], !a.bn || scale[j] >= 0.f),
                                                  a.bn, mean[j], rinv[j], scale[j], bias[j], a.act);
                     if (co < a.Cout && r0 < a.npix) {
                         if (a.y_f16) ((_Float16 *)a.y)[(size_t)(r0 >> 2) * a.ldy + co] = (_Float16)m;
@@ -902,7 +834,7 @@ __global__ __launch_bounds__(256, Y2_FIRST_MINB) void conv_first_kernel(ConvK a)
             for (int r = 0; r < 16; ++r) {
                 const long p = prow + (r & 3) + 8 * (r >> 2);
                 if (co < a.Cout && p < a.npix) {
-                    const float v = epilogue_f32(acc[j][r], a.bn, mean[j], rinv[j], scale[j], bias[j], a.act);
+                    const float v = epilogue(acc[j][r], a.bn, mean[j], rinv[j], scale[j], bias[j], a.act);
                     if (a.y_f16) ((_Float16 *)a.y)[(size_t)p * a.ldy + co] = (_Float16)v;
                     else a.y[(size_t)p * a.ldy + co] = v;
                 }
@@ -961,7 +893,7 @@ __global__ __launch_bounds__(256, Y2_FIRST_MINB) void conv_first_kernel(ConvK a)
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
                         const long r0 = prow + 8 * g;
-                        const float m = epilogue_f32(pool_pick(acc[j][4 * g], acc[j][4 * g + 1], acc[j][4 * g + 2], acc[j][4 * g + 3], scale[j] >= 0.f),
+                        const float m = epilogue(pool_pick(acc[j][4 * g], acc[j][4 * g + 1], acc[j][4 * g + 2], acc[j][4 * g + 3], scale[j] >= 0.f),
                                                      true, mean[j], rinv[j], scale[j], bias[j], Y2H_ACT_LEAKY);
                         put((unsigned long)(r0 >> 2), co, m, co < a.Cout && r0 < a.npix);
                     }
@@ -969,7 +901,7 @@ __global__ __launch_bounds__(256, Y2_FIRST_MINB) void conv_first_kernel(ConvK a)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const long p = prow + (r & 3) + 8 * (r >> 2);
-                        put((unsigned long)p, co, epilogue_f32(acc[j][r], true, mean[j], rinv[j], scale[j], bias[j], Y2H_ACT_LEAKY),
+                        put((unsigned long)p, co, epilogue(acc[j][r], true, mean[j], rinv[j], scale[j], bias[j], Y2H_ACT_LEAKY),
                             co < a.Cout && p < a.npix);
                     }
                 }
@@ -1099,7 +1031,7 @@ __global__ __launch_bounds__(256) void conv_stem_kernel(ConvK a)
             for (int r = 0; r < 16; ++r) {
                 const long p = prow + (r & 3) + 8 * (r >> 2);
                 if (co < a.Cout && p < a.npix)
-                    a.y[(size_t)p * a.ldy + co] = epilogue_f32(acc[j][r], a.bn, mean[j], rinv[j], scale[j], bias[j], a.act);
+                    a.y[(size_t)p * a.ldy + co] = epilogue(acc[j][r], a.bn, mean[j], rinv[j], scale[j], bias[j], a.act);
             }
         }
     }
@@ -1118,7 +1050,7 @@ __global__ __launch_bounds__(256) void conv_stem_kernel(ConvK a)
 //   * an MFMA row tile is a 2 x 16 pixel strip in pool-major order; lane (pixel li, half h) takes channels 8 g + 4 h .. + 3 of
 //     a tap with ONE ds_read_b128, which feeds four MFMAs (the k pairing of conv_mfma_kernel).  Pixel pitch 144 B, row pitch
 //     2688 B: the 16-lane groups of a ds_read_b128 hit sixteen distinct 16-byte slots;
-//   * the epilogue is the reference's arithmetic (epilogue_f32 / pool_pick), outputs leave as 16-byte stores through a
+//   * the epilogue is the reference's arithmetic (epilogue / pool_pick), outputs leave as 16-byte stores through a
 //     wave-private LDS transpose.
 // K order = (tap, channel): any order gives the same fp32 sum up to association; exact on integer data like every tile.
 // ---------------------------------------------------------------------------
@@ -1220,7 +1152,7 @@ __global__ __launch_bounds__(512, 2) void conv_c32_f32_kernel(ConvK a)
             if (POOL) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
-                    es[(2 * g + lh) * (ES_B / 4) + li] = epilogue_f32(pool_pick(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3],
+                    es[(2 * g + lh) * (ES_B / 4) + li] = epilogue(pool_pick(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3],
                                                                                 !BN_ || scale >= 0.f), BN_, mean, rinv, scale, bias, ACT_);
                 const u32x4 v = *(const u32x4 *)&es[(lane >> 3) * (ES_B / 4) + (lane & 7) * 4];
                 const unsigned prow = (unsigned)((n * Hp + (oy0 >> 1) + rp) * Wp + (ox0 >> 1) + (lane >> 3));
@@ -1230,7 +1162,7 @@ __global__ __launch_bounds__(512, 2) void conv_c32_f32_kernel(ConvK a)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int rr = (r & 3) + 8 * (r >> 2) + 4 * lh;            // GEMM row = 4 * window + corner
-                    es[rr * (ES_B / 4) + li] = epilogue_f32(acc[r], BN_, mean, rinv, scale, bias, ACT_);
+                    es[rr * (ES_B / 4) + li] = epilogue(acc[r], BN_, mean, rinv, scale, bias, ACT_);
                 }
 #pragma unroll
                 for (int p4 = 0; p4 < 4; ++p4) {
@@ -1339,20 +1271,17 @@ struct Variant {
 };
 
 #define VAR(BM, BN, BK, KS, WM, WN)                                                             \
-    { "conv_mfma_f32_" #BM "x" #BN "x" #BK "_k" #KS, BM, BN, BK, KS, conv_mfma_kernel<BM, BN, BK, KS, WM, WN, Y2_PIPE>, \
+    { "conv_mfma_f32_" #BM "x" #BN "x" #BK "_k" #KS, BM, BN, BK, KS, conv_mfma_kernel<BM, BN, BK, KS, WM, WN>, \
       (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float) + (WM * WN == 8 ? (size_t)8 * 16 * 36 * sizeof(float) : 0), WM * WN * 64, nullptr, nullptr, nullptr }
 #define VARSK(BM, BN, BK, KS, WM, WN)                                                           \
-    { "conv_mfma_f32_" #BM "x" #BN "x" #BK "_k" #KS, BM, BN, BK, KS, conv_mfma_kernel<BM, BN, BK, KS, WM, WN, Y2_PIPE>, \
+    { "conv_mfma_f32_" #BM "x" #BN "x" #BK "_k" #KS, BM, BN, BK, KS, conv_mfma_kernel<BM, BN, BK, KS, WM, WN>, \
       (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float) + (WM * WN == 8 ? (size_t)8 * 16 * 36 * sizeof(float) : 0), WM * WN * 64, \
-      nullptr, conv_mfma_kernel<BM, BN, BK, KS, WM, WN, Y2_PIPE, false, 1>, conv_mfma_kernel<BM, BN, BK, KS, WM, WN, Y2_PIPE, false, 2> }
+      nullptr, conv_mfma_kernel<BM, BN, BK, KS, WM, WN, false, 1>, conv_mfma_kernel<BM, BN, BK, KS, WM, WN, false, 2> }
 #define VARXO(BM, BN, BK, KS, WM, WN)                                                           \
-    { "conv_mfma_f32_" #BM "x" #BN "x" #BK "_k" #KS, BM, BN, BK, KS, conv_mfma_kernel<BM, BN, BK, KS, WM, WN, Y2_PIPE>, \
+    { "conv_mfma_f32_" #BM "x" #BN "x" #BK "_k" #KS, BM, BN, BK, KS, conv_mfma_kernel<BM, BN, BK, KS, WM, WN>, \
       (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float) + (WM * WN == 8 ? (size_t)8 * 16 * 36 * sizeof(float) : 0), WM * WN * 64, \
-      conv_mfma_kernel<BM, BN, BK, KS, WM, WN, Y2_PIPE, true>, nullptr, nullptr }
+      conv_mfma_kernel<BM, BN, BK, KS, WM, WN, true>, nullptr, nullptr }
 
-#ifndef Y2_PIPE
-#define Y2_PIPE true
-#endif
 static Variant g_variants[] = {
     // 8 waves (2 per SIMD), ONE workgroup per CU: the co-resident partner wave that hides LDS/barrier
     // stalls comes from the same workgroup, so a CU never ends up with a lone half-speed pair in the tail
@@ -1430,6 +1359,35 @@ static int variant_bpc(const Variant &v)               // workgroups co-resident
 // partial sums go through an fp32 workspace and splitk_reduce_kernel.  Chosen together with the tile.
 static unsigned long g_skf_launches = 0;
 extern "C" unsigned long y2h_f32_stream_k_launches(void) { return g_skf_launches; }
+
+// the share rule the kernels compile (include/y2_streamk_rule.h), for the host tests
+extern "C" int y2h_sk_shares(long tiles, int nk, long G, int *out)
+{
+    if (!out || !y2_sk_fits(tiles, nk, G)) return -1;
+    for (long w = 0; w < G; ++w) {
+        const y2_sk_share s = y2_sk_share_of(w, tiles, nk, G);
+        int *o = out + 5 * w;
+        o[0] = s.n; o[1] = s.tile; o[2] = s.kb0; o[3] = s.ke0; o[4] = s.ke1;
+    }
+    return 0;
+}
+extern "C" int y2h_sk_first(long tiles, int nk, long G, int *out)
+{
+    if (!out || !y2_sk_fits(tiles, nk, G)) return -1;
+    for (long t = 0; t < tiles; ++t) out[t] = (int)y2_sk_first(t, tiles, nk, G);
+    return 0;
+}
+extern "C" int y2h_sk_walk(long tiles, int nk, long G, int *out, int max)
+{
+    if (!out || !y2_sk_fits(tiles, nk, G)) return -1;
+    int n = 0, piece;
+    for (long t = 0; t < tiles; ++t)
+        for (long w = y2_sk_first(t, tiles, nk, G); y2_sk_walk(&w, &piece, t, tiles, nk, G); ++w, ++n) {
+            if (n >= max) return -1;
+            out[3 * n] = (int)t; out[3 * n + 1] = (int)w; out[3 * n + 2] = piece;
+        }
+    return n;
+}
 
 // sk_wgs_out (optional): > 0 when the choice is the stream-K form of the tile (conv_mfma_kernel<..., SKM>) on that many
 // workgroups -- then *ksplit_out is 1.  Env: Y2_SKF=0 off; Y2_SKF_WGS=n forces stream-K on n workgroups for the (forced) tile.
@@ -1554,7 +1512,7 @@ static bool pick_variant(const y2h_conv *d, ConvPlan &p)
             long wgs = (long)CUS * bpc;
             if (wgs > tiles * nk / 8) wgs = tiles * nk / 8;             // shares of >= 8 K-steps
             if (sk_force > 0) wgs = sk_force;
-            if (tiles <= wgs && wgs >= 2 && (sk_force > 0 || tiles * 2 < (long)CUS * bpc * 2)) {
+            if (y2_sk_fits(tiles, nk, wgs) && wgs >= 2 && (sk_force > 0 || tiles * 2 < (long)CUS * bpc * 2)) {
                 const double share = (double)tiles * nk / wgs;
                 const long cu_load = (wgs + CUS - 1) / CUS;                // workgroups a CU hosts
                 double c_sk = (double)cu_load * v.bm * v.bn * v.bk / 128.0 * (share + 7.5) / eff;

@@ -15,18 +15,11 @@
 // per flop: 256x256 tiles so that the L2->LDS traffic per MFMA stays under what a CU can pull
 // ((BM+BN)*BK*2 bytes per BM*BN*BK*2 flops), BK = 64 halves = one 128-byte line per pixel and tap,
 // LDS rows padded by 16 bytes so the ds_read_b128 operand reads (8 halves = the k-fragment of one
-// lane of a 32x32x16 MFMA) are bank-conflict free.
+// lane of a 32x32x16 MFMA) are bank-conflict free.  conv_mfma_f16_kernel's staging side is the fp32 kernel's own
+// code (y2_conv_shared.hpp) instantiated for halves, and the fix-up launch walks the stream-K pieces by the shared rule
+// (include/y2_streamk_rule.h).
 #include "y2_conv_shared.hpp"
 #include <type_traits>
-
-// Tuning ablations (profiles/r01_notes.md): build with -DY2_F16_ABLATE and set Y2_DBG to a mask of
-// 1 no LDS staging writes, 2 no global loads, 4 no output stores, 8 scalar output stores, 16 no barrier,
-// 32 no fragment reads.  Results are garbage; compiled out by default so the K loop carries no extra branches.
-#ifdef Y2_F16_ABLATE
-#define ABL(bit) (a.dbg & (bit))
-#else
-#define ABL(bit) false
-#endif
 
 template <int BM, int BN, int BK, int KS, int WM, int WN, int MINB, bool DB, bool M16>
 __global__ __launch_bounds__(WM *WN * 64, MINB) void conv_mfma_f16_kernel(ConvK a)
@@ -65,40 +58,9 @@ __global__ __launch_bounds__(WM *WN * 64, MINB) void conv_mfma_f16_kernel(ConvK 
         c0 = 0;
         tap = 0;
         const int p0 = a.row0 + (tile / a.tiles_n) * BM, n0 = (tile % a.tiles_n) * BN;
-        // Row geometry with ONE coordinate decode per thread and tile: this thread's rows are RP apart, so the
-        // image coordinates of the following rows come from a carry update.  (With a matrix pipe this fast the
-        // per-row divisions and nine tap tests of the fp32 kernel's setup were ~10 % of a tile.)  Unit grid:
-        // pooling windows (row r = 4*window + corner) with the fused pool, pixels without.
-        const int Wu = a.pool ? a.W >> 1 : a.W, Hu = a.pool ? a.H >> 1 : a.H;
-        const int r0 = p0 + sr;
-        const int u0 = a.pool ? r0 >> 2 : r0, tc = r0 & 3;      // RP is a multiple of 4: the corner is the same for all q
-        int cn = u0 / (Hu * Wu);
-        int cy = (u0 - cn * Hu * Wu) / Wu, cx = u0 - cn * Hu * Wu - cy * Wu;
-        constexpr int USTEP_P = RP / 4, USTEP_N = RP;
-#pragma unroll
-        for (int q = 0; q < PA; ++q) {
-            const int r = r0 + q * RP;
-            const int py = a.pool ? 2 * cy + (tc >> 1) : cy, px = a.pool ? 2 * cx + (tc & 1) : cx;
-            a_off[q] = ((unsigned)((cn * a.H + py) * a.W + px) * (unsigned)a.ldx + (unsigned)sc * 8u) * 2u;
-            unsigned m = 0;
-            if (live && r < a.npix && (BM % RP == 0 || sr + q * RP < BM)) {
-                if (KS == 1) m = 1u;
-                else {
-                    // bit kh*3+kw = tap inside the image: (column pattern) x (row pattern spread 3 bits apart), no carries
-                    const unsigned xm = (px > 0 ? 1u : 0u) | 2u | (px < a.W - 1 ? 4u : 0u);
-                    const unsigned ym = (py > 0 ? 1u : 0u) | 8u | (py < a.H - 1 ? 64u : 0u);
-                    m = xm * ym;
-                }
-            }
-            a_msk[q] = m;
-            cx += a.pool ? USTEP_P : USTEP_N;
-            while (cx >= Wu) { cx -= Wu; if (++cy >= Hu) { cy = 0; ++cn; } }
-        }
-#pragma unroll
-        for (int q = 0; q < PB; ++q) {
-            const unsigned co = (unsigned)(n0 + sr + q * RP);
-            b_off[q] = (live && co < (unsigned)a.Cout && sr + q * RP < BN) ? (co * (unsigned)a.K + (unsigned)sc * 8u) * 2u : a.wbytes;
-        }
+        // (with a matrix pipe this fast the per-row divisions and nine tap tests of a naive setup were ~10 % of a tile)
+        conv_stage_rows<_Float16, KS, BM, RP, PA>(a, live, p0, sr, (unsigned)sc * 16u, a_off, a_msk);
+        conv_stage_filters<_Float16, BN, RP, PB>(a, live, n0, sr, (unsigned)sc * 16u, b_off);
     };
 
     f32x16 acc[M16 ? 1 : TM][M16 ? 1 : TN];
@@ -116,37 +78,10 @@ __global__ __launch_bounds__(WM *WN * 64, MINB) void conv_mfma_f16_kernel(ConvK 
     int lti = 0, stage_k = 0;          // staging cursor: tile index in this workgroup's sequence, slices loaded of it
     setup_tile(tile_at(0));
     auto load_slice = [&]() {
-        int delta = 0;
-        if (KS == 3) {
-            const int kh = tap / 3, kw = tap - kh * 3;
-            delta = ((kh - 1) * a.W + (kw - 1)) * a.ldx;
-        }
-        const unsigned add = (unsigned)((delta + c0) * 2);
-#pragma unroll
-        for (int q = 0; q < PA; ++q) {
-            const bool ok = (a_msk[q] >> tap) & 1u;
-            const unsigned off = ok ? a_off[q] + add : a.xbytes;
-            ra[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, off, 0, 0));
-        }
-        const unsigned kadd = (unsigned)((tap * a.Cin + c0) * 2);
-#pragma unroll
-        for (int q = 0; q < PB; ++q) {
-            const unsigned off = (b_off[q] == a.wbytes) ? a.wbytes : b_off[q] + kadd;
-            rb[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wr, off, 0, 0));
-        }
-        if (++tap == KS * KS) { tap = 0; c0 += BK; }
+        conv_load_slice<_Float16, KS, BK>(a, xr, wr, tap, c0, a_off, a_msk, b_off, ra, rb);
         ++stage_k;
     };
-    auto store_slice = [&](int buf) {
-        _Float16 *As = smem_h + buf * BUF;
-        _Float16 *Bs = As + BM * LS;
-#pragma unroll
-        for (int q = 0; q < PA; ++q)
-            if (BM % RP == 0 || sr + q * RP < BM) *(f32x4 *)&As[(sr + q * RP) * LS + sc * 8] = ra[q];
-#pragma unroll
-        for (int q = 0; q < PB; ++q)
-            if (BN % RP == 0 || sr + q * RP < BN) *(f32x4 *)&Bs[(sr + q * RP) * LS + sc * 8] = rb[q];
-    };
+    auto store_slice = [&](int buf) { conv_store_slice<_Float16, BM, BN, LS, RP>(smem_h + buf * BUF, sr, sc, ra, rb); };
 
     load_slice();
     store_slice(0);
@@ -223,21 +158,18 @@ __global__ __launch_bounds__(WM *WN * 64, MINB) void conv_mfma_f16_kernel(ConvK 
             for (int kg = 0; kg < NG; ++kg) {
                 const int c = DB ? (kg & 1) : 0, n = DB ? (c ^ 1) : 0;
                 if (!DB) {
-                    if (!ABL(32) || kt == 0) {
 #pragma unroll
                     for (int i = 0; i < TM; ++i) af[0][i] = *(const f16x8 *)&As[i * 32 * LS + kg * 16];
 #pragma unroll
                     for (int j = 0; j < TN; ++j) bf[0][j] = *(const f16x8 *)&Bs[j * 32 * LS + kg * 16];
-                    }
                 } else if (kg + 1 < NG) {
 #pragma unroll
                     for (int i = 0; i < TM; ++i) af[n][i] = *(const f16x8 *)&As[i * 32 * LS + (kg + 1) * 16];
 #pragma unroll
                     for (int j = 0; j < TN; ++j) bf[n][j] = *(const f16x8 *)&Bs[j * 32 * LS + (kg + 1) * 16];
                 }
-                if (kg == 0 && !ABL(1)) store_slice(cur ^ 1);     // the slice loaded one step ago
-                if (kg == 1 && !ABL(2)) load_slice();             // two slices ahead
-                if (kg == 1 && ABL(2)) ++stage_k;
+                if (kg == 0) store_slice(cur ^ 1);     // the slice loaded one step ago
+                if (kg == 1) load_slice();             // two slices ahead
                 if (!DB) __builtin_amdgcn_s_setprio(2);     // matrix issue ahead of the partner wave's staging traffic
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
@@ -272,16 +204,10 @@ __global__ __launch_bounds__(WM *WN * 64, MINB) void conv_mfma_f16_kernel(ConvK 
             // Raw barrier: wait for this wave's LDS traffic only.  __syncthreads() would also drain vmcnt(0), i.e.
             // wait at every K-step for the global loads of the slice two steps ahead that were just issued --
             // the latency the two-slice distance exists to hide.
-#ifdef Y2_F16_SYNCTHREADS
-            __syncthreads();
-#else
-            if (!ABL(16)) {
-                __builtin_amdgcn_sched_barrier(0);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#endif
+            __builtin_amdgcn_sched_barrier(0);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
             cur ^= 1;
         }
 
@@ -385,7 +311,7 @@ __global__ __launch_bounds__(WM *WN * 64, MINB) void conv_mfma_f16_kernel(ConvK 
                             }
                             const f32x4 v = *(const f32x4 *)&es[rrow * ES + rchunk];
                             const int prow = (pb >> 2) + rrow;
-                            if (lane < 32 && 4 * prow < a.npix && cb + rchunk < a.Cout && !ABL(4))
+                            if (lane < 32 && 4 * prow < a.npix && cb + rchunk < a.Cout)
                                 *(f32x4 *)&yh[(size_t)prow * a.ldy + cb + rchunk] = v;
                         } else {
 #pragma unroll
@@ -395,7 +321,7 @@ __global__ __launch_bounds__(WM *WN * 64, MINB) void conv_mfma_f16_kernel(ConvK 
                             for (int h2 = 0; h2 < 2; ++h2) {
                                 const f32x4 v = *(const f32x4 *)&es[(rrow + 16 * h2) * ES + rchunk];
                                 const int p = pb + rrow + 16 * h2;
-                                if (p < a.npix && cb + rchunk < a.Cout && !ABL(4)) *(f32x4 *)&yh[(size_t)p * a.ldy + cb + rchunk] = v;
+                                if (p < a.npix && cb + rchunk < a.Cout) *(f32x4 *)&yh[(size_t)p * a.ldy + cb + rchunk] = v;
                             }
                         }
                     }
@@ -406,7 +332,7 @@ __global__ __launch_bounds__(WM *WN * 64, MINB) void conv_mfma_f16_kernel(ConvK 
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 const int co = n0 + wn * (BN / WN) + j * 32 + li;
-                const bool cok = co < a.Cout && !ABL(4);
+                const bool cok = co < a.Cout;
                 const float alpha = cok ? a.alpha[co] : 0.f, beta = cok ? a.beta[co] : 0.f;
 #pragma unroll
                 for (int i = 0; i < TM; ++i) {
@@ -535,35 +461,24 @@ __device__ __forceinline__ void p8_epilogue_quadrant(const ConvK &a, const int A
     }
 }
 
-// Stream-K share of workgroup w: K-tile iterations [w * I / G, (w + 1) * I / G) of the I = sk_tiles * nk iterations of the
-// tail tiles (the kernel and the fix-up launch must agree on this arithmetic)
-__device__ __host__ static inline long sk_share_begin(long w, long I, long G) { return w * I / G; }
-
 // Second launch of a stream-K convolution: block (tail tile ts, wave wv of the producing workgroups), its four waves take
 // the four quadrants of that wave's share.  A piece slot holds the accumulators as the producing thread held them:
 // [slot][e = ((x*2+y)*4+i)*2+j][thread 0..511] f32x4, so both sides move whole 1 KB lines.  Pieces are added in ascending
-// K order (= ascending workgroup number), a fixed order: results are reproducible run to run.
+// K order (= ascending workgroup number, the walk of y2_streamk_rule.h), a fixed order: results are reproducible run to run.
 __global__ __launch_bounds__(256) void conv_p8_fixup_kernel(ConvK a, int nk)
 {
     __shared__ __attribute__((aligned(16))) _Float16 es_all[4 * 32 * 40];
     const int ts = blockIdx.x >> 3, wv = blockIdx.x & 7;
     const int qd = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int x = qd >> 1, y = qd & 1, wm = wv >> 2, wn = wv & 3;
-    const long I = (long)a.sk_tiles * nk, G = a.sk_wgs;
-    const long tb = (long)ts * nk, te = tb + nk;
-    long w = tb * G / I;
-    while (w > 0 && sk_share_begin(w, I, G) > tb) --w;
-    while (w + 1 < G && sk_share_begin(w + 1, I, G) <= tb) ++w;        // first share that reaches into this tile
     f32x4 q[4][2];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) q[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (; w < G; ++w) {
-        const long lo = sk_share_begin(w, I, G), hi = sk_share_begin(w + 1, I, G);
-        if (lo >= te) break;
-        if (hi <= lo) continue;
-        const int slot = 2 * (int)w + (lo < tb ? 1 : 0);       // a share that began in the previous tile: its second piece
+    int piece;
+    for (long w = y2_sk_first(ts, a.sk_tiles, nk, a.sk_wgs); y2_sk_walk(&w, &piece, ts, a.sk_tiles, nk, a.sk_wgs); ++w) {
+        const int slot = 2 * (int)w + piece;                   // a share that began in the previous tile: its second piece
         const f32x4 *src = (const f32x4 *)a.ws + ((size_t)slot * 32 + (size_t)(x * 2 + y) * 8) * 512 + wv * 64 + lane;
 #pragma unroll
         for (int i = 0; i < 4; ++i)
@@ -603,6 +518,10 @@ __global__ __launch_bounds__(512, 1) void conv_p8_f16_kernel(ConvK a)
     const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void *)a.w, 0, a.wbytes, 0x00020000);
 
     // ---- staging role: 16-byte chunk `sc` of rows sr + 64 q (q = 0..3) of the A tile and of the B tile ----
+    // (This kernel keeps its own copy of y2_sk_share_of, include/y2_streamk_rule.h, written out on y2_sk_begin, and of the
+    // staging side of y2_conv_shared.hpp -- conv_stage_rows / conv_stage_filters / conv_slice_a / _b / _next.  Its stream is
+    // hand-scheduled: with the shared staging side darknet19_448 b128 measured 1 % slower, with y2_sk_share_of alone -- four
+    // instructions' difference -- 0.75 %, profiles/conv_staging_ab.txt.  tests/test_stream_k_plan.py restates the same share.)
     const int sc = t & 7, sr = t >> 3;
     const unsigned scs = (unsigned)(sc ^ ((sr >> 1) & 7)) * 16u;      // swizzled source chunk (bytes); (row >> 1) & 7 == (sr >> 1) & 7
     unsigned a_off[4], a_msk[4], b_off[4];
@@ -622,7 +541,7 @@ __global__ __launch_bounds__(512, 1) void conv_p8_f16_kernel(ConvK a)
     int n_sk = 0, sk_t0 = 0, sk_kb0 = 0, sk_ke0 = 0, sk_ke1 = 0;
     if (a.sk_tiles > 0 && wgid < a.sk_wgs) {
         const long I = (long)a.sk_tiles * nk;
-        const long lo = sk_share_begin(wgid, I, a.sk_wgs), hi = sk_share_begin(wgid + 1, I, a.sk_wgs);
+        const long lo = y2_sk_begin(wgid, I, a.sk_wgs), hi = y2_sk_begin(wgid + 1, I, a.sk_wgs);
         if (hi > lo) {
             const int t0 = (int)(lo / nk), k0 = (int)(lo - (long)t0 * nk), len = (int)(hi - lo);      // len <= nk: sk_tiles <= sk_wgs
             sk_t0 = ndp + t0; sk_kb0 = k0; sk_ke0 = k0 + len < nk ? k0 + len : nk; n_sk = 1;
@@ -1314,6 +1233,17 @@ static int bpc_h(const VariantH &v)
     return bpc < 1 ? 1 : bpc;
 }
 
+// tiles the busiest CU gets when `tiles` tiles of v are dealt over 256 CUs, bpc_h(v) workgroups at a time
+static long per_cu_h(const VariantH &v, long tiles)
+{
+    const int bpc = bpc_h(v);
+    if (tiles <= 256L * bpc) return (tiles + 255) / 256;
+    return (long)bpc * ((tiles + 256L * bpc - 1) / (256L * bpc));
+}
+
+// half outputs can leave as 16-byte stores (ConvK.vec_store; the M16 variants need them)
+static bool vec_ok(const y2h_conv *d) { return d->y_f16 && d->ldy % 8 == 0 && d->n % 8 == 0 && ((uintptr_t)d->y % 16) == 0; }
+
 // Tile choice.  Per 16-deep MFMA step a CU spends max(matrix time, L2->LDS staging time): BM*BN/128 cycles on
 // its four matrix pipes against (BM+BN)*32 bytes at the ~40 B/clk a CU sustains from L2, so small tiles are
 // staging bound; the grid quantisation over 256 CUs is counted as in the fp32 picker.  Y2_CONV_TILE forces.
@@ -1323,7 +1253,6 @@ static VariantH *pick_h(const y2h_conv *d)
     const long npix = (long)d->batch * d->h * d->w;
     int force_bm = 0, force_bn = 0;
     if (const char *f = getenv("Y2_CONV_TILE")) sscanf(f, "%dx%d", &force_bm, &force_bn);
-    const bool vec_ok = d->y_f16 && d->ldy % 8 == 0 && d->n % 8 == 0 && ((uintptr_t)d->y % 16) == 0;
     const bool no_m16 = getenv("Y2_NO_M16") != nullptr;      // A/B switch: keep to the 32x32x16 variants
     const bool no_p8 = getenv("Y2_F16_NO_P8") != nullptr;    // A/B switch: the register-staged 256x256 kernel
     VariantH *best = nullptr;
@@ -1331,15 +1260,11 @@ static VariantH *pick_h(const y2h_conv *d)
     for (VariantH &v : g_variants_h) {
         if (v.bk != bk || v.ks != d->size) continue;
         if (force_bm && (v.bm != force_bm || v.bn != force_bn)) continue;
-        if (v.m16 && (!vec_ok || no_m16)) continue;
+        if (v.m16 && (!vec_ok(d) || no_m16)) continue;
         if (v.p8 && no_p8) continue;
         const long tiles = ((npix + v.bm - 1) / v.bm) * ((d->n + v.bn - 1) / v.bn);
-        const int bpc = bpc_h(v);
-        long per_cu;
-        if (tiles <= 256L * bpc) per_cu = (tiles + 255) / 256;
-        else per_cu = (long)bpc * ((tiles + 256L * bpc - 1) / (256L * bpc));
         const double mfma = (double)v.bm * v.bn / 128.0, stage = (double)(v.bm + v.bn) * 0.8;
-        const double cost = (double)per_cu * (mfma > stage ? mfma : stage);
+        const double cost = (double)per_cu_h(v, tiles) * (mfma > stage ? mfma : stage);
         if (!best || cost < best_cost * 0.999 || (cost <= best_cost * 1.001 && v.bm * v.bn > best->bm * best->bn)) {
             best = &v;
             best_cost = cost;
@@ -1359,6 +1284,16 @@ static VariantH *pick_h(const y2h_conv *d)
 static unsigned long g_sk_launches = 0;
 extern "C" unsigned long y2h_stream_k_launches(void) { return g_sk_launches; }
 
+static const double SK_C_TILE = 5.0;
+// `before` + the estimate of a last round of R tiles cut over wgs workgroups
+static double sk_round_cost(double before, long R, int nk, long wgs)
+{
+    const double FIX_LAUNCH = 3.0, FIX_PIECE = 0.04;
+    const double share = (double)R * nk / wgs;
+    const double pieces = (double)wgs + (double)R;          // every share is one piece, plus one more per tile boundary it crosses
+    return before + share + SK_C_TILE * (1.0 + (double)R / wgs) + FIX_LAUNCH + pieces * FIX_PIECE;
+}
+
 extern "C" int y2h_p8_stream_k_plan(long ntiles, int nk, long grid, int *sk_tiles, int *sk_wgs)
 {
     *sk_tiles = 0; *sk_wgs = 0;
@@ -1377,19 +1312,16 @@ extern "C" int y2h_p8_stream_k_plan(long ntiles, int nk, long grid, int *sk_tile
     }
     const long R = ntiles % grid;
     if (R == 0) return 0;
-    const double C_TILE = 5.0, FIX_LAUNCH = 3.0, FIX_PIECE = 0.04;
     int MINK = 4;
     double margin = 0.97;                                   // sweeps: Y2_SK_MARGIN=2 splits whenever a split is possible
     if (const char *m = getenv("Y2_SK_MARGIN")) margin = atof(m);
     if (const char *m = getenv("Y2_SK_MINK")) { if (atoi(m) > 0) MINK = atoi(m); }
     const long rounds = ntiles / grid;
-    const double t_plain = (double)(rounds + 1) * (nk + C_TILE);
+    const double t_plain = (double)(rounds + 1) * (nk + SK_C_TILE);
     long wgs = (R * nk) / MINK;
     if (wgs > grid) wgs = grid;
     if (wgs <= R) return 0;                                 // shares of a whole tile or more: nothing to gain
-    const double share = (double)R * nk / wgs;
-    const double pieces = (double)wgs + (double)R;          // every share is one piece, plus one more per tile boundary it crosses
-    const double t_sk = (double)rounds * (nk + C_TILE) + share + C_TILE * (1.0 + (double)R / wgs) + FIX_LAUNCH + pieces * FIX_PIECE;
+    const double t_sk = sk_round_cost((double)rounds * (nk + SK_C_TILE), R, nk, wgs);
     if (t_sk >= margin * t_plain) return 0;
     *sk_tiles = (int)R; *sk_wgs = (int)wgs;
     return 1;
@@ -1407,10 +1339,10 @@ extern "C" int y2h_p8_stream_k_plan(long ntiles, int nk, long grid, int *sk_tile
 // Env: Y2_TAIL=0 off; Y2_TAIL_TILE=BMxBN forces the tail tile (and the tail itself whenever there is a partial round),
 // Y2_TAIL_TILES=n the number of 256x256 tiles handed to it (tests).
 // ---------------------------------------------------------------------------
-static VariantH *find_h(int bm, int bn, int bk, int ks, bool vec_ok)
+static VariantH *find_h(int bm, int bn, int bk, int ks, bool vec)
 {
     for (VariantH &v : g_variants_h)
-        if (!v.p8 && v.bm == bm && v.bn == bn && v.bk == bk && v.ks == ks && (!v.m16 || vec_ok)) return &v;
+        if (!v.p8 && v.bm == bm && v.bn == bn && v.bk == bk && v.ks == ks && (!v.m16 || vec)) return &v;
     return nullptr;
 }
 
@@ -1427,17 +1359,12 @@ static double tail_cost(const VariantH &v, long rows, int n, int nk)
     else if (v.bm == 128 && v.bn == 64) rel = 0.40;
     else if (v.bm == 64 && v.bn == 64) rel = 0.30;
     const long tiles = ((rows + v.bm - 1) / v.bm) * ((n + v.bn - 1) / v.bn);
-    const int bpc = bpc_h(v);
-    long per_cu;
-    if (tiles <= 256L * bpc) per_cu = (tiles + 255) / 256;
-    else per_cu = (long)bpc * ((tiles + 256L * bpc - 1) / (256L * bpc));
-    return 1.5 + (double)per_cu * ((double)v.bm * v.bn / 65536.0) / rel * (nk + 6.0);
+    return 1.5 + (double)per_cu_h(v, tiles) * ((double)v.bm * v.bn / 65536.0) / rel * (nk + 6.0);
 }
 
 static P8Plan p8_plan(const y2h_conv *d, long ntiles, int tiles_n, int nk, long grid)
 {
     P8Plan pl = {0, 0, 0, nullptr};
-    const bool vec_ok = d->y_f16 && d->ldy % 8 == 0 && d->n % 8 == 0 && ((uintptr_t)d->y % 16) == 0;
     const char *toff = getenv("Y2_TAIL");
     const bool tail_on = !(toff && atoi(toff) == 0);
     int fbm = 0, fbn = 0;
@@ -1445,7 +1372,7 @@ static P8Plan p8_plan(const y2h_conv *d, long ntiles, int tiles_n, int nk, long 
     const char *ftn = getenv("Y2_TAIL_TILES");
     const long npix = (long)d->batch * d->h * d->w;
     if (tail_on && fbm && ((ftn && atol(ftn) > 0) || ntiles % grid)) {          // forced
-        VariantH *tv = find_h(fbm, fbn, 64, d->size, vec_ok);
+        VariantH *tv = find_h(fbm, fbn, 64, d->size, vec_ok(d));
         long t = (ftn && atol(ftn) > 0) ? atol(ftn) : ntiles % grid;
         if (t > ntiles) t = ntiles;
         while ((ntiles - t) % tiles_n) ++t;                 // the whole-tile part ends on a row boundary
@@ -1454,19 +1381,14 @@ static P8Plan p8_plan(const y2h_conv *d, long ntiles, int tiles_n, int nk, long 
     if (y2h_p8_stream_k_plan(ntiles, nk, grid, &pl.sk_tiles, &pl.sk_wgs) && (getenv("Y2_SK_TILES") || !tail_on)) return pl;
     const long R = ntiles % grid;
     if (R == 0 || !tail_on || (ntiles - R) % tiles_n) return pl;
-    // three candidates for the last round: as it is, stream-K (estimate inside y2h_p8_stream_k_plan, recomputed here), tail
-    const double C_TILE = 5.0;
-    const double t_round = nk + C_TILE;
-    double t_sk = 1e30;
-    if (pl.sk_tiles) {
-        const double share = (double)R * nk / pl.sk_wgs, pieces = (double)pl.sk_wgs + (double)R;
-        t_sk = share + C_TILE * (1.0 + (double)R / pl.sk_wgs) + 3.0 + pieces * 0.04;
-    }
+    // three candidates for the last round: as it is, stream-K (the plan's own estimate), tail
+    const double t_round = nk + SK_C_TILE;
+    const double t_sk = pl.sk_tiles ? sk_round_cost(0.0, R, nk, pl.sk_wgs) : 1e30;
     const long rows = npix - ((ntiles - R) / tiles_n) * 256;
     VariantH *best = nullptr;
     double t_tail = 1e30;
     for (VariantH &tv : g_variants_h) {
-        if (tv.p8 || tv.bk != 64 || tv.ks != d->size || (tv.m16 && !vec_ok) || (tv.bm == 256 && tv.bn == 256)) continue;
+        if (tv.p8 || tv.bk != 64 || tv.ks != d->size || (tv.m16 && !vec_ok(d)) || (tv.bm == 256 && tv.bn == 256)) continue;
         const double c = tail_cost(tv, rows, d->n, nk);
         if (c < t_tail) { t_tail = c; best = &tv; }
     }
@@ -1486,7 +1408,7 @@ static int mfma_h_launch(const ConvPlan &p, const y2h_conv *d, ConvK &a, y2h_str
     a.tiles_n = p.h_tiles_n;
     a.ksplit = 1;
     if (const char *dbg = getenv("Y2_DBG")) a.dbg = atoi(dbg);
-    a.vec_store = d->y_f16 && d->ldy % 8 == 0 && d->n % 8 == 0 && ((uintptr_t)d->y % 16) == 0 && !ABL(8);
+    a.vec_store = vec_ok(d);
     Y2H_CHECK(y2h_lds_limit((const void *)v->fn, v->lds));
     a.ntiles = (int)p.h_ntiles;
     if (v->p8 && getenv("Y2_P8_REMAP")) a.dbg |= 64;            // A/B: XCD-contiguous placement of workgroups

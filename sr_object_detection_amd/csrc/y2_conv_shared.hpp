@@ -1,6 +1,7 @@
 // Shared between the fp32 (y2_conv.hip) and fp16 (y2_conv_f16.hip) convolution kernels.
 #pragma once
 #include "y2_common.hpp"
+#include "y2_streamk_rule.h"
 #include <stdlib.h>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -33,9 +34,9 @@ struct ConvK {
     int ksplit;        // >= 1: number of K ranges each output tile is cut into (split-K)
     float *ws;         // split-K partial sums [ksplit][npix][Cout]; stream-K: piece slots (see sk_tiles)
     // Stream-K (persistent kernels): the LAST sk_tiles output tiles are not walked whole.  Their sk_tiles * nk K-tile
-    // iterations are dealt in equal contiguous shares to workgroups 0 .. sk_wgs-1 (share <= one tile: sk_tiles <= sk_wgs),
-    // each share is one or two pieces (tile, K range) whose raw fp32 sums go to slot 2*wg + piece of `ws`, and a fix-up
-    // launch adds a tile's pieces in ascending K order and applies the epilogue.  0 = every tile is walked whole.
+    // iterations are dealt in equal contiguous shares to workgroups 0 .. sk_wgs-1 by the rule of y2_streamk_rule.h (share <=
+    // one tile: sk_tiles <= sk_wgs), each share is one or two pieces (tile, K range) whose raw fp32 sums go to slot 2*wg + piece
+    // of `ws`, and a fix-up launch adds a tile's pieces in ascending K order and applies the epilogue.  0 = every tile is walked whole.
     int sk_tiles, sk_wgs;
     int *sk_flags;     // hybrid stream-K of the fp32 kernel (conv_mfma_kernel<..., 2>): one flag per piece slot (2 * sk_wgs ints), zeroed before the launch
     // fp32 matrix-core kernel, wide heads (yolo9000's 28 269-filter 1x1: 116 MB of weights against 9.5 MB of input): tiles are
@@ -62,27 +63,6 @@ __device__ __forceinline__ float epilogue(float v, bool bn, float mean, double r
     else if (act == Y2H_ACT_LOGISTIC) v = (float)(1. / (1. + exp(-(double)v)));       // activations.h:35
     else if (act == Y2H_ACT_RELU) v = v * (float)(v > 0);                             // activations.h:37
     return v;
-}
-
-// Build option -DY2_FAST_EPILOGUE: the same steps in fp32 arithmetic for the matrix-core kernels (at most 2 ulp from
-// epilogue()).  Measured on yolo.cfg 608 b32: +0.5-0.9 % images/s (A/B on one box) -- not worth leaving the reference's
-// arithmetic, so the default keeps the exact form everywhere.
-__device__ __forceinline__ float epilogue_f32(float v, bool bn, float mean, double rinv, float scale, float bias, int act)
-{
-#ifndef Y2_FAST_EPILOGUE
-    return epilogue(v, bn, mean, rinv, scale, bias, act);
-#else
-    if (bn) {
-        float d = v - mean;
-        v = d * (float)rinv;
-        v = v * scale;
-    }
-    v = v + bias;
-    if (act == Y2H_ACT_LEAKY) v = (v > 0) ? v : .1f * v;
-    else if (act == Y2H_ACT_LOGISTIC) v = (float)(1. / (1. + exp(-(double)v)));
-    else if (act == Y2H_ACT_RELU) v = v * (float)(v > 0);
-    return v;
-#endif
 }
 
 // Fused conv + maxpool: the epilogue is a MONOTONE function of the accumulator -- every step (x - mean, * rinv > 0 in
@@ -122,6 +102,125 @@ __device__ __forceinline__ int pool_pixel(int r, int H, int W)
     const int n = q / HWp, rem = q - n * HWp;
     const int yo = rem / Wp, xo = rem - yo * Wp;
     return (n * H + 2 * yo + (t >> 1)) * W + 2 * xo + (t & 1);
+}
+
+// ---------------------------------------------------------------------------
+// The staging side of the implicit-GEMM kernels.  conv_mfma_f16_kernel uses all of it; conv_mfma_kernel the tap mask and the
+// slice address, conv_p8_f16_kernel neither: those two carry their own copy of the rest, with a comment that says why.
+// A thread stages one 16-byte chunk, at byte offset `chunk` of a row's BK channels, of the GEMM rows sr + q * RP of the
+// pixel tile and of the filter tile.  T = element type, KS = filter size; what callers differ in is a template argument.
+// ---------------------------------------------------------------------------
+// bit kh*KS+kw = tap (kh, kw) of the pixel (px, py) lies inside the W x H image (pad = KS/2): a column pattern times a row
+// pattern spread KS bits apart, no carries.  Any odd size with KS*KS <= 32 taps (5x5: alexnet.cfg).
+template <int KS>
+__device__ __forceinline__ unsigned conv_tap_mask(int px, int py, int W, int H)
+{
+    static_assert(KS * KS <= 32, "one mask bit per tap");
+    if (KS == 1) return 1u;
+    if (KS == 3) {
+        const unsigned xm = (px > 0 ? 1u : 0u) | 2u | (px < W - 1 ? 4u : 0u);
+        const unsigned ym = (py > 0 ? 1u : 0u) | 8u | (py < H - 1 ? 64u : 0u);
+        return xm * ym;
+    }
+    unsigned xm = 0, ym = 0;
+#pragma unroll
+    for (int k = 0; k < KS; ++k) {
+        if (px + k - KS / 2 >= 0 && px + k - KS / 2 < W) xm |= 1u << k;
+        if (py + k - KS / 2 >= 0 && py + k - KS / 2 < H) ym |= 1u << (k * KS);
+    }
+    return xm * ym;
+}
+
+// K-slice (tap, c0) = channels c0 .. c0 + BK - 1 of one filter tap.  K order: channel chunk outermost, the KS*KS taps
+// innermost -- the taps of one chunk touch the same (neighbouring) pixel lines, so all but one of the A-slice reads hit L1/L2.
+// Byte offset of the slice from the centre pixel's channel 0 ...
+template <int KS, int ESZ>
+__device__ __forceinline__ unsigned conv_slice_a(int tap, int c0, int W, int ldx)
+{
+    int delta = 0;        // element offset of the tap relative to the centre pixel
+    if (KS > 1) {
+        const int kh = tap / KS, kw = tap - kh * KS;
+        delta = ((kh - KS / 2) * W + (kw - KS / 2)) * ldx;
+    }
+    return (unsigned)((delta + c0) * ESZ);
+}
+// ... and from the start of a packed weight row
+template <int ESZ>
+__device__ __forceinline__ unsigned conv_slice_b(int tap, int c0, int Cin) { return (unsigned)((tap * Cin + c0) * ESZ); }
+template <int KS, int BK>
+__device__ __forceinline__ void conv_slice_next(int &tap, int &c0) { if (++tap == KS * KS) { tap = 0; c0 += BK; } }
+
+// Row metadata of the pixel tile at GEMM row p0 (`live` false: a tile past the end, everything masked): a_off = byte
+// offset of the row's centre pixel (+ chunk), a_msk = its tap mask.  ONE coordinate decode per thread and tile: this
+// thread's rows are RP apart, so the image coordinates of the following rows come from a carry update (unit grid = pooling
+// windows, row r = 4*window + corner, with the fused pool; pixels without).  Stride 1: the GEMM rows enumerate a.H x a.W.
+template <typename T, int KS, int BM, int RP, int PA>
+__device__ __forceinline__ void conv_stage_rows(const ConvK a, bool live, int p0, int sr, unsigned chunk, unsigned (&a_off)[PA], unsigned (&a_msk)[PA])
+{
+    static_assert(RP % 4 == 0, "rows of one thread must keep their pooling-window corner");
+    const int Wu = a.pool ? a.W >> 1 : a.W, Hu = a.pool ? a.H >> 1 : a.H;
+    const int r0 = p0 + sr;
+    const int u0 = a.pool ? r0 >> 2 : r0, tc = r0 & 3;
+    int cn = u0 / (Hu * Wu);
+    int cy = (u0 - cn * Hu * Wu) / Wu, cx = u0 - cn * Hu * Wu - cy * Wu;
+#pragma unroll
+    for (int q = 0; q < PA; ++q) {
+        const int r = r0 + q * RP;                            // GEMM row
+        const int py = a.pool ? 2 * cy + (tc >> 1) : cy, px = a.pool ? 2 * cx + (tc & 1) : cx;
+        a_off[q] = (unsigned)((cn * a.H + py) * a.W + px) * (unsigned)a.ldx * (unsigned)sizeof(T) + chunk;
+        a_msk[q] = (live && r < a.npix && (BM % RP == 0 || sr + q * RP < BM)) ? conv_tap_mask<KS>(px, py, a.W, a.H) : 0u;
+        cx += a.pool ? RP / 4 : RP;
+        while (cx >= Wu) { cx -= Wu; if (++cy >= Hu) { cy = 0; ++cn; } }
+    }
+}
+
+// b_off = byte offset of the filter tile's weight rows (+ chunk); rows past Cout or the tile: a.wbytes, which reads as zero
+template <typename T, int BN, int RP, int PB>
+__device__ __forceinline__ void conv_stage_filters(const ConvK &a, bool live, int n0, int sr, unsigned chunk, unsigned (&b_off)[PB])
+{
+#pragma unroll
+    for (int q = 0; q < PB; ++q) {
+        const unsigned co = (unsigned)(n0 + sr + q * RP);
+        b_off[q] = (live && co < (unsigned)a.Cout && (BN % RP == 0 || sr + q * RP < BN)) ? co * (unsigned)a.K * (unsigned)sizeof(T) + chunk : a.wbytes;
+    }
+}
+
+// Register-staged kernels: fetch slice (tap, c0) into ra / rb and move on to the next slice; padding taps and rows past
+// the end are out-of-range buffer loads (zeros, no memory traffic) -- cheaper than a branch, which would split the
+// scheduling region.
+template <typename T, int KS, int BK, int PA, int PB>
+__device__ __forceinline__ void conv_load_slice(const ConvK &a, __amdgpu_buffer_rsrc_t xr, __amdgpu_buffer_rsrc_t wr, int &tap, int &c0,
+                                                const unsigned (&a_off)[PA], const unsigned (&a_msk)[PA], const unsigned (&b_off)[PB],
+                                                f32x4 (&ra)[PA], f32x4 (&rb)[PB])
+{
+    const unsigned add = conv_slice_a<KS, (int)sizeof(T)>(tap, c0, a.W, a.ldx);
+#pragma unroll
+    for (int q = 0; q < PA; ++q) {
+        const bool ok = (a_msk[q] >> tap) & 1u;
+        const unsigned off = ok ? a_off[q] + add : a.xbytes;
+        ra[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, off, 0, 0));
+    }
+    const unsigned kadd = conv_slice_b<(int)sizeof(T)>(tap, c0, a.Cin);
+#pragma unroll
+    for (int q = 0; q < PB; ++q) {
+        const unsigned off = (b_off[q] == a.wbytes) ? a.wbytes : b_off[q] + kadd;
+        rb[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wr, off, 0, 0));
+    }
+    conv_slice_next<KS, BK>(tap, c0);
+}
+
+// ... and write it to the LDS buffer at As: [BM + BN rows][LS elements], this thread's chunk sc of rows sr + q * RP
+template <typename T, int BM, int BN, int LS, int RP, int PA, int PB>
+__device__ __forceinline__ void conv_store_slice(T *As, int sr, int sc, const f32x4 (&ra)[PA], const f32x4 (&rb)[PB])
+{
+    constexpr int CW = 16 / (int)sizeof(T);       // elements per 16-byte chunk
+    T *Bs = As + BM * LS;
+#pragma unroll
+    for (int q = 0; q < PA; ++q)
+        if (BM % RP == 0 || sr + q * RP < BM) *(f32x4 *)&As[(sr + q * RP) * LS + sc * CW] = ra[q];
+#pragma unroll
+    for (int q = 0; q < PB; ++q)
+        if (BN % RP == 0 || sr + q * RP < BN) *(f32x4 *)&Bs[(sr + q * RP) * LS + sc * CW] = rb[q];
 }
 
 // Which kernel runs a convolution and how it is launched: decided once per descriptor by conv_plan (y2_conv.hip), whose

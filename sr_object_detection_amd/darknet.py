@@ -367,6 +367,10 @@ def lib():
     L.y2h_hierarchy_rows.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                      C.c_void_p, C.c_void_p, C.c_void_p]
     L.y2h_p8_stream_k_plan.argtypes = [C.c_long, C.c_int, C.c_long, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    if hasattr(L, "y2h_sk_shares"):     # (an A/B library with an older revision's conv kernels, tools/build_variant.sh --src-rev, has none)
+        L.y2h_sk_shares.argtypes = [C.c_long, C.c_int, C.c_long, C.POINTER(C.c_int)]
+        L.y2h_sk_first.argtypes = [C.c_long, C.c_int, C.c_long, C.POINTER(C.c_int)]
+        L.y2h_sk_walk.argtypes = [C.c_long, C.c_int, C.c_long, C.POINTER(C.c_int), C.c_int]
     L.y2h_stream_k_launches.restype = C.c_ulong
     L.y2h_tail_launches.restype = C.c_ulong
     L.y2h_xcd_order_launches.restype = C.c_ulong
