@@ -211,6 +211,27 @@ int y2h_conv_forward(const y2h_conv *d, int strict, y2h_stream s);
 /* name of the kernel variant last chosen for this descriptor (for profiles) */
 const char *y2h_conv_variant(const y2h_conv *d, int strict);
 
+/* ---- Winograd F(2x2,3x3) for the fp32 stride-1 3x3 convolutions (the rule: include/y2_wino_rule.h) ---- */
+typedef struct y2h_wino {
+    int eligible;                /* the shape is one the three Winograd kernels take                       */
+    int take;                    /* the rule's answer (Y2_WINO=0: never, Y2_WINO=1: every eligible layer)   */
+    int bm, bn;                  /* tile of the batched GEMM                                               */
+    long tiles, tiles_pad;       /* 2x2 output patches per component, and padded to a multiple of bm       */
+    size_t u_bytes;              /* transformed filters U[16][n][c]                                        */
+    size_t v_bytes, m_bytes;     /* transformed input V[16][tiles_pad][c] and raw products M[16][tiles_pad][n] */
+    double direct_cost, gemm_cost, wino_cost;   /* CU cycles, as the tile cost model counts them           */
+} y2h_wino;
+/* Host arithmetic only (no GPU).  Leaves what y2h_conv_variant / _candidates / _workspace_bytes / _uses_mfma answer alone. */
+int y2h_wino_plan(const y2h_conv *d, y2h_wino *out);
+/* bytes of scratch (V and M) y2h_conv_wino_forward needs in d->ws when the rule takes the descriptor, else 0 */
+size_t y2h_wino_workspace_bytes(const y2h_conv *d);
+/* The convolution as input transform -> batched GEMM -> output transform + epilogue.  d->w_packed holds U[16][n][c]
+ * (y2_wino_filter of every (filter, channel), component-major), d->ws at least y2h_wino_workspace_bytes(d).  Y2H_EINVAL
+ * unless y2h_wino_plan takes the descriptor. */
+int y2h_conv_wino_forward(const y2h_conv *d, y2h_stream s);
+/* number of such forwards issued by this process so far (tests) */
+unsigned long y2h_wino_launches(void);
+
 /* ---- other layers (NHWC) ---- */
 int y2h_maxpool(const float *x, int ldx, float *y, int ldy, int batch, int h, int w, int c,
                 int size, int stride, int pad, int out_h, int out_w, y2h_stream s);

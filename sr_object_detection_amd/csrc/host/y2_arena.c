@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "y2_internal.h"
+#include "y2_wino_rule.h"
 
 /* the layer types that own arena space: layout, signature and packing all iterate with this */
 static int owns_arena(const layer *l)
@@ -87,7 +88,8 @@ void y2_arena_layout(network *net)
             d->off_bias = off; off = align_up(off + (size_t)l->outputs * sizeof(float), 64);
             continue;
         }
-        d->off_w_packed = off; off = align_up(off + (w_half ? wbytes / 2 : wbytes), 256);
+        /* a Winograd layer keeps U[16][n][c] = G g G^T in place of its nine packed taps */
+        d->off_w_packed = off; off = align_up(off + (d->wino ? (size_t)16 * l->n * l->c * sizeof(float) : w_half ? wbytes / 2 : wbytes), 256);
         if (d->has_w_ref) { d->off_w_ref = off; off = align_up(off + wbytes, 256); }
         d->off_bias = off; off = align_up(off + l->n * sizeof(float), 64);
         if (w_half) {
@@ -118,6 +120,7 @@ static uint64_t arena_signature(const network *net)
         SIG_MIX(i); SIG_MIX(d->off_w_packed); SIG_MIX(d->has_w_ref ? d->off_w_ref + 1 : 0); SIG_MIX(d->off_bias);
         SIG_MIX(d->uses_mfma); SIG_MIX(y2_half_weights(net, i));
         SIG_MIX(l->batch_normalize ? d->off_rinv + 1 : 0);
+        if (d->wino) SIG_MIX(0x57494e4f);      /* the filter slot holds U, not the packed taps (mixed only where it does) */
     }
     SIG_MIX(e->strict); SIG_MIX(e->half); SIG_MIX(e->arena_need);
 #undef SIG_MIX
@@ -211,6 +214,21 @@ static void pack_filters(float *wp, const network *net, int i, int w_half)
     }
 }
 
+/* the filters of a Winograd layer: U[g][n][c] = component g of G g G^T of filter n, channel c (y2_wino_filter: evaluated
+ * in double, rounded once), each component in the [n][c] layout the 1x1 matrix-core tiles read.  Reference layout
+ * [n][c][3][3] (im2col.c:24-27). */
+static void pack_wino(float *up, const layer *l)
+{
+    const size_t comp = (size_t)l->n * l->c;
+    int co, ci, g;
+    for (co = 0; co < l->n; ++co)
+        for (ci = 0; ci < l->c; ++ci) {
+            float u[16];
+            y2_wino_filter(l->weights + ((size_t)co * l->c + ci) * 9, u);
+            for (g = 0; g < 16; ++g) up[g * comp + (size_t)co * l->c + ci] = u[g];
+        }
+}
+
 /* a [convolutional] or [connected] layer: filters, the reference-layout copy where the layer needs one, constants */
 static void pack_dense(unsigned char *host, const network *net, int i)
 {
@@ -218,7 +236,8 @@ static void pack_dense(unsigned char *host, const network *net, int i)
     const y2_ldev *d = ld_of(l);
     const int K = l->size * l->size * l->c, w_half = y2_half_weights(net, i);
     int co, f, q;
-    pack_filters((float *)(host + d->off_w_packed), net, i, w_half);
+    if (d->wino) pack_wino((float *)(host + d->off_w_packed), l);
+    else pack_filters((float *)(host + d->off_w_packed), net, i, w_half);
     if (w_half) {
         /* folded batch-norm for the fp16 kernels: y = act(acc*alpha + beta), constants evaluated in double */
         float *al = (float *)(host + d->off_alpha), *be = (float *)(host + d->off_beta);

@@ -23,7 +23,8 @@ typedef struct y2_ldev {
     size_t off_w_packed, off_w_ref, off_bias, off_mean, off_scale, off_rinv;
     int has_w_ref;
     int uses_mfma;
-    int fused_pool;            /* conv: the following 2x2/2 maxpool runs in this conv's epilogue */
+    int wino;                  /* conv: runs as Winograd F(2x2,3x3) (y2_plan.c plan_wino); off_w_packed then holds U[16][n][c] */
+    int fused_pool;           /* conv: the following 2x2/2 maxpool runs in this conv's epilogue */
     int fused_into;            /* maxpool: index of the conv that computes it, or -1 */
     int out_half;              /* this layer's activations are IEEE half (fp16 mode), out_ld counts halves */
     size_t off_alpha, off_beta; /* fp16 mode: folded batch-norm, y = act(acc*alpha + beta) */

@@ -42,6 +42,10 @@
 //    Strides are free (the GEMM rows enumerate the output grid; taps are centred on input (oy*s, ox*s)); sizes 1, 3
 //    and 5 are instantiated (one tap-validity mask bit per tap, pad = size/2).
 //
+//    The 1x1 tiles 192x256 and 128x128 also exist in a WG form: the batched GEMM of the Winograd F(2x2,3x3) path that the deep
+//    stride-1 3x3 layers take by the rule of include/y2_wino_rule.h (y2h_wino_plan / y2h_conv_wino_forward below; the two
+//    transform passes around it: y2_wino.hip).
+//
 //  * conv_direct_kernel -- plain VALU kernel for shapes the MFMA kernels do
 //    not take (Cin not a multiple of 16 behind the first layer, even sizes) and for the strict mode:
 //    it accumulates in the reference's exact order (ci, kh, kw ascending;
@@ -61,9 +65,13 @@
 // MFMA implicit GEMM
 // ---------------------------------------------------------------------------
 __device__ int g_skh_timeouts = 0;     // hybrid stream-K: flag waits that gave up (a bug or a lost workgroup; results of that launch are wrong)
-template <int BM, int BN, int BK, int KS, int WM, int WN, bool XO = false, int SKMODE = 0>
+template <int BM, int BN, int BK, int KS, int WM, int WN, bool XO = false, int SKMODE = 0, bool WG = false>
 __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
 {
+    // WG (the batched GEMM of the Winograd path, 1x1 tiles only): the GEMM rows are sixteen components of a.tiles_m pixel tiles
+    // each, component g multiplies by the weight block g (a.Cout rows of a.K), and the sums leave raw: no batch-norm, bias or
+    // activation, 16-byte stores.  A template parameter like XO: every other instantiation compiles to what it was.
+    static_assert(!WG || (KS == 1 && !XO && SKMODE == 0), "the Winograd GEMM is a plain 1x1 tile walk");
     constexpr bool SKM = SKMODE == 1;     // stream-K over ALL tiles, pieces finished by sk_reduce_kernel (grids smaller than the machine)
     constexpr bool SKH = SKMODE == 2;     // hybrid: whole tiles + the last partial round cut along K, finished inside this launch
     constexpr int NT = WM * WN * 64;
@@ -173,6 +181,7 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
         const unsigned co = (unsigned)(n0 + sr + q * RP);
         // rows past Cout (or past the tile) land beyond wbytes and read as zero
         b_off[q] = (live && co < (unsigned)a.Cout && sr + q * RP < BN) ? (co * (unsigned)a.K + (unsigned)sc * 4u) * 4u : a.wbytes;
+        if constexpr (WG) { if (b_off[q] != a.wbytes) b_off[q] += (unsigned)((tile / a.tiles_n) / a.tiles_m) * (unsigned)a.Cout * (unsigned)a.K * 4u; }
     }
     };
 
@@ -417,8 +426,8 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
     auto epilogue_pass = [&](auto MODEC, auto VSTC) {
         constexpr int MODE = decltype(MODEC)::value;
         constexpr bool VS = decltype(VSTC)::value;            // 16-byte stores through the LDS transpose        // 0 run-time bn / act, 1 batch-norm + leaky, 2 batch-norm + linear
-        const bool BN_ = MODE ? true : (bool)a.bn;
-        const int ACT_ = MODE == 1 ? (int)Y2H_ACT_LEAKY : MODE == 2 ? (int)Y2H_ACT_LINEAR : a.act;
+        const bool BN_ = MODE == 3 ? false : MODE ? true : (bool)a.bn;        // 3 (WG): the raw sums, x + 0
+        const int ACT_ = MODE == 1 ? (int)Y2H_ACT_LEAKY : (MODE == 2 || MODE == 3) ? (int)Y2H_ACT_LINEAR : a.act;
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             const int co = n0 + wn * (BN / WN) + j * 32 + li;
@@ -426,7 +435,7 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
             float mean = 0.f, scale = 1.f, bias = 0.f;
             double rinv = 1.0;
             if (cok) {
-                bias = a.bias[co];
+                if (MODE != 3) bias = a.bias[co];
                 if (BN_) { mean = a.mean[co]; rinv = a.rinv[co]; scale = a.scale[co]; }
             }
 #pragma unroll
@@ -600,6 +609,13 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
             F32_STAMP(6);
         }
     }
+    if constexpr (WG) {
+        epilogue_pass(std::integral_constant<int, 3>{}, std::true_type{});
+        if (!ES_OWN) {
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+        }
+    } else
     if (SKM || (a.ksplit > 1 && (a.Cout & 3) == 0)) {
         partial_pass();
         if (!ES_OWN) {
@@ -1268,6 +1284,7 @@ struct Variant {
     void (*fn_xo)(ConvK);  // the same tile with the XCD-grouped tile order (ConvK.xcd_order), where instantiated
     void (*fn_sk)(ConvK);  // the same tile with stream-K work items (ConvK.sk_tiles / sk_wgs), where instantiated
     void (*fn_skh)(ConvK); // the same tile, hybrid: whole tiles + the last partial round as stream-K pieces finished in the launch
+    void (*fn_wg)(ConvK);  // the same tile as the batched GEMM of the Winograd path (1x1 tiles the rule may pick)
 };
 
 #define VAR(BM, BN, BK, KS, WM, WN)                                                             \
@@ -1282,14 +1299,19 @@ struct Variant {
       (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float) + (WM * WN == 8 ? (size_t)8 * 16 * 36 * sizeof(float) : 0), WM * WN * 64, \
       conv_mfma_kernel<BM, BN, BK, KS, WM, WN, true>, nullptr, nullptr }
 
+#define VARWG(BM, BN, BK, KS, WM, WN)                                                           \
+    { "conv_mfma_f32_" #BM "x" #BN "x" #BK "_k" #KS, BM, BN, BK, KS, conv_mfma_kernel<BM, BN, BK, KS, WM, WN>, \
+      (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float) + (WM * WN == 8 ? (size_t)8 * 16 * 36 * sizeof(float) : 0), WM * WN * 64, \
+      conv_mfma_kernel<BM, BN, BK, KS, WM, WN, true>, nullptr, nullptr, conv_mfma_kernel<BM, BN, BK, KS, WM, WN, false, 0, true> }
+
 static Variant g_variants[] = {
     // 8 waves (2 per SIMD), ONE workgroup per CU: the co-resident partner wave that hides LDS/barrier
     // stalls comes from the same workgroup, so a CU never ends up with a lone half-speed pair in the tail
-    VARSK(192, 256, 32, 3, 2, 4), VARXO(192, 256, 32, 1, 2, 4),
+    VARSK(192, 256, 32, 3, 2, 4), VARWG(192, 256, 32, 1, 2, 4),
     VAR(256, 128, 32, 3, 4, 2), VAR(256, 128, 32, 1, 4, 2),
     VAR(256, 64, 32, 3, 8, 1),  VAR(256, 64, 32, 1, 8, 1),
     // 4 waves, two workgroups per CU
-    VARSK(128, 128, 32, 3, 2, 2), VARXO(128, 128, 32, 1, 2, 2),
+    VARSK(128, 128, 32, 3, 2, 2), VARWG(128, 128, 32, 1, 2, 2),
     VAR(128, 64, 32, 3, 2, 2),  VAR(128, 64, 32, 1, 2, 2),
     VAR(64, 64, 32, 3, 2, 2),   VARXO(64, 64, 32, 1, 2, 2),
     VAR(128, 32, 32, 3, 4, 1),  VAR(128, 32, 32, 1, 4, 1),
@@ -1436,8 +1458,31 @@ static size_t skh_ws_bytes(const Variant &v)
     return wgs * v.bm * v.bn * sizeof(float) + wgs * sizeof(int);
 }
 
-// Fills p.v / p.ksplit (the choice among whole-tile launches), p.sk_v / p.sk_wgs (stream-K), p.tile / p.tile_ksplit and
-// p.skh_tiles.  Env: Y2_SKF=0 no stream-K; Y2_SKF_WGS=n forces stream-K on n workgroups for the (forced) tile.
+// measured in-tile efficiency relative to the 192x256 tile (yolo.cfg 608x608 b32 sweep,
+// profiles/r01_tile_sweep.txt): bigger wave tiles re-read less LDS per MFMA; the small
+// 64x64 tile wins on short-K 1x1 layers, where prologue/epilogue dominate and four
+// co-resident workgroups overlap them
+static double variant_eff(const Variant &v, int size)
+{
+    double eff = 0.6;
+    if (v.bm == 192 && v.bn == 256) eff = 1.0;
+    else if (v.bm == 128 && v.bn == 128) eff = 0.96;
+    else if (v.bm == 256 && v.bn == 128) eff = 0.945;
+    else if (v.bm == 64 && v.bn == 64) eff = (size == 1) ? 1.0 : 0.90;
+    else if (v.bm == 128 && v.bn == 64) eff = size == 3 ? 0.92 : 0.86;     // r3: 0.94-0.95 against the 64x64 tile's 0.90 on grids of 3-5 tiles per CU (52x52 / 68x68 128->256 at batch 8)
+    else if (v.bm == 256 && v.bn == 64) eff = 0.82;
+    else if (v.bm == 128 && v.bn == 32) eff = (size == 1) ? 0.95 : 0.7;
+    return eff;
+}
+// in CU cycles: one K-step of a tile = bm*bn*bk*2 flop at 256 flop/clk; ~5 K-steps of fixed cost
+// per work item (measured).  per_cu = work items of the busiest CU, ksteps = K-steps per work item.
+static double whole_tile_cost(const Variant &v, long per_cu, double ksteps, double eff)
+{
+    return (double)per_cu * v.bm * v.bn * v.bk / 128.0 * (ksteps + 5.0) / eff;
+}
+
+// Fills p.v / p.ksplit (the choice among whole-tile launches), p.sk_v / p.sk_wgs (stream-K), p.tile / p.tile_ksplit,
+// p.skh_tiles and p.cost (the chosen plan's modelled CU cycles: what the Winograd rule compares with).  Env: Y2_SKF=0 no stream-K; Y2_SKF_WGS=n forces stream-K on n workgroups for the (forced) tile.
 static bool pick_variant(const y2h_conv *d, ConvPlan &p)
 {
     const int bk = (d->c % 32 == 0) ? 32 : 16;
@@ -1477,21 +1522,9 @@ static bool pick_variant(const y2h_conv *d, ConvPlan &p)
         // tail in whole groups of bpc: that over-charged the small tiles on grids of 1.3-2.6 rounds -- autotune logs of yolo 416
         // b8 / yolo9000 544 b8, profiles/r03_notes.md section 11.)
         const long per_cu = (blocks + CUS - 1) / CUS;
-        // measured in-tile efficiency relative to the 192x256 tile (yolo.cfg 608x608 b32 sweep,
-        // profiles/r01_tile_sweep.txt): bigger wave tiles re-read less LDS per MFMA; the small
-        // 64x64 tile wins on short-K 1x1 layers, where prologue/epilogue dominate and four
-        // co-resident workgroups overlap them
-        double eff = 0.6;
-        if (v.bm == 192 && v.bn == 256) eff = 1.0;
-        else if (v.bm == 128 && v.bn == 128) eff = 0.96;
-        else if (v.bm == 256 && v.bn == 128) eff = 0.945;
-        else if (v.bm == 64 && v.bn == 64) eff = (d->size == 1) ? 1.0 : 0.90;
-        else if (v.bm == 128 && v.bn == 64) eff = d->size == 3 ? 0.92 : 0.86;     // r3: 0.94-0.95 against the 64x64 tile's 0.90 on grids of 3-5 tiles per CU (52x52 / 68x68 128->256 at batch 8)
-        else if (v.bm == 256 && v.bn == 64) eff = 0.82;
-        else if (v.bm == 128 && v.bn == 32) eff = (d->size == 1) ? 0.95 : 0.7;
-        // in CU cycles: one K-step of a tile = bm*bn*bk*2 flop at 256 flop/clk; ~5 K-steps of fixed cost
-        // per work item (measured); a split pays the workspace round trip (~4 TB/s) and a launch
-        double cost = (double)per_cu * v.bm * v.bn * v.bk / 128.0 * ((double)nk / ksplit + 5.0) / eff;
+        // a split pays the workspace round trip (~4 TB/s) and a launch
+        const double eff = variant_eff(v, d->size);
+        double cost = whole_tile_cost(v, per_cu, (double)nk / ksplit, eff);
         if (ksplit > 1) cost += (double)npix * d->n * 4.0 * (ksplit + 1) * 5.75e-4 + 5000.0;
         if (!plain || cost < plain_cost * 0.999 || (cost <= plain_cost * 1.001 && v.bm * v.bn > plain->bm * plain->bn)) {
             plain = &v;
@@ -1533,6 +1566,7 @@ static bool pick_variant(const y2h_conv *d, ConvPlan &p)
     p.sk_wgs = best_sk;
     p.tile = best_sk ? plain : best;
     p.tile_ksplit = best_sk ? plain_split : best_split;
+    p.cost = best_cost;
     if (best->fn_skh && best_sk == 0 && best_split == 1 && !getenv("Y2_CONV_GRID")) {
         const long tiles = ((npix + best->bm - 1) / best->bm) * ((d->n + best->bn - 1) / best->bn);
         p.skh_tiles = skh_plan(tiles, nk, skh_slots(*best), best->bm, best->bn, best->bk, variant_bpc(*best));
@@ -1740,6 +1774,70 @@ extern "C" int y2h_conv_uses_mfma(const y2h_conv *d)
 extern "C" const char *y2h_conv_variant(const y2h_conv *d, int strict) { return conv_plan(d, strict).name; }
 
 // ---------------------------------------------------------------------------
+// Winograd F(2x2,3x3): the rule of include/y2_wino_rule.h put together with the tile table and the direct plan's cost.
+// The batched GEMM is 16 components x tiles_pad rows x n filters over K = c on the 1x1 tiles instantiated with the WG flag;
+// its cost is the whole-tile formula of pick_variant on that grid.  Y2_WINO=0: never; Y2_WINO=1: every eligible layer
+// (tests); Y2_CONV_TILE forces the GEMM's tile like the direct kernel's (a shape without a WG form: not eligible).
+// By the rule alone a layer is taken only when its direct plan walks whole tiles (no split-K, no stream-K) and the batched
+// GEMM gives every CU a tile: on grids smaller than the machine the cost model is off by 10-40 % of a layer (the reason
+// y2_set_autotune exists), more than the margin the comparison is decided by.
+// ---------------------------------------------------------------------------
+static Variant *wino_variant(int bm, int bn)
+{
+    for (Variant &v : g_variants) if (v.fn_wg && v.bm == bm && v.bn == bn) return &v;
+    return nullptr;
+}
+
+extern "C" int y2h_wino_plan(const y2h_conv *d, y2h_wino *out)
+{
+    if (!d || !out) return Y2H_EINVAL;
+    memset(out, 0, sizeof *out);
+    int mode = -1;
+    if (const char *f = getenv("Y2_WINO")) mode = atoi(f) != 0 ? 1 : 0;
+    if (!y2_wino_shape_ok(d->size, d->stride, d->pad, d->c, d->n, d->h, d->w, d->out_h, d->out_w, d->fuse_maxpool2, d->x_f16, d->y_f16,
+                          d->x_halo, d->x_nchw, d->ldx)) return Y2H_OK;
+    const ConvPlan p = conv_plan(d, 0);
+    if (p.kind != CK_MFMA_F32) return Y2H_OK;
+    int force_bm = 0, force_bn = 0;
+    if (const char *f = getenv("Y2_CONV_TILE")) sscanf(f, "%dx%d", &force_bm, &force_bn);
+    const long tiles = y2_wino_tiles(d->batch, d->h, d->w);
+    const int nk = d->c / 32;
+    const Variant *best = nullptr;
+    double best_cost = 0, best_gemm = 0;
+    long best_blocks = 0;
+    for (Variant &v : g_variants) {
+        if (!v.fn_wg || v.bk != 32 || v.ks != 1) continue;
+        if (force_bm && (v.bm != force_bm || v.bn != force_bn)) continue;
+        const long tp = y2_wino_tiles_pad(tiles, v.bm);
+        const long blocks = 16 * (tp / v.bm) * ((d->n + v.bn - 1) / v.bn);
+        const double gemm = whole_tile_cost(v, (blocks + 255) / 256, (double)nk, variant_eff(v, 1));
+        const double cost = y2_wino_cost(gemm, y2_wino_transform_bytes(d->batch, d->h, d->w, d->c, d->n, d->fuse_maxpool2, tp));
+        if (!best || cost < best_cost * 0.999 || (cost <= best_cost * 1.001 && v.bm * v.bn > best->bm * best->bn)) {
+            best = &v; best_cost = cost; best_gemm = gemm; best_blocks = blocks;
+        }
+    }
+    if (!best) return Y2H_OK;
+    const long tp = y2_wino_tiles_pad(tiles, best->bm);
+    const double vb = 16.0 * (double)tp * d->c * 4.0, mb = 16.0 * (double)tp * d->n * 4.0, ub = 16.0 * (double)d->n * d->c * 4.0;
+    if (vb >= 4294967000.0 || mb >= 4294967000.0 || ub >= 4294967000.0) return Y2H_OK;        // 32-bit buffer offsets
+    out->eligible = 1;
+    out->bm = best->bm; out->bn = best->bn;
+    out->tiles = tiles; out->tiles_pad = tp;
+    out->u_bytes = (size_t)ub; out->v_bytes = (size_t)vb; out->m_bytes = (size_t)mb;
+    out->direct_cost = p.cost; out->gemm_cost = best_gemm; out->wino_cost = best_cost;
+    if (mode >= 0) out->take = mode;
+    else out->take = p.sk_wgs == 0 && p.tile_ksplit == 1 && best_blocks >= 256 && y2_wino_wins(p.cost, best_cost);
+    return Y2H_OK;
+}
+
+extern "C" size_t y2h_wino_workspace_bytes(const y2h_conv *d)
+{
+    y2h_wino w;
+    if (y2h_wino_plan(d, &w) != Y2H_OK || !w.take) return 0;
+    return w.v_bytes + w.m_bytes;
+}
+
+// ---------------------------------------------------------------------------
 // launch routines, one per kind of the fp32 side (the fp16 side: y2_f16_launch)
 // ---------------------------------------------------------------------------
 // first-layer kernel: the input with a one-pixel halo, or the NCHW planes of the network input (x_nchw)
@@ -1908,6 +2006,52 @@ extern "C" int y2h_conv_forward(const y2h_conv *d, int strict, y2h_stream s)
     case CK_DIRECT: return direct_launch(d, a, s);
     default: return y2_f16_launch(p, d, a, s);
     }
+}
+
+// The same convolution through F(2x2,3x3): V = B^T d B (y2_wino.hip), M[g] = V[g] U[g]^T for the sixteen components in ONE
+// launch of the 1x1 tile's WG form (GEMM rows = 16 x tiles_pad "pixels" of a 1-row image, raw sums), y = epilogue(A^T M A).
+static unsigned long g_wino_launches = 0;
+extern "C" unsigned long y2h_wino_launches(void) { return g_wino_launches; }
+
+extern "C" int y2h_conv_wino_forward(const y2h_conv *d, y2h_stream s)
+{
+    if (!d || !d->x || !d->y || !d->bias || !d->w_packed) return Y2H_EINVAL;
+    if (d->batch <= 0 || d->h <= 0 || d->w <= 0 || d->c <= 0 || d->n <= 0 || d->ldx < d->c || d->ldy < d->n) return Y2H_EINVAL;
+    if (d->batch_normalize && (!d->mean || !d->rinv || !d->scale)) return Y2H_EINVAL;
+    y2h_wino w;
+    if (y2h_wino_plan(d, &w) != Y2H_OK || !w.take) return Y2H_EINVAL;
+    if (!d->ws || d->ws_bytes < w.v_bytes + w.m_bytes || ((uintptr_t)d->ws % 16) != 0) return Y2H_EINVAL;
+    const Variant *v = wino_variant(w.bm, w.bn);
+    if (!v) return Y2H_EINVAL;
+    float *V = d->ws, *M = d->ws + w.v_bytes / sizeof(float);
+    int rc = y2_wino_input_launch(d, V, w.tiles, w.tiles_pad, s);
+    if (rc != Y2H_OK) return rc;
+
+    ConvK a;
+    memset(&a, 0, sizeof a);
+    a.x = V; a.w = d->w_packed; a.y = M;
+    a.npix = (int)(16 * w.tiles_pad);
+    a.H = 1; a.W = a.npix; a.out_h = 1; a.out_w = a.npix; a.batch = 1;
+    a.Cin = d->c; a.ldx = d->c; a.Cout = d->n; a.ldy = d->n; a.K = d->c;
+    a.size = 1; a.stride = 1;
+    a.act = Y2H_ACT_LINEAR;
+    a.xbytes = (unsigned)w.v_bytes; a.wbytes = (unsigned)w.u_bytes; a.ybytes = (unsigned)w.m_bytes;
+    a.vec_store = 1;
+    a.ksplit = 1;
+    a.tiles_n = (d->n + v->bn - 1) / v->bn;
+    a.tiles_m = (int)(w.tiles_pad / v->bm);                 // pixel tiles per component
+    a.ntiles = 16 * a.tiles_m * a.tiles_n;
+    long grid = 256L * variant_bpc(*v);
+    if (const char *g = getenv("Y2_CONV_GRID")) { if (atol(g) > 0 && atol(g) < grid) grid = atol(g); }
+    if (grid > a.ntiles) grid = a.ntiles;
+    Y2H_CHECK(y2h_lds_limit((const void *)v->fn_wg, v->lds));
+    hipLaunchKernelGGL(v->fn_wg, dim3((unsigned)grid), dim3(v->threads), v->lds, S(s), a);
+    Y2H_LAUNCH_CHECK();
+
+    rc = y2_wino_output_launch(d, M, w.tiles, w.tiles_pad, s);
+    if (rc != Y2H_OK) return rc;
+    ++g_wino_launches;
+    return Y2H_OK;
 }
 
 // ---------------------------------------------------------------------------

@@ -2,6 +2,7 @@
 #pragma once
 #include "y2_common.hpp"
 #include "y2_streamk_rule.h"
+#include "y2_wino_rule.h"
 #include <stdlib.h>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -259,6 +260,7 @@ struct ConvPlan {
     int tile_ksplit, skh_tiles;
     long grid;
     int xcd_order, tiles_m, pblk;
+    double cost;                   // modelled CU cycles of the choice (pick_variant): the Winograd rule's "direct" side
     // fp16 matrix-core kernel (nullptr: no tile fits the descriptor -- the launch fails)
     VariantH *vh;
     long h_ntiles, h_grid;
@@ -271,6 +273,11 @@ bool y2_f16_plan(const y2h_conv *d, ConvPlan &p);
 int y2_f16_launch(const ConvPlan &p, const y2h_conv *d, ConvK &a, y2h_stream s);
 bool y2_f16_first_ok(const y2h_conv *d);
 bool y2_f16_first_nchw_ok(const y2h_conv *d);
+
+// Winograd F(2x2,3x3) transforms (y2_wino.hip), the passes in front of and behind the batched GEMM of y2h_conv_wino_forward:
+// V[16][tiles_pad][c] from the NHWC input of d; the layer's output from M[16][tiles_pad][n] through the shared epilogue.
+int y2_wino_input_launch(const y2h_conv *d, float *V, long tiles, long tiles_pad, y2h_stream s);
+int y2_wino_output_launch(const y2h_conv *d, const float *M, long tiles, long tiles_pad, y2h_stream s);
 
 // Grid of a kernel that walks its tiles with a grid stride: exactly what is co-resident (256 CUs x the runtime's answer for
 // this kernel), no more -- a surplus block only starts when a resident one has finished ALL its tiles, i.e. runs a second,

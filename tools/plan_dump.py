@@ -4,7 +4,8 @@ batch, what pick_variant (y2_conv.hip, host arithmetic only) would launch -- ker
 check that a change of the cost model leaves the plan of the headline configuration alone.
     tools/plan_dump.py yolo 608 32 [yolo 416 8 ...]
     tools/plan_dump.py --sweep       every dispatch query for every zoo network, a digest per configuration (tests/golden/conv_plan_table.txt)
-    tools/plan_dump.py --sweep-rows  the same queries, one line per conv layer: diff two builds' output (Y2_LIB) to see what moved"""
+    tools/plan_dump.py --sweep-rows  the same queries, one line per conv layer: diff two builds' output (Y2_LIB) to see what moved
+    tools/plan_dump.py --wino        the Winograd rule's answer for every 3x3 layer of every zoo network (tests/golden/wino_plan_table.txt)"""
 import ctypes as C
 import os
 import sys
@@ -119,6 +120,49 @@ def sweep(lib, rows):
         del os.environ[k]
 
 
+class Wino(C.Structure):          # include/y2_hip.h: y2h_wino
+    _fields_ = [("eligible", C.c_int), ("take", C.c_int), ("bm", C.c_int), ("bn", C.c_int), ("tiles", C.c_long), ("tiles_pad", C.c_long),
+                ("u_bytes", C.c_size_t), ("v_bytes", C.c_size_t), ("m_bytes", C.c_size_t),
+                ("direct_cost", C.c_double), ("gemm_cost", C.c_double), ("wino_cost", C.c_double)]
+
+
+def wino_plan(lib, f):
+    """y2h_wino_plan for one descriptor (a dict of y2h_conv fields)"""
+    d, w = Conv(**f), Wino()
+    assert lib.y2h_wino_plan(C.byref(d), C.byref(w)) == 0
+    return w
+
+
+def wino_cases():
+    """every zoo network at its default size (the full-size detectors at 416 and 608 too), batch 1, 8, 32 and 128"""
+    for net in zoo.SPECS:
+        sizes = [zoo.DEFAULT_SIZE[net]]
+        if sizes[0] >= 416 and any(l["type"] == "region" for l in zoo.resolve(net, sizes[0])):
+            sizes += [s for s in (416, 608) if s not in sizes]
+        for s in sizes:
+            for b in (1, 8, 32, 128):
+                yield net, s, b
+
+
+def wino_rows(lib):
+    """The Winograd rule's answer (include/y2_wino_rule.h through y2h_wino_plan) for every 3x3 conv layer of every zoo
+    network: tests/golden/wino_plan_table.txt.  Costs in thousands of CU cycles."""
+    for k in [k for k in os.environ if k.startswith("Y2_")]:
+        del os.environ[k]
+    yield "# net size batch layer | h w c n pool | fp32: eligible take tile tiles_pad direct gemm wino (kcycles) | fp16: eligible take"
+    for net, size, batch in wino_cases():
+        rows = {}
+        for half in (0, 1):
+            for i, f in _descs(net, size, batch, half, ALIGNED):
+                if f["size"] != 3 or f.get("x_halo") or f.get("x_nchw"):
+                    continue
+                rows.setdefault(i, (f, []))[1].append(wino_plan(lib, f))
+        for i, (f, (w, wh)) in sorted(rows.items()):
+            yield "%s %d b%d L%d | %d %d %d %d %d | %d %d %dx%d %d %.0f %.0f %.0f | %d %d" % (
+                net, size, batch, i, f["h"], f["w"], f["c"], f["n"], f["fuse_maxpool2"], w.eligible, w.take, w.bm, w.bn, w.tiles_pad,
+                w.direct_cost / 1e3, w.gemm_cost / 1e3, w.wino_cost / 1e3, wh.eligible, wh.take)
+
+
 def main():
     lib = C.CDLL(os.environ.get("Y2_LIB") or os.path.join(ROOT, "sr_object_detection_amd", "libsr_yolo2.so"))
     lib.y2h_conv_variant.restype = C.c_char_p
@@ -127,6 +171,8 @@ def main():
     args = sys.argv[1:]
     if args in (["--sweep"], ["--sweep-rows"]):
         return sweep(lib, args == ["--sweep-rows"])
+    if args == ["--wino"]:
+        return print("\n".join(wino_rows(lib)))
     for k in range(0, len(args), 3):
         net, size, batch = args[k], int(args[k + 1]), int(args[k + 2])
         layers = zoo.resolve(net, size)
