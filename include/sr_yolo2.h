@@ -122,7 +122,7 @@ struct layer {
     float *biases, *scales, *weights;     /* host copies, reference layouts ([n][c][k][k]) */
     float *rolling_mean, *rolling_variance;
     float *output;                        /* host; non-NULL only for the network's output layer */
-    float *delta;                         /* always NULL (no training) */
+    float *delta;                         /* always NULL (the trainer's deltas live in HBM: y2_train_pull) */
     float *cost;
     size_t workspace_size;                /* the reference's im2col bytes (convolutional_layer.c:135); informational */
     void *dev;                            /* opaque device-side state */
@@ -639,6 +639,53 @@ int y2_depth_set_grasp_filter(network net, int on);
 int y2_plane_samples(const uint16_t *depth, int dh, int dw, float far_m, int iters, unsigned seed, int *triples);
 int y2_plane_from_points(const float *p0, const float *p1, const float *p2, float *plane);
 int y2_plane_fit(const double *sums, double *plane);
+/* ------------------------------------------------------------------------- */
+/* Training on the device: the other half of network.c (train_network_datum     */
+/* :225-243 = forward with train = 1, backward_network, update_network), fp32,  */
+/* for convolutional classifiers.  The trainer owns its buffers (master         */
+/* weights, update buffers, per layer output / delta / x / x_norm / mean /      */
+/* variance); the inference plan is untouched, struct network and struct layer  */
+/* keep their layout and layer.delta stays NULL.                                */
+/* Trainable: [convolutional] (any size / pad, stride 1, batch_normalize 0 / 1, */
+/* linear / leaky / logistic / relu), [maxpool], [avgpool], [softmax] (groups   */
+/* 1, no tree), [cost] type=sse.  Refused by name before any device allocation, */
+/* layer number and type in y2_last_error(): every other section type, stride   */
+/* > 1, xnor, another activation, adam=1, policy=random, another cost type, a   */
+/* tree / groups > 1 softmax, fp16 mode, a recurrent network, a batch-normalised */
+/* layer with batch * out_h * out_w < 2 (the reference divides by zero).        */
+/* Every reduction has a fixed order: a step run twice from the same state      */
+/* gives the same bytes.                                                        */
+/* ------------------------------------------------------------------------- */
+/* network.c:225: *net.seen += net.batch; forward(train); backward; the loss; the update when
+ * (*net.seen / net.batch) % net.subdivisions == 0.  x: [batch][c][h][w], y: [batch][outputs], host memory.  Prepares
+ * lazily.  Returns the loss (get_network_cost), NAN after a failure. */
+float train_network_datum(network net, float *x, float *y);
+float get_current_rate(network net);             /* network.c:48: constant, step, steps, exp, poly (burn_in), sig */
+int get_current_batch(network net);              /* network.c:31 */
+float get_network_cost(network net);             /* network.c:183: mean of the [cost] layers' cost[0] */
+/* Builds the trainer from the host weights (load_weights, or whatever the layer arrays hold).  0 / -1. */
+int y2_train_prepare(network *net);
+int y2_train_step(network *net, const float *x, const float *y, float *loss);            /* what train_network_datum calls */
+int y2_train_step_device(network *net, const float *d_x, const float *d_y, float *loss); /* the inputs already in HBM */
+/* After a step the network is dirty: network_predict and every entry built on the forward pass, save_weights[_upto] and
+ * y2_weights_arena first bring the masters (weights, biases, scales, rolling statistics) down into the host layer arrays
+ * and re-pack the inference arena, so a caller that trains and then predicts or saves sees what it trained -- as with the
+ * reference (y2_weights_arena uploads the arena before it hands it out, so a launcher that copies it itself gets the trained
+ * weights).  y2_train_sync does that now.  A clean network does exactly what it did before.  set_batch_network,
+ * resize_network and y2_denormalize_network sync and then drop the trainer (y2_train_free): train, set_batch_network(&net, 1),
+ * predict keeps the steps, as with the reference.  load_weights and free_network drop it without a sync: the file's weights
+ * replace the trained ones.  denormalize_convolutional_layer, which sees one layer and not the network, refuses while a
+ * trainer exists. */
+int y2_train_sync(network *net);
+/* One array of layer `layer` as the reference holds it: activations as [batch][c][h][w], weights as [n][c][size][size]. */
+enum { Y2_TRAIN_OUTPUT = 0, Y2_TRAIN_DELTA, Y2_TRAIN_X, Y2_TRAIN_X_NORM, Y2_TRAIN_MEAN, Y2_TRAIN_VARIANCE, Y2_TRAIN_MEAN_DELTA,
+       Y2_TRAIN_VARIANCE_DELTA, Y2_TRAIN_WEIGHT_UPDATES, Y2_TRAIN_BIAS_UPDATES, Y2_TRAIN_SCALE_UPDATES, Y2_TRAIN_WEIGHTS,
+       Y2_TRAIN_BIASES, Y2_TRAIN_SCALES, Y2_TRAIN_ROLLING_MEAN, Y2_TRAIN_ROLLING_VARIANCE };
+int y2_train_pull(network *net, int layer, int what, float *dst, size_t n);
+void y2_train_free(network *net);
+/* The trainer's weight layout, [size][size][c][n], to and from the host's [n][c][size][size]: pure permutations. */
+void y2_train_pack_weights(const float *ref, float *packed, int n, int c, int size);
+void y2_train_unpack_weights(const float *packed, float *ref, int n, int c, int size);
 /* Copy layer i's activations to host as NCHW [batch][out_c][out_h][out_w] (or [batch][outputs]). */
 int y2_pull_layer_output(network net, int i, float *dst);
 /* Per-layer device time of the last forward in ms (needs y2_set_timing(net,1)); returns layers written. */

@@ -646,6 +646,60 @@ int y2h_rnn_feed(const int *tok, float *x, int rows, int inputs, y2h_stream s);
 int y2h_rnn_score(const float *out, int outputs, const int *next, int rows, float *p_next, float *probs, y2h_stream s);
 unsigned long y2h_rnn_sample_launches(void);     /* y2h_rnn_sample launches of this process */
 
+/* ---- training (y2_train.hip): the reference's forward(train) / backward / update loop nests, fp32 ----
+ * Activations and deltas are dense NHWC ([batch][h][w][c], no channel stride).  Trainer weights are [size][size][c][n]
+ * (row (ky*size + kx)*c + ci, column filter): a pure permutation of the host's [n][c][size][size].
+ * The three products of a stride-1 convolution run as one implicit-GEMM kernel on the fp32 matrix cores
+ * (v_mfma_f32_32x32x2_f32: exact fp32 products, fp32 sums), 64x64 output tiles, operands gathered straight from the NHWC
+ * tensors with guarded edges (any channel count, any image size, any size / pad):
+ *   forward   y[m][f]   = sum_k  x(m, k) * w[k][f]            m = (b, oy, ox), k = (ky, kx, ci)
+ *   dinput    dx[p][ci] = sum_r dy(p, r) * w[(ky, kx, ci)][f]  p = (b, iy, ix), r = (ky, kx, f)
+ *   dweight   dw[k][f] += sum_m  x(m, k) * dy[m][f]            the reduction over m is cut into y2h_train_dweight_splits
+ *             ranges, a function of the shape alone; every range writes its own partial tile into `ws`, and a second
+ *             launch adds the partials to dw in range order.  No atomics: two runs give the same bytes.
+ * Every other reduction (per-channel sums, the cost) uses a fixed split with a second pass or a fixed tree as well. */
+typedef struct { int batch, h, w, c, n, size, pad, out_h, out_w; } y2h_train_conv;
+int    y2h_train_conv_forward(const y2h_train_conv *g, const float *x, const float *w, float *y, y2h_stream s);
+int    y2h_train_conv_dinput(const y2h_train_conv *g, const float *dy, const float *w, float *dx, y2h_stream s);
+int    y2h_train_dweight_splits(const y2h_train_conv *g);
+size_t y2h_train_dweight_ws_bytes(const y2h_train_conv *g);
+int    y2h_train_conv_dweight(const y2h_train_conv *g, const float *x, const float *dy, float *dw, float *ws, y2h_stream s);
+/* per-channel sums over rows = batch * spatial pixels; `scratch` holds y2h_train_reduce_scratch_bytes(rows, c) bytes.
+ *   stats     batchnorm_layer.c:129-137: mean, variance (/(rows-1)), rolling = .9f * rolling + .1f * new  (two sweeps)
+ *   bias      backward_bias (+ backward_scale_cpu when x_norm != NULL): bias_updates += sum delta, scale_updates += sum delta*x_norm
+ *   bn_deltas scale_bias on delta, mean_delta_cpu and variance_delta_cpu in one sweep; delta itself is left unscaled:
+ *             y2h_train_bn_backward multiplies by the scale again while it applies normalize_delta_cpu */
+size_t y2h_train_reduce_scratch_bytes(long rows, int c);
+int y2h_train_bn_stats(const float *x, long rows, int c, float *mean, float *variance, float *rolling_mean,
+                       float *rolling_variance, float *scratch, y2h_stream s);
+int y2h_train_bias_grad(const float *delta, const float *x_norm, long rows, int c, float *bias_updates, float *scale_updates,
+                        float *scratch, y2h_stream s);
+int y2h_train_bn_deltas(const float *delta, const float *x, const float *scales, const float *mean, const float *variance,
+                        long rows, int c, float *mean_delta, float *variance_delta, float *scratch, y2h_stream s);
+int y2h_train_bn_backward(float *delta, const float *x, const float *scales, const float *mean, const float *variance,
+                          const float *mean_delta, const float *variance_delta, long rows, int c, y2h_stream s);
+/* y (the raw product, in place): with mean != NULL x = y, x_norm = (y - mean) / (sqrt(var) + 1e-6f), y = x_norm * scale;
+ * then y = act(y + bias) (convolutional_layer.c:466-472) */
+int y2h_train_bn_apply(float *y, float *x, float *x_norm, const float *mean, const float *variance, const float *scales,
+                       const float *biases, int act, long rows, int c, y2h_stream s);
+int y2h_train_act_gradient(const float *y, float *delta, int act, long n, y2h_stream s);   /* gradient_array */
+/* maxpool_layer.c:79-117: the first maximum in (row, column) scan order, strict >, padding reads as -FLT_MAX; idx holds
+ * iy * w + ix of the winner (-1: none).  Backward gathers, per input pixel, the windows that cover it in output order. */
+int y2h_train_maxpool_forward(const float *x, float *y, int *idx, int batch, int h, int w, int c, int size, int stride, int pad,
+                              int out_h, int out_w, y2h_stream s);
+int y2h_train_maxpool_backward(const float *dy, const int *idx, float *dx, int batch, int h, int w, int c, int size, int stride,
+                               int pad, int out_h, int out_w, y2h_stream s);
+int y2h_train_avgpool_forward(const float *x, float *y, int batch, int hw, int c, y2h_stream s);
+int y2h_train_avgpool_backward(const float *dy, float *dx, int batch, int hw, int c, y2h_stream s);
+int y2h_train_softmax(const float *x, float *y, int rows, int n, float temperature, y2h_stream s);
+/* l2_cpu + sum_array (cost_layer.c:85-87) and backward_cost_layer into a zeroed delta: delta = truth - pred,
+ * error = delta^2 (the layer's output), cost[0] = sum error (fixed tree), delta_prev = scale * delta */
+int y2h_train_cost_sse(const float *pred, const float *truth, float *error, float *delta, float *delta_prev, float scale, long n,
+                       float *cost, y2h_stream s);
+/* update_convolutional_layer's three statements per array: updates += wd * w (skipped when wd == 0), w += rate * updates,
+ * updates *= momentum */
+int y2h_train_sgd(float *w, float *updates, long n, float rate, float wd, float momentum, y2h_stream s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -301,9 +301,11 @@ int y2_upload_weights(network *net)
 int y2_weights_arena(network *net, void **dev_ptr, size_t *bytes)
 {
     y2_engine *e;
-    int keep;
+    int keep, trained;
     if (!y2_engine_of(net)) return -1;
     e = y2_engine_of(net);
+    trained = y2_train_is_dirty(net);
+    if (y2_train_sync_if_dirty(net) != 0) return -1;
     /* building must not try to upload host weights that were never loaded */
     keep = e->weights_dirty;
     if (!e->built || e->built_strict != e->strict || e->built_half != e->half || e->built_fusion != e->fusion ||
@@ -313,6 +315,10 @@ int y2_weights_arena(network *net, void **dev_ptr, size_t *bytes)
         e->arena_pending = 1;                /* this build uploads nothing: the arena is uninitialised HBM until it is filled from outside */
         if (y2_engine_build(net) != 0) { e->weights_external = 0; e->arena_pending = 0; return -1; }
         e->weights_external = 0; e->weights_dirty = keep;
+    }
+    if (trained) {                           /* after training steps the arena handed out holds what was trained */
+        if (y2_upload_weights(net) != 0) return -1;
+        e->arena_pending = 0;
     }
     if (dev_ptr) *dev_ptr = e->arena;
     if (bytes) *bytes = e->arena_bytes;

@@ -950,6 +950,7 @@ network parse_network_cfg(char *filename)    /* parser.c:585-700 */
     section *s;
     shape p;
     int count = 0;
+    y2_lr_schedule lr;
 
     memset(&empty, 0, sizeof empty);
     (void)y2_failed();                        /* a stale failure of an earlier call must not fail this parse */
@@ -976,9 +977,10 @@ network parse_network_cfg(char *filename)    /* parser.c:585-700 */
     net.c = option_find_int_quiet(s->options, "channels", 0);
     net.inputs = option_find_int_quiet(s->options, "inputs", net.h * net.w * net.c);
     net.max_batches = option_find_int_quiet(s->options, "max_batches", 0);
+    y2_lr_parse(s->options, &lr);
     touch(s->options, net_quiet);
-    if (!net.inputs && !(net.h && net.w && net.c)) { y2_fail("No input parameters supplied"); return empty; }
-    if (net.batch <= 0) { y2_fail("batch/subdivisions gives a batch of %d", net.batch); return empty; }
+    if (!net.inputs && !(net.h && net.w && net.c)) { y2_fail("No input parameters supplied"); goto fail; }
+    if (net.batch <= 0) { y2_fail("batch/subdivisions gives a batch of %d", net.batch); goto fail; }
 
     p.h = net.h; p.w = net.w; p.c = net.c; p.inputs = net.inputs; p.batch = net.batch; p.index = 0;
     free_section(s);
@@ -1020,7 +1022,7 @@ network parse_network_cfg(char *filename)    /* parser.c:585-700 */
             memset(&l, 0, sizeof l);
             y2_fail("layer type %s is outside the YOLOv2/Darknet-19 forward path this engine implements", t);
         }
-        if (y2_failed()) { g_flag = 1; return empty; }
+        if (y2_failed()) { g_flag = 1; goto fail; }
         if (l.type != SHORTCUT) l.index = count;      /* a shortcut keeps the index of its `from` layer there */
         l.dontload = option_find_int_quiet(s->options, "dontload", 0);
         l.dontloadscales = option_find_int_quiet(s->options, "dontloadscales", 0);
@@ -1031,7 +1033,11 @@ network parse_network_cfg(char *filename)    /* parser.c:585-700 */
     }
     free_list(sections);
     net.outputs = net.layers[y2_out_layer(&net)].outputs;
-    if (y2_engine_create(&net) != 0) return empty;
+    if (y2_engine_create(&net) != 0) goto fail;
+    y2_engine_of(&net)->lr = lr;
     net.output = NULL;                        /* allocated with the plan; see get_network_output */
     return net;
+fail:                                         /* the schedule's lists belong to the engine, which does not exist */
+    free(lr.steps); free(lr.scales);
+    return empty;
 }

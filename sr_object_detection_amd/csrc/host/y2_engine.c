@@ -107,6 +107,8 @@ void y2_engine_destroy(network *net)
     int i;
     if (!e) return;
     if (e->stream || e->arena || e->built) y2h_set_device(e->device);
+    y2_train_free(net);
+    free(e->lr.steps); free(e->lr.scales);
     y2_free_plan(net);
     y2_feed_close(net);
     for (i = 0; i < net->n; ++i) {
@@ -141,6 +143,7 @@ static int ensure_built(network *net)
 {
     y2_engine *e = y2_engine_of(net);
     if (!e) { y2_fail("network has no engine (was it built by parse_network_cfg?)"); return -1; }
+    if (y2_train_sync_if_dirty(net) != 0) return -1;
     if (!e->built || e->built_batch != net->batch || e->built_w != net->w || e->built_h != net->h ||
         e->built_strict != e->strict || e->built_fusion != e->fusion || e->built_half != e->half ||
         e->built_autotune != e->autotune) {
@@ -698,6 +701,8 @@ void set_batch_network(network *net, int b)  /* network.c:308-320 */
         }
     for (i = 0; i < net->n; ++i)
         if (is_recurrent(&net->layers[i])) { y2_engine_invalidate(net); break; }   /* the re-plan zeroes the state */
+    if (y2_train_sync_if_dirty(net) != 0) return;      /* train, set_batch_network(&net, 1), predict: the steps are kept */
+    y2_train_free(net);
     net->batch = b;
     for (i = 0; i < net->n; ++i) net->layers[i].batch = is_recurrent(&net->layers[i]) ? b / net->layers[i].steps : b;
     y2_engine_host_output(net);     /* HBM buffers are re-planned at the next predict if the batch changed */
@@ -719,6 +724,8 @@ int resize_network(network *net, int w, int h)   /* network.c:322-388 */
             y2_fail("Cannot resize this type of layer");
             return -1;
         }
+    if (y2_train_sync_if_dirty(net) != 0) return -1;
+    y2_train_free(net);
     net->w = w; net->h = h;
     net->inputs = w * h * net->c;
     for (i = 0; i < net->n; ++i) {

@@ -66,6 +66,16 @@ typedef struct y2_ldev {
 /* how a recurrent layer's dense products run (y2_rec.c rec_form) */
 enum { Y2_REC_REF = 0, Y2_REC_SKINNY = 1, Y2_REC_MFMA = 2 };
 
+/* network.h:15-17 and the fields of struct network that get_current_rate reads (network.c:48-79); kept here because the
+ * layout of struct network is part of the ABI */
+enum { Y2_LR_CONSTANT = 0, Y2_LR_STEP, Y2_LR_EXP, Y2_LR_POLY, Y2_LR_STEPS, Y2_LR_SIG, Y2_LR_RANDOM };
+typedef struct {
+    int policy, step, burn_in, num_steps, adam;
+    float scale, gamma, power;
+    int *steps;
+    float *scales;
+} y2_lr_schedule;
+
 typedef struct y2_engine {
     int device;
     y2h_stream stream;
@@ -165,6 +175,9 @@ typedef struct y2_engine {
     y2h_event *ev;             /* n+1 events */
     int n_ev;
     int n_layers;
+    /* training (y2_train.c): the [net] section's learning-rate schedule, and the trainer once y2_train_prepare built it */
+    y2_lr_schedule lr;
+    struct y2_trainer *trainer;
 } y2_engine;
 
 /* How the network input (fp32 NCHW) reaches layer 0: a plain NHWC copy; an NHWC copy with a zero border of in_halo_px
@@ -254,6 +267,11 @@ int y2_depth_filter_check(const char *who, network net, const y2_region *items, 
 const unsigned char *y2_depth_plane8(const y2_engine *e, int *W);
 const unsigned short *y2_depth_plane_grasp(const y2_engine *e);
 void y2_depth_free(y2_engine *e);
+
+/* training (y2_train.c) */
+int y2_train_is_dirty(const network *net);     /* steps ran since the masters last reached the host arrays */
+int y2_train_sync_if_dirty(network *net);      /* a trained network's masters reach the host arrays before they are read */
+void y2_lr_parse(list *options, y2_lr_schedule *lr);
 
 /* cfg helpers shared with other files */
 char *y2_fgetl(FILE *fp);

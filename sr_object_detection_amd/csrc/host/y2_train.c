@@ -1,0 +1,587 @@
+/*
+ * Training on the device: host-side replacement for the other half of src_yolo2/network.c -- train_network_datum
+ * (:225-243), backward_network (:197-215), update_network (:160-171), get_current_rate (:48-79) -- and for the
+ * forward(train) / backward / update functions of the convolutional, batch-norm, maxpool, avgpool, softmax and cost
+ * layers, whose loop nests run as the y2h_train_* kernels (y2_train.hip).
+ *
+ * The inference plan folds batch norm, fuses pooling and keeps weights in per-kernel layouts, so nothing of it is
+ * reused: the trainer owns master parameters, their update buffers and per layer output / delta / x / x_norm / mean /
+ * variance, all dense NHWC.  struct network and struct layer are untouched (layer.delta stays NULL); the schedule of
+ * the [net] section lives in the engine.
+ *
+ * Every delta buffer is written exactly once per backward pass by the one layer behind it (there are no routes), so
+ * the reference's "zero every delta, then add" (network.c:152-154, col2im_cpu, backward_maxpool_layer ...) is a plain
+ * store here: 0 + v == v.
+ */
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include "y2_internal.h"
+
+typedef struct {
+    float *out, *delta;                 /* [batch][out_h][out_w][out_c] */
+    float *x, *x_norm;                  /* batch-normalised convolutions */
+    float *mean, *variance, *mean_delta, *variance_delta;
+    float *weights, *weight_updates, *biases, *bias_updates, *scales, *scale_updates, *rolling_mean, *rolling_variance;
+    int *idx;                           /* [maxpool] winners */
+    float *cost;                        /* [cost]: one float */
+    y2h_train_conv g;
+} y2_tlayer;
+
+typedef struct y2_trainer {
+    int n, batch;
+    y2_tlayer *L;
+    float *d_x_nchw, *d_x, *d_truth;    /* the step's input as given, as NHWC, and its truth */
+    float *ws, *scratch, *stage;        /* weight-gradient partial tiles, reduction partials, NCHW staging of y2_train_pull */
+    size_t stage_floats;
+    float *h_cost, *h_in, *h_pull;      /* pinned: one float per layer; the host batch and truth of y2_train_step; the landing
+                                           buffer of every copy down (stage_floats, at least the largest weight array) */
+    int dirty;                          /* steps ran since the masters last reached the host arrays */
+} y2_trainer;
+
+/* ------------------------------------------------------------------ */
+/* the schedule (parser.c:538-576, network.c:31-79)                    */
+/* ------------------------------------------------------------------ */
+void y2_lr_parse(list *o, y2_lr_schedule *lr)
+{
+    char *p = option_find(o, "policy");
+    memset(lr, 0, sizeof *lr);
+    if (!p) p = "constant";
+    lr->policy = !strcmp(p, "random") ? Y2_LR_RANDOM : !strcmp(p, "poly") ? Y2_LR_POLY : !strcmp(p, "step") ? Y2_LR_STEP :
+                 !strcmp(p, "exp") ? Y2_LR_EXP : !strcmp(p, "sigmoid") ? Y2_LR_SIG : !strcmp(p, "steps") ? Y2_LR_STEPS : Y2_LR_CONSTANT;
+    lr->adam = option_find_int_quiet(o, "adam", 0);
+    lr->burn_in = option_find_int_quiet(o, "burn_in", 0);
+    lr->step = option_find_int_quiet(o, "step", 1);
+    lr->scale = option_find_float_quiet(o, "scale", 1);
+    lr->gamma = option_find_float_quiet(o, "gamma", 1);
+    lr->power = option_find_float_quiet(o, "power", 1);
+    if (lr->policy == Y2_LR_STEPS) {
+        char *l = option_find(o, "steps"), *s = option_find(o, "scales");
+        int n = 1, i;
+        if (!l || !s) return;                       /* the reference exits; the forward path never needed them */
+        for (i = 0; l[i]; ++i) if (l[i] == ',') ++n;
+        lr->steps = calloc(n, sizeof(int));
+        lr->scales = calloc(n, sizeof(float));
+        for (i = 0; i < n && l && s; ++i) {
+            lr->steps[i] = atoi(l);
+            lr->scales[i] = atof(s);
+            l = strchr(l, ','); if (l) ++l;
+            s = strchr(s, ','); if (s) ++s;
+        }
+        lr->num_steps = i;
+    }
+}
+
+int get_current_batch(network net)
+{
+    return (*net.seen) / (net.batch * net.subdivisions);
+}
+
+float get_current_rate(network net)
+{
+    const y2_engine *e = y2_engine_of(&net);
+    const y2_lr_schedule *s = e ? &e->lr : NULL;
+    int batch_num = get_current_batch(net);
+    int i;
+    float rate;
+    if (!s) return net.learning_rate;
+    switch (s->policy) {
+    case Y2_LR_CONSTANT:
+        return net.learning_rate;
+    case Y2_LR_STEP:
+        return net.learning_rate * pow(s->scale, batch_num / s->step);
+    case Y2_LR_STEPS:
+        rate = net.learning_rate;
+        for (i = 0; i < s->num_steps; ++i) {
+            if (s->steps[i] > batch_num) return rate;
+            rate *= s->scales[i];
+        }
+        return rate;
+    case Y2_LR_EXP:
+        return net.learning_rate * pow(s->gamma, batch_num);
+    case Y2_LR_POLY:
+        if (batch_num < s->burn_in) return net.learning_rate * pow((float)batch_num / s->burn_in, s->power);
+        return net.learning_rate * pow(1 - (float)batch_num / net.max_batches, s->power);
+    case Y2_LR_SIG:
+        return net.learning_rate * (1. / (1. + exp(s->gamma * (batch_num - s->step))));
+    default:
+        return net.learning_rate;
+    }
+}
+
+float get_network_cost(network net)
+{
+    int i, count = 0;
+    float sum = 0;
+    for (i = 0; i < net.n; ++i)
+        if (net.layers[i].cost) { sum += net.layers[i].cost[0]; ++count; }
+    return sum / count;
+}
+
+/* ------------------------------------------------------------------ */
+/* the weight layout                                                   */
+/* ------------------------------------------------------------------ */
+void y2_train_pack_weights(const float *ref, float *packed, int n, int c, int size)
+{
+    int f, ci, ky, kx;
+    for (f = 0; f < n; ++f)
+        for (ci = 0; ci < c; ++ci)
+            for (ky = 0; ky < size; ++ky)
+                for (kx = 0; kx < size; ++kx)
+                    packed[((size_t)(ky * size + kx) * c + ci) * n + f] = ref[(((size_t)f * c + ci) * size + ky) * size + kx];
+}
+
+void y2_train_unpack_weights(const float *packed, float *ref, int n, int c, int size)
+{
+    int f, ci, ky, kx;
+    for (f = 0; f < n; ++f)
+        for (ci = 0; ci < c; ++ci)
+            for (ky = 0; ky < size; ++ky)
+                for (kx = 0; kx < size; ++kx)
+                    ref[(((size_t)f * c + ci) * size + ky) * size + kx] = packed[((size_t)(ky * size + kx) * c + ci) * n + f];
+}
+
+/* ------------------------------------------------------------------ */
+/* refusals                                                            */
+/* ------------------------------------------------------------------ */
+static int refuse(const network *net)
+{
+    const y2_engine *e = y2_engine_of(net);
+    int i, flat = 0;           /* the running activation reads the same as [batch][c][h][w] and as [batch][h][w][c] */
+    if (!e || !net->layers || net->n <= 0) { y2_fail("y2_train_prepare: network has no engine (was it built by parse_network_cfg?)"); return -1; }
+    if (e->half) { y2_fail("training is fp32 only: the network is in fp16 mode (y2_set_half / Y2_FP16)"); return -1; }
+    if (e->lr.adam) { y2_fail("training: adam=1 is not implemented (SGD with momentum only)"); return -1; }
+    if (e->lr.policy == Y2_LR_RANDOM) { y2_fail("training: policy=random is refused (its rate is a draw of rand(), not a function of the step)"); return -1; }
+    if (e->lr.policy == Y2_LR_STEPS && !e->lr.num_steps) { y2_fail("training: STEPS policy must have steps and scales in cfg file"); return -1; }
+    for (i = 0; i < net->n; ++i) {
+        const layer *l = &net->layers[i];
+        const char *t = get_layer_string(l->type);
+        if (is_recurrent(l)) { y2_fail("training: layer %d (%s): a recurrent network cannot be trained", i, t); return -1; }
+        if ((l->type == SOFTMAX || l->type == COST) && !flat) {
+            y2_fail("training: layer %d (%s): its input must be one value per channel (put an [avgpool] in front): rows of an "
+                    "image are ordered by channel in the truth and by pixel on the device", i, t);
+            return -1;
+        }
+        if (l->type == CONVOLUTIONAL || l->type == MAXPOOL) flat = l->out_h * l->out_w == 1 || l->out_c == 1;
+        if (l->type == AVGPOOL) flat = 1;
+        switch (l->type) {
+        case CONVOLUTIONAL:
+            if (l->stride != 1) { y2_fail("training: layer %d (%s): stride %d is not trainable (stride 1 only)", i, t, l->stride); return -1; }
+            if (l->xnor || l->binary) { y2_fail("training: layer %d (%s): xnor / binary weights are not trainable", i, t); return -1; }
+            if (l->activation != LINEAR && l->activation != LEAKY && l->activation != LOGISTIC && l->activation != RELU) {
+                y2_fail("training: layer %d (%s): activation %d is not trainable (linear, leaky, logistic, relu)", i, t, (int)l->activation);
+                return -1;
+            }
+            if (l->batch_normalize && (long)net->batch * l->out_h * l->out_w < 2) {
+                y2_fail("training: layer %d (%s): batch normalisation over batch*out_h*out_w = %ld value divides by zero in the reference",
+                        i, t, (long)net->batch * l->out_h * l->out_w);
+                return -1;
+            }
+            break;
+        case MAXPOOL: case AVGPOOL:
+            break;
+        case SOFTMAX:
+            if (l->softmax_tree || l->groups > 1) { y2_fail("training: layer %d (%s): a tree or groups > 1 softmax is not trainable", i, t); return -1; }
+            break;
+        case COST:
+            if (l->cost_type != SSE) { y2_fail("training: layer %d (%s): only type=sse is trainable", i, t); return -1; }
+            if (i == 0) { y2_fail("training: layer %d (%s): a cost layer needs a layer in front of it", i, t); return -1; }
+            if (i != net->n - 1) { y2_fail("training: layer %d (%s): only the last layer may be a cost layer (one truth per step)", i, t); return -1; }
+            break;
+        default:
+            y2_fail("training: layer %d (%s) is not trainable (convolutional, maxpool, avgpool, softmax, cost)", i, t);
+            return -1;
+        }
+    }
+    if (net->h <= 0 || net->w <= 0 || net->c <= 0) { y2_fail("training: the network input must be an image (h, w, c > 0)"); return -1; }
+    if (net->layers[net->n - 1].type != COST) { y2_fail("training: layer %d (%s): the last layer must be [cost]", net->n - 1, get_layer_string(net->layers[net->n - 1].type)); return -1; }
+    return 0;
+}
+
+/* ------------------------------------------------------------------ */
+/* lifecycle                                                           */
+/* ------------------------------------------------------------------ */
+void y2_train_free(network *net)
+{
+    y2_engine *e = y2_engine_of(net);
+    y2_trainer *t = e ? e->trainer : NULL;
+    int i;
+    if (!t) return;
+    y2h_set_device(e->device);
+    if (e->stream) y2h_stream_sync(e->stream);
+    for (i = 0; i < t->n; ++i) {
+        y2_tlayer *L = &t->L[i];
+        float *all[] = { L->out, L->delta, L->x, L->x_norm, L->mean, L->variance, L->mean_delta, L->variance_delta, L->weights,
+                         L->weight_updates, L->biases, L->bias_updates, L->scales, L->scale_updates, L->rolling_mean,
+                         L->rolling_variance, L->cost };
+        size_t k;
+        for (k = 0; k < sizeof all / sizeof all[0]; ++k) y2h_free(all[k]);
+        y2h_free(L->idx);
+    }
+    y2h_free(t->d_x_nchw); y2h_free(t->d_x); y2h_free(t->d_truth);
+    y2h_free(t->ws); y2h_free(t->scratch); y2h_free(t->stage);
+    y2h_host_free(t->h_cost); y2h_host_free(t->h_in); y2h_host_free(t->h_pull);
+    free(t->L);
+    free(t);
+    e->trainer = NULL;
+}
+
+static int dev_floats(float **p, size_t n, y2_engine *e)
+{
+    HIP_OR_ERR(y2h_malloc((void **)p, (n ? n : 1) * sizeof(float)));
+    HIP_OR_ERR(y2h_memset(*p, 0, (n ? n : 1) * sizeof(float), e->stream));
+    return 0;
+}
+
+static int push(float *dst, const float *src, size_t n, float *pinned, y2_engine *e)
+{
+    memcpy(pinned, src, n * sizeof(float));
+    HIP_OR_ERR(y2h_memcpy_h2d(dst, pinned, n * sizeof(float), e->stream));
+    HIP_OR_ERR(y2h_stream_sync(e->stream));
+    return 0;
+}
+
+static size_t max_z(size_t a, size_t b) { return a > b ? a : b; }
+
+int y2_train_prepare(network *net)
+{
+    y2_engine *e = y2_engine_of(net);
+    y2_trainer *t;
+    float *pin, *tmp = NULL;
+    size_t ws = 16, scratch = 16, stage;
+    int i, rc = -1;
+    if (refuse(net) != 0) return -1;
+    y2_train_free(net);
+    HIP_OR_ERR(y2h_set_device(e->device));
+    if (!e->stream) HIP_OR_ERR(y2h_stream_create(&e->stream));
+    t = calloc(1, sizeof *t);
+    t->n = net->n; t->batch = net->batch;
+    t->L = calloc(net->n, sizeof *t->L);
+    e->trainer = t;
+    stage = (size_t)net->batch * net->inputs;
+    for (i = 0; i < net->n; ++i) {
+        const layer *l = &net->layers[i];
+        stage = max_z(stage, (size_t)net->batch * l->outputs);
+        if (l->type == CONVOLUTIONAL) stage = max_z(stage, (size_t)l->n * l->c * l->size * l->size);
+    }
+    t->stage_floats = stage;
+    if (y2h_host_alloc((void **)&t->h_pull, stage * sizeof(float)) != 0) { y2_fail("y2_train_prepare: no pinned memory: %s", y2h_last_error()); goto cleanup; }
+    pin = t->h_pull;
+    tmp = malloc(stage * sizeof(float));
+    HIP_OR_CLEANUP(y2h_host_alloc((void **)&t->h_cost, (size_t)net->n * sizeof(float)));
+    HIP_OR_CLEANUP(y2h_host_alloc((void **)&t->h_in, ((size_t)net->batch * net->inputs + (size_t)net->batch * net->layers[net->n - 1].inputs) * sizeof(float)));
+    if (dev_floats(&t->d_x_nchw, (size_t)net->batch * net->inputs, e) || dev_floats(&t->d_x, (size_t)net->batch * net->inputs, e) ||
+        dev_floats(&t->d_truth, (size_t)net->batch * net->layers[net->n - 1].inputs, e)) goto cleanup;
+    for (i = 0; i < net->n; ++i) {
+        const layer *l = &net->layers[i];
+        y2_tlayer *L = &t->L[i];
+        const size_t outs = (size_t)net->batch * l->outputs;
+        if (dev_floats(&L->out, outs, e) || dev_floats(&L->delta, outs, e)) goto cleanup;
+        if (l->type == MAXPOOL) HIP_OR_CLEANUP(y2h_malloc((void **)&L->idx, outs * sizeof(int)));
+        if (l->type == COST && dev_floats(&L->cost, 1, e)) goto cleanup;
+        if (l->type != CONVOLUTIONAL) continue;
+        {
+            const size_t nw = (size_t)l->n * l->c * l->size * l->size;
+            const long rows = (long)net->batch * l->out_h * l->out_w;
+            y2h_train_conv g = { net->batch, l->h, l->w, l->c, l->n, l->size, l->pad, l->out_h, l->out_w };
+            L->g = g;
+            if (l->out_h != l->h + 2 * l->pad - l->size + 1 || y2h_train_dweight_ws_bytes(&g) == 0) {
+                y2_fail("training: layer %d (convolutional): shape outside what the kernels take", i);
+                goto cleanup;
+            }
+            ws = max_z(ws, y2h_train_dweight_ws_bytes(&g));
+            scratch = max_z(scratch, y2h_train_reduce_scratch_bytes(rows, l->n));
+            if (dev_floats(&L->weights, nw, e) || dev_floats(&L->weight_updates, nw, e) || dev_floats(&L->biases, l->n, e) ||
+                dev_floats(&L->bias_updates, l->n, e)) goto cleanup;
+            y2_train_pack_weights(l->weights, tmp, l->n, l->c, l->size);
+            if (push(L->weights, tmp, nw, pin, e) || push(L->biases, l->biases, l->n, pin, e)) goto cleanup;
+            if (!l->batch_normalize) continue;
+            if (dev_floats(&L->x, outs, e) || dev_floats(&L->x_norm, outs, e) || dev_floats(&L->mean, l->n, e) ||
+                dev_floats(&L->variance, l->n, e) || dev_floats(&L->mean_delta, l->n, e) || dev_floats(&L->variance_delta, l->n, e) ||
+                dev_floats(&L->scales, l->n, e) || dev_floats(&L->scale_updates, l->n, e) || dev_floats(&L->rolling_mean, l->n, e) ||
+                dev_floats(&L->rolling_variance, l->n, e)) goto cleanup;
+            if (push(L->scales, l->scales, l->n, pin, e) || push(L->rolling_mean, l->rolling_mean, l->n, pin, e) ||
+                push(L->rolling_variance, l->rolling_variance, l->n, pin, e)) goto cleanup;
+        }
+    }
+    HIP_OR_CLEANUP(y2h_malloc((void **)&t->ws, ws));
+    HIP_OR_CLEANUP(y2h_malloc((void **)&t->scratch, scratch));
+    HIP_OR_CLEANUP(y2h_malloc((void **)&t->stage, stage * sizeof(float)));
+    HIP_OR_CLEANUP(y2h_stream_sync(e->stream));
+    rc = 0;
+cleanup:
+    free(tmp);
+    if (rc != 0) y2_train_free(net);
+    return rc;
+}
+
+/* ------------------------------------------------------------------ */
+/* the step                                                            */
+/* ------------------------------------------------------------------ */
+static int forward_train(network *net, y2_trainer *t, y2_engine *e)
+{
+    const float *in = t->d_x;
+    int i;
+    for (i = 0; i < net->n; ++i) {
+        const layer *l = &net->layers[i];
+        y2_tlayer *L = &t->L[i];
+        switch (l->type) {
+        case CONVOLUTIONAL: {
+            const long rows = (long)net->batch * l->out_h * l->out_w;
+            HIP_OR_ERR(y2h_train_conv_forward(&L->g, in, L->weights, L->out, e->stream));
+            if (l->batch_normalize)
+                HIP_OR_ERR(y2h_train_bn_stats(L->out, rows, l->n, L->mean, L->variance, L->rolling_mean, L->rolling_variance, t->scratch, e->stream));
+            HIP_OR_ERR(y2h_train_bn_apply(L->out, L->x, L->x_norm, l->batch_normalize ? L->mean : NULL, L->variance, L->scales, L->biases,
+                                          y2_act_code(l->activation), rows, l->n, e->stream));
+        } break;
+        case MAXPOOL:
+            HIP_OR_ERR(y2h_train_maxpool_forward(in, L->out, L->idx, net->batch, l->h, l->w, l->c, l->size, l->stride, l->pad, l->out_h, l->out_w, e->stream));
+            break;
+        case AVGPOOL:
+            HIP_OR_ERR(y2h_train_avgpool_forward(in, L->out, net->batch, l->h * l->w, l->c, e->stream));
+            break;
+        case SOFTMAX:
+            HIP_OR_ERR(y2h_train_softmax(in, L->out, net->batch, l->inputs, l->temperature, e->stream));
+            break;
+        case COST:      /* forward and backward_cost_layer in one launch */
+            HIP_OR_ERR(y2h_train_cost_sse(in, t->d_truth, L->out, L->delta, t->L[i - 1].delta, l->scale, (long)net->batch * l->inputs, L->cost, e->stream));
+            break;
+        default:
+            return -1;
+        }
+        if (l->type != COST) in = L->out;
+    }
+    return 0;
+}
+
+static int backward_train(network *net, y2_trainer *t, y2_engine *e)
+{
+    int i;
+    for (i = net->n - 1; i >= 0; --i) {
+        const layer *l = &net->layers[i];
+        y2_tlayer *L = &t->L[i];
+        const float *in = i ? t->L[i - 1].out : t->d_x;
+        float *din = i ? t->L[i - 1].delta : NULL;          /* network.c:204-206: layer 0 has no state.delta */
+        switch (l->type) {
+        case CONVOLUTIONAL: {
+            const long rows = (long)net->batch * l->out_h * l->out_w;
+            HIP_OR_ERR(y2h_train_act_gradient(L->out, L->delta, y2_act_code(l->activation), rows * l->n, e->stream));
+            HIP_OR_ERR(y2h_train_bias_grad(L->delta, l->batch_normalize ? L->x_norm : NULL, rows, l->n, L->bias_updates,
+                                           l->batch_normalize ? L->scale_updates : NULL, t->scratch, e->stream));
+            if (l->batch_normalize) {
+                HIP_OR_ERR(y2h_train_bn_deltas(L->delta, L->x, L->scales, L->mean, L->variance, rows, l->n, L->mean_delta, L->variance_delta,
+                                               t->scratch, e->stream));
+                HIP_OR_ERR(y2h_train_bn_backward(L->delta, L->x, L->scales, L->mean, L->variance, L->mean_delta, L->variance_delta, rows, l->n,
+                                                 e->stream));
+            }
+            HIP_OR_ERR(y2h_train_conv_dweight(&L->g, in, L->delta, L->weight_updates, t->ws, e->stream));
+            if (din) HIP_OR_ERR(y2h_train_conv_dinput(&L->g, L->delta, L->weights, din, e->stream));
+        } break;
+        case MAXPOOL:
+            if (din) HIP_OR_ERR(y2h_train_maxpool_backward(L->delta, L->idx, din, net->batch, l->h, l->w, l->c, l->size, l->stride, l->pad,
+                                                           l->out_h, l->out_w, e->stream));
+            break;
+        case AVGPOOL:
+            if (din) HIP_OR_ERR(y2h_train_avgpool_backward(L->delta, din, net->batch, l->h * l->w, l->c, e->stream));
+            break;
+        case SOFTMAX:   /* softmax_layer.c:57-63: state.delta += l.delta */
+            if (din) HIP_OR_ERR(y2h_memcpy_d2d(din, L->delta, (size_t)net->batch * l->inputs * sizeof(float), e->stream));
+            break;
+        case COST:      /* done with its forward */
+            break;
+        default:
+            return -1;
+        }
+    }
+    return 0;
+}
+
+static int update_train(network *net, y2_trainer *t, y2_engine *e)
+{
+    const int batch = net->batch * net->subdivisions;
+    const float rate = get_current_rate(*net);
+    int i;
+    for (i = 0; i < net->n; ++i) {
+        const layer *l = &net->layers[i];
+        y2_tlayer *L = &t->L[i];
+        if (l->type != CONVOLUTIONAL) continue;
+        HIP_OR_ERR(y2h_train_sgd(L->biases, L->bias_updates, l->n, rate / batch, 0.f, net->momentum, e->stream));
+        if (l->batch_normalize) HIP_OR_ERR(y2h_train_sgd(L->scales, L->scale_updates, l->n, rate / batch, 0.f, net->momentum, e->stream));
+        HIP_OR_ERR(y2h_train_sgd(L->weights, L->weight_updates, (long)l->n * l->c * l->size * l->size, rate / batch, -net->decay * batch,
+                                 net->momentum, e->stream));
+    }
+    return 0;
+}
+
+/* everything of a step behind `*net.seen += net.batch` */
+static int step_enqueue(network *net, const float *d_x_nchw, const float *d_y, float *loss)
+{
+    y2_engine *e = y2_engine_of(net);
+    y2_trainer *t = e->trainer;
+    int i, costs = 0;
+    float sum = 0;
+    HIP_OR_ERR(y2h_nchw_to_nhwc(d_x_nchw, t->d_x, net->batch, net->c, net->h, net->w, net->c, e->stream));
+    if (d_y != t->d_truth)
+        HIP_OR_ERR(y2h_memcpy_d2d(t->d_truth, d_y, (size_t)net->batch * net->layers[net->n - 1].inputs * sizeof(float), e->stream));
+    t->dirty = 1;          /* from the first launch on: the forward pass already moves the rolling statistics */
+    if (forward_train(net, t, e) != 0 || backward_train(net, t, e) != 0) return -1;
+    if ((*net->seen / net->batch) % net->subdivisions == 0 && update_train(net, t, e) != 0) return -1;
+    for (i = 0; i < net->n; ++i)
+        if (t->L[i].cost) HIP_OR_ERR(y2h_memcpy_d2h(t->h_cost + costs++, t->L[i].cost, sizeof(float), e->stream));
+    HIP_OR_ERR(y2h_stream_sync(e->stream));
+    for (i = 0, costs = 0; i < net->n; ++i)
+        if (t->L[i].cost) { net->layers[i].cost[0] = t->h_cost[costs++]; sum += net->layers[i].cost[0]; }
+    if (loss) *loss = sum / costs;              /* get_network_cost */
+    return 0;
+}
+
+static int step_on_device(network *net, const float *d_x_nchw, const float *d_y, float *loss)
+{
+    *net->seen += net->batch;                   /* first, as in the reference: the update's rate reads it */
+    if (step_enqueue(net, d_x_nchw, d_y, loss) == 0) return 0;
+    *net->seen -= net->batch;                   /* a step that failed does not move the schedule */
+    return -1;
+}
+
+static y2_trainer *trainer_for_step(network *net)
+{
+    y2_engine *e = y2_engine_of(net);
+    if (!e) { y2_fail("y2_train_step: network has no engine (was it built by parse_network_cfg?)"); return NULL; }
+    if ((!e->trainer || e->trainer->batch != net->batch) && y2_train_prepare(net) != 0) return NULL;
+    if (y2h_set_device(e->device) != 0) { y2_fail("y2_train_step: %s", y2h_last_error()); return NULL; }
+    return e->trainer;
+}
+
+int y2_train_step_device(network *net, const float *d_x, const float *d_y, float *loss)
+{
+    if (!d_x || !d_y) { y2_fail("y2_train_step_device: NULL input"); return -1; }
+    if (!trainer_for_step(net)) return -1;
+    return step_on_device(net, d_x, d_y, loss);
+}
+
+int y2_train_step(network *net, const float *x, const float *y, float *loss)
+{
+    y2_engine *e = y2_engine_of(net);
+    y2_trainer *t;
+    size_t nx, ny;
+    if (!x || !y) { y2_fail("y2_train_step: NULL input"); return -1; }
+    if (!(t = trainer_for_step(net))) return -1;
+    nx = (size_t)net->batch * net->inputs;
+    ny = (size_t)net->batch * net->layers[net->n - 1].inputs;
+    /* pinned staging (h_in: nx + ny floats, made with the trainer): no pageable buffer of a caller is handed to an
+     * asynchronous copy; the step's final wait is behind both copies, so the buffer is free again when it returns */
+    memcpy(t->h_in, x, nx * sizeof(float));
+    memcpy(t->h_in + nx, y, ny * sizeof(float));
+    HIP_OR_ERR(y2h_memcpy_h2d(t->d_x_nchw, t->h_in, nx * sizeof(float), e->stream));
+    HIP_OR_ERR(y2h_memcpy_h2d(t->d_truth, t->h_in + nx, ny * sizeof(float), e->stream));
+    if (step_on_device(net, t->d_x_nchw, t->d_truth, loss) != 0) { y2h_stream_sync(e->stream); return -1; }
+    return 0;
+}
+
+float train_network_datum(network net, float *x, float *y)
+{
+    float loss = NAN;
+    if (y2_train_step(&net, x, y, &loss) != 0) return NAN;
+    return loss;
+}
+
+/* ------------------------------------------------------------------ */
+/* looking at it                                                       */
+/* ------------------------------------------------------------------ */
+/* through the trainer's pinned landing buffer (n <= stage_floats: checked by the caller's size test) */
+static int pull_flat(y2_engine *e, const float *src, float *dst, size_t n)
+{
+    float *pin = e->trainer->h_pull;
+    if (n > e->trainer->stage_floats) { y2_fail("y2_train_pull: %zu floats exceed the staging buffer", n); return -1; }
+    HIP_OR_ERR(y2h_memcpy_d2h(pin, src, n * sizeof(float), e->stream));
+    HIP_OR_ERR(y2h_stream_sync(e->stream));
+    memcpy(dst, pin, n * sizeof(float));
+    return 0;
+}
+
+int y2_train_pull(network *net, int i, int what, float *dst, size_t n)
+{
+    y2_engine *e = y2_engine_of(net);
+    y2_trainer *t = e ? e->trainer : NULL;
+    const layer *l;
+    y2_tlayer *L;
+    const float *src = NULL;
+    size_t have = 0;
+    int image = 0, weights = 0;
+    if (!t) { y2_fail("y2_train_pull: no trainer (y2_train_prepare)"); return -1; }
+    if (i < 0 || i >= net->n || !dst) { y2_fail("y2_train_pull: layer %d of %d", i, net->n); return -1; }
+    l = &net->layers[i];
+    L = &t->L[i];
+    switch (what) {
+    case Y2_TRAIN_OUTPUT: src = L->out; image = 1; break;
+    case Y2_TRAIN_DELTA: src = L->delta; image = 1; break;
+    case Y2_TRAIN_X: src = L->x; image = 1; break;
+    case Y2_TRAIN_X_NORM: src = L->x_norm; image = 1; break;
+    case Y2_TRAIN_MEAN: src = L->mean; break;
+    case Y2_TRAIN_VARIANCE: src = L->variance; break;
+    case Y2_TRAIN_MEAN_DELTA: src = L->mean_delta; break;
+    case Y2_TRAIN_VARIANCE_DELTA: src = L->variance_delta; break;
+    case Y2_TRAIN_WEIGHT_UPDATES: src = L->weight_updates; weights = 1; break;
+    case Y2_TRAIN_WEIGHTS: src = L->weights; weights = 1; break;
+    case Y2_TRAIN_BIAS_UPDATES: src = L->bias_updates; break;
+    case Y2_TRAIN_BIASES: src = L->biases; break;
+    case Y2_TRAIN_SCALE_UPDATES: src = L->scale_updates; break;
+    case Y2_TRAIN_SCALES: src = L->scales; break;
+    case Y2_TRAIN_ROLLING_MEAN: src = L->rolling_mean; break;
+    case Y2_TRAIN_ROLLING_VARIANCE: src = L->rolling_variance; break;
+    }
+    if (!src) { y2_fail("y2_train_pull: layer %d (%s) has no array %d", i, get_layer_string(l->type), what); return -1; }
+    have = image ? (size_t)net->batch * l->outputs : weights ? (size_t)l->n * l->c * l->size * l->size : (size_t)l->n;
+    if (n != have) { y2_fail("y2_train_pull: layer %d array %d holds %zu floats, not %zu", i, what, have, n); return -1; }
+    HIP_OR_ERR(y2h_set_device(e->device));
+    if (image && (l->type == CONVOLUTIONAL || l->type == MAXPOOL) && l->out_h * l->out_w > 1) {
+        HIP_OR_ERR(y2h_nhwc_to_nchw(src, l->out_c, t->stage, net->batch, l->out_c, l->out_h, l->out_w, e->stream));
+        return pull_flat(e, t->stage, dst, n);
+    }
+    if (weights) {
+        float *tmp = malloc(n * sizeof(float));
+        int rc = pull_flat(e, src, tmp, n);
+        if (rc == 0) y2_train_unpack_weights(tmp, dst, l->n, l->c, l->size);
+        free(tmp);
+        return rc;
+    }
+    return pull_flat(e, src, dst, n);
+}
+
+int y2_train_is_dirty(const network *net)
+{
+    const y2_engine *e = y2_engine_of(net);
+    return e && e->trainer && e->trainer->dirty;
+}
+
+/* masters -> host layer arrays; the inference arena is re-packed by whoever reads it next */
+int y2_train_sync_if_dirty(network *net)
+{
+    y2_engine *e = y2_engine_of(net);
+    y2_trainer *t = e ? e->trainer : NULL;
+    int i;
+    if (!t || !t->dirty) return 0;
+    for (i = 0; i < net->n; ++i) {
+        layer *l = &net->layers[i];
+        if (l->type != CONVOLUTIONAL) continue;
+        if (y2_train_pull(net, i, Y2_TRAIN_WEIGHTS, l->weights, (size_t)l->n * l->c * l->size * l->size) != 0 ||
+            y2_train_pull(net, i, Y2_TRAIN_BIASES, l->biases, l->n) != 0) return -1;
+        if (l->batch_normalize &&
+            (y2_train_pull(net, i, Y2_TRAIN_SCALES, l->scales, l->n) != 0 || y2_train_pull(net, i, Y2_TRAIN_ROLLING_MEAN, l->rolling_mean, l->n) != 0 ||
+             y2_train_pull(net, i, Y2_TRAIN_ROLLING_VARIANCE, l->rolling_variance, l->n) != 0)) return -1;
+    }
+    t->dirty = 0;
+    e->weights_dirty = 1;
+    e->weights_external = 0;
+    return 0;
+}
+
+int y2_train_sync(network *net)
+{
+    y2_engine *e = y2_engine_of(net);
+    if (!e || !e->trainer) { y2_fail("y2_train_sync: no trainer (y2_train_prepare)"); return -1; }
+    if (y2_train_sync_if_dirty(net) != 0) return -1;
+    if (e->built && e->weights_dirty && y2_upload_weights(net) != 0) return -1;
+    return 0;
+}

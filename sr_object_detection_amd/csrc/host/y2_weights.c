@@ -74,6 +74,7 @@ void load_weights_upto(network *net, char *filename, int cutoff)
     int32_t major = 0, minor = 0, revision = 0;
     int i;
     if (!net || !net->layers) { y2_fail("load_weights: empty network"); return; }
+    y2_train_free(net);
     fprintf(stderr, "Loading weight file......");
     fp = fopen(filename, "rb");
     if (!fp) { file_error(filename); return; }
@@ -157,9 +158,11 @@ void load_weights(network *net, char *filename) { load_weights_upto(net, filenam
 
 void save_weights_upto(network net, char *filename, int cutoff)
 {
-    FILE *fp = fopen(filename, "wb");
+    FILE *fp;
     int32_t hdr[4];
     int i;
+    if (y2_train_sync_if_dirty(&net) != 0) return;
+    fp = fopen(filename, "wb");
     fprintf(stderr, "Saving weights to %s\n", filename);
     if (!fp) { file_error(filename); return; }
     hdr[0] = 0; hdr[1] = 1; hdr[2] = 0;       /* version 0.1.0: 32-bit seen (parser.c:833-839) */
@@ -214,6 +217,11 @@ void denormalize_convolutional_layer(layer l)
     int i, j;
     const int per = l.c * l.size * l.size;
     if (l.type != CONVOLUTIONAL || !l.weights || !l.scales) return;
+    if (l.dev && ((y2_ldev *)l.dev)->eng && ((y2_ldev *)l.dev)->eng->trainer) {
+        /* the trainer's masters would overwrite the folded arrays at the next sync; only the network knows how to drop it */
+        y2_fail("denormalize_convolutional_layer: the network has a trainer: call y2_train_sync and y2_train_free first, or y2_denormalize_network");
+        return;
+    }
     for (i = 0; i < l.n; ++i) {
         float scale = l.scales[i] / sqrt(l.rolling_variance[i] + .00001);
         for (j = 0; j < per; ++j) l.weights[(size_t)i * per + j] *= scale;
@@ -229,6 +237,8 @@ void denormalize_convolutional_layer(layer l)
 void y2_denormalize_network(network *net)
 {
     int i;
+    if (y2_train_sync_if_dirty(net) != 0) return;   /* fold what was trained, then let no master overwrite the folded arrays */
+    y2_train_free(net);
     for (i = 0; i < net->n; ++i) {
         layer l = net->layers[i];
         if (l.type == CONVOLUTIONAL && l.batch_normalize) {

@@ -145,6 +145,10 @@ class View(C.Structure):     # include/y2_hip.h y2h_view: one view of y2h_views_
 VIEWS_CROP10, VIEWS_MULTI, VIEWS_FULL = 0, 1, 2             # include/sr_yolo2.h Y2_VIEWS_*
 
 
+class TrainConv(C.Structure):  # include/y2_hip.h y2h_train_conv: the shape of one trainable convolution
+    _fields_ = [(k, C.c_int) for k in ("batch", "h", "w", "c", "n", "size", "pad", "out_h", "out_w")]
+
+
 class RecArgs(C.Structure):  # include/y2_hip.h y2h_rec_args: one launch of y2h_rec_step
     _fields_ = [("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("mean", C.c_void_p), ("scale", C.c_void_p),
                 ("rinv", C.c_void_p), ("bn", C.c_int), ("act", C.c_int), ("pre", C.c_void_p), ("rows", C.c_int), ("k", C.c_int),
@@ -371,6 +375,45 @@ def lib():
         L.y2h_sk_shares.argtypes = [C.c_long, C.c_int, C.c_long, C.POINTER(C.c_int)]
         L.y2h_sk_first.argtypes = [C.c_long, C.c_int, C.c_long, C.POINTER(C.c_int)]
         L.y2h_sk_walk.argtypes = [C.c_long, C.c_int, C.c_long, C.POINTER(C.c_int), C.c_int]
+    L.train_network_datum.restype = C.c_float
+    L.train_network_datum.argtypes = [CNetwork, C.c_void_p, C.c_void_p]
+    L.get_current_rate.restype = C.c_float
+    L.get_current_rate.argtypes = [CNetwork]
+    L.get_current_batch.argtypes = [CNetwork]
+    L.get_network_cost.restype = C.c_float
+    L.get_network_cost.argtypes = [CNetwork]
+    L.y2_train_prepare.argtypes = [C.POINTER(CNetwork)]
+    L.y2_train_step.argtypes = [C.POINTER(CNetwork), C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+    L.y2_train_step_device.argtypes = [C.POINTER(CNetwork), C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+    L.y2_train_sync.argtypes = [C.POINTER(CNetwork)]
+    L.y2_train_pull.argtypes = [C.POINTER(CNetwork), C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+    L.y2_train_free.restype = None
+    L.y2_train_free.argtypes = [C.POINTER(CNetwork)]
+    L.y2_train_pack_weights.restype = None
+    L.y2_train_pack_weights.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
+    L.y2_train_unpack_weights.restype = None
+    L.y2_train_unpack_weights.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
+    L.y2h_train_conv_forward.argtypes = [C.POINTER(TrainConv), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.y2h_train_conv_dinput.argtypes = [C.POINTER(TrainConv), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.y2h_train_dweight_splits.argtypes = [C.POINTER(TrainConv)]
+    L.y2h_train_dweight_ws_bytes.restype = C.c_size_t
+    L.y2h_train_dweight_ws_bytes.argtypes = [C.POINTER(TrainConv)]
+    L.y2h_train_conv_dweight.argtypes = [C.POINTER(TrainConv), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.y2h_train_reduce_scratch_bytes.restype = C.c_size_t
+    L.y2h_train_reduce_scratch_bytes.argtypes = [C.c_long, C.c_int]
+    L.y2h_train_bn_stats.argtypes = [C.c_void_p, C.c_long, C.c_int] + [C.c_void_p] * 6
+    L.y2h_train_bias_grad.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int] + [C.c_void_p] * 4
+    L.y2h_train_bn_deltas.argtypes = [C.c_void_p] * 5 + [C.c_long, C.c_int] + [C.c_void_p] * 4
+    L.y2h_train_bn_backward.argtypes = [C.c_void_p] * 7 + [C.c_long, C.c_int, C.c_void_p]
+    L.y2h_train_bn_apply.argtypes = [C.c_void_p] * 7 + [C.c_int, C.c_long, C.c_int, C.c_void_p]
+    L.y2h_train_act_gradient.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_void_p]
+    L.y2h_train_maxpool_forward.argtypes = [C.c_void_p] * 3 + [C.c_int] * 9 + [C.c_void_p]
+    L.y2h_train_maxpool_backward.argtypes = [C.c_void_p] * 3 + [C.c_int] * 9 + [C.c_void_p]
+    L.y2h_train_avgpool_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.y2h_train_avgpool_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.y2h_train_softmax.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]
+    L.y2h_train_cost_sse.argtypes = [C.c_void_p] * 5 + [C.c_float, C.c_long, C.c_void_p, C.c_void_p]
+    L.y2h_train_sgd.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_float, C.c_float, C.c_float, C.c_void_p]
     L.y2h_stream_k_launches.restype = C.c_ulong
     L.y2h_tail_launches.restype = C.c_ulong
     L.y2h_xcd_order_launches.restype = C.c_ulong
@@ -671,6 +714,62 @@ class Network:
             raise Y2Error("test_detector_img_for_grasping: " + _check())
         return [dict(x=o.x, y=o.y, w=o.w, h=o.h, prob=o.prob, objClass=o.objClass, name=o.name.decode(), boxRGB=tuple(o.boxRGB))
                 for o in objs[:cnt.value]]
+
+    # --- training (include/sr_yolo2.h: train_network_datum and the y2_train_* calls it is written on) ---
+    TRAIN_ARRAYS = ("output", "delta", "x", "x_norm", "mean", "variance", "mean_delta", "variance_delta", "weight_updates",
+                    "bias_updates", "scale_updates", "weights", "biases", "scales", "rolling_mean", "rolling_variance")
+
+    def train_prepare(self) -> None:
+        if lib().y2_train_prepare(C.byref(self.net)) != 0:
+            raise Y2Error("y2_train_prepare: " + _check())
+
+    def train_step(self, x: np.ndarray, y: np.ndarray) -> float:
+        """one train_network_datum: x [batch][c][h][w], y [batch][outputs] -> the loss"""
+        x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+        y = np.ascontiguousarray(y, dtype=np.float32).reshape(-1)
+        if x.size != self.net.batch * self.net.inputs or y.size != self.net.batch * self.net.layers[self.net.n - 1].inputs:
+            raise ValueError("train_step: x has %d floats, y has %d" % (x.size, y.size))
+        loss = C.c_float(0)
+        if lib().y2_train_step(C.byref(self.net), _ptr(x), _ptr(y), C.byref(loss)) != 0:
+            raise Y2Error("y2_train_step: " + _check())
+        return float(loss.value)
+
+    def train_step_device(self, d_x: int, d_y: int) -> float:
+        loss = C.c_float(0)
+        if lib().y2_train_step_device(C.byref(self.net), C.c_void_p(d_x), C.c_void_p(d_y), C.byref(loss)) != 0:
+            raise Y2Error("y2_train_step_device: " + _check())
+        return float(loss.value)
+
+    def train_sync(self) -> None:
+        if lib().y2_train_sync(C.byref(self.net)) != 0:
+            raise Y2Error("y2_train_sync: " + _check())
+
+    def train_pull(self, layer: int, what: str) -> np.ndarray:
+        """one array of the trainer in the reference's order: activations [batch][c][h][w], weights [n][c][size][size]"""
+        l = self.net.layers[layer]
+        code = self.TRAIN_ARRAYS.index(what)
+        if code < 4:
+            n = self.net.batch * l.outputs
+        elif what in ("weights", "weight_updates"):
+            n = l.n * l.c * l.size * l.size
+        else:
+            n = l.n
+        out = np.zeros(max(n, 1), np.float32)
+        if lib().y2_train_pull(C.byref(self.net), layer, code, _ptr(out), n) != 0:
+            raise Y2Error("y2_train_pull: " + _check())
+        return out[:n]
+
+    def train_free(self) -> None:
+        lib().y2_train_free(C.byref(self.net))
+
+    def get_current_rate(self) -> float:
+        return float(lib().get_current_rate(self.net))
+
+    def get_current_batch(self) -> int:
+        return int(lib().get_current_batch(self.net))
+
+    def get_network_cost(self) -> float:
+        return float(lib().get_network_cost(self.net))
 
     # --- extensions ---
     def prepare(self) -> None:

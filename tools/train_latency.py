@@ -1,0 +1,162 @@
+#!/usr/bin/env python3
+"""What a training step costs on the device: Darknet-19 (cfg/darknet19.cfg: the trunk, 1x1 -> 1000, avgpool, softmax, cost)
+at 224x224, by default at batch 16 and batch 64.
+
+Per batch size:
+  step      y2_train_step_device (input and truth already in HBM) after a warm-up: event times on the engine's stream
+            around each call -> p50 ms per step and images/s.  A step ends with the copy of the loss, so the span is
+            host-visible.
+  products  per convolution, the three products of y2_train.hip launched on buffers of the layer's shape, event-timed the
+            same way: forward y = x * w, dinput dx = dy * w^T, dweight dw += x^T * dy (its two launches together), each
+            as ms and achieved TFLOP/s (2 * batch*out_h*out_w * size*size*c * n flops per product; dinput of layer 0 is
+            timed although a step skips it)
+  reference the wall-clock time of the same step through the compiled reference on this host (oracle/_ref/train_ref time,
+            built by `tests/golden/gen_train_golden.py --driver-only` where the reference checkout exists; OMP_NUM_THREADS
+            as the environment has it); skipped when the driver is not there or with --no-reference
+
+usage: train_latency.py [--batches 16,64] [--steps 10] [--warmup 3] [--reps 5] [--ref-batch 16] [--no-reference]
+                        [--no-products] [--layers 4,18]"""
+import argparse
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from sr_object_detection_amd import darknet, synth, zoo  # noqa: E402
+
+SIZE = 224
+TRAIN_REF = os.path.join(ROOT, "oracle", "_ref", "train_ref")
+
+
+class Timer:
+    def __init__(self, stream):
+        self.L, self.stream = darknet.lib(), stream
+        self.e0, self.e1 = C.c_void_p(), C.c_void_p()
+        assert self.L.y2h_event_create(C.byref(self.e0)) == 0 and self.L.y2h_event_create(C.byref(self.e1)) == 0
+
+    def ms(self, fn):
+        ms = C.c_float(0)
+        assert self.L.y2h_event_record(self.e0, self.stream) == 0
+        fn()
+        assert self.L.y2h_event_record(self.e1, self.stream) == 0
+        assert self.L.y2h_event_elapsed_ms(self.e0, self.e1, C.byref(ms)) == 0
+        return float(ms.value)
+
+
+def dev_floats(L, n, fill=None):
+    p = C.c_void_p()
+    assert L.y2h_malloc(C.byref(p), max(n, 4) * 4) == 0, L.y2h_last_error()
+    if fill is not None:
+        a = np.ascontiguousarray(fill, dtype=np.float32)
+        assert L.y2h_memcpy_h2d(p, a.ctypes.data, a.nbytes, None) == 0 and L.y2h_device_sync() == 0
+    return p
+
+
+def p50(v):
+    return float(np.percentile(np.asarray(v), 50))
+
+
+def products(net, timer, reps, only=None):
+    L = darknet.lib()
+    rows = []
+    for i in range(net.n):
+        l = net.layer(i)
+        if l.type != 0 or (only is not None and i not in only):                       # CONVOLUTIONAL
+            continue
+        g = darknet.TrainConv(net.batch, l.h, l.w, l.c, l.n, l.size, l.pad, l.out_h, l.out_w)
+        nx, ny, nw = net.batch * l.h * l.w * l.c, net.batch * l.out_h * l.out_w * l.n, l.size * l.size * l.c * l.n
+        x = dev_floats(L, nx, synth.uniform(7 + i, nx, -1, 1))
+        dy = dev_floats(L, ny, synth.uniform(70 + i, ny, -1, 1))
+        w = dev_floats(L, nw, synth.uniform(700 + i, nw, -.1, .1))
+        y, dx, dw = dev_floats(L, ny), dev_floats(L, nx), dev_floats(L, nw, np.zeros(nw, np.float32))
+        ws = C.c_void_p()
+        assert L.y2h_malloc(C.byref(ws), L.y2h_train_dweight_ws_bytes(C.byref(g))) == 0
+        calls = {"forward": lambda: L.y2h_train_conv_forward(C.byref(g), x, w, y, timer.stream),
+                 "dinput": lambda: L.y2h_train_conv_dinput(C.byref(g), dy, w, dx, timer.stream),
+                 "dweight": lambda: L.y2h_train_conv_dweight(C.byref(g), x, dy, dw, ws, timer.stream)}
+        flops = 2.0 * net.batch * l.out_h * l.out_w * l.size * l.size * l.c * l.n
+        row = {"layer": i, "shape": "%dx%dx%d -> %d, %dx%d" % (l.w, l.h, l.c, l.n, l.size, l.size), "gflop": round(flops / 1e9, 2),
+               "dweight_splits": int(L.y2h_train_dweight_splits(C.byref(g)))}
+        for name, fn in calls.items():
+            assert fn() == 0, L.y2h_last_error()
+            t = p50([timer.ms(fn) for _ in range(reps)])
+            row[name + "_ms"] = round(t, 4)
+            row[name + "_tflops"] = round(flops / (t * 1e-3) / 1e12, 2)
+        for p in (x, dy, w, y, dx, dw, ws):
+            L.y2h_free(p)
+        print("    " + json.dumps(row))
+        rows.append(row)
+    return rows
+
+
+def reference_step(tmp, wts, batch, steps=2):
+    if not os.path.exists(TRAIN_REF):
+        return None
+    cfg = os.path.join(tmp, "d19_ref_b%d.cfg" % batch)
+    open(cfg, "w").write(zoo.cfg_text("darknet19", SIZE, SIZE, batch))
+    out = subprocess.run([TRAIN_REF, "time", cfg, wts, str(steps)], capture_output=True, text=True, check=True).stdout
+    secs = [float(line.split()[3]) for line in out.splitlines() if line.startswith("step")]
+    return {"batch": batch, "threads": os.environ.get("OMP_NUM_THREADS", "unset"), "seconds_per_step": secs}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", default="16,64")
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--ref-batch", type=int, default=16)
+    ap.add_argument("--no-reference", action="store_true")
+    ap.add_argument("--no-products", action="store_true")
+    ap.add_argument("--layers", default=None, help="only these layers' products, e.g. 4,18 (with --steps 0 --warmup 0 "
+                    "--no-reference: the few launches a counter run wants, `rocprofv3 --pmc ... -- python tools/train_latency.py ...`)")
+    a = ap.parse_args()
+    L = darknet.lib()
+    tmp = tempfile.mkdtemp()
+    wts = os.path.join(tmp, "d19.weights")
+    synth.write_weights(wts, zoo.resolve("darknet19", SIZE), 41, 1.0)
+    print("darknet19 at %d, device %s" % (SIZE, darknet.device_name()))
+    out = []
+    for batch in [int(b) for b in a.batches.split(",")]:
+        cfg = os.path.join(tmp, "d19_b%d.cfg" % batch)
+        open(cfg, "w").write(zoo.cfg_text("darknet19", SIZE, SIZE, batch))
+        net = darknet.Network.parse_network_cfg(cfg)
+        net.load_weights(wts)
+        net.train_prepare()
+        outputs = net.layer(net.n - 1).inputs
+        y = np.zeros((batch, outputs), np.float32)
+        y[np.arange(batch), np.arange(batch) % outputs] = 1
+        d_x = dev_floats(L, batch * net.net.inputs, synth.uniform(5, batch * net.net.inputs, -1, 1))
+        d_y = dev_floats(L, y.size, y)
+        timer = Timer(net.stream())
+        losses = [net.train_step_device(d_x.value, d_y.value) for _ in range(a.warmup)]
+        ms = []
+        for _ in range(a.steps):
+            ms.append(timer.ms(lambda: losses.append(net.train_step_device(d_x.value, d_y.value))))
+        res = {"batch": batch}
+        if ms:
+            res.update(step_p50_ms=round(p50(ms), 3), step_max_ms=round(max(ms), 3),
+                       images_per_s=round(batch / (p50(ms) * 1e-3), 1), first_loss=losses[0], last_loss=losses[-1])
+        print("  " + json.dumps(res))
+        if not a.no_products:
+            res["products"] = products(net, timer, a.reps, None if a.layers is None else {int(v) for v in a.layers.split(",")})
+            for k in ("forward", "dinput", "dweight"):
+                res[k + "_sum_ms"] = round(sum(r[k + "_ms"] for r in res["products"]), 3)
+        L.y2h_free(d_x)
+        L.y2h_free(d_y)
+        net.free()
+        out.append(res)
+    ref = None if a.no_reference else reference_step(tmp, wts, a.ref_batch)
+    if ref:
+        print("  reference: " + json.dumps(ref))
+    print(json.dumps({"tool": "train_latency", "device": darknet.device_name(), "size": SIZE, "rows": out, "reference": ref}))
+
+
+if __name__ == "__main__":
+    main()
