@@ -642,13 +642,17 @@ int y2_plane_fit(const double *sums, double *plane);
 /* ------------------------------------------------------------------------- */
 /* Training on the device: the other half of network.c (train_network_datum     */
 /* :225-243 = forward with train = 1, backward_network, update_network), fp32,  */
-/* for convolutional classifiers.  The trainer owns its buffers (master         */
+/* for convolutional classifiers and YOLOv2 detectors ([region] loss, [route],  */
+/* [reorg]; the truth of a [region] network is [batch][150], see                */
+/* y2_train_truth_floats).  The trainer owns its buffers (master                */
 /* weights, update buffers, per layer output / delta / x / x_norm / mean /      */
 /* variance); the inference plan is untouched, struct network and struct layer  */
 /* keep their layout and layer.delta stays NULL.                                */
 /* Trainable: [convolutional] (any size / pad, stride 1, batch_normalize 0 / 1, */
 /* linear / leaky / logistic / relu), [maxpool], [avgpool], [softmax] (groups   */
-/* 1, no tree), [cost] type=sse.  Refused by name before any device allocation, */
+/* 1, no tree), [cost] type=sse; in a network that ends in [region] also        */
+/* [route], [reorg] (reverse=0) and the [region] head (softmax=1, no tree= /    */
+/* map=, classfix=0).  Refused by name before any device allocation,            */
 /* layer number and type in y2_last_error(): every other section type, stride   */
 /* > 1, xnor, another activation, adam=1, policy=random, another cost type, a   */
 /* tree / groups > 1 softmax, fp16 mode, a recurrent network, a batch-normalised */
@@ -665,6 +669,10 @@ int get_current_batch(network net);              /* network.c:31 */
 float get_network_cost(network net);             /* network.c:183: mean of the [cost] layers' cost[0] */
 /* Builds the trainer from the host weights (load_weights, or whatever the layer arrays hold).  0 / -1. */
 int y2_train_prepare(network *net);
+/* Floats of truth per image of a step: the inputs of a closing [cost]; l.truths = 150 behind a closing [region], 30 rows of
+ * x, y, w, h, class in relative units, the list ended by the first x == 0.  -1 (and y2_last_error) for a network the
+ * trainer refuses; touches no device. */
+int y2_train_truth_floats(network *net);
 int y2_train_step(network *net, const float *x, const float *y, float *loss);            /* what train_network_datum calls */
 int y2_train_step_device(network *net, const float *d_x, const float *d_y, float *loss); /* the inputs already in HBM */
 /* After a step the network is dirty: network_predict and every entry built on the forward pass, save_weights[_upto] and
@@ -682,6 +690,10 @@ enum { Y2_TRAIN_OUTPUT = 0, Y2_TRAIN_DELTA, Y2_TRAIN_X, Y2_TRAIN_X_NORM, Y2_TRAI
        Y2_TRAIN_VARIANCE_DELTA, Y2_TRAIN_WEIGHT_UPDATES, Y2_TRAIN_BIAS_UPDATES, Y2_TRAIN_SCALE_UPDATES, Y2_TRAIN_WEIGHTS,
        Y2_TRAIN_BIASES, Y2_TRAIN_SCALES, Y2_TRAIN_ROLLING_MEAN, Y2_TRAIN_ROLLING_VARIANCE };
 int y2_train_pull(network *net, int layer, int what, float *dst, size_t n);
+/* What forward_region_layer prints per call (region_layer.c:320), of the last step: the sums divided as in that printf, so
+ * avg_iou, avg_class, avg_obj and recall are NaN when the batch held no truth.  The library prints nothing. */
+typedef struct { float avg_iou, avg_class, avg_obj, avg_noobj, recall; int count, class_count; } y2_region_stats;
+int y2_train_region_stats(network *net, int layer, y2_region_stats *out);
 void y2_train_free(network *net);
 /* The trainer's weight layout, [size][size][c][n], to and from the host's [n][c][size][size]: pure permutations. */
 void y2_train_pack_weights(const float *ref, float *packed, int n, int c, int size);

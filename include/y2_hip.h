@@ -700,6 +700,29 @@ int y2h_train_cost_sse(const float *pred, const float *truth, float *error, floa
  * updates *= momentum */
 int y2h_train_sgd(float *w, float *updates, long n, float rate, float wd, float momentum, y2h_stream s);
 
+/* ---- training, the detector's tail (y2_train_det.hip) ----
+ * The [region] head with state.train = 1 (region_layer.c:144-321, CPU branch, DOABS 1, flat softmax) and
+ * backward_region_layer.  `in` is the last convolution's dense NHWC output, which IS the reference's flattened layout
+ * [batch][h*w][n*(5+classes)]; out (logistic on objectness, softmax over the classes) and delta keep that layout.
+ * truth is [batch][150]: at most 30 rows of x, y, w, h, class per image, ended by the first x == 0; `seen` is *net.seen
+ * as the step sees it (the prior-box delta runs while it is < 12800).  delta_prev receives delta (a store: the head is
+ * the first writer of the layer in front), cost[0] = pow(mag_array(delta), 2) as a fixed-order two-pass sum, stats the
+ * figures the reference prints.  A truth whose cell (int)(x*w), (int)(y*h) lies outside the grid is skipped whole.
+ * anchors: 2*n floats in HBM.  scratch: y2h_train_region_scratch_bytes(g) bytes, 8-byte aligned.  No atomics. */
+typedef struct { int batch, h, w, n, classes, bias_match, rescore; float thresh, coord_scale, object_scale, noobject_scale, class_scale; } y2h_train_region;
+typedef struct { float avg_iou, avg_class, avg_obj, avg_noobj, recall; int count, class_count; } y2h_train_region_stats;
+size_t y2h_train_region_scratch_bytes(const y2h_train_region *g);
+int y2h_train_region_loss(const y2h_train_region *g, const float *in, const float *anchors, const float *truth, int seen, float *out,
+                          float *delta, float *delta_prev, float *cost, y2h_train_region_stats *stats, void *scratch, y2h_stream s);
+/* [route] on dense NHWC tensors of `pixels` = batch*h*w pixels: forward copies the source's c channels to channels
+ * off .. off+c-1 of the route's ldc; backward stores (add == 0) or adds that slice of the route's delta to the source's */
+int y2h_train_route_forward(const float *src, int c, float *dst, int ldc, int off, long pixels, y2h_stream s);
+int y2h_train_route_backward(const float *droute, int ldc, int off, float *dsrc, int c, long pixels, int add, y2h_stream s);
+int y2h_train_add(float *dst, const float *src, long n, y2h_stream s);                      /* dst += src */
+/* backward of a non-reverse [reorg] whose input is h x w x c (reorg_layer.c:92): the exact inverse of y2h_reorg(reverse = 0),
+ * an assignment.  dy is dense NHWC [h/stride][w/stride][c*stride*stride], dx dense NHWC [h][w][c]. */
+int y2h_train_reorg_backward(const float *dy, float *dx, int batch, int h, int w, int c, int stride, y2h_stream s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,17 +1,20 @@
 /*
  * Training on the device: host-side replacement for the other half of src_yolo2/network.c -- train_network_datum
  * (:225-243), backward_network (:197-215), update_network (:160-171), get_current_rate (:48-79) -- and for the
- * forward(train) / backward / update functions of the convolutional, batch-norm, maxpool, avgpool, softmax and cost
- * layers, whose loop nests run as the y2h_train_* kernels (y2_train.hip).
+ * forward(train) / backward / update functions of the convolutional, batch-norm, maxpool, avgpool, softmax, cost, route,
+ * reorg and region layers, whose loop nests run as the y2h_train_* kernels (y2_train.hip, y2_train_det.hip).
  *
  * The inference plan folds batch norm, fuses pooling and keeps weights in per-kernel layouts, so nothing of it is
  * reused: the trainer owns master parameters, their update buffers and per layer output / delta / x / x_norm / mean /
  * variance, all dense NHWC.  struct network and struct layer are untouched (layer.delta stays NULL); the schedule of
  * the [net] section lives in the engine.
  *
- * Every delta buffer is written exactly once per backward pass by the one layer behind it (there are no routes), so
- * the reference's "zero every delta, then add" (network.c:152-154, col2im_cpu, backward_maxpool_layer ...) is a plain
- * store here: 0 + v == v.
+ * The reference zeroes every delta in the forward pass (network.c:152-154); in the backward pass the consumers of a layer
+ * then add to its delta in descending layer order (col2im_cpu, backward_maxpool_layer, backward_route_layer ...), and
+ * [reorg] assigns.  plan_deltas walks that order once at prepare time: the first writer of a delta stores (0 + v == v),
+ * every later one adds -- its kernel writes into the staging buffer, which a step does not use otherwise, and one add
+ * follows -- and a reorg always stores.  A delta nobody writes keeps the zeros it was allocated with.  A network
+ * without [route] has one writer per delta and launches what it launched before routes were known here.
  */
 #include <math.h>
 #include <stdio.h>
@@ -25,15 +28,21 @@ typedef struct {
     float *mean, *variance, *mean_delta, *variance_delta;
     float *weights, *weight_updates, *biases, *bias_updates, *scales, *scale_updates, *rolling_mean, *rolling_variance;
     int *idx;                           /* [maxpool] winners */
-    float *cost;                        /* [cost]: one float */
+    float *cost;                        /* [cost], [region]: one float */
     y2h_train_conv g;
+    int din_add;                        /* this layer is not the first writer of the delta in front of it (plan_deltas) */
+    int *src_add;                       /* [route]: the same per source */
+    y2h_train_region rg;                /* [region]; its anchors are `biases`, 2*n floats */
+    y2h_train_region_stats *stats;
 } y2_tlayer;
 
 typedef struct y2_trainer {
     int n, batch;
     y2_tlayer *L;
     float *d_x_nchw, *d_x, *d_truth;    /* the step's input as given, as NHWC, and its truth */
-    float *ws, *scratch, *stage;        /* weight-gradient partial tiles, reduction partials, NCHW staging of y2_train_pull */
+    float *ws, *scratch, *stage;        /* weight-gradient partial tiles, reduction partials (and the region head's), NCHW staging
+                                           of y2_train_pull and landing buffer of a delta's later writers */
+    size_t truth_floats;                /* per step: batch * l.truths of a [region] head, batch * inputs of a [cost] */
     size_t stage_floats;
     float *h_cost, *h_in, *h_pull;      /* pinned: one float per layer; the host batch and truth of y2_train_step; the landing
                                            buffer of every copy down (stage_floats, at least the largest weight array) */
@@ -165,6 +174,11 @@ static int refuse(const network *net)
         }
         if (l->type == CONVOLUTIONAL || l->type == MAXPOOL) flat = l->out_h * l->out_w == 1 || l->out_c == 1;
         if (l->type == AVGPOOL) flat = 1;
+        if (l->type == ROUTE || l->type == REORG || l->type == REGION) flat = 0;
+        if ((l->type == ROUTE || l->type == REORG) && net->layers[net->n - 1].type != REGION) {
+            y2_fail("training: layer %d (%s) trains only in a network that ends in [region]", i, t);
+            return -1;
+        }
         switch (l->type) {
         case CONVOLUTIONAL:
             if (l->stride != 1) { y2_fail("training: layer %d (%s): stride %d is not trainable (stride 1 only)", i, t, l->stride); return -1; }
@@ -189,14 +203,50 @@ static int refuse(const network *net)
             if (i == 0) { y2_fail("training: layer %d (%s): a cost layer needs a layer in front of it", i, t); return -1; }
             if (i != net->n - 1) { y2_fail("training: layer %d (%s): only the last layer may be a cost layer (one truth per step)", i, t); return -1; }
             break;
+        case ROUTE:
+            if (l->n <= 0 || l->out_h <= 0 || l->out_w <= 0) { y2_fail("training: layer %d (%s): its sources must have one spatial size", i, t); return -1; }
+            break;
+        case REORG:
+            if (l->reverse) { y2_fail("training: layer %d (%s): reverse=1 is not trainable", i, t); return -1; }
+            if (i == 0 || l->stride <= 0 || l->h % l->stride || l->w % l->stride || l->c % (l->stride * l->stride)) {
+                y2_fail("training: layer %d (%s): %d x %d x %d does not divide by stride %d", i, t, l->w, l->h, l->c, l->stride);
+                return -1;
+            }
+            break;
+        case REGION:
+            if (l->softmax_tree || l->map) { y2_fail("training: layer %d (%s): tree= / map= is not trainable", i, t); return -1; }
+            if (l->classfix != 0) { y2_fail("training: layer %d (%s): classfix=%d is not trainable (0 only)", i, t, l->classfix); return -1; }
+            if (l->softmax != 1) { y2_fail("training: layer %d (%s): only softmax=1 is trainable", i, t); return -1; }
+            if (i != net->n - 1) { y2_fail("training: layer %d (%s): only the last layer may be a region layer (one truth per step)", i, t); return -1; }
+            if (i == 0 || l->classes <= 0 || net->layers[i - 1].out_h != l->h || net->layers[i - 1].out_w != l->w ||
+                net->layers[i - 1].out_c != l->n * (5 + l->classes)) {
+                y2_fail("training: layer %d (%s): the layer in front must give %d channels on the %d x %d grid", i, t, l->n * (5 + l->classes), l->w, l->h);
+                return -1;
+            }
+            break;
         default:
-            y2_fail("training: layer %d (%s) is not trainable (convolutional, maxpool, avgpool, softmax, cost)", i, t);
+            y2_fail("training: layer %d (%s) is not trainable (convolutional, maxpool, avgpool, softmax, cost, route, reorg, region)", i, t);
             return -1;
         }
     }
     if (net->h <= 0 || net->w <= 0 || net->c <= 0) { y2_fail("training: the network input must be an image (h, w, c > 0)"); return -1; }
-    if (net->layers[net->n - 1].type != COST) { y2_fail("training: layer %d (%s): the last layer must be [cost]", net->n - 1, get_layer_string(net->layers[net->n - 1].type)); return -1; }
+    if (net->layers[net->n - 1].type != COST && net->layers[net->n - 1].type != REGION) {
+        y2_fail("training: layer %d (%s): the last layer must be [cost] or [region]", net->n - 1, get_layer_string(net->layers[net->n - 1].type));
+        return -1;
+    }
     return 0;
+}
+
+static int truths_per_image(const network *net)
+{
+    const layer *last = &net->layers[net->n - 1];
+    return last->type == REGION ? last->truths : last->inputs;
+}
+
+int y2_train_truth_floats(network *net)
+{
+    if (!net || refuse(net) != 0) return -1;
+    return truths_per_image(net);
 }
 
 /* ------------------------------------------------------------------ */
@@ -218,6 +268,8 @@ void y2_train_free(network *net)
         size_t k;
         for (k = 0; k < sizeof all / sizeof all[0]; ++k) y2h_free(all[k]);
         y2h_free(L->idx);
+        y2h_free(L->stats);
+        free(L->src_add);
     }
     y2h_free(t->d_x_nchw); y2h_free(t->d_x); y2h_free(t->d_truth);
     y2h_free(t->ws); y2h_free(t->scratch); y2h_free(t->stage);
@@ -244,6 +296,25 @@ static int push(float *dst, const float *src, size_t n, float *pinned, y2_engine
 
 static size_t max_z(size_t a, size_t b) { return a > b ? a : b; }
 
+/* the reference's backward order (network.c:204-223), walked once: who finds a delta already written */
+static void plan_deltas(const network *net, y2_trainer *t)
+{
+    int *written = calloc(net->n, sizeof(int));
+    int i, k;
+    for (i = net->n - 1; i >= 0; --i) {
+        const layer *l = &net->layers[i];
+        y2_tlayer *L = &t->L[i];
+        if (l->type == ROUTE) {
+            L->src_add = calloc(l->n, sizeof(int));
+            for (k = 0; k < l->n; ++k) { L->src_add[k] = written[l->input_layers[k]]; written[l->input_layers[k]] = 1; }
+        } else if (i > 0) {
+            L->din_add = l->type == REORG ? 0 : written[i - 1];        /* reorg_layer.c:92 assigns */
+            written[i - 1] = 1;
+        }
+    }
+    free(written);
+}
+
 int y2_train_prepare(network *net)
 {
     y2_engine *e = y2_engine_of(net);
@@ -258,7 +329,9 @@ int y2_train_prepare(network *net)
     t = calloc(1, sizeof *t);
     t->n = net->n; t->batch = net->batch;
     t->L = calloc(net->n, sizeof *t->L);
+    t->truth_floats = (size_t)net->batch * truths_per_image(net);
     e->trainer = t;
+    plan_deltas(net, t);
     stage = (size_t)net->batch * net->inputs;
     for (i = 0; i < net->n; ++i) {
         const layer *l = &net->layers[i];
@@ -270,9 +343,9 @@ int y2_train_prepare(network *net)
     pin = t->h_pull;
     tmp = malloc(stage * sizeof(float));
     HIP_OR_CLEANUP(y2h_host_alloc((void **)&t->h_cost, (size_t)net->n * sizeof(float)));
-    HIP_OR_CLEANUP(y2h_host_alloc((void **)&t->h_in, ((size_t)net->batch * net->inputs + (size_t)net->batch * net->layers[net->n - 1].inputs) * sizeof(float)));
+    HIP_OR_CLEANUP(y2h_host_alloc((void **)&t->h_in, ((size_t)net->batch * net->inputs + t->truth_floats) * sizeof(float)));
     if (dev_floats(&t->d_x_nchw, (size_t)net->batch * net->inputs, e) || dev_floats(&t->d_x, (size_t)net->batch * net->inputs, e) ||
-        dev_floats(&t->d_truth, (size_t)net->batch * net->layers[net->n - 1].inputs, e)) goto cleanup;
+        dev_floats(&t->d_truth, t->truth_floats, e)) goto cleanup;
     for (i = 0; i < net->n; ++i) {
         const layer *l = &net->layers[i];
         y2_tlayer *L = &t->L[i];
@@ -280,6 +353,16 @@ int y2_train_prepare(network *net)
         if (dev_floats(&L->out, outs, e) || dev_floats(&L->delta, outs, e)) goto cleanup;
         if (l->type == MAXPOOL) HIP_OR_CLEANUP(y2h_malloc((void **)&L->idx, outs * sizeof(int)));
         if (l->type == COST && dev_floats(&L->cost, 1, e)) goto cleanup;
+        if (l->type == REGION) {
+            y2h_train_region rg = { net->batch, l->h, l->w, l->n, l->classes, l->bias_match, l->rescore, l->thresh, l->coord_scale,
+                                    l->object_scale, l->noobject_scale, l->class_scale };
+            L->rg = rg;
+            if (y2h_train_region_scratch_bytes(&rg) == 0) { y2_fail("training: layer %d (region): shape outside what the kernels take", i); goto cleanup; }
+            scratch = max_z(scratch, y2h_train_region_scratch_bytes(&rg));
+            if (dev_floats(&L->cost, 1, e) || dev_floats(&L->biases, (size_t)2 * l->n, e) ||
+                dev_floats((float **)&L->stats, sizeof(y2h_train_region_stats) / sizeof(float), e) ||
+                push(L->biases, l->biases, (size_t)2 * l->n, pin, e)) goto cleanup;
+        }
         if (l->type != CONVOLUTIONAL) continue;
         {
             const size_t nw = (size_t)l->n * l->c * l->size * l->size;
@@ -347,6 +430,22 @@ static int forward_train(network *net, y2_trainer *t, y2_engine *e)
         case COST:      /* forward and backward_cost_layer in one launch */
             HIP_OR_ERR(y2h_train_cost_sse(in, t->d_truth, L->out, L->delta, t->L[i - 1].delta, l->scale, (long)net->batch * l->inputs, L->cost, e->stream));
             break;
+        case ROUTE: {
+            int k, off = 0;
+            for (k = 0; k < l->n; ++k) {
+                const layer *src = &net->layers[l->input_layers[k]];
+                HIP_OR_ERR(y2h_train_route_forward(t->L[l->input_layers[k]].out, src->out_c, L->out, l->out_c, off,
+                                                   (long)net->batch * l->out_h * l->out_w, e->stream));
+                off += src->out_c;
+            }
+        } break;
+        case REORG:
+            HIP_OR_ERR(y2h_reorg(in, l->c, L->out, l->out_c, net->batch, l->h, l->w, l->c, l->stride, 0, e->stream));
+            break;
+        case REGION:    /* forward and backward_region_layer; the last layer, so the first writer of the delta in front */
+            HIP_OR_ERR(y2h_train_region_loss(&L->rg, in, L->biases, t->d_truth, *net->seen, L->out, L->delta, t->L[i - 1].delta, L->cost,
+                                             L->stats, t->scratch, e->stream));
+            break;
         default:
             return -1;
         }
@@ -362,7 +461,8 @@ static int backward_train(network *net, y2_trainer *t, y2_engine *e)
         const layer *l = &net->layers[i];
         y2_tlayer *L = &t->L[i];
         const float *in = i ? t->L[i - 1].out : t->d_x;
-        float *din = i ? t->L[i - 1].delta : NULL;          /* network.c:204-206: layer 0 has no state.delta */
+        float *own = i ? t->L[i - 1].delta : NULL;          /* network.c:204-206: layer 0 has no state.delta */
+        float *din = own && L->din_add ? t->stage : own;    /* a later writer lands in the staging buffer and is added below */
         switch (l->type) {
         case CONVOLUTIONAL: {
             const long rows = (long)net->batch * l->out_h * l->out_w;
@@ -388,11 +488,24 @@ static int backward_train(network *net, y2_trainer *t, y2_engine *e)
         case SOFTMAX:   /* softmax_layer.c:57-63: state.delta += l.delta */
             if (din) HIP_OR_ERR(y2h_memcpy_d2d(din, L->delta, (size_t)net->batch * l->inputs * sizeof(float), e->stream));
             break;
-        case COST:      /* done with its forward */
+        case COST: case REGION:     /* done with its forward */
+            break;
+        case ROUTE: {
+            int k, off = 0;
+            for (k = 0; k < l->n; ++k) {
+                const layer *src = &net->layers[l->input_layers[k]];
+                HIP_OR_ERR(y2h_train_route_backward(L->delta, l->out_c, off, t->L[l->input_layers[k]].delta, src->out_c,
+                                                    (long)net->batch * l->out_h * l->out_w, L->src_add[k], e->stream));
+                off += src->out_c;
+            }
+        } break;
+        case REORG:
+            HIP_OR_ERR(y2h_train_reorg_backward(L->delta, own, net->batch, l->h, l->w, l->c, l->stride, e->stream));
             break;
         default:
             return -1;
         }
+        if (own && L->din_add) HIP_OR_ERR(y2h_train_add(own, t->stage, (long)net->batch * net->layers[i - 1].outputs, e->stream));
     }
     return 0;
 }
@@ -423,7 +536,7 @@ static int step_enqueue(network *net, const float *d_x_nchw, const float *d_y, f
     float sum = 0;
     HIP_OR_ERR(y2h_nchw_to_nhwc(d_x_nchw, t->d_x, net->batch, net->c, net->h, net->w, net->c, e->stream));
     if (d_y != t->d_truth)
-        HIP_OR_ERR(y2h_memcpy_d2d(t->d_truth, d_y, (size_t)net->batch * net->layers[net->n - 1].inputs * sizeof(float), e->stream));
+        HIP_OR_ERR(y2h_memcpy_d2d(t->d_truth, d_y, t->truth_floats * sizeof(float), e->stream));
     t->dirty = 1;          /* from the first launch on: the forward pass already moves the rolling statistics */
     if (forward_train(net, t, e) != 0 || backward_train(net, t, e) != 0) return -1;
     if ((*net->seen / net->batch) % net->subdivisions == 0 && update_train(net, t, e) != 0) return -1;
@@ -468,7 +581,7 @@ int y2_train_step(network *net, const float *x, const float *y, float *loss)
     if (!x || !y) { y2_fail("y2_train_step: NULL input"); return -1; }
     if (!(t = trainer_for_step(net))) return -1;
     nx = (size_t)net->batch * net->inputs;
-    ny = (size_t)net->batch * net->layers[net->n - 1].inputs;
+    ny = t->truth_floats;
     /* pinned staging (h_in: nx + ny floats, made with the trainer): no pageable buffer of a caller is handed to an
      * asynchronous copy; the step's final wait is behind both copies, so the buffer is free again when it returns */
     memcpy(t->h_in, x, nx * sizeof(float));
@@ -531,11 +644,16 @@ int y2_train_pull(network *net, int i, int what, float *dst, size_t n)
     case Y2_TRAIN_ROLLING_MEAN: src = L->rolling_mean; break;
     case Y2_TRAIN_ROLLING_VARIANCE: src = L->rolling_variance; break;
     }
+    if (l->type == REGION && !image) src = NULL;             /* its `biases` are the anchors, not a trainable array */
     if (!src) { y2_fail("y2_train_pull: layer %d (%s) has no array %d", i, get_layer_string(l->type), what); return -1; }
     have = image ? (size_t)net->batch * l->outputs : weights ? (size_t)l->n * l->c * l->size * l->size : (size_t)l->n;
     if (n != have) { y2_fail("y2_train_pull: layer %d array %d holds %zu floats, not %zu", i, what, have, n); return -1; }
     HIP_OR_ERR(y2h_set_device(e->device));
-    if (image && (l->type == CONVOLUTIONAL || l->type == MAXPOOL) && l->out_h * l->out_w > 1) {
+    if (l->type == REGION && what == Y2_TRAIN_DELTA && l->h * l->w > 1) {      /* the reference un-flattens only the delta */
+        HIP_OR_ERR(y2h_nhwc_to_nchw(src, l->n * (5 + l->classes), t->stage, net->batch, l->n * (5 + l->classes), l->h, l->w, e->stream));
+        return pull_flat(e, t->stage, dst, n);
+    }
+    if (image && (l->type == CONVOLUTIONAL || l->type == MAXPOOL || l->type == ROUTE || l->type == REORG) && l->out_h * l->out_w > 1) {
         HIP_OR_ERR(y2h_nhwc_to_nchw(src, l->out_c, t->stage, net->batch, l->out_c, l->out_h, l->out_w, e->stream));
         return pull_flat(e, t->stage, dst, n);
     }
@@ -547,6 +665,19 @@ int y2_train_pull(network *net, int i, int what, float *dst, size_t n)
         return rc;
     }
     return pull_flat(e, src, dst, n);
+}
+
+int y2_train_region_stats(network *net, int i, y2_region_stats *out)
+{
+    y2_engine *e = y2_engine_of(net);
+    y2_trainer *t = e ? e->trainer : NULL;
+    if (!t) { y2_fail("y2_train_region_stats: no trainer (y2_train_prepare)"); return -1; }
+    if (i < 0 || i >= net->n || !out || !t->L[i].stats) { y2_fail("y2_train_region_stats: layer %d of %d is no [region] layer", i, net->n); return -1; }
+    HIP_OR_ERR(y2h_set_device(e->device));
+    HIP_OR_ERR(y2h_memcpy_d2h(t->h_pull, t->L[i].stats, sizeof(y2h_train_region_stats), e->stream));
+    HIP_OR_ERR(y2h_stream_sync(e->stream));
+    memcpy(out, t->h_pull, sizeof *out);     /* y2_region_stats and y2h_train_region_stats are one layout */
+    return 0;
 }
 
 int y2_train_is_dirty(const network *net)

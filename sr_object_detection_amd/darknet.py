@@ -149,6 +149,16 @@ class TrainConv(C.Structure):  # include/y2_hip.h y2h_train_conv: the shape of o
     _fields_ = [(k, C.c_int) for k in ("batch", "h", "w", "c", "n", "size", "pad", "out_h", "out_w")]
 
 
+class TrainRegion(C.Structure):  # include/y2_hip.h y2h_train_region: one [region] head in training mode
+    _fields_ = [(k, C.c_int) for k in ("batch", "h", "w", "n", "classes", "bias_match", "rescore")] + \
+               [(k, C.c_float) for k in ("thresh", "coord_scale", "object_scale", "noobject_scale", "class_scale")]
+
+
+class RegionStats(C.Structure):  # include/sr_yolo2.h y2_region_stats == include/y2_hip.h y2h_train_region_stats
+    _fields_ = [(k, C.c_float) for k in ("avg_iou", "avg_class", "avg_obj", "avg_noobj", "recall")] + \
+               [("count", C.c_int), ("class_count", C.c_int)]
+
+
 class RecArgs(C.Structure):  # include/y2_hip.h y2h_rec_args: one launch of y2h_rec_step
     _fields_ = [("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("mean", C.c_void_p), ("scale", C.c_void_p),
                 ("rinv", C.c_void_p), ("bn", C.c_int), ("act", C.c_int), ("pre", C.c_void_p), ("rows", C.c_int), ("k", C.c_int),
@@ -414,6 +424,15 @@ def lib():
     L.y2h_train_softmax.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]
     L.y2h_train_cost_sse.argtypes = [C.c_void_p] * 5 + [C.c_float, C.c_long, C.c_void_p, C.c_void_p]
     L.y2h_train_sgd.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_float, C.c_float, C.c_float, C.c_void_p]
+    L.y2_train_region_stats.argtypes = [C.POINTER(CNetwork), C.c_int, C.POINTER(RegionStats)]
+    L.y2_train_truth_floats.argtypes = [C.POINTER(CNetwork)]
+    L.y2h_train_region_scratch_bytes.restype = C.c_size_t
+    L.y2h_train_region_scratch_bytes.argtypes = [C.POINTER(TrainRegion)]
+    L.y2h_train_region_loss.argtypes = [C.POINTER(TrainRegion), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7
+    L.y2h_train_route_forward.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_long, C.c_void_p]
+    L.y2h_train_route_backward.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_void_p]
+    L.y2h_train_add.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]
+    L.y2h_train_reorg_backward.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]
     L.y2h_stream_k_launches.restype = C.c_ulong
     L.y2h_tail_launches.restype = C.c_ulong
     L.y2h_xcd_order_launches.restype = C.c_ulong
@@ -724,10 +743,12 @@ class Network:
             raise Y2Error("y2_train_prepare: " + _check())
 
     def train_step(self, x: np.ndarray, y: np.ndarray) -> float:
-        """one train_network_datum: x [batch][c][h][w], y [batch][outputs] -> the loss"""
+        """one train_network_datum: x [batch][c][h][w]; y [batch][outputs] for a network that ends in [cost],
+        [batch][30][x, y, w, h, class] (relative units, the list ends at the first x == 0) for one that ends in [region]
+        -> the loss"""
         x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
         y = np.ascontiguousarray(y, dtype=np.float32).reshape(-1)
-        if x.size != self.net.batch * self.net.inputs or y.size != self.net.batch * self.net.layers[self.net.n - 1].inputs:
+        if x.size != self.net.batch * self.net.inputs or y.size != self.net.batch * self.truth_floats():
             raise ValueError("train_step: x has %d floats, y has %d" % (x.size, y.size))
         loss = C.c_float(0)
         if lib().y2_train_step(C.byref(self.net), _ptr(x), _ptr(y), C.byref(loss)) != 0:
@@ -758,6 +779,20 @@ class Network:
         if lib().y2_train_pull(C.byref(self.net), layer, code, _ptr(out), n) != 0:
             raise Y2Error("y2_train_pull: " + _check())
         return out[:n]
+
+    def truth_floats(self) -> int:
+        """floats of truth per image of a training step: l.truths (150) behind a [region] head, the inputs of a [cost]"""
+        n = lib().y2_train_truth_floats(C.byref(self.net))
+        if n < 0:
+            raise Y2Error("y2_train_truth_floats: " + _check())       # a network the trainer refuses says so first
+        return n
+
+    def train_region_stats(self, layer: int = -1) -> dict:
+        """what the reference prints per forward_region_layer call, of the last step (NaN averages when count == 0)"""
+        st = RegionStats()
+        if lib().y2_train_region_stats(C.byref(self.net), layer if layer >= 0 else self.net.n - 1, C.byref(st)) != 0:
+            raise Y2Error("y2_train_region_stats: " + _check())
+        return {k: getattr(st, k) for k, _ in RegionStats._fields_}
 
     def train_free(self) -> None:
         lib().y2_train_free(C.byref(self.net))

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """What a training step costs on the device: Darknet-19 (cfg/darknet19.cfg: the trunk, 1x1 -> 1000, avgpool, softmax, cost)
-at 224x224, by default at batch 16 and batch 64.
+at 224x224, by default at batch 16 and batch 64; with --net tiny-yolo-voc or --net yolo the detector at 416x416 (batch 16 / 8
+by default) with its [region] head in training mode: yolo.cfg's training options, three truths per image.
 
 Per batch size:
   step      y2_train_step_device (input and truth already in HBM) after a warm-up: event times on the engine's stream
@@ -11,10 +12,15 @@ Per batch size:
             as ms and achieved TFLOP/s (2 * batch*out_h*out_w * size*size*c * n flops per product; dinput of layer 0 is
             timed although a step skips it)
   reference the wall-clock time of the same step through the compiled reference on this host (oracle/_ref/train_ref time,
-            built by `tests/golden/gen_train_golden.py --driver-only` where the reference checkout exists; OMP_NUM_THREADS
-            as the environment has it); skipped when the driver is not there or with --no-reference
+            built by `tests/golden/gen_train_golden.py --driver-only` where the reference checkout exists; for a detector
+            oracle/_ref/train_det_ref, by `tests/golden/gen_train_det_golden.py --driver-only`; OMP_NUM_THREADS as the
+            environment has it); skipped when the driver is not there or with --no-reference
 
-usage: train_latency.py [--batches 16,64] [--steps 10] [--warmup 3] [--reps 5] [--ref-batch 16] [--no-reference]
+A detector's row also names the launches of its head (y2_train_det.hip: region_cells, region_truths, region_sumsq,
+region_finish): their share of the step is read from one `rocprofv3 --kernel-trace --stats -- python tools/train_latency.py
+--net yolo --no-products --no-reference` run.
+
+usage: train_latency.py [--net darknet19|tiny-yolo-voc|yolo] [--batches 16,64] [--steps 10] [--warmup 3] [--reps 5] [--ref-batch 16] [--no-reference]
                         [--no-products] [--layers 4,18]"""
 import argparse
 import ctypes as C
@@ -30,8 +36,28 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from sr_object_detection_amd import darknet, synth, zoo  # noqa: E402
 
-SIZE = 224
-TRAIN_REF = os.path.join(ROOT, "oracle", "_ref", "train_ref")
+# name: (size, default batches, default reference batch, reference driver)
+NETS = {"darknet19": (224, "16,64", 16, "train_ref"), "tiny-yolo-voc": (416, "16", 16, "train_det_ref"), "yolo": (416, "8", 8, "train_det_ref")}
+# what cfg/yolo.cfg sets for training behind softmax=1
+REGION_TRAINING = "softmax=1\nbias_match=1\nrescore=1\nobject_scale=5\nnoobject_scale=1\nclass_scale=1\ncoord_scale=1\nthresh=.6\njitter=.3"
+
+
+def cfg_for(name, size, batch):
+    return zoo.cfg_text(name, size, size, batch).replace("softmax=1", REGION_TRAINING)
+
+
+def truth_for(net, batch):
+    """one-hot rows for a classifier; for a detector three boxes per image (the pattern of train_det_ref time)"""
+    per = net.truth_floats()
+    y = np.zeros((batch, per), np.float32)
+    last = net.layer(net.n - 1)
+    if last.type == darknet.LAYER_TYPES.index("REGION"):
+        for i in range(batch):
+            for t in range(3):
+                y[i, 5 * t:5 * t + 5] = (.2 + .3 * t, .7 - .2 * t, .1 + .15 * t, .4 - .1 * t, (i + t) % last.classes)
+    else:
+        y[np.arange(batch), np.arange(batch) % per] = 1
+    return y
 
 
 class Timer:
@@ -95,43 +121,44 @@ def products(net, timer, reps, only=None):
     return rows
 
 
-def reference_step(tmp, wts, batch, steps=2):
-    if not os.path.exists(TRAIN_REF):
+def reference_step(tmp, wts, name, size, batch, steps=2):
+    driver = os.path.join(ROOT, "oracle", "_ref", NETS[name][3])
+    if not os.path.exists(driver):
         return None
-    cfg = os.path.join(tmp, "d19_ref_b%d.cfg" % batch)
-    open(cfg, "w").write(zoo.cfg_text("darknet19", SIZE, SIZE, batch))
-    out = subprocess.run([TRAIN_REF, "time", cfg, wts, str(steps)], capture_output=True, text=True, check=True).stdout
+    cfg = os.path.join(tmp, "ref_b%d.cfg" % batch)
+    open(cfg, "w").write(cfg_for(name, size, batch))
+    out = subprocess.run([driver, "time", cfg, wts, str(steps)], capture_output=True, text=True, check=True).stdout
     secs = [float(line.split()[3]) for line in out.splitlines() if line.startswith("step")]
     return {"batch": batch, "threads": os.environ.get("OMP_NUM_THREADS", "unset"), "seconds_per_step": secs}
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--batches", default="16,64")
+    ap.add_argument("--net", default="darknet19", choices=sorted(NETS))
+    ap.add_argument("--batches", default=None)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--ref-batch", type=int, default=16)
+    ap.add_argument("--ref-batch", type=int, default=None)
     ap.add_argument("--no-reference", action="store_true")
     ap.add_argument("--no-products", action="store_true")
     ap.add_argument("--layers", default=None, help="only these layers' products, e.g. 4,18 (with --steps 0 --warmup 0 "
                     "--no-reference: the few launches a counter run wants, `rocprofv3 --pmc ... -- python tools/train_latency.py ...`)")
     a = ap.parse_args()
+    SIZE, batches, ref_batch = NETS[a.net][:3]
     L = darknet.lib()
     tmp = tempfile.mkdtemp()
-    wts = os.path.join(tmp, "d19.weights")
-    synth.write_weights(wts, zoo.resolve("darknet19", SIZE), 41, 1.0)
-    print("darknet19 at %d, device %s" % (SIZE, darknet.device_name()))
+    wts = os.path.join(tmp, "net.weights")
+    synth.write_weights(wts, zoo.resolve(a.net, SIZE), 41, 1.0)
+    print("%s at %d, device %s" % (a.net, SIZE, darknet.device_name()))
     out = []
-    for batch in [int(b) for b in a.batches.split(",")]:
-        cfg = os.path.join(tmp, "d19_b%d.cfg" % batch)
-        open(cfg, "w").write(zoo.cfg_text("darknet19", SIZE, SIZE, batch))
+    for batch in [int(b) for b in (a.batches or batches).split(",")]:
+        cfg = os.path.join(tmp, "net_b%d.cfg" % batch)
+        open(cfg, "w").write(cfg_for(a.net, SIZE, batch))
         net = darknet.Network.parse_network_cfg(cfg)
         net.load_weights(wts)
         net.train_prepare()
-        outputs = net.layer(net.n - 1).inputs
-        y = np.zeros((batch, outputs), np.float32)
-        y[np.arange(batch), np.arange(batch) % outputs] = 1
+        y = truth_for(net, batch)
         d_x = dev_floats(L, batch * net.net.inputs, synth.uniform(5, batch * net.net.inputs, -1, 1))
         d_y = dev_floats(L, y.size, y)
         timer = Timer(net.stream())
@@ -143,6 +170,8 @@ def main():
         if ms:
             res.update(step_p50_ms=round(p50(ms), 3), step_max_ms=round(max(ms), 3),
                        images_per_s=round(batch / (p50(ms) * 1e-3), 1), first_loss=losses[0], last_loss=losses[-1])
+        if ms and a.net != "darknet19":
+            res["region"] = {k: (None if v != v else v) for k, v in net.train_region_stats().items()}
         print("  " + json.dumps(res))
         if not a.no_products:
             res["products"] = products(net, timer, a.reps, None if a.layers is None else {int(v) for v in a.layers.split(",")})
@@ -152,10 +181,10 @@ def main():
         L.y2h_free(d_y)
         net.free()
         out.append(res)
-    ref = None if a.no_reference else reference_step(tmp, wts, a.ref_batch)
+    ref = None if a.no_reference else reference_step(tmp, wts, a.net, SIZE, a.ref_batch or ref_batch)
     if ref:
         print("  reference: " + json.dumps(ref))
-    print(json.dumps({"tool": "train_latency", "device": darknet.device_name(), "size": SIZE, "rows": out, "reference": ref}))
+    print(json.dumps({"tool": "train_latency", "device": darknet.device_name(), "net": a.net, "size": SIZE, "rows": out, "reference": ref}))
 
 
 if __name__ == "__main__":
