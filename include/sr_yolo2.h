@@ -698,6 +698,64 @@ void y2_train_free(network *net);
 /* The trainer's weight layout, [size][size][c][n], to and from the host's [n][c][size][size]: pure permutations. */
 void y2_train_pack_weights(const float *ref, float *packed, int n, int c, int size);
 void y2_train_unpack_weights(const float *packed, float *ref, int n, int c, int size);
+/* ------------------------------------------------------------------------- */
+/* The detection loader (data.c:664-714 load_data_detection): a training batch  */
+/* is built from 8-bit frames and label rows.  The draws and the truth are made */
+/* on the host, device-free (y2_aug.c); crop with jitter, the two-pass bilinear */
+/* resize, flip, the HSV distortion and the clamp run as one kernel that writes */
+/* the trainer's input where the step reads it.  The classifier loader          */
+/* (load_data_augment: rotation) and load_data_region stay with the caller.     */
+/* ------------------------------------------------------------------------- */
+/* One image of a batch: the frame as in y2_region (8-bit interleaved, h x w x c, `step` bytes between rows; channels
+ * past the third are skipped), the draws of load_data_detection, and the label rows as the label file holds them,
+ * boxes[nboxes][5] = id x y w h.  swaps[nboxes] are the indices randomize_boxes draws (row i is exchanged with row
+ * swaps[i], i ascending); NULL means no shuffle.  The window (pleft, ptop, swidth x sheight) may reach outside the frame on
+ * every side: edge pixels repeat (crop_image's constrain_int). */
+typedef struct {
+    const unsigned char *data; int h, w, c, step;
+    int pleft, ptop, swidth, sheight, flip;
+    float dhue, dsat, dexp;
+    const float *boxes; int nboxes;
+    const int *swaps;
+} y2_aug_item;
+/* The draws of one image, libc rand() called in exactly the reference's order: dw = (int)(ow * jitter), dh likewise; pleft,
+ * pright, ptop, pbot = rand_uniform_strong(-dw, dw) .. truncated to int; flip = random_gen() % 2; dhue =
+ * rand_uniform_strong(-hue, hue); dsat = rand_scale(saturation), dexp = rand_scale(exposure) (two calls each, 1. / scale in
+ * double); then the nboxes indices of randomize_boxes, written to swaps[] when it is not NULL (drawn either way).  Fills
+ * the draws of *item and sets item->swaps = swaps; the frame and the boxes of *item are not touched.  After srand(s),
+ * y2_aug_random_paths for the batch and then this call image by image give the reference's single-threaded sequence.
+ * (load_thread's `saturation == 0 -> 1`, `exposure == 0 -> 1` are the caller's: y2_net_augment reports what the cfg says.) */
+void y2_aug_draw_detection(int ow, int oh, float jitter, float hue, float saturation, float exposure, int nboxes,
+                           y2_aug_item *item, int *swaps);
+void y2_aug_random_paths(int n, int m, int *out);    /* get_random_paths (data.c:42): out[i] = random_gen() % m */
+int y2_aug_random_dim(void);                         /* detector.c:91-97, random=1: (rand() % 10 + 10) * 32; resize_network does the rest */
+/* The truth row of one image, truth[5 * num_boxes] (num_boxes = 30 for a [region] head): zeroed; randomize_boxes with
+ * item->swaps; correct_boxes with the dx, dy, 1./sx, 1./sy of data.c:693-707 in the reference's float / double promotions
+ * (a row with x == 0 && y == 0 becomes 999999, the flip, the constrains); fill_truth_detection.  That function's quirk is
+ * kept: a box whose corrected w or h is under .01 is skipped BUT KEEPS ITS SLOT, and the zero row it leaves ends the list for
+ * the region layer, which stops at the first x == 0 -- the boxes behind it are not trained on, as in the reference.
+ * 0, or -1 (y2_last_error) for a bad item.  Touches no device. */
+int y2_aug_truth_detection(const y2_aug_item *item, int num_boxes, float *truth);
+/* What train_detector reads of the cfg: jitter and random of the closing [region] layer, [net] hue / saturation / exposure
+ * (parser.c:532-534, defaults 0 / 1 / 1).  Any pointer may be NULL.  -1 for a network that does not end in [region]. */
+int y2_net_augment(network net, float *jitter, float *hue, float *saturation, float *exposure, int *random);
+/* load_data_detection's pixel and truth work for one batch, n == net.batch items, into the trainer (prepared lazily, as by
+ * train_network_datum): only the source rows and columns each window touches, the descriptor table and the n * 150 truth
+ * floats are packed into one pinned staging buffer and go up in one copy; one kernel writes the trainer's NHWC input, the
+ * truth is copied beside it.  The call returns once the copy has left the staging buffer.  Channel k of the input is byte
+ * k of a pixel, 2 - k with swap_rb (BGR frames).  Refused before any allocation, upload or launch, the item named in
+ * y2_last_error(): n != net.batch, net.c != 3, a network that does not end in [region] or that the trainer refuses, NULL
+ * data, c < 3, step < w * c, a frame without pixels, swidth < 1 or sheight < 1, nboxes < 0, nboxes > 0 with NULL boxes, a
+ * swap index outside the rows. */
+int y2_train_load_detection(network *net, const y2_aug_item *items, int n, int swap_rb);
+/* step_on_device on what y2_train_load_detection loaded; a second step on the same load is allowed.  Refused with nothing
+ * loaded, and after set_batch_network / resize_network dropped the trainer (load again). */
+int y2_train_step_loaded(network *net, float *loss);
+/* The loaded input as [batch][3][h][w] and the truth [batch][150], either may be NULL: for tests and callers that look. */
+int y2_train_pull_input(network *net, float *x_nchw, float *truth);
+/* Host wall time of the last y2_train_load_detection in ms: ms[0] pack (pixels, table, truth), ms[1] enqueueing the copy,
+ * the kernel and the truth copy, ms[2] waiting for the copy to leave the staging buffer. */
+int y2_train_load_times(network *net, float *ms);
 /* Copy layer i's activations to host as NCHW [batch][out_c][out_h][out_w] (or [batch][outputs]). */
 int y2_pull_layer_output(network net, int i, float *dst);
 /* Per-layer device time of the last forward in ms (needs y2_set_timing(net,1)); returns layers written. */

@@ -496,6 +496,32 @@ int y2h_regions_to_input_grasp(const y2h_region_f *desc, int n, const unsigned c
                                const unsigned short *grasp16, int W, int batch, int planes, int swap_rb, int h, int w,
                                float *dst, y2h_stream s);
 
+/* One item of y2h_augment_to_input: one image of load_data_detection (data.c:676-711).  `src` is a rectangle of the
+ * 8-bit interleaved frame, rw x rh pixels whose first pixel is the frame's (x0, y0); it must hold every pixel the window
+ * touches after constrain_int, i.e. columns clamp(pleft .. pleft + swidth - 1, 0, ow - 1) and the rows likewise (the kernel
+ * clamps its taps into the rectangle, which never acts for such a descriptor).  The window may reach outside the frame
+ * on every side.  The scales are computed on the host exactly as y2h_resize_chw computes them:
+ * (float)(swidth - 1) / (w - 1) and (float)(sheight - 1) / (h - 1). */
+typedef struct y2h_aug {
+    long long src;              /* byte offset of the rectangle's first pixel from `pixels` */
+    int pitch;                  /* bytes between its rows */
+    int c;                      /* bytes per pixel (>= 3) */
+    int x0, y0, rw, rh;         /* the rectangle inside the frame */
+    int ow, oh;                 /* frame size */
+    int pleft, ptop, swidth, sheight;       /* crop_image(orig, pleft, ptop, swidth, sheight) */
+    int flip;
+    float dhue, dsat, dexp;     /* distort_image(sized, dhue, dsat, dexp) */
+    float w_scale, h_scale;
+} y2h_aug;
+
+/* Fill the dense NHWC fp32 training input dst[n][h][w][3] in one launch: per output pixel the (float)(v / 255.) plane
+ * value, crop_image's constrain_int taps, resize_image's column and row pass, flip_image, rgb_to_hsv, the saturation and
+ * exposure scales, the hue shift with its two wraps, hsv_to_rgb and constrain_image (image.c), every expression in the
+ * reference's order and precision: bit for bit what that chain computes.  Channel k reads byte k of a pixel, 2 - k when
+ * swap_rb.  No atomics, no reductions: the output is a pure function of the table. */
+int y2h_augment_to_input(const y2h_aug *desc, int n, const unsigned char *pixels, int swap_rb, int h, int w, float *dst_nhwc,
+                         y2h_stream s);
+
 /* ---- depth stage of the Kinect loop (y2_depth.hip; KinectUtil_with_cam.cpp:394-442, :1482-1706) ---- */
 /* Register a dh x dw depth frame (and body-index frame, or NULL) to the H x W colour frame: for every colour pixel
  * (dx, dy) = y2_depth_coord of map[pixel] (NULL map: the pixel's own position, H == dh and W == dw); inside the depth

@@ -951,6 +951,7 @@ network parse_network_cfg(char *filename)    /* parser.c:585-700 */
     shape p;
     int count = 0;
     y2_lr_schedule lr;
+    float hue, saturation, exposure;
 
     memset(&empty, 0, sizeof empty);
     (void)y2_failed();                        /* a stale failure of an earlier call must not fail this parse */
@@ -978,6 +979,9 @@ network parse_network_cfg(char *filename)    /* parser.c:585-700 */
     net.inputs = option_find_int_quiet(s->options, "inputs", net.h * net.w * net.c);
     net.max_batches = option_find_int_quiet(s->options, "max_batches", 0);
     y2_lr_parse(s->options, &lr);
+    hue = option_find_float_quiet(s->options, "hue", 0);                  /* parser.c:532-534: the loader's, y2_net_augment */
+    saturation = option_find_float_quiet(s->options, "saturation", 1);
+    exposure = option_find_float_quiet(s->options, "exposure", 1);
     touch(s->options, net_quiet);
     if (!net.inputs && !(net.h && net.w && net.c)) { y2_fail("No input parameters supplied"); goto fail; }
     if (net.batch <= 0) { y2_fail("batch/subdivisions gives a batch of %d", net.batch); goto fail; }
@@ -1035,6 +1039,9 @@ network parse_network_cfg(char *filename)    /* parser.c:585-700 */
     net.outputs = net.layers[y2_out_layer(&net)].outputs;
     if (y2_engine_create(&net) != 0) goto fail;
     y2_engine_of(&net)->lr = lr;
+    y2_engine_of(&net)->aug_hue = hue;
+    y2_engine_of(&net)->aug_saturation = saturation;
+    y2_engine_of(&net)->aug_exposure = exposure;
     net.output = NULL;                        /* allocated with the plan; see get_network_output */
     return net;
 fail:                                         /* the schedule's lists belong to the engine, which does not exist */

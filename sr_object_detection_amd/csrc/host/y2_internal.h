@@ -178,6 +178,7 @@ typedef struct y2_engine {
     /* training (y2_train.c): the [net] section's learning-rate schedule, and the trainer once y2_train_prepare built it */
     y2_lr_schedule lr;
     struct y2_trainer *trainer;
+    float aug_hue, aug_saturation, aug_exposure;   /* [net] hue / saturation / exposure (parser.c:532-534): what y2_net_augment reports */
 } y2_engine;
 
 /* How the network input (fp32 NCHW) reaches layer 0: a plain NHWC copy; an NHWC copy with a zero border of in_halo_px
@@ -272,6 +273,12 @@ void y2_depth_free(y2_engine *e);
 int y2_train_is_dirty(const network *net);     /* steps ran since the masters last reached the host arrays */
 int y2_train_sync_if_dirty(network *net);      /* a trained network's masters reach the host arrays before they are read */
 void y2_lr_parse(list *options, y2_lr_schedule *lr);
+
+/* the detection loader's host half (y2_aug.c), device-free */
+int y2_aug_check(const char *who, const y2_aug_item *items, int n);        /* every refusal that reads only the items */
+void y2_aug_rect(const y2_aug_item *it, int *x0, int *y0, int *rw, int *rh);
+size_t y2_aug_pack_bytes(const y2_aug_item *items, int n);
+void y2_aug_pack(const y2_aug_item *items, int n, int net_w, int net_h, y2h_aug *desc, unsigned char *pixels);
 
 /* cfg helpers shared with other files */
 char *y2_fgetl(FILE *fp);

@@ -15,11 +15,16 @@
  * every later one adds -- its kernel writes into the staging buffer, which a step does not use otherwise, and one add
  * follows -- and a reorg always stores.  A delta nobody writes keeps the zeros it was allocated with.  A network
  * without [route] has one writer per delta and launches what it launched before routes were known here.
+ *
+ * The detection loader's trainer entries live here too (y2_train_load_detection, y2_train_step_loaded, y2_train_pull_input):
+ * data.c:664-714 load_data_detection with its pixel work as one kernel (y2_augment.hip) that writes the trainer's NHWC input
+ * in place; the draws, the truth and the packer are the device-free y2_aug.c.
  */
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <time.h>
 #include "y2_internal.h"
 
 typedef struct {
@@ -47,6 +52,13 @@ typedef struct y2_trainer {
     float *h_cost, *h_in, *h_pull;      /* pinned: one float per layer; the host batch and truth of y2_train_step; the landing
                                            buffer of every copy down (stage_floats, at least the largest weight array) */
     int dirty;                          /* steps ran since the masters last reached the host arrays */
+    /* y2_train_load_detection: descriptor table | truth | packed source pixels, staged in pinned memory and sent up in one
+     * copy (both grow-only); d_x and d_truth hold a loaded batch while `loaded` */
+    unsigned char *h_load, *d_load;
+    size_t h_load_cap, d_load_cap;
+    y2h_event ev_load;                  /* recorded behind that copy: the call waits for it before it returns */
+    int loaded;
+    float load_ms[3];                   /* the last load's host wall time: pack, enqueue (copy + launch), wait for the copy */
 } y2_trainer;
 
 /* ------------------------------------------------------------------ */
@@ -274,6 +286,8 @@ void y2_train_free(network *net)
     y2h_free(t->d_x_nchw); y2h_free(t->d_x); y2h_free(t->d_truth);
     y2h_free(t->ws); y2h_free(t->scratch); y2h_free(t->stage);
     y2h_host_free(t->h_cost); y2h_host_free(t->h_in); y2h_host_free(t->h_pull);
+    y2h_host_free(t->h_load); y2h_free(t->d_load);
+    if (t->ev_load) y2h_event_destroy(t->ev_load);
     free(t->L);
     free(t);
     e->trainer = NULL;
@@ -332,7 +346,7 @@ int y2_train_prepare(network *net)
     t->truth_floats = (size_t)net->batch * truths_per_image(net);
     e->trainer = t;
     plan_deltas(net, t);
-    stage = (size_t)net->batch * net->inputs;
+    stage = max_z((size_t)net->batch * net->inputs, t->truth_floats);       /* y2_train_pull_input lands the truth there */
     for (i = 0; i < net->n; ++i) {
         const layer *l = &net->layers[i];
         stage = max_z(stage, (size_t)net->batch * l->outputs);
@@ -527,14 +541,18 @@ static int update_train(network *net, y2_trainer *t, y2_engine *e)
     return 0;
 }
 
-/* everything of a step behind `*net.seen += net.batch` */
+/* everything of a step behind `*net.seen += net.batch`; d_x_nchw == NULL: the trainer's NHWC input is already in place
+ * (y2_train_load_detection) */
 static int step_enqueue(network *net, const float *d_x_nchw, const float *d_y, float *loss)
 {
     y2_engine *e = y2_engine_of(net);
     y2_trainer *t = e->trainer;
     int i, costs = 0;
     float sum = 0;
-    HIP_OR_ERR(y2h_nchw_to_nhwc(d_x_nchw, t->d_x, net->batch, net->c, net->h, net->w, net->c, e->stream));
+    if (d_x_nchw) {
+        t->loaded = 0;
+        HIP_OR_ERR(y2h_nchw_to_nhwc(d_x_nchw, t->d_x, net->batch, net->c, net->h, net->w, net->c, e->stream));
+    }
     if (d_y != t->d_truth)
         HIP_OR_ERR(y2h_memcpy_d2d(t->d_truth, d_y, t->truth_floats * sizeof(float), e->stream));
     t->dirty = 1;          /* from the first launch on: the forward pass already moves the rolling statistics */
@@ -597,6 +615,111 @@ float train_network_datum(network net, float *x, float *y)
     float loss = NAN;
     if (y2_train_step(&net, x, y, &loss) != 0) return NAN;
     return loss;
+}
+
+/* ------------------------------------------------------------------ */
+/* the detection loader (data.c:664-714): frames and label rows in      */
+/* ------------------------------------------------------------------ */
+int y2_net_augment(network net, float *jitter, float *hue, float *saturation, float *exposure, int *random)
+{
+    const y2_engine *e = y2_engine_of(&net);
+    const layer *last = net.layers && net.n > 0 ? &net.layers[net.n - 1] : NULL;
+    if (!e || !last) { y2_fail("y2_net_augment: network has no engine (was it built by parse_network_cfg?)"); return -1; }
+    if (last->type != REGION) { y2_fail("y2_net_augment: layer %d (%s): the network must end in [region]", net.n - 1, get_layer_string(last->type)); return -1; }
+    if (jitter) *jitter = last->jitter;
+    if (random) *random = last->random;
+    if (hue) *hue = e->aug_hue;
+    if (saturation) *saturation = e->aug_saturation;
+    if (exposure) *exposure = e->aug_exposure;
+    return 0;
+}
+
+static double now_ms(void)
+{
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
+}
+
+static int grow_load(y2_trainer *t, size_t need)
+{
+    if (need > t->h_load_cap) {
+        y2h_host_free(t->h_load); t->h_load = NULL; t->h_load_cap = 0;
+        HIP_OR_ERR(y2h_host_alloc((void **)&t->h_load, need));
+        t->h_load_cap = need;
+    }
+    if (need > t->d_load_cap) {
+        y2h_free(t->d_load); t->d_load = NULL; t->d_load_cap = 0;
+        HIP_OR_ERR(y2h_malloc((void **)&t->d_load, need));
+        t->d_load_cap = need;
+    }
+    if (!t->ev_load) HIP_OR_ERR(y2h_event_create(&t->ev_load));
+    return 0;
+}
+
+int y2_train_load_detection(network *net, const y2_aug_item *items, int n, int swap_rb)
+{
+    static const char who[] = "y2_train_load_detection";
+    y2_engine *e;
+    y2_trainer *t;
+    size_t desc_bytes, truth_bytes, need;
+    double t0, t1, t2;
+    float *truth;
+    int i, truths;
+    if (!net || !net->layers || net->n <= 0) { y2_fail("%s: no network", who); return -1; }
+    if (n != net->batch) { y2_fail("%s: %d items for a batch-%d network", who, n, net->batch); return -1; }
+    if (net->c != 3) { y2_fail("%s: the network reads %d channels, the loader makes 3", who, net->c); return -1; }
+    if (net->layers[net->n - 1].type != REGION) {
+        y2_fail("%s: layer %d (%s): the network must end in [region] (the truth is [batch][150])", who, net->n - 1,
+                get_layer_string(net->layers[net->n - 1].type));
+        return -1;
+    }
+    if (refuse(net) != 0 || y2_aug_check(who, items, n) != 0) return -1;
+    if (!(t = trainer_for_step(net))) return -1;
+    e = y2_engine_of(net);
+    truths = truths_per_image(net);
+    desc_bytes = align_up((size_t)n * sizeof(y2h_aug), 64);
+    truth_bytes = align_up(t->truth_floats * sizeof(float), 64);
+    need = desc_bytes + truth_bytes + y2_aug_pack_bytes(items, n);
+    t->loaded = 0;
+    /* the staging buffer is free: the last load waited for its copy before it returned */
+    if (grow_load(t, need) != 0) return -1;
+    t0 = now_ms();
+    y2_aug_pack(items, n, net->w, net->h, (y2h_aug *)t->h_load, t->h_load + desc_bytes + truth_bytes);
+    truth = (float *)(t->h_load + desc_bytes);
+    for (i = 0; i < n; ++i)
+        if (y2_aug_truth_detection(&items[i], truths / 5, truth + (size_t)i * truths) != 0) return -1;
+    t1 = now_ms();
+    HIP_OR_ERR(y2h_memcpy_h2d(t->d_load, t->h_load, need, e->stream));
+    HIP_OR_ERR(y2h_event_record(t->ev_load, e->stream));
+    HIP_OR_ERR(y2h_augment_to_input((const y2h_aug *)t->d_load, n, t->d_load + desc_bytes + truth_bytes, swap_rb, net->h, net->w, t->d_x,
+                                    e->stream));
+    HIP_OR_ERR(y2h_memcpy_d2d(t->d_truth, t->d_load + desc_bytes, t->truth_floats * sizeof(float), e->stream));
+    t2 = now_ms();
+    HIP_OR_ERR(y2h_event_sync(t->ev_load));
+    t->load_ms[0] = (float)(t1 - t0); t->load_ms[1] = (float)(t2 - t1); t->load_ms[2] = (float)(now_ms() - t2);
+    t->loaded = 1;
+    return 0;
+}
+
+int y2_train_step_loaded(network *net, float *loss)
+{
+    y2_engine *e = net ? y2_engine_of(net) : NULL;
+    y2_trainer *t = e ? e->trainer : NULL;
+    if (!t || !t->loaded || t->batch != net->batch) {
+        y2_fail("y2_train_step_loaded: nothing is loaded (y2_train_load_detection; set_batch_network and resize_network drop a load)");
+        return -1;
+    }
+    HIP_OR_ERR(y2h_set_device(e->device));
+    return step_on_device(net, NULL, t->d_truth, loss);
+}
+
+int y2_train_load_times(network *net, float *ms)
+{
+    y2_engine *e = net ? y2_engine_of(net) : NULL;
+    if (!e || !e->trainer || !ms) { y2_fail("y2_train_load_times: no trainer (y2_train_load_detection)"); return -1; }
+    memcpy(ms, e->trainer->load_ms, sizeof e->trainer->load_ms);
+    return 0;
 }
 
 /* ------------------------------------------------------------------ */
@@ -665,6 +788,20 @@ int y2_train_pull(network *net, int i, int what, float *dst, size_t n)
         return rc;
     }
     return pull_flat(e, src, dst, n);
+}
+
+int y2_train_pull_input(network *net, float *x_nchw, float *truth)
+{
+    y2_engine *e = net ? y2_engine_of(net) : NULL;
+    y2_trainer *t = e ? e->trainer : NULL;
+    if (!t || !t->loaded) { y2_fail("y2_train_pull_input: nothing is loaded (y2_train_load_detection)"); return -1; }
+    HIP_OR_ERR(y2h_set_device(e->device));
+    if (x_nchw) {
+        HIP_OR_ERR(y2h_nhwc_to_nchw(t->d_x, net->c, t->stage, net->batch, net->c, net->h, net->w, e->stream));
+        if (pull_flat(e, t->stage, x_nchw, (size_t)net->batch * net->inputs) != 0) return -1;
+    }
+    if (truth && pull_flat(e, t->d_truth, truth, t->truth_floats) != 0) return -1;
+    return 0;
 }
 
 int y2_train_region_stats(network *net, int i, y2_region_stats *out)

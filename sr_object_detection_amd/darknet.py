@@ -159,6 +159,20 @@ class RegionStats(C.Structure):  # include/sr_yolo2.h y2_region_stats == include
                [("count", C.c_int), ("class_count", C.c_int)]
 
 
+class AugItem(C.Structure):  # include/sr_yolo2.h y2_aug_item: one image of y2_train_load_detection
+    _fields_ = [("data", C.c_void_p), ("h", C.c_int), ("w", C.c_int), ("c", C.c_int), ("step", C.c_int),
+                ("pleft", C.c_int), ("ptop", C.c_int), ("swidth", C.c_int), ("sheight", C.c_int), ("flip", C.c_int),
+                ("dhue", C.c_float), ("dsat", C.c_float), ("dexp", C.c_float),
+                ("boxes", C.c_void_p), ("nboxes", C.c_int), ("swaps", C.c_void_p)]
+
+
+class Aug(C.Structure):      # include/y2_hip.h y2h_aug: one item of y2h_augment_to_input
+    _fields_ = [("src", C.c_longlong), ("pitch", C.c_int), ("c", C.c_int), ("x0", C.c_int), ("y0", C.c_int), ("rw", C.c_int),
+                ("rh", C.c_int), ("ow", C.c_int), ("oh", C.c_int), ("pleft", C.c_int), ("ptop", C.c_int), ("swidth", C.c_int),
+                ("sheight", C.c_int), ("flip", C.c_int), ("dhue", C.c_float), ("dsat", C.c_float), ("dexp", C.c_float),
+                ("w_scale", C.c_float), ("h_scale", C.c_float)]
+
+
 class RecArgs(C.Structure):  # include/y2_hip.h y2h_rec_args: one launch of y2h_rec_step
     _fields_ = [("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("mean", C.c_void_p), ("scale", C.c_void_p),
                 ("rinv", C.c_void_p), ("bn", C.c_int), ("act", C.c_int), ("pre", C.c_void_p), ("rows", C.c_int), ("k", C.c_int),
@@ -433,6 +447,17 @@ def lib():
     L.y2h_train_route_backward.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_void_p]
     L.y2h_train_add.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]
     L.y2h_train_reorg_backward.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]
+    L.y2_aug_draw_detection.restype = None
+    L.y2_aug_draw_detection.argtypes = [C.c_int, C.c_int] + [C.c_float] * 4 + [C.c_int, C.POINTER(AugItem), C.c_void_p]
+    L.y2_aug_random_paths.restype = None
+    L.y2_aug_random_paths.argtypes = [C.c_int, C.c_int, C.c_void_p]
+    L.y2_aug_truth_detection.argtypes = [C.POINTER(AugItem), C.c_int, C.c_void_p]
+    L.y2_net_augment.argtypes = [CNetwork] + [C.POINTER(C.c_float)] * 4 + [C.POINTER(C.c_int)]
+    L.y2_train_load_detection.argtypes = [C.POINTER(CNetwork), C.POINTER(AugItem), C.c_int, C.c_int]
+    L.y2_train_step_loaded.argtypes = [C.POINTER(CNetwork), C.POINTER(C.c_float)]
+    L.y2_train_pull_input.argtypes = [C.POINTER(CNetwork), C.c_void_p, C.c_void_p]
+    L.y2_train_load_times.argtypes = [C.POINTER(CNetwork), C.c_void_p]
+    L.y2h_augment_to_input.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.y2h_stream_k_launches.restype = C.c_ulong
     L.y2h_tail_launches.restype = C.c_ulong
     L.y2h_xcd_order_launches.restype = C.c_ulong
@@ -471,6 +496,68 @@ def regions(items):
         x, y, rw, rh = rect if rect is not None else (0, 0, 0, 0)
         arr[i] = Region(f.ctypes.data, h, w, c, f.strides[0], x, y, rw, rh)
     return arr, keep
+
+
+def aug_items(items):
+    """items: list of dicts -- frame (uint8 [h][w][c >= 3]; a view of a wider buffer keeps its row pitch), the draws pleft,
+    ptop, swidth, sheight, flip, dhue, dsat, dexp (default: the whole frame, unchanged), boxes (float32 [n][5] = id x y w h, or
+    None) and swaps (int32 [n], or None) -> (AugItem array, arrays kept alive for the call)"""
+    arr = (AugItem * max(len(items), 1))()
+    keep = []
+    for i, it in enumerate(items):
+        f = np.asarray(it["frame"])
+        if f.ndim != 3 or f.dtype != np.uint8 or f.strides[2] != 1 or f.strides[1] != f.shape[2] or f.strides[0] < f.shape[1] * f.shape[2]:
+            f = np.ascontiguousarray(f, dtype=np.uint8)
+            if f.ndim == 2:
+                f = f[:, :, None]
+        h, w, c = f.shape
+        boxes = it.get("boxes")
+        boxes = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 5) if boxes is not None and len(boxes) else None
+        swaps = it.get("swaps")
+        swaps = np.ascontiguousarray(swaps, dtype=np.int32) if swaps is not None and boxes is not None else None
+        keep += [f, boxes, swaps]
+        arr[i] = AugItem(f.ctypes.data, h, w, c, f.strides[0], it.get("pleft", 0), it.get("ptop", 0), it.get("swidth", w),
+                         it.get("sheight", h), int(it.get("flip", 0)), it.get("dhue", 0.), it.get("dsat", 1.), it.get("dexp", 1.),
+                         boxes.ctypes.data if boxes is not None else None, len(boxes) if boxes is not None else 0,
+                         swaps.ctypes.data if swaps is not None else None)
+    return arr, keep
+
+
+def aug_random_paths(n: int, m: int) -> np.ndarray:
+    """y2_aug_random_paths: get_random_paths' n draws of random_gen() % m, from libc rand()"""
+    out = np.zeros(max(n, 1), np.int32)
+    lib().y2_aug_random_paths(n, m, _ptr(out))
+    return out[:n]
+
+
+def aug_draw_detection(ow: int, oh: int, jitter: float, hue: float, saturation: float, exposure: float, nboxes: int) -> dict:
+    """y2_aug_draw_detection: one image's draws of load_data_detection, in the reference's rand() order -> the keys of
+    aug_items (without frame and boxes)"""
+    it = AugItem()
+    swaps = np.zeros(max(nboxes, 1), np.int32)
+    lib().y2_aug_draw_detection(ow, oh, jitter, hue, saturation, exposure, nboxes, C.byref(it), _ptr(swaps))
+    d = {k: getattr(it, k) for k in ("pleft", "ptop", "swidth", "sheight", "flip", "dhue", "dsat", "dexp")}
+    d["swaps"] = swaps[:nboxes]
+    return d
+
+
+def aug_random_dim() -> int:
+    """y2_aug_random_dim: train_detector's random=1 size, (rand() % 10 + 10) * 32"""
+    return int(lib().y2_aug_random_dim())
+
+
+def aug_truth_detection(item: dict, num_boxes: int = 30) -> np.ndarray:
+    """y2_aug_truth_detection: the truth row [num_boxes * 5] of one aug_items dict (its frame gives ow, oh)"""
+    arr, keep = aug_items([item])
+    out = np.zeros(num_boxes * 5, np.float32)
+    if lib().y2_aug_truth_detection(arr, num_boxes, _ptr(out)) != 0:
+        raise Y2Error("y2_aug_truth_detection: " + _check())
+    return out
+
+
+def srand(seed: int) -> None:
+    """libc srand: the loader's draws come from libc rand(), as the reference's do"""
+    C.CDLL(None).srand(C.c_uint(seed))
 
 
 def images(frames):
@@ -760,6 +847,41 @@ class Network:
         if lib().y2_train_step_device(C.byref(self.net), C.c_void_p(d_x), C.c_void_p(d_y), C.byref(loss)) != 0:
             raise Y2Error("y2_train_step_device: " + _check())
         return float(loss.value)
+
+    def net_augment(self) -> dict:
+        """y2_net_augment: jitter and random of the closing [region] layer, [net] hue / saturation / exposure"""
+        f = [C.c_float(0) for _ in range(4)]
+        r = C.c_int(0)
+        if lib().y2_net_augment(self.net, *[C.byref(v) for v in f], C.byref(r)) != 0:
+            raise Y2Error("y2_net_augment: " + _check())
+        return dict(jitter=f[0].value, hue=f[1].value, saturation=f[2].value, exposure=f[3].value, random=r.value)
+
+    def train_load_detection(self, items, swap_rb: bool = False) -> None:
+        """y2_train_load_detection: one batch of aug_items dicts -> the trainer's input and truth, built on the device"""
+        arr, keep = aug_items(items)
+        if lib().y2_train_load_detection(C.byref(self.net), arr, len(items), int(swap_rb)) != 0:
+            raise Y2Error("y2_train_load_detection: " + _check())
+
+    def train_step_loaded(self) -> float:
+        loss = C.c_float(0)
+        if lib().y2_train_step_loaded(C.byref(self.net), C.byref(loss)) != 0:
+            raise Y2Error("y2_train_step_loaded: " + _check())
+        return float(loss.value)
+
+    def train_pull_input(self):
+        """the loaded batch as the reference holds it: x [batch][3][h][w], truth [batch][150]"""
+        x = np.zeros((self.net.batch, self.net.c, self.net.h, self.net.w), np.float32)
+        y = np.zeros((self.net.batch, 150), np.float32)
+        if lib().y2_train_pull_input(C.byref(self.net), _ptr(x), _ptr(y)) != 0:
+            raise Y2Error("y2_train_pull_input: " + _check())
+        return x, y
+
+    def train_load_times(self) -> tuple:
+        """host wall ms of the last load: (pack, enqueue, wait for the copy)"""
+        ms = np.zeros(3, np.float32)
+        if lib().y2_train_load_times(C.byref(self.net), _ptr(ms)) != 0:
+            raise Y2Error("y2_train_load_times: " + _check())
+        return tuple(float(v) for v in ms)
 
     def train_sync(self) -> None:
         if lib().y2_train_sync(C.byref(self.net)) != 0:
