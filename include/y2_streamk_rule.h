@@ -1,7 +1,6 @@
 /*
- * The stream-K share rule.  conv_mfma_kernel's stream-K and hybrid forms take their share from y2_sk_share_of; the launches
- * that add the pieces up (sk_reduce_kernel, conv_p8_fixup_kernel) start at y2_sk_first and go by y2_sk_walk; the hybrid's
- * finisher starts at y2_sk_first and writes the walk out on y2_sk_begin (it stops at its own share).  conv_p8_f16_kernel
+ * The stream-K share rule.  conv_mfma_kernel's stream-K form takes its share from y2_sk_share_of; the launches that add
+ * the pieces up (sk_reduce_kernel, conv_p8_fixup_kernel) start at y2_sk_first and go by y2_sk_walk.  conv_p8_f16_kernel
  * still writes y2_sk_share_of out on y2_sk_begin (its comment says why).  Plain integer arithmetic, host and device alike.
  *
  * `tiles` output tiles of `nk` K-steps each are I = tiles * nk K-steps in tile-major order.  Workgroup w of G owns the
@@ -10,8 +9,8 @@
  * PRECONDITION: 1 <= tiles <= G and nk >= 1 (y2_sk_fits).  Then a share is never longer than one tile, so it is empty,
  * one piece (tile, [kb0, ke0)), or that piece up to the end of its tile plus the head [0, ke1) of the next tile.
  *
- * Slots are the callers' business: 2 * w + piece where both pieces of a share are stored (conv_mfma_kernel's stream-K
- * form, conv_p8_f16_kernel), w where only the piece that does not end its tile is (the hybrid form's producer).
+ * Slots are the callers' business: 2 * w + piece, both pieces of a share stored (conv_mfma_kernel's stream-K form,
+ * conv_p8_f16_kernel).
  */
 #ifndef Y2_STREAMK_RULE_H
 #define Y2_STREAMK_RULE_H

@@ -64,16 +64,14 @@
 // ---------------------------------------------------------------------------
 // MFMA implicit GEMM
 // ---------------------------------------------------------------------------
-__device__ int g_skh_timeouts = 0;     // hybrid stream-K: flag waits that gave up (a bug or a lost workgroup; results of that launch are wrong)
-template <int BM, int BN, int BK, int KS, int WM, int WN, bool XO = false, int SKMODE = 0, bool WG = false>
+template <int BM, int BN, int BK, int KS, int WM, int WN, bool XO = false, bool SKM = false, bool WG = false>
 __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
 {
     // WG (the batched GEMM of the Winograd path, 1x1 tiles only): the GEMM rows are sixteen components of a.tiles_m pixel tiles
     // each, component g multiplies by the weight block g (a.Cout rows of a.K), and the sums leave raw: no batch-norm, bias or
     // activation, 16-byte stores.  A template parameter like XO: every other instantiation compiles to what it was.
-    static_assert(!WG || (KS == 1 && !XO && SKMODE == 0), "the Winograd GEMM is a plain 1x1 tile walk");
-    constexpr bool SKM = SKMODE == 1;     // stream-K over ALL tiles, pieces finished by sk_reduce_kernel (grids smaller than the machine)
-    constexpr bool SKH = SKMODE == 2;     // hybrid: whole tiles + the last partial round cut along K, finished inside this launch
+    // SKM: stream-K over ALL tiles, pieces finished by sk_reduce_kernel (grids smaller than the machine)
+    static_assert(!WG || (KS == 1 && !XO && !SKM), "the Winograd GEMM is a plain 1x1 tile walk");
     constexpr int NT = WM * WN * 64;
     constexpr int LS = BK + 4;            // LDS row stride (floats); (LS/4) odd -> conflict-free b128 reads
     constexpr int CH = BK / 4;            // 16-byte chunks per staged row
@@ -122,33 +120,18 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
     // at most two work items = pieces (tile, K range); work item v in {0, 1} is piece v, its raw sums go to workspace slot
     // 2 * wg + v in tile-local layout [BM][BN], and sk_reduce_kernel adds a tile's pieces in ascending K order.  Against
     // the integer split-K above every workgroup gets the same number of K-steps whatever the tile count.
-    // SKH (hybrid stream-K, grids of several rounds: batch 32): the first ndp = ntiles - sk_tiles output tiles are walked whole
-    // (b, b + G, ...); the K loops of the last sk_tiles tiles -- the partial last round -- are dealt in equal contiguous
-    // shares to ALL G workgroups, again at most two pieces each.  A piece that does not reach the end of its tile's K loop
-    // ("producer"; at most one per workgroup) leaves its raw sums in slot wg and raises that slot's flag; the piece that does ("finisher")
-    // waits for the flags of the tile's earlier pieces, adds their sums to its accumulators and runs the ordinary epilogue.
-    // A workgroup computes its producer piece FIRST, then its finisher piece, then its whole tiles: no producer ever waits,
-    // so the hand-off cannot deadlock (workgroups are dispatched in order: a finisher's producers, all lower-numbered,
-    // are on the machine before it), and by the time a finisher has computed its own piece its producers, who started at the
-    // same moment with a piece no longer than the finisher's share, have published.  Work-item codes in SKH: 0 .. ndp - 1 a
-    // whole tile, ntiles + v piece v of this workgroup (v = 0: in tile sk_t0, from sk_kb0; v = 1: the head of tile sk_t0 + 1).
-    const int ndp = SKH ? a.ntiles - a.sk_tiles : 0;
     int n_sk = 0, sk_t0 = 0, sk_kb0 = 0, sk_ke0 = 0, sk_ke1 = 0;
-    if constexpr (SKM || SKH) {       // this workgroup's share of the sk_tiles cut tiles, which follow the ndp whole ones
+    if constexpr (SKM) {       // this workgroup's share of the sk_tiles cut tiles
         const y2_sk_share sh = y2_sk_share_of(blockIdx.x, a.sk_tiles, nk, a.sk_wgs);
-        n_sk = sh.n; sk_t0 = ndp + sh.tile; sk_kb0 = sh.kb0; sk_ke0 = sh.ke0; sk_ke1 = sh.ke1;
+        n_sk = sh.n; sk_t0 = sh.tile; sk_kb0 = sh.kb0; sk_ke0 = sh.ke0; sk_ke1 = sh.ke1;
     }
-    const int END = SKM ? 2 : SKH ? a.ntiles + 2 : a.ntiles;       // work-item number that means "past the end"
+    const int END = SKM ? 2 : a.ntiles;       // work-item number that means "past the end"
     auto setup_tile = [&](int vtile) {
     const bool live = vtile < END;
-    const bool piece = SKH && vtile >= a.ntiles;                   // (SKH) a stream-K piece of this workgroup
-    const int tile = SKM ? sk_t0 + (vtile & 1) : piece ? sk_t0 + (vtile - a.ntiles) : vtile / a.ksplit;
-    const int kb = SKM ? (vtile == 0 ? sk_kb0 : 0)
-                 : SKH ? (piece && vtile == a.ntiles ? sk_kb0 : 0)
-                       : ((vtile - tile * a.ksplit) * nk) / a.ksplit;     // first slice of this work item
+    const int tile = SKM ? sk_t0 + (vtile & 1) : vtile / a.ksplit;
+    const int kb = SKM ? (vtile == 0 ? sk_kb0 : 0) : ((vtile - tile * a.ksplit) * nk) / a.ksplit;     // first slice of this work item
     s_n = !live ? 0x40000000                                                                       // past the end: never hop again
           : SKM ? (vtile == 0 ? sk_ke0 - sk_kb0 : sk_ke1)
-          : SKH ? (!piece ? nk : vtile == a.ntiles ? sk_ke0 - sk_kb0 : sk_ke1)
                 : (((vtile - tile * a.ksplit) + 1) * nk) / a.ksplit - kb;
     c0 = (kb / (KS * KS)) * BK;
     tap = kb % (KS * KS);
@@ -191,11 +174,7 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
     // i-th tile of this workgroup (a.ntiles = none): b, b+G, b+2G, ...  (Cutting the tile range into
     // one contiguous chunk per XCD, so that neighbouring pixel tiles share halo rows in one L2, was
     // measured slower on every layer: profiles/r01_notes.md.)
-    int wgid = blockIdx.x;
-    if (a.dbg & 64) {         // A/B (env Y2_CONV_XCD_REMAP): XCD-contiguous tile numbers (bijective for any grid)
-        const int nwg = gridDim.x, xcd = wgid & 7, q = nwg >> 3, r = nwg & 7;
-        wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (wgid >> 3);
-    }
+    const int wgid = blockIdx.x;
     auto tile_at = [&](int i) -> int {
         if constexpr (XO) {        // (a template parameter: as a run-time switch its scalar state costs the 192x256 kernel 88 B more scratch per lane)
             // work list of XCD x: for each block of pblk pixel tiles, for each of its filter tiles x, x + 8, ..., the block's
@@ -216,11 +195,6 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
             return (pb * a.pblk + pi) * a.tiles_n + xcd + 8 * fi;
         }
         if constexpr (SKM) return i < n_sk ? i : END;
-        if constexpr (SKH) {
-            if (i < n_sk) return a.ntiles + (n_sk == 2 ? 1 - i : 0);          // the producer piece (head of the next tile) first
-            const long tl = (long)blockIdx.x + (long)(i - n_sk) * gridDim.x;
-            return tl < ndp ? (int)tl : END;
-        }
         const long tl = (long)wgid + (long)i * gridDim.x;
         return tl < a.ntiles ? (int)tl : a.ntiles;
     };
@@ -304,7 +278,7 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
     int cur = 0;
 #ifdef Y2_F32_STAMPS
     // diagnostic: cycles per wave in [0] tile setup + accumulator clear, [1] K loop, [2] epilogue; [3] K-steps, [4] tiles
-    unsigned long long st[7] = {0, 0, 0, 0, 0, 0, 0}, st_bar = 0, st_prev = __builtin_amdgcn_s_memtime();      // [5] producer publish, [6] finisher wait + gather (hybrid stream-K)
+    unsigned long long st[5] = {0, 0, 0, 0, 0}, st_bar = 0, st_prev = __builtin_amdgcn_s_memtime();
 #define F32_STAMP(k) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st[k] += t_ - st_prev; st_prev = t_; } while (0)
 #else
 #define F32_STAMP(k) do { } while (0)
@@ -312,20 +286,11 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
     for (int cti = 0;; ++cti) {
     const int vt = tile_at(cti);
     if (vt >= END) break;
-    const bool piece = SKH && vt >= a.ntiles;
-    const int ct = SKM ? sk_t0 + vt : piece ? sk_t0 + (vt - a.ntiles) : vt / a.ksplit;
-    const int ks = SKM ? 2 * (int)blockIdx.x + vt : piece ? (int)blockIdx.x : vt - ct * a.ksplit;       // SKM: piece slot; SKH: a workgroup has at most ONE producer piece, slot = workgroup
-    const int kb = SKM ? (vt == 0 ? sk_kb0 : 0) : SKH ? (piece && vt == a.ntiles ? sk_kb0 : 0) : (ks * nk) / a.ksplit;
-    const int ke = SKM ? (vt == 0 ? sk_ke0 : sk_ke1) : SKH ? (!piece ? nk : vt == a.ntiles ? sk_ke0 : sk_ke1) : ((ks + 1) * nk) / a.ksplit;
+    const int ct = SKM ? sk_t0 + vt : vt / a.ksplit;
+    const int ks = SKM ? 2 * (int)blockIdx.x + vt : vt - ct * a.ksplit;       // SKM: piece slot
+    const int kb = SKM ? (vt == 0 ? sk_kb0 : 0) : (ks * nk) / a.ksplit;
+    const int ke = SKM ? (vt == 0 ? sk_ke0 : sk_ke1) : ((ks + 1) * nk) / a.ksplit;
     const int p0 = (ct / a.tiles_n) * BM, n0 = (ct % a.tiles_n) * BN;
-    if constexpr (SKH) {
-        // Every vector-memory operation retired before a work item starts, as a wait the compiler's waitcnt pass SEES (an asm
-        // wait is invisible to it): otherwise a register reload issued in front of the tile loop stays "pending" in the pass's
-        // merged state at the K loop's header, and the K-step opens with vmcnt(4) / vmcnt(0) -- the slice loads issued under
-        // the previous step's last MFMA group get 1 300 cycles of cover instead of 4 500 (K-step 12.8 k -> 16.2 k cycles).
-        // Costs the tail of the previous item's stores once per work item.
-        __builtin_amdgcn_s_waitcnt(0x0F70);       // vmcnt(0) expcnt(7) lgkmcnt(15)
-    }
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -548,67 +513,6 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
                 __builtin_amdgcn_sched_barrier(0);
             }
     };
-    if constexpr (SKH) {
-        constexpr int NE = TM * TN * 4;                   // 16-byte groups of accumulators per lane
-        if (piece && ke < nk) {
-            // producer: the raw sums leave as the lanes hold them, NE coalesced 16-byte write-through (sc1) stores per lane into
-            // [slot][e][thread]; every wave drains its stores, then ONE lane raises the flag (MI355X hand-off rules: sc1 payload,
-            // vmcnt(0) in asm -- the compiler may drop a waitcnt it thinks redundant --, sc1 flag)
-            const __amdgpu_buffer_rsrc_t pr = __builtin_amdgcn_make_buffer_rsrc((void *)(a.ws + (size_t)ks * (BM * BN)), 0, (unsigned)(BM * BN * 4), 0x00020000);
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const f32x4 v = {acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]};
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), pr, (unsigned)((((i * TN + j) * 4 + q) * NT + t) * 16), 0, 16);
-                    }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            if (t == 0) __hip_atomic_store(a.sk_flags + ks, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            F32_STAMP(5);
-            continue;
-        }
-        if (piece && kb > 0) {
-            // finisher: the earlier pieces of this tile belong to the workgroups below this one whose shares reach into it
-            // (y2_sk_walk of y2_streamk_rule.h from the tile's first share, stopped at this workgroup's own share -- written out on
-            // y2_sk_begin, empty shares skipped: through y2_sk_walk the 128x128 form spills one register more; slot = producer workgroup)
-            const long w0 = y2_sk_first(ct - ndp, a.sk_tiles, nk, a.sk_wgs);
-            const long I = (long)a.sk_tiles * nk, G = a.sk_wgs;
-            if (t == 0) {
-                for (long w = w0; w < (long)blockIdx.x; ++w) {
-                    if (y2_sk_begin(w + 1, I, G) <= y2_sk_begin(w, I, G)) continue;
-                    int *fl = a.sk_flags + w;
-                    int spins = 0;
-                    while (__hip_atomic_load(fl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 1) {
-                        if (++spins > (1 << 22)) { atomicAdd(&g_skh_timeouts, 1); break; }        // seconds: counted (y2h_f32_stream_k_timeouts), never a hang
-                        __builtin_amdgcn_s_sleep(4);
-                    }
-                }
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // (the polling lane's last load has returned; see above)
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");                          // no payload load may be scheduled in front of the barrier
-            for (long w = w0; w < (long)blockIdx.x; ++w) {
-                if (y2_sk_begin(w + 1, I, G) <= y2_sk_begin(w, I, G)) continue;
-                const size_t slot = (size_t)w;
-                const __amdgpu_buffer_rsrc_t pr = __builtin_amdgcn_make_buffer_rsrc((void *)(a.ws + slot * (BM * BN)), 0, (unsigned)(BM * BN * 4), 0x00020000);
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(pr, (unsigned)((((i * TN + j) * 4 + q) * NT + t) * 16), 0, 16));
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) acc[i][j][4 * q + e] += v[e];
-                        }
-            }
-            F32_STAMP(6);
-        }
-    }
     if constexpr (WG) {
         epilogue_pass(std::integral_constant<int, 3>{}, std::true_type{});
         if (!ES_OWN) {
@@ -637,7 +541,7 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void conv_mfma_kernel(ConvK a)
     }   // tile loop
 #ifdef Y2_F32_STAMPS
     if (lane == 0 && a.stamps)
-        for (int k = 0; k < 7; ++k) a.stamps[((size_t)blockIdx.x * (NT / 64) + wv) * 7 + k] = (k == 0) ? st_bar : st[k];      // [0]: barrier wait (setup dropped)
+        for (int k = 0; k < 5; ++k) a.stamps[((size_t)blockIdx.x * (NT / 64) + wv) * 5 + k] = (k == 0) ? st_bar : st[k];      // [0]: barrier wait (setup dropped)
 #endif
 }
 
@@ -1283,26 +1187,25 @@ struct Variant {
     int threads;
     void (*fn_xo)(ConvK);  // the same tile with the XCD-grouped tile order (ConvK.xcd_order), where instantiated
     void (*fn_sk)(ConvK);  // the same tile with stream-K work items (ConvK.sk_tiles / sk_wgs), where instantiated
-    void (*fn_skh)(ConvK); // the same tile, hybrid: whole tiles + the last partial round as stream-K pieces finished in the launch
     void (*fn_wg)(ConvK);  // the same tile as the batched GEMM of the Winograd path (1x1 tiles the rule may pick)
 };
 
 #define VAR(BM, BN, BK, KS, WM, WN)                                                             \
     { "conv_mfma_f32_" #BM "x" #BN "x" #BK "_k" #KS, BM, BN, BK, KS, conv_mfma_kernel<BM, BN, BK, KS, WM, WN>, \
-      (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float) + (WM * WN == 8 ? (size_t)8 * 16 * 36 * sizeof(float) : 0), WM * WN * 64, nullptr, nullptr, nullptr }
+      (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float) + (WM * WN == 8 ? (size_t)8 * 16 * 36 * sizeof(float) : 0), WM * WN * 64, nullptr, nullptr }
 #define VARSK(BM, BN, BK, KS, WM, WN)                                                           \
     { "conv_mfma_f32_" #BM "x" #BN "x" #BK "_k" #KS, BM, BN, BK, KS, conv_mfma_kernel<BM, BN, BK, KS, WM, WN>, \
       (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float) + (WM * WN == 8 ? (size_t)8 * 16 * 36 * sizeof(float) : 0), WM * WN * 64, \
-      nullptr, conv_mfma_kernel<BM, BN, BK, KS, WM, WN, false, 1>, conv_mfma_kernel<BM, BN, BK, KS, WM, WN, false, 2> }
+      nullptr, conv_mfma_kernel<BM, BN, BK, KS, WM, WN, false, true> }
 #define VARXO(BM, BN, BK, KS, WM, WN)                                                           \
     { "conv_mfma_f32_" #BM "x" #BN "x" #BK "_k" #KS, BM, BN, BK, KS, conv_mfma_kernel<BM, BN, BK, KS, WM, WN>, \
       (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float) + (WM * WN == 8 ? (size_t)8 * 16 * 36 * sizeof(float) : 0), WM * WN * 64, \
-      conv_mfma_kernel<BM, BN, BK, KS, WM, WN, true>, nullptr, nullptr }
+      conv_mfma_kernel<BM, BN, BK, KS, WM, WN, true>, nullptr }
 
 #define VARWG(BM, BN, BK, KS, WM, WN)                                                           \
     { "conv_mfma_f32_" #BM "x" #BN "x" #BK "_k" #KS, BM, BN, BK, KS, conv_mfma_kernel<BM, BN, BK, KS, WM, WN>, \
       (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float) + (WM * WN == 8 ? (size_t)8 * 16 * 36 * sizeof(float) : 0), WM * WN * 64, \
-      conv_mfma_kernel<BM, BN, BK, KS, WM, WN, true>, nullptr, nullptr, conv_mfma_kernel<BM, BN, BK, KS, WM, WN, false, 0, true> }
+      conv_mfma_kernel<BM, BN, BK, KS, WM, WN, true>, nullptr, conv_mfma_kernel<BM, BN, BK, KS, WM, WN, false, false, true> }
 
 static Variant g_variants[] = {
     // 8 waves (2 per SIMD), ONE workgroup per CU: the co-resident partner wave that hides LDS/barrier
@@ -1331,16 +1234,15 @@ extern "C" unsigned long y2h_xcd_order_launches(void) { return g_xcd_order_launc
 static void f32_stamps_report(const Variant *v, const y2h_conv *d, long grid, unsigned long long *d_st, y2h_stream s)
 {
     if (!getenv("Y2_F32_STAMPS")) return;
-    static unsigned long long h[1024 * 8 * 7];
+    static unsigned long long h[1024 * 8 * 5];
     if (hipStreamSynchronize(S(s)) != hipSuccess || hipMemcpy(h, d_st, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) return;
-    double tot[7] = {0, 0, 0, 0, 0, 0, 0};
+    double tot[5] = {0, 0, 0, 0, 0};
     const int waves = v->threads / 64;
-    for (long b = 0; b < grid; ++b) for (int w = 0; w < waves; ++w) for (int k = 0; k < 7; ++k) tot[k] += (double)h[(b * waves + w) * 7 + k];
+    for (long b = 0; b < grid; ++b) for (int w = 0; w < waves; ++w) for (int k = 0; k < 5; ++k) tot[k] += (double)h[(b * waves + w) * 5 + k];
     const double tiles = tot[4] > 0 ? tot[4] : 1, steps = tot[3] > 0 ? tot[3] : 1, nw = (double)grid * waves;
     fprintf(stderr, "f32 stamps %s %dx%d c%d n%d: per wave: K-step %.0f cycles of which %.0f at the barrier (%.1f steps per work item), epilogue %.0f per work item; "
-            "per wave and launch: K loop %.0f, epilogue %.0f, publish %.0f, wait+gather %.0f kcycles\n",
-            v->name, d->h, d->w, d->c, d->n, tot[1] / steps, tot[0] / steps, steps / tiles, tot[2] / tiles, tot[1] / nw / 1e3, tot[2] / nw / 1e3,
-            tot[5] / nw / 1e3, tot[6] / nw / 1e3);
+            "per wave and launch: K loop %.0f, epilogue %.0f kcycles\n",
+            v->name, d->h, d->w, d->c, d->n, tot[1] / steps, tot[0] / steps, steps / tiles, tot[2] / tiles, tot[1] / nw / 1e3, tot[2] / nw / 1e3);
 }
 #endif
 
@@ -1413,50 +1315,6 @@ extern "C" int y2h_sk_walk(long tiles, int nk, long G, int *out, int max)
 
 // sk_wgs_out (optional): > 0 when the choice is the stream-K form of the tile (conv_mfma_kernel<..., SKM>) on that many
 // workgroups -- then *ksplit_out is 1.  Env: Y2_SKF=0 off; Y2_SKF_WGS=n forces stream-K on n workgroups for the (forced) tile.
-// Hybrid stream-K plan (conv_mfma_kernel<..., 2>): of `tiles` output tiles of nk K-steps on `slots` co-resident workgroups, how
-// many tiles of the last, partial round are cut along K over all the workgroups (0 = none).  In microseconds of one CU:
-// the partial round costs a whole tile time whatever it holds; cut, every workgroup gets R / slots of a tile plus a second
-// work item's fixed cost, one 16-byte-store pass of its accumulators, one read pass per earlier piece of the tile it
-// finishes, and the launch pays a flag memset.  OFF by default: measured in the benchmark's own context (yolo.cfg 608 b32, four
-// interleaved runs, profiles/r03_notes.md section 9) the hybrid instantiation's K loop comes out of the compiler 2.5 % of a
-// step slower than the plain one (the kernel sits at the 256-register ceiling; the extra scalar state moves the fragment
-// reads of the software pipeline) and cutting the partial rounds wins back 1.2 %.  Env Y2_SKH=1 whenever a partial round
-// exists (tests), 2 by the cost model below.
-static unsigned long g_skh_launches = 0;
-extern "C" unsigned long y2h_f32_hybrid_stream_k_launches(void) { return g_skh_launches; }
-extern "C" int y2h_f32_stream_k_timeouts(void)
-{
-    int n = -1;
-    if (hipMemcpyFromSymbol(&n, HIP_SYMBOL(g_skh_timeouts), sizeof n) != hipSuccess) return -1;
-    return n;
-}
-static int skh_plan(long tiles, int nk, long slots, int bm, int bn, int bk, int bpc)
-{
-    int mode = 0;
-    if (const char *f = getenv("Y2_SKH")) mode = atoi(f);
-    if (mode <= 0 || tiles < 1 || slots < 2) return 0;
-    const long R = tiles < slots ? tiles : tiles % slots;
-    if (R == 0) return 0;
-    const long share = R * nk / slots;
-    if (share < 4) return 0;
-    if (mode == 1) return (int)R;
-    const double kstep_us = (double)bm * bn * bk / 128.0 * bpc / 2400.0;
-    const double piece_us = (double)bm * bn * 4.0 / 65e3;                       // one slot at ~65 GB/s per workgroup (cross-XCD hand-off read)
-    const double gain = (1.0 - (double)R / slots) * (nk + 1.2) * kstep_us;
-    const double cost = 1.6 * kstep_us + piece_us + piece_us * (double)((slots + R - 1) / R) + 4.0;
-    return gain > 1.3 * cost ? (int)R : 0;
-}
-
-static long skh_slots(const Variant &v)      // workgroups of a hybrid stream-K launch: all that are co-resident (Y2_SKH_WGS=n: tests, small shapes)
-{
-    if (const char *f = getenv("Y2_SKH_WGS")) { if (atol(f) >= 2 && atol(f) <= 256L * variant_bpc(v)) return atol(f); }
-    return 256L * variant_bpc(v);
-}
-static size_t skh_ws_bytes(const Variant &v)
-{
-    const size_t wgs = (size_t)skh_slots(v);
-    return wgs * v.bm * v.bn * sizeof(float) + wgs * sizeof(int);
-}
 
 // measured in-tile efficiency relative to the 192x256 tile (yolo.cfg 608x608 b32 sweep,
 // profiles/r01_tile_sweep.txt): bigger wave tiles re-read less LDS per MFMA; the small
@@ -1481,8 +1339,8 @@ static double whole_tile_cost(const Variant &v, long per_cu, double ksteps, doub
     return (double)per_cu * v.bm * v.bn * v.bk / 128.0 * (ksteps + 5.0) / eff;
 }
 
-// Fills p.v / p.ksplit (the choice among whole-tile launches), p.sk_v / p.sk_wgs (stream-K), p.tile / p.tile_ksplit,
-// p.skh_tiles and p.cost (the chosen plan's modelled CU cycles: what the Winograd rule compares with).  Env: Y2_SKF=0 no stream-K; Y2_SKF_WGS=n forces stream-K on n workgroups for the (forced) tile.
+// Fills p.v / p.ksplit (the choice among whole-tile launches), p.sk_v / p.sk_wgs (stream-K), p.tile / p.tile_ksplit
+// and p.cost (the chosen plan's modelled CU cycles: what the Winograd rule compares with).  Env: Y2_SKF=0 no stream-K; Y2_SKF_WGS=n forces stream-K on n workgroups for the (forced) tile.
 static bool pick_variant(const y2h_conv *d, ConvPlan &p)
 {
     const int bk = (d->c % 32 == 0) ? 32 : 16;
@@ -1567,10 +1425,6 @@ static bool pick_variant(const y2h_conv *d, ConvPlan &p)
     p.tile = best_sk ? plain : best;
     p.tile_ksplit = best_sk ? plain_split : best_split;
     p.cost = best_cost;
-    if (best->fn_skh && best_sk == 0 && best_split == 1 && !getenv("Y2_CONV_GRID")) {
-        const long tiles = ((npix + best->bm - 1) / best->bm) * ((d->n + best->bn - 1) / best->bn);
-        p.skh_tiles = skh_plan(tiles, nk, skh_slots(*best), best->bm, best->bn, best->bk, variant_bpc(*best));
-    }
     return true;
 }
 
@@ -1722,7 +1576,6 @@ static ConvPlan conv_plan(const y2h_conv *d, int strict)
         p.name = p.v->name;
         tile_shape(d, p);
         if (p.sk_wgs > 0) p.ws = (size_t)2 * p.sk_wgs * p.sk_v->bm * p.sk_v->bn * sizeof(float);    // stream-K piece slots
-        else if (p.skh_tiles > 0) p.ws = skh_ws_bytes(*p.tile);                                     // one slot and one flag per workgroup
         else if (p.tile_ksplit > 1) p.ws = (size_t)p.tile_ksplit * d->batch * d->out_h * d->out_w * d->n * sizeof(float);
     } else if (stem_ok(d)) {
         p.kind = CK_STEM;
@@ -1877,7 +1730,7 @@ static int stem_launch(const y2h_conv *d, ConvK &a, y2h_stream s)
     return Y2H_OK;
 }
 
-// fp32 matrix-core kernel: stream-K, hybrid stream-K, XCD-ordered or plain whole tiles (+ the split-K reduction)
+// fp32 matrix-core kernel: stream-K, XCD-ordered or plain whole tiles (+ the split-K reduction)
 static int mfma_launch(const ConvPlan &p, const y2h_conv *d, ConvK &a, y2h_stream s)
 {
     const bool sk = p.sk_wgs > 0;
@@ -1898,11 +1751,10 @@ static int mfma_launch(const ConvPlan &p, const y2h_conv *d, ConvK &a, y2h_strea
     a.tiles_n = (d->n + v->bn - 1) / v->bn;
     const long tiles_m = ((long)a.npix + v->bm - 1) / v->bm;
     a.ntiles = (int)(tiles_m * a.tiles_n) * ksplit;
-    if (getenv("Y2_CONV_XCD_REMAP")) a.dbg |= 64;      // A/B switch; measured 0.2-0.5 % slower in the pipelined step (r02 notes)
 #ifdef Y2_F32_STAMPS
     static unsigned long long *d_st = nullptr;
-    if (!d_st) Y2H_CHECK(hipMalloc((void **)&d_st, 1024 * 8 * 7 * sizeof(unsigned long long)));
-    Y2H_CHECK(hipMemsetAsync(d_st, 0, 1024 * 8 * 7 * sizeof(unsigned long long), S(s)));
+    if (!d_st) Y2H_CHECK(hipMalloc((void **)&d_st, 1024 * 8 * 5 * sizeof(unsigned long long)));
+    Y2H_CHECK(hipMemsetAsync(d_st, 0, 1024 * 8 * 5 * sizeof(unsigned long long), S(s)));
     a.stamps = d_st;
 #endif
     if (sk) {
@@ -1918,23 +1770,6 @@ static int mfma_launch(const ConvPlan &p, const y2h_conv *d, ConvK &a, y2h_strea
                            d->size * d->size * (d->c / v->bk));
         Y2H_LAUNCH_CHECK();
         ++g_skf_launches;
-        return Y2H_OK;
-    }
-    if (p.skh_tiles > 0 && !p.xcd_order) {
-        // hybrid stream-K: the partial last round's K loops in equal shares over ALL co-resident workgroups, finished in-launch
-        const long wgs = skh_slots(*v);
-        a.sk_tiles = getenv("Y2_SKH_NOSPLIT") ? 0 : p.skh_tiles;      // (diagnostic: the hybrid instantiation walking every tile whole)
-        a.sk_wgs = (int)wgs;
-        a.ws = d->ws;
-        a.sk_flags = (int *)(d->ws + (size_t)wgs * v->bm * v->bn);
-        Y2H_CHECK(hipMemsetAsync(a.sk_flags, 0, (size_t)wgs * sizeof(int), S(s)));
-        Y2H_CHECK(y2h_lds_limit((const void *)v->fn_skh, v->lds));
-        hipLaunchKernelGGL(v->fn_skh, dim3((unsigned)wgs), dim3(v->threads), v->lds, S(s), a);
-        Y2H_LAUNCH_CHECK();
-        ++g_skh_launches;
-#ifdef Y2_F32_STAMPS
-        f32_stamps_report(v, d, wgs, d_st, s);
-#endif
         return Y2H_OK;
     }
     void (*fn)(ConvK) = v->fn;
@@ -1982,8 +1817,7 @@ extern "C" int y2h_conv_forward(const y2h_conv *d, int strict, y2h_stream s)
     if (p.kind == CK_NONE) return Y2H_EINVAL;
     // only the matrix-core kernels pool in their epilogue (the stem kernel does not take a pooled layer), and 2x2/2 windows need even dims
     if (d->fuse_maxpool2 && (p.kind == CK_DIRECT || ((d->h | d->w) & 1))) return Y2H_EINVAL;
-    // no room in ws: stream-K runs the whole tiles of the integer split instead, hybrid stream-K every tile whole
-    if (p.skh_tiles > 0 && (!d->ws || d->ws_bytes < skh_ws_bytes(*p.tile) || ((uintptr_t)d->ws % 16) != 0)) p.skh_tiles = 0;
+    // no room in ws: stream-K runs the whole tiles of the integer split instead
     if (p.sk_wgs > 0 && (!d->ws || d->ws_bytes < p.ws || ((uintptr_t)d->y % 16) != 0 || ((uintptr_t)d->ws % 16) != 0)) p.sk_wgs = 0;
 
     ConvK a;

@@ -526,14 +526,10 @@ __global__ __launch_bounds__(512, 1) void conv_p8_f16_kernel(ConvK a)
     const unsigned scs = (unsigned)(sc ^ ((sr >> 1) & 7)) * 16u;      // swizzled source chunk (bytes); (row >> 1) & 7 == (sr >> 1) & 7
     unsigned a_off[4], a_msk[4], b_off[4];
     const int nk = KS * KS * (a.Cin / BK);
-    // Optional XCD-aware placement (env Y2_P8_REMAP): workgroups are dealt round-robin over the 8 XCDs (b and b + 8 share
-    // one L2); remapped, each XCD owns a contiguous run of tile numbers in every round.  Measured neutral to slightly
-    // negative on darknet19_448 b128 (the kernel is bound by the CU's own L2 -> LDS path, not by L2 misses), so it is off.
-    int wgid = blockIdx.x;
-    if (a.dbg & 64) {
-        const int nwg = gridDim.x, xcd = wgid & 7, q = nwg >> 3, r = nwg & 7;
-        wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (wgid >> 3);
-    }
+    // (Workgroups are dealt round-robin over the 8 XCDs -- b and b + 8 share one L2.  Renumbering them so that each XCD owns a
+    // contiguous run of tile numbers in every round measured neutral to slightly negative on darknet19_448 b128: the kernel is
+    // bound by the CU's own L2 -> LDS path, not by L2 misses.)
+    const int wgid = blockIdx.x;
     // Work items of this workgroup: first its stream-K share of the tail tiles (0, 1 or 2 pieces = (tile, K range), raw sums
     // to piece slot 2*wg + piece), then whole tiles wg, wg + G, ... of the first ntiles - sk_tiles.  The pieces come FIRST, so
     // their 256 KB stores drain under the whole tiles that follow and every workgroup ends on a full-tile epilogue.
@@ -1411,7 +1407,6 @@ static int mfma_h_launch(const ConvPlan &p, const y2h_conv *d, ConvK &a, y2h_str
     a.vec_store = vec_ok(d);
     Y2H_CHECK(y2h_lds_limit((const void *)v->fn, v->lds));
     a.ntiles = (int)p.h_ntiles;
-    if (v->p8 && getenv("Y2_P8_REMAP")) a.dbg |= 64;            // A/B: XCD-contiguous placement of workgroups
     long grid = p.h_grid;
     // stream-K needs its piece slots in y2h_conv.ws; without them the plan runs every tile whole (no tail launch either)
     const bool sk = p.p8.sk_tiles && d->ws && d->ws_bytes >= (size_t)2 * p.p8.sk_wgs * 256 * 256 * sizeof(float);

@@ -8,7 +8,7 @@ restated in oracle/y2_oracle.c):
   1. the four 5x5 tiles (conv_mfma_kernel<.., 5>: the generic one-bit-per-tap mask), forced, several tiles per workgroup,
      split-K with range boundaries inside a filter's 25 taps, images smaller than the filter's reach;
   2. a.stride in the fp32 tile kernel (coordinate decode, a_off, the masks against a.W / a.H) on large and small tiles,
-     with split-K, stream-K and hybrid stream-K;
+     with split-K and stream-K;
   3. conv_stem_kernel<NT> for NT = 1..4, K odd / even / a multiple of 16 (the zero-weight padding taps), 1, 3 and 4
      input channels, and the walk over several tiles per wave (Y2_CONV_GRID caps stem_launch's workgroups);
   4. conv_direct_kernel<XH> outside strict mode: what no fast kernel takes in fp32, and its three storage combinations
@@ -31,8 +31,8 @@ from tests.test_gpu_tiles import TESTED_F32
 pytestmark = pytest.mark.gpu
 
 # every switch a case may set: cleared first, so that a case runs under exactly its own
-SWITCHES = ("Y2_CONV_TILE", "Y2_CONV_GRID", "Y2_CONV_KSPLIT", "Y2_SKF", "Y2_SKF_WGS", "Y2_SKH", "Y2_SKH_WGS", "Y2_XCD_ORDER",
-            "Y2_NO_C32F", "Y2_C32F_MIN_TILES", "Y2_NO_FIRST_NCHW", "Y2_F32_SCALAR_STORES", "Y2_SKH_NOSPLIT")
+SWITCHES = ("Y2_CONV_TILE", "Y2_CONV_GRID", "Y2_CONV_KSPLIT", "Y2_SKF", "Y2_SKF_WGS", "Y2_XCD_ORDER", "Y2_NO_C32F",
+            "Y2_C32F_MIN_TILES", "Y2_NO_FIRST_NCHW", "Y2_F32_SCALAR_STORES")
 
 STEM = "conv_stem_mfma_f32"
 DIRECT32 = "conv_direct_f32"
@@ -216,19 +216,6 @@ def test_strided_tile_stream_k_is_exact(oracle, workdir, monkeypatch):
     before = darknet.lib().y2h_f32_stream_k_launches()
     _check_exact(oracle, workdir, monkeypatch, case)
     assert darknet.lib().y2h_f32_stream_k_launches() > before
-
-
-def test_strided_tile_hybrid_stream_k_is_exact(oracle, workdir, monkeypatch):
-    """3x3 stride 2, 8 tiles of 128x128 on 5 workgroups: one full round of whole tiles, the 3 tiles of the partial round cut
-    along K over all 5 workgroups (skh_plan: R = 8 % 5 = 3, shares of 3 * 27 / 5 = 16 K-steps >= 4) and finished inside
-    the launch; no flag wait may time out"""
-    case = _tile_case("k3_s2_128x128_hybrid_stream_k", (128, 128), 3, 96, w=22, h=27, batch=3, stride=2, grid=None,
-                      env={"Y2_SKH": 1, "Y2_SKH_WGS": 5, "Y2_SKF": 0})
-    L = darknet.lib()
-    before = L.y2h_f32_hybrid_stream_k_launches()
-    _check_exact(oracle, workdir, monkeypatch, case)
-    assert L.y2h_f32_hybrid_stream_k_launches() > before
-    assert L.y2h_f32_stream_k_timeouts() == 0
 
 
 def test_strided_conv_in_front_of_maxpool_is_not_fused(oracle, workdir, monkeypatch):

@@ -3,8 +3,8 @@
 
 Every kernel that cuts K loops and every launch that adds the pieces up derives them from share boundaries floor(w * I / G)
 through one header; the y2h_sk_* wrappers run that very code on the host.  This test restates the rule in Python as the
-independent check and compares the two: for the plans the host really makes and for the fp32 forms (every tile cut; the
-hybrid's one producer slot per workgroup), that the pieces partition the cut tiles' K loops exactly once, that no share
+independent check and compares the two: for the plans the host really makes and for the fp32 form (every tile cut) and
+the one unfinished piece per workgroup, that the pieces partition the cut tiles' K loops exactly once, that no share
 exceeds one tile (at most two pieces per workgroup: the slot scheme 2*wg + piece relies on it), that the first share of a
 tile and the walk from it are what a brute-force search finds, and that the BASELINE fp16 shapes (darknet19_448 b128: 392 /
 784 / 1568 tiles on 256 workgroups) are split as DESIGN.md says."""
@@ -52,7 +52,7 @@ def _first(sk_tiles, sk_wgs, nk):
 
 
 def _walk(sk_tiles, sk_wgs, nk):
-    """(tile, wg, piece) in the order the reduce / fix-up kernels and the hybrid's finisher visit them"""
+    """(tile, wg, piece) in the order the reduce / fix-up kernels visit them"""
     buf = (C.c_int * (3 * (sk_tiles + sk_wgs)))()
     n = darknet.lib().y2h_sk_walk(sk_tiles, nk, sk_wgs, buf, sk_tiles + sk_wgs)
     assert n >= 0
@@ -164,10 +164,11 @@ def test_fp32_stream_k_all_tiles_cut(tiles, G, nk):
 
 
 @pytest.mark.parametrize("ntiles,sk_tiles,G,nk", [(1444, 164, 256, 36), (300, 44, 256, 72), (9, 2, 7, 18), (40, 8, 8, 4), (513, 1, 512, 27)])
-def test_fp32_hybrid_one_producer_per_workgroup(ntiles, sk_tiles, G, nk):
-    """conv_mfma_kernel<..., 2>: the last sk_tiles of ntiles tiles are cut over all G workgroups.  A piece that does not end
-    its tile's K loop (producer) goes to slot wg -- at most one per workgroup -- and the piece that does (finisher) gathers
-    the slots of the shares its tile's walk visits below its own workgroup: exactly the tile's producers, ascending K"""
+def test_share_rule_one_unfinished_piece_per_workgroup(ntiles, sk_tiles, G, nk):
+    """A property of the share rule that conv_p8_f16_kernel relies on (the last sk_tiles of ntiles tiles cut over G workgroups):
+    at most one piece per workgroup does not end its tile's K loop ("producer"), and the earlier pieces of a tile belong to
+    the workgroups below the one that ends it ("finisher"): the shares its tile's walk visits below that workgroup are exactly
+    the tile's producers, ascending K"""
     pieces, _ = _check_rule(sk_tiles, G, nk)
     producers = [(wg, tile) for (wg, piece, tile, kb, ke) in pieces if ke < nk]
     assert len({wg for wg, _ in producers}) == len(producers)           # slot = workgroup is unique

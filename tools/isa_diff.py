@@ -4,8 +4,9 @@ instruction stream the same text, and what do the two builds say about its regis
 
     tools/isa_diff.py parent.s new.s [--rename REGEX REPL]... [--memops]
 
-A kernel's stream is the lines between its label and .Lfunc_end with comments, directives and the function number of
-.LBB labels removed ("identical" = the same instructions, registers and operands).  The figures come from the code
+A kernel's stream is the lines between its label and .Lfunc_end with comments, directives, the function number of
+.LBB labels and the number of .Lpost_getpc labels (a long branch's own anchor, counted through the whole file) removed
+("identical" = the same instructions, registers and operands).  The figures come from the code
 object metadata the compiler writes behind the code (.vgpr_count, .sgpr_count, .private_segment_fixed_size,
 .vgpr_spill_count, .sgpr_spill_count).  Kernels are paired by demangled name; --rename rewrites the parent's names first
 (a template parameter that went away: --rename '(conv_mfma_kernel<(?:[^,]+, ){6})true, ' '\\1').  --memops adds, for the
@@ -59,7 +60,7 @@ def parse(path):
             l = l.split(";")[0].strip()
             if not l or (l.startswith(".") and not l.startswith(".LBB")):
                 continue
-            lines.append(re.sub(r"\.LBB\d+_", ".LBB_", l))
+            lines.append(re.sub(r"\.Lpost_getpc\d+", ".Lpost_getpc", re.sub(r"\.LBB\d+_", ".LBB_", l)))
         streams[name] = lines
     return meta, streams
 

@@ -75,10 +75,10 @@ KEY = ("batch", "h", "w", "c", "ldx", "x_halo", "n", "size", "stride", "pad", "f
 
 # forcing switches, set in-process between calls as the tile tests do; each applies to the FORCED configurations below
 FORCED_ENV = [("Y2_CONV_TILE", "128x64"), ("Y2_CONV_TILE", "256x128"), ("Y2_CONV_KSPLIT", "2"), ("Y2_CONV_GRID", "64"),
-              ("Y2_SKF", "0"), ("Y2_SKF_WGS", "200"), ("Y2_SKH", "1"), ("Y2_SKH", "2"), ("Y2_SKH_WGS", "64"),
-              ("Y2_SK", "0"), ("Y2_SK_TILES", "4"), ("Y2_SK_WGS", "96"), ("Y2_TAIL", "0"), ("Y2_TAIL_TILE", "128x128"),
-              ("Y2_TAIL_TILES", "8"), ("Y2_C32F_MIN_TILES", "1"), ("Y2_C64_MIN_TILES", "1"), ("Y2_NO_C32F", "1"), ("Y2_NO_C64", "1"),
-              ("Y2_NO_M16", "1"), ("Y2_F16_NO_P8", "1"), ("Y2_NO_FIRST_NCHW", "1")]
+              ("Y2_SKF", "0"), ("Y2_SKF_WGS", "200"), ("Y2_SK", "0"), ("Y2_SK_TILES", "4"), ("Y2_SK_WGS", "96"),
+              ("Y2_TAIL", "0"), ("Y2_TAIL_TILE", "128x128"), ("Y2_TAIL_TILES", "8"), ("Y2_C32F_MIN_TILES", "1"),
+              ("Y2_C64_MIN_TILES", "1"), ("Y2_NO_C32F", "1"), ("Y2_NO_C64", "1"), ("Y2_NO_M16", "1"), ("Y2_F16_NO_P8", "1"),
+              ("Y2_NO_FIRST_NCHW", "1")]
 FORCED = [("yolo", 608, 32), ("yolo", 416, 1), ("yolo9000", 544, 8), ("darknet19", 448, 128), ("tiny-yolo-voc", 416, 1)]
 FORMS = [(0, ALIGNED, "f32"), (0, MISALIGNED, "f32 y+4"), (1, ALIGNED, "f16"), (1, MISALIGNED, "f16 y+4")]
 
