@@ -226,6 +226,22 @@ int y2h_conv_wino_forward(const y2h_conv *d, y2h_stream s);
 /* number of such forwards issued by this process so far (tests) */
 unsigned long y2h_wino_launches(void);
 
+/* ---- stationary Winograd: F(2x2,3x3) as one fused kernel, filters in registers (the rule: include/y2_winos_rule.h) ---- */
+typedef struct y2h_winos {
+    int eligible;                /* the shape is one a form of the kernel takes                              */
+    int take;                    /* the rule's answer (Y2_WINOS=0: never, Y2_WINOS=1: every eligible layer)  */
+    int form;                    /* input channels of the form that takes it (32), 0: none                   */
+    long patches;                /* 8 x 16-pixel output patches the persistent grid walks                    */
+    size_t u_bytes;              /* transformed filters in the kernel's register order (y2_winos_u_index)    */
+} y2h_winos;
+/* Host arithmetic only (no GPU).  Leaves what every other query answers alone; needs no workspace. */
+int y2h_winos_plan(const y2h_conv *d, y2h_winos *out);
+/* The convolution as one launch.  d->w_packed holds U in register order (y2_winos_u_index of y2_wino_filter of every
+ * (filter, channel)).  Y2H_EINVAL unless y2h_winos_plan takes the descriptor. */
+int y2h_conv_winos_forward(const y2h_conv *d, y2h_stream s);
+/* number of such forwards issued by this process so far (tests) */
+unsigned long y2h_winos_launches(void);
+
 /* ---- other layers (NHWC) ---- */
 int y2h_maxpool(const float *x, int ldx, float *y, int ldy, int batch, int h, int w, int c,
                 int size, int stride, int pad, int out_h, int out_w, y2h_stream s);

@@ -9,6 +9,7 @@
 #include <string.h>
 #include "y2_internal.h"
 #include "y2_wino_rule.h"
+#include "y2_winos_rule.h"
 
 /* the layer types that own arena space: layout, signature and packing all iterate with this */
 static int owns_arena(const layer *l)
@@ -88,8 +89,8 @@ void y2_arena_layout(network *net)
             d->off_bias = off; off = align_up(off + (size_t)l->outputs * sizeof(float), 64);
             continue;
         }
-        /* a Winograd layer keeps U[16][n][c] = G g G^T in place of its nine packed taps */
-        d->off_w_packed = off; off = align_up(off + (d->wino ? (size_t)16 * l->n * l->c * sizeof(float) : w_half ? wbytes / 2 : wbytes), 256);
+        /* a Winograd layer keeps U[16][n][c] = G g G^T in place of its nine packed taps, a stationary one U in register order */
+        d->off_w_packed = off; off = align_up(off + (d->winos ? y2_winos_u_floats(l->n) * sizeof(float) : d->wino ? (size_t)16 * l->n * l->c * sizeof(float) : w_half ? wbytes / 2 : wbytes), 256);
         if (d->has_w_ref) { d->off_w_ref = off; off = align_up(off + wbytes, 256); }
         d->off_bias = off; off = align_up(off + l->n * sizeof(float), 64);
         if (w_half) {
@@ -121,6 +122,7 @@ static uint64_t arena_signature(const network *net)
         SIG_MIX(d->uses_mfma); SIG_MIX(y2_half_weights(net, i));
         SIG_MIX(l->batch_normalize ? d->off_rinv + 1 : 0);
         if (d->wino) SIG_MIX(0x57494e4f);      /* the filter slot holds U, not the packed taps (mixed only where it does) */
+        if (d->winos) SIG_MIX(0x57494e53);     /* ... or U in the stationary kernel's register order */
     }
     SIG_MIX(e->strict); SIG_MIX(e->half); SIG_MIX(e->arena_need);
 #undef SIG_MIX
@@ -229,6 +231,21 @@ static void pack_wino(float *up, const layer *l)
         }
 }
 
+/* the filters of a stationary-Winograd layer: the same U = G g G^T (y2_wino_filter), each value where the kernel's wave
+ * (filter tile, component row) and lane load it as part of one 16-byte register (y2_winos_u_index); filters past n in the
+ * last 32-filter tile are zero */
+static void pack_winos(float *up, const layer *l)
+{
+    int co, ci, g;
+    memset(up, 0, y2_winos_u_floats(l->n) * sizeof(float));
+    for (co = 0; co < l->n; ++co)
+        for (ci = 0; ci < l->c; ++ci) {
+            float u[16];
+            y2_wino_filter(l->weights + ((size_t)co * l->c + ci) * 9, u);
+            for (g = 0; g < 16; ++g) up[y2_winos_u_index(co, ci, g >> 2, g & 3)] = u[g];
+        }
+}
+
 /* a [convolutional] or [connected] layer: filters, the reference-layout copy where the layer needs one, constants */
 static void pack_dense(unsigned char *host, const network *net, int i)
 {
@@ -236,7 +253,8 @@ static void pack_dense(unsigned char *host, const network *net, int i)
     const y2_ldev *d = ld_of(l);
     const int K = l->size * l->size * l->c, w_half = y2_half_weights(net, i);
     int co, f, q;
-    if (d->wino) pack_wino((float *)(host + d->off_w_packed), l);
+    if (d->winos) pack_winos((float *)(host + d->off_w_packed), l);
+    else if (d->wino) pack_wino((float *)(host + d->off_w_packed), l);
     else pack_filters((float *)(host + d->off_w_packed), net, i, w_half);
     if (w_half) {
         /* folded batch-norm for the fp16 kernels: y = act(acc*alpha + beta), constants evaluated in double */

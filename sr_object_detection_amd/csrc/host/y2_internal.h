@@ -24,6 +24,8 @@ typedef struct y2_ldev {
     int has_w_ref;
     int uses_mfma;
     int wino;                  /* conv: runs as Winograd F(2x2,3x3) (y2_plan.c plan_wino); off_w_packed then holds U[16][n][c] */
+    int winos;                 /* conv: runs as the fused stationary Winograd kernel (y2_plan.c plan_winos); off_w_packed then
+                                  holds U in its register order (y2_winos_rule.h) */
     int fused_pool;           /* conv: the following 2x2/2 maxpool runs in this conv's epilogue */
     int fused_into;            /* maxpool: index of the conv that computes it, or -1 */
     int out_half;              /* this layer's activations are IEEE half (fp16 mode), out_ld counts halves */

@@ -33,6 +33,7 @@ void y2_free_plan(network *net)
         d->fused_pool = 0; d->fused_into = -1;
         d->out_half = 0;
         d->wino = 0;
+        d->winos = 0;
         d->tile_bm = d->tile_bn = d->ksplit = 0;
         d->conn_ranges = 0;
     }
@@ -267,6 +268,7 @@ static int plan_workspace(network *net)
         y2_input_view(net, i, &x, &ldx);
         conv_query(net, i, &c, x, ldx);
         b = ld_of(&net->layers[i])->wino ? y2h_wino_workspace_bytes(&c) : y2h_conv_workspace_bytes(&c);      /* Winograd: V and M */
+        if (ld_of(&net->layers[i])->winos) b = 0;                                                             /* stationary Winograd: none */
         if (b > need) need = b;
     }
     return grow_workspace(e, need);
@@ -296,7 +298,7 @@ static int autotune_layers(network *net)
         y2_ldev *d = ld_of(l);
         y2h_conv c;
         const float *x; int ldx, n, bm[64], bn[64], ks[64];
-        if (l->type != CONVOLUTIONAL || !d->uses_mfma || l->xnor || d->wino) continue;      /* (a Winograd layer has no direct tile to measure) */
+        if (l->type != CONVOLUTIONAL || !d->uses_mfma || l->xnor || d->wino || d->winos) continue;      /* (a Winograd layer has no direct tile to measure) */
         y2_input_view(net, i, &x, &ldx);
         y2_conv_desc(net, i, &c, x, ldx);
         n = y2h_conv_candidates(&c, bm, bn, ks, 64);
@@ -314,7 +316,7 @@ static int autotune_layers(network *net)
         y2h_conv c;
         const float *x; int ldx, n, hit = 0, bm[64], bn[64], ks[64], best = 0;
         float best_ms = 0.f;
-        if (l->type != CONVOLUTIONAL || !d->uses_mfma || l->xnor || d->wino) continue;      /* (a Winograd layer has no direct tile to measure) */
+        if (l->type != CONVOLUTIONAL || !d->uses_mfma || l->xnor || d->wino || d->winos) continue;      /* (a Winograd layer has no direct tile to measure) */
         y2_input_view(net, i, &x, &ldx);
         y2_conv_desc(net, i, &c, x, ldx);
         pthread_mutex_lock(&g_tuned_mu);
@@ -954,6 +956,31 @@ static int plan_wino(network *net)
     return 0;
 }
 
+/* which of the shallow fp32 3x3 convolutions run as the fused stationary Winograd kernel (the rule: include/y2_winos_rule.h,
+ * asked through y2h_winos_plan).  Such a layer keeps U in the kernel's register order in the arena in place of its packed
+ * filters, is named conv_winos_f32_c<channels> and needs no workspace.  Gated like plan_wino, whose layers it leaves alone. */
+static int plan_winos(network *net)
+{
+    y2_engine *e = y2_engine_of(net);
+    int i;
+    if (e->strict || e->half) return 0;
+    for (i = 0; i < net->n; ++i) {
+        layer *l = &net->layers[i];
+        y2_ldev *d = ld_of(l);
+        y2h_conv c;
+        y2h_winos w;
+        const float *x; int ldx;
+        if (l->type != CONVOLUTIONAL || !d->uses_mfma || l->xnor || d->wino) continue;
+        y2_input_view(net, i, &x, &ldx);
+        conv_query(net, i, &c, x, ldx);
+        if (y2h_winos_plan(&c, &w) != 0 || !w.take) continue;
+        d->winos = 1;
+        snprintf(d->kname, sizeof d->kname, "conv_winos_f32_c%d%s", w.form, d->fused_pool ? "+maxpool2" : "");
+        d->kernel = d->kname;
+    }
+    return 0;
+}
+
 /* timing events */
 static int plan_timing_events(network *net)
 {
@@ -976,7 +1003,7 @@ int y2_engine_build(network *net)
     y2_free_plan(net);
     if (plan_batches(net) != 0 || plan_routes(net) != 0 || plan_pool_fusion(net) != 0 || plan_half(net) != 0 ||
         plan_activations(net) != 0 || plan_input_copies(net) != 0 || plan_input(net) != 0 || plan_output(net) != 0 ||
-        plan_head_constants(net) != 0 || plan_conv_kernels(net) != 0 || plan_wino(net) != 0) return -1;
+        plan_head_constants(net) != 0 || plan_conv_kernels(net) != 0 || plan_wino(net) != 0 || plan_winos(net) != 0) return -1;
     y2_arena_layout(net);
     /* the arena commit: signature, reallocation, the refusal of a replicated rank whose layout changed */
     if (plan_workspace(net) != 0 || y2_arena_commit(net) != 0 || plan_timing_events(net) != 0) return -1;
