@@ -704,7 +704,8 @@ void y2_train_unpack_weights(const float *packed, float *ref, int n, int c, int 
 /* on the host, device-free (y2_aug.c); crop with jitter, the two-pass bilinear */
 /* resize, flip, the HSV distortion and the clamp run as one kernel that writes */
 /* the trainer's input where the step reads it.  The classifier loader          */
-/* (load_data_augment: rotation) and load_data_region stay with the caller.     */
+/* (load_data_augment: rotation) is built the same way, further down;           */
+/* load_data_region stays with the caller.                                      */
 /* ------------------------------------------------------------------------- */
 /* One image of a batch: the frame as in y2_region (8-bit interleaved, h x w x c, `step` bytes between rows; channels
  * past the third are skipped), the draws of load_data_detection, and the label rows as the label file holds them,
@@ -748,13 +749,58 @@ int y2_net_augment(network net, float *jitter, float *hue, float *saturation, fl
  * data, c < 3, step < w * c, a frame without pixels, swidth < 1 or sheight < 1, nboxes < 0, nboxes > 0 with NULL boxes, a
  * swap index outside the rows. */
 int y2_train_load_detection(network *net, const y2_aug_item *items, int n, int swap_rb);
-/* step_on_device on what y2_train_load_detection loaded; a second step on the same load is allowed.  Refused with nothing
- * loaded, and after set_batch_network / resize_network dropped the trainer (load again). */
+/* ---- the classifier loader (data.c:870-879 load_data_augment): rotated, scaled, aspect-stretched bilinear crop,
+ * flip, HSV distortion, the label row.  PINNED to the compiled reference, run whole through recording stubs
+ * (tests/golden/aug_cls.npz): the rand primitives, the sequence around them (paths, the per-image call order, the flip
+ * draw between the two image calls), the label and hierarchy rows.  RESTATED only (image.c does not compile without
+ * OpenCV): the order of the five draws in random_augment_image and the three in random_distort_image, the arithmetic
+ * between them, and the pixel chain, which is held to tests/aug_cls_rule.py by array_equal. ---- */
+/* One image: the frame as in y2_aug_item, what random_augment_image hands to rotate_crop_image (image.c:1702), the flip
+ * and the distortion. */
+typedef struct {
+    const unsigned char *data; int h, w, c, step;
+    float aspect, scale, rad, dx, dy;
+    int flip;
+    float dhue, dsat, dexp;
+} y2_aug_cls_item;
+/* The draws of one image of load_image_augment_paths for an ow x oh frame, libc rand() called in the reference's order:
+ * aspect = rand_scale(aspect); r = rand_int(min, max); int m = (oh < ow*aspect) ? oh : ow*aspect (truncated);
+ * scale = (float)r / m; rad = rand_uniform(-angle, angle) * TWO_PI / 360. (in double, rounded once);
+ * dx = (ow*scale/aspect - size) / 2., dy = (oh*scale - size) / 2., each clamped at 0, then rand_uniform(-dx, dx),
+ * rand_uniform(-dy, dy); flip = random_gen() % 2; dhue = rand_uniform_strong(-hue, hue); dsat = rand_scale(saturation);
+ * dexp = rand_scale(exposure) -- a bound below 1 goes through rand_uniform_strong's swap.  Fills the draws of *item; the
+ * frame fields are not touched.  -1 when the truncated m is 0 (the reference divides by it); every draw is still made, so
+ * the sequence stays the reference's.  After srand(s), y2_aug_random_paths for the batch and then this call image by image
+ * give the reference's single-threaded sequence. */
+int y2_aug_draw_classification(int ow, int oh, int min, int max, int size, float angle, float aspect, float hue,
+                               float saturation, float exposure, y2_aug_cls_item *item);
+/* fill_truth (data.c:387): truth[i] = 1 where labels[i] occurs in path (strstr), 0 elsewhere; with a hierarchy,
+ * fill_hierarchy (data.c:401): every ancestor of a set entry is set, and each group without a set member is filled with
+ * the reference's SECRET_NUM (-1234).  Returns the number of labels that matched (the reference prints when it is not 1;
+ * nothing is printed here), -1 for NULL arguments.  On the host, like hierarchy_predictions: the trainer refuses a tree
+ * softmax. */
+int y2_aug_labels(const char *path, char **labels, int k, const tree *hierarchy, float *truth);
+/* What train_classifier reads of the [net] section (parser.c:527-534): min_crop (default net.w), max_crop (net.w * 2),
+ * angle (0), aspect (1), hue (0), saturation (1), exposure (1).  Any pointer may be NULL.  -1 without an engine. */
+int y2_net_augment_classifier(network net, int *min_crop, int *max_crop, float *angle, float *aspect, float *hue,
+                              float *saturation, float *exposure);
+/* load_data_augment's pixel work for one batch, n == net.batch items, into the trainer, staged as
+ * y2_train_load_detection stages: the frame rectangle each image's taps can touch, the descriptor table and `truth`
+ * ([n][inputs of the closing [cost] layer], as y2_train_step takes it) go up in one copy from one pinned buffer, one
+ * kernel writes the net.w x net.w NHWC input (size = net.w, as args.size in train_classifier), the truth is copied beside
+ * it.  Refused before any allocation, upload or launch, by name in y2_last_error(): n != net.batch, net.c != 3,
+ * net.h != net.w (the reference would hand the network a batch of the wrong length), a network that ends in [region] or
+ * that the trainer refuses, NULL truth or data, c < 3, step < w * c, a frame without pixels, a scale or aspect that is
+ * not finite and positive, a rad, dx or dy that is not finite.  A refused load leaves nothing loaded. */
+int y2_train_load_classification(network *net, const y2_aug_cls_item *items, const float *truth, int n, int swap_rb);
+/* step_on_device on what y2_train_load_detection or y2_train_load_classification loaded; a second step on the same load is
+ * allowed.  Refused with nothing loaded, and after set_batch_network / resize_network dropped the trainer (load again). */
 int y2_train_step_loaded(network *net, float *loss);
-/* The loaded input as [batch][3][h][w] and the truth [batch][150], either may be NULL: for tests and callers that look. */
+/* The loaded input as [batch][3][h][w] and the truth ([batch][150] behind a [region] head, [batch][y2_train_truth_floats]
+ * for a classifier), either may be NULL: for tests and callers that look. */
 int y2_train_pull_input(network *net, float *x_nchw, float *truth);
-/* Host wall time of the last y2_train_load_detection in ms: ms[0] pack (pixels, table, truth), ms[1] enqueueing the copy,
- * the kernel and the truth copy, ms[2] waiting for the copy to leave the staging buffer. */
+/* Host wall time of the last y2_train_load_detection / y2_train_load_classification in ms: ms[0] pack (pixels, table,
+ * truth), ms[1] enqueueing the copy, the kernel and the truth copy, ms[2] waiting for the copy to leave the staging buffer. */
 int y2_train_load_times(network *net, float *ms);
 /* Copy layer i's activations to host as NCHW [batch][out_c][out_h][out_w] (or [batch][outputs]). */
 int y2_pull_layer_output(network net, int i, float *dst);

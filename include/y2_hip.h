@@ -532,6 +532,36 @@ typedef struct y2h_aug {
 int y2h_augment_to_input(const y2h_aug *desc, int n, const unsigned char *pixels, int swap_rb, int h, int w, float *dst_nhwc,
                          y2h_stream s);
 
+/* One item of y2h_augment_cls_to_input: one image of load_image_augment_paths (data.c:107-132).  `src` is a rectangle of
+ * the 8-bit interleaved frame, rw x rh pixels whose first pixel is the frame's (x0, y0); it must hold every pixel a tap of
+ * bilinear_interpolate touches after get_pixel_extend's clamp (y2_aug_cls_rect computes it; the kernel clamps into the
+ * rectangle as well, which never acts for such a descriptor).  The crop may reach outside the frame on every side.
+ * What does not depend on the output pixel is formed on the host, each the C expression's own operation chain:
+ *   cosr, sinr   cos((double)rad), sin((double)rad) of the host's libm -- the device never computes them
+ *   s, aspect    the floats, promoted
+ *   ax, ay       dx / s * aspect and dy / s: float operations in C (all three operands are floats), then promoted
+ *   cx, cy       (float)(ow / 2.), (float)(oh / 2.) */
+typedef struct y2h_aug_cls {
+    long long src;              /* byte offset of the rectangle's first pixel from `pixels` */
+    double cosr, sinr, s, aspect, ax, ay;
+    float cx, cy;
+    int pitch;                  /* bytes between its rows */
+    int c;                      /* bytes per pixel (>= 3) */
+    int x0, y0, rw, rh;         /* the rectangle inside the frame */
+    int ow, oh;                 /* frame size */
+    int flip;
+    float dhue, dsat, dexp;     /* distort_image(crop, dhue, dsat, dexp) */
+} y2h_aug_cls;
+
+/* Fill the dense NHWC fp32 training input dst[n][size][size][3] in one launch: per output pixel (x, y) -- column
+ * size - 1 - x when flip, flip_image runs on the crop -- rotate_crop_image's rx and ry (image.c:1471-1472) in double,
+ * operation for operation, rounded to float; bilinear_interpolate (image.c:1935-1948) with floorf, float weights and the
+ * four get_pixel_extend taps of (float)(v / 255.) plane values summed left to right; then distort_image and
+ * constrain_image exactly as y2h_augment_to_input does them.  Channel k reads byte k of a pixel, 2 - k when swap_rb.
+ * No atomics, no reductions: the output is a pure function of the table. */
+int y2h_augment_cls_to_input(const y2h_aug_cls *desc, int n, const unsigned char *pixels, int swap_rb, int size,
+                             float *dst_nhwc, y2h_stream s);
+
 /* ---- depth stage of the Kinect loop (y2_depth.hip; KinectUtil_with_cam.cpp:394-442, :1482-1706) ---- */
 /* Register a dh x dw depth frame (and body-index frame, or NULL) to the H x W colour frame: for every colour pixel
  * (dx, dy) = y2_depth_coord of map[pixel] (NULL map: the pixel's own position, H == dh and W == dw); inside the depth

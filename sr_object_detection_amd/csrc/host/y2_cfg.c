@@ -951,7 +951,8 @@ network parse_network_cfg(char *filename)    /* parser.c:585-700 */
     shape p;
     int count = 0;
     y2_lr_schedule lr;
-    float hue, saturation, exposure;
+    float hue, saturation, exposure, angle, aspect;
+    int min_crop, max_crop;
 
     memset(&empty, 0, sizeof empty);
     (void)y2_failed();                        /* a stale failure of an earlier call must not fail this parse */
@@ -979,6 +980,10 @@ network parse_network_cfg(char *filename)    /* parser.c:585-700 */
     net.inputs = option_find_int_quiet(s->options, "inputs", net.h * net.w * net.c);
     net.max_batches = option_find_int_quiet(s->options, "max_batches", 0);
     y2_lr_parse(s->options, &lr);
+    max_crop = option_find_int_quiet(s->options, "max_crop", net.w * 2);  /* parser.c:527-531: the classifier loader's, y2_net_augment_classifier */
+    min_crop = option_find_int_quiet(s->options, "min_crop", net.w);
+    angle = option_find_float_quiet(s->options, "angle", 0);
+    aspect = option_find_float_quiet(s->options, "aspect", 1);
     hue = option_find_float_quiet(s->options, "hue", 0);                  /* parser.c:532-534: the loader's, y2_net_augment */
     saturation = option_find_float_quiet(s->options, "saturation", 1);
     exposure = option_find_float_quiet(s->options, "exposure", 1);
@@ -1042,6 +1047,10 @@ network parse_network_cfg(char *filename)    /* parser.c:585-700 */
     y2_engine_of(&net)->aug_hue = hue;
     y2_engine_of(&net)->aug_saturation = saturation;
     y2_engine_of(&net)->aug_exposure = exposure;
+    y2_engine_of(&net)->aug_min_crop = min_crop;
+    y2_engine_of(&net)->aug_max_crop = max_crop;
+    y2_engine_of(&net)->aug_angle = angle;
+    y2_engine_of(&net)->aug_aspect = aspect;
     net.output = NULL;                        /* allocated with the plan; see get_network_output */
     return net;
 fail:                                         /* the schedule's lists belong to the engine, which does not exist */

@@ -181,6 +181,8 @@ typedef struct y2_engine {
     y2_lr_schedule lr;
     struct y2_trainer *trainer;
     float aug_hue, aug_saturation, aug_exposure;   /* [net] hue / saturation / exposure (parser.c:532-534): what y2_net_augment reports */
+    int aug_min_crop, aug_max_crop;                /* [net] min_crop / max_crop / angle / aspect (parser.c:527-531): y2_net_augment_classifier */
+    float aug_angle, aug_aspect;
 } y2_engine;
 
 /* How the network input (fp32 NCHW) reaches layer 0: a plain NHWC copy; an NHWC copy with a zero border of in_halo_px
@@ -281,6 +283,15 @@ int y2_aug_check(const char *who, const y2_aug_item *items, int n);        /* ev
 void y2_aug_rect(const y2_aug_item *it, int *x0, int *y0, int *rw, int *rh);
 size_t y2_aug_pack_bytes(const y2_aug_item *items, int n);
 void y2_aug_pack(const y2_aug_item *items, int n, int net_w, int net_h, y2h_aug *desc, unsigned char *pixels);
+/* the classifier loader's: the same three steps for y2_aug_cls_item (size = the output's edge) */
+int y2_aug_cls_check(const char *who, const y2_aug_cls_item *items, int n);
+void y2_aug_cls_rect(const y2_aug_cls_item *it, int size, int *x0, int *y0, int *rw, int *rh);
+size_t y2_aug_cls_pack_bytes(const y2_aug_cls_item *items, int n, int size);
+void y2_aug_cls_pack(const y2_aug_cls_item *items, int n, int size, y2h_aug_cls *desc, unsigned char *pixels);
+/* the two halves of y2_aug_cls_pack, for a caller that sizes its buffer between them: the table (and the bytes its
+ * rectangles take), then the copy */
+size_t y2_aug_cls_describe(const y2_aug_cls_item *items, int n, int size, y2h_aug_cls *desc);
+void y2_aug_cls_copy(const y2_aug_cls_item *items, int n, const y2h_aug_cls *desc, unsigned char *pixels);
 
 /* cfg helpers shared with other files */
 char *y2_fgetl(FILE *fp);

@@ -18,7 +18,9 @@
  *
  * The detection loader's trainer entries live here too (y2_train_load_detection, y2_train_step_loaded, y2_train_pull_input):
  * data.c:664-714 load_data_detection with its pixel work as one kernel (y2_augment.hip) that writes the trainer's NHWC input
- * in place; the draws, the truth and the packer are the device-free y2_aug.c.
+ * in place; the draws, the truth and the packer are the device-free y2_aug.c.  The classifier loader (data.c:870-879
+ * load_data_augment) is y2_train_load_classification, staged the same way: rotate_crop_image, flip and distortion are the
+ * second kernel of y2_augment.hip, the draws and the label row come from y2_aug.c.
  */
 #include <math.h>
 #include <stdio.h>
@@ -702,12 +704,82 @@ int y2_train_load_detection(network *net, const y2_aug_item *items, int n, int s
     return 0;
 }
 
+/* ------------------------------------------------------------------ */
+/* the classifier loader (data.c:870-879 load_data_augment)             */
+/* ------------------------------------------------------------------ */
+int y2_net_augment_classifier(network net, int *min_crop, int *max_crop, float *angle, float *aspect, float *hue,
+                              float *saturation, float *exposure)
+{
+    const y2_engine *e = y2_engine_of(&net);
+    if (!e) { y2_fail("y2_net_augment_classifier: network has no engine (was it built by parse_network_cfg?)"); return -1; }
+    if (min_crop) *min_crop = e->aug_min_crop;
+    if (max_crop) *max_crop = e->aug_max_crop;
+    if (angle) *angle = e->aug_angle;
+    if (aspect) *aspect = e->aug_aspect;
+    if (hue) *hue = e->aug_hue;
+    if (saturation) *saturation = e->aug_saturation;
+    if (exposure) *exposure = e->aug_exposure;
+    return 0;
+}
+
+int y2_train_load_classification(network *net, const y2_aug_cls_item *items, const float *truth, int n, int swap_rb)
+{
+    static const char who[] = "y2_train_load_classification";
+    y2_engine *e;
+    y2_trainer *t;
+    y2h_aug_cls *desc;
+    size_t desc_bytes, truth_bytes, need;
+    double t0, t1, t2;
+    if (!net || !net->layers || net->n <= 0) { y2_fail("%s: no network", who); return -1; }
+    e = y2_engine_of(net);
+    if (e && e->trainer) e->trainer->loaded = 0;         /* a refused load leaves nothing to step on */
+    if (n != net->batch) { y2_fail("%s: %d items for a batch-%d network", who, n, net->batch); return -1; }
+    if (net->c != 3) { y2_fail("%s: the network reads %d channels, the loader makes 3", who, net->c); return -1; }
+    if (net->h != net->w) {
+        y2_fail("%s: the network is %d x %d: the loader makes net.w x net.w crops (args.size = net.w)", who, net->w, net->h);
+        return -1;
+    }
+    if (net->layers[net->n - 1].type == REGION) {
+        y2_fail("%s: layer %d (region): the network ends in [region] (y2_train_load_detection loads a detector)", who, net->n - 1);
+        return -1;
+    }
+    if (refuse(net) != 0) return -1;
+    if (!truth) { y2_fail("%s: truth is NULL", who); return -1; }
+    if (y2_aug_cls_check(who, items, n) != 0) return -1;
+    if (!(t = trainer_for_step(net))) return -1;
+    e = y2_engine_of(net);
+    desc_bytes = align_up((size_t)n * sizeof(y2h_aug_cls), 64);
+    truth_bytes = align_up(t->truth_floats * sizeof(float), 64);
+    t->loaded = 0;
+    t0 = now_ms();
+    /* the table first, once: it says how many pixel bytes the staging buffer must hold */
+    if (!(desc = malloc((size_t)n * sizeof *desc))) { y2_fail("%s: out of memory", who); return -1; }
+    need = desc_bytes + truth_bytes + y2_aug_cls_describe(items, n, net->w, desc);
+    /* the staging buffer is free: the last load waited for its copy before it returned */
+    if (grow_load(t, need) != 0) { free(desc); return -1; }
+    memcpy(t->h_load, desc, (size_t)n * sizeof *desc);
+    y2_aug_cls_copy(items, n, desc, t->h_load + desc_bytes + truth_bytes);
+    free(desc);
+    memcpy(t->h_load + desc_bytes, truth, t->truth_floats * sizeof(float));
+    t1 = now_ms();
+    HIP_OR_ERR(y2h_memcpy_h2d(t->d_load, t->h_load, need, e->stream));
+    HIP_OR_ERR(y2h_event_record(t->ev_load, e->stream));
+    HIP_OR_ERR(y2h_augment_cls_to_input((const y2h_aug_cls *)t->d_load, n, t->d_load + desc_bytes + truth_bytes, swap_rb, net->w, t->d_x,
+                                        e->stream));
+    HIP_OR_ERR(y2h_memcpy_d2d(t->d_truth, t->d_load + desc_bytes, t->truth_floats * sizeof(float), e->stream));
+    t2 = now_ms();
+    HIP_OR_ERR(y2h_event_sync(t->ev_load));
+    t->load_ms[0] = (float)(t1 - t0); t->load_ms[1] = (float)(t2 - t1); t->load_ms[2] = (float)(now_ms() - t2);
+    t->loaded = 1;
+    return 0;
+}
+
 int y2_train_step_loaded(network *net, float *loss)
 {
     y2_engine *e = net ? y2_engine_of(net) : NULL;
     y2_trainer *t = e ? e->trainer : NULL;
     if (!t || !t->loaded || t->batch != net->batch) {
-        y2_fail("y2_train_step_loaded: nothing is loaded (y2_train_load_detection; set_batch_network and resize_network drop a load)");
+        y2_fail("y2_train_step_loaded: nothing is loaded (y2_train_load_detection / y2_train_load_classification; set_batch_network and resize_network drop a load)");
         return -1;
     }
     HIP_OR_ERR(y2h_set_device(e->device));
@@ -717,7 +789,7 @@ int y2_train_step_loaded(network *net, float *loss)
 int y2_train_load_times(network *net, float *ms)
 {
     y2_engine *e = net ? y2_engine_of(net) : NULL;
-    if (!e || !e->trainer || !ms) { y2_fail("y2_train_load_times: no trainer (y2_train_load_detection)"); return -1; }
+    if (!e || !e->trainer || !ms) { y2_fail("y2_train_load_times: no trainer (y2_train_load_detection / y2_train_load_classification)"); return -1; }
     memcpy(ms, e->trainer->load_ms, sizeof e->trainer->load_ms);
     return 0;
 }
@@ -794,7 +866,7 @@ int y2_train_pull_input(network *net, float *x_nchw, float *truth)
 {
     y2_engine *e = net ? y2_engine_of(net) : NULL;
     y2_trainer *t = e ? e->trainer : NULL;
-    if (!t || !t->loaded) { y2_fail("y2_train_pull_input: nothing is loaded (y2_train_load_detection)"); return -1; }
+    if (!t || !t->loaded) { y2_fail("y2_train_pull_input: nothing is loaded (y2_train_load_detection / y2_train_load_classification)"); return -1; }
     HIP_OR_ERR(y2h_set_device(e->device));
     if (x_nchw) {
         HIP_OR_ERR(y2h_nhwc_to_nchw(t->d_x, net->c, t->stage, net->batch, net->c, net->h, net->w, e->stream));

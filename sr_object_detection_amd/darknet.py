@@ -173,6 +173,19 @@ class Aug(C.Structure):      # include/y2_hip.h y2h_aug: one item of y2h_augment
                 ("w_scale", C.c_float), ("h_scale", C.c_float)]
 
 
+class AugClsItem(C.Structure):  # include/sr_yolo2.h y2_aug_cls_item: one image of y2_train_load_classification
+    _fields_ = [("data", C.c_void_p), ("h", C.c_int), ("w", C.c_int), ("c", C.c_int), ("step", C.c_int),
+                ("aspect", C.c_float), ("scale", C.c_float), ("rad", C.c_float), ("dx", C.c_float), ("dy", C.c_float),
+                ("flip", C.c_int), ("dhue", C.c_float), ("dsat", C.c_float), ("dexp", C.c_float)]
+
+
+class AugCls(C.Structure):   # include/y2_hip.h y2h_aug_cls: one item of y2h_augment_cls_to_input
+    _fields_ = [("src", C.c_longlong)] + [(k, C.c_double) for k in ("cosr", "sinr", "s", "aspect", "ax", "ay")] + \
+               [("cx", C.c_float), ("cy", C.c_float)] + \
+               [(k, C.c_int) for k in ("pitch", "c", "x0", "y0", "rw", "rh", "ow", "oh", "flip")] + \
+               [("dhue", C.c_float), ("dsat", C.c_float), ("dexp", C.c_float)]
+
+
 class RecArgs(C.Structure):  # include/y2_hip.h y2h_rec_args: one launch of y2h_rec_step
     _fields_ = [("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("mean", C.c_void_p), ("scale", C.c_void_p),
                 ("rinv", C.c_void_p), ("bn", C.c_int), ("act", C.c_int), ("pre", C.c_void_p), ("rows", C.c_int), ("k", C.c_int),
@@ -458,6 +471,17 @@ def lib():
     L.y2_train_pull_input.argtypes = [C.POINTER(CNetwork), C.c_void_p, C.c_void_p]
     L.y2_train_load_times.argtypes = [C.POINTER(CNetwork), C.c_void_p]
     L.y2h_augment_to_input.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.y2_aug_draw_classification.argtypes = [C.c_int] * 5 + [C.c_float] * 5 + [C.POINTER(AugClsItem)]
+    L.y2_aug_labels.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(Tree), C.c_void_p]
+    L.y2_net_augment_classifier.argtypes = [CNetwork] + [C.POINTER(C.c_int)] * 2 + [C.POINTER(C.c_float)] * 5
+    L.y2_train_load_classification.argtypes = [C.POINTER(CNetwork), C.POINTER(AugClsItem), C.c_void_p, C.c_int, C.c_int]
+    L.y2_aug_cls_rect.restype = None
+    L.y2_aug_cls_rect.argtypes = [C.POINTER(AugClsItem), C.c_int] + [C.POINTER(C.c_int)] * 4
+    L.y2_aug_cls_pack_bytes.restype = C.c_size_t
+    L.y2_aug_cls_pack_bytes.argtypes = [C.POINTER(AugClsItem), C.c_int, C.c_int]
+    L.y2_aug_cls_pack.restype = None
+    L.y2_aug_cls_pack.argtypes = [C.POINTER(AugClsItem), C.c_int, C.c_int, C.POINTER(AugCls), C.c_void_p]
+    L.y2h_augment_cls_to_input.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.y2h_stream_k_launches.restype = C.c_ulong
     L.y2h_tail_launches.restype = C.c_ulong
     L.y2h_xcd_order_launches.restype = C.c_ulong
@@ -551,6 +575,57 @@ def aug_truth_detection(item: dict, num_boxes: int = 30) -> np.ndarray:
     if lib().y2_aug_truth_detection(arr, num_boxes, _ptr(out)) != 0:
         raise Y2Error("y2_aug_truth_detection: " + _check())
     return out
+
+
+CLS_DRAWS = ("aspect", "scale", "rad", "dx", "dy", "flip", "dhue", "dsat", "dexp")
+
+
+def aug_cls_items(items):
+    """items: list of dicts -- frame (uint8 [h][w][c >= 3]; a view of a wider buffer keeps its row pitch) and the draws
+    aspect, scale, rad, dx, dy, flip, dhue, dsat, dexp (default: the centred crop at scale 1, unchanged) -> (AugClsItem
+    array, arrays kept alive for the call)"""
+    arr = (AugClsItem * max(len(items), 1))()
+    keep = []
+    for i, it in enumerate(items):
+        f = np.asarray(it["frame"])
+        if f.ndim != 3 or f.dtype != np.uint8 or f.strides[2] != 1 or f.strides[1] != f.shape[2] or f.strides[0] < f.shape[1] * f.shape[2]:
+            f = np.ascontiguousarray(f, dtype=np.uint8)
+            if f.ndim == 2:
+                f = f[:, :, None]
+        h, w, c = f.shape
+        keep.append(f)
+        arr[i] = AugClsItem(f.ctypes.data, h, w, c, f.strides[0], it.get("aspect", 1.), it.get("scale", 1.), it.get("rad", 0.),
+                            it.get("dx", 0.), it.get("dy", 0.), int(it.get("flip", 0)), it.get("dhue", 0.), it.get("dsat", 1.),
+                            it.get("dexp", 1.))
+    return arr, keep
+
+
+def aug_draw_classification(ow: int, oh: int, min_crop: int, max_crop: int, size: int, angle: float, aspect: float, hue: float,
+                            saturation: float, exposure: float) -> dict:
+    """y2_aug_draw_classification: one image's draws of load_image_augment_paths, in the reference's rand() order -> the
+    draw keys of aug_cls_items; Y2Error when the frame's shorter side truncates to 0"""
+    it = AugClsItem()
+    if lib().y2_aug_draw_classification(ow, oh, min_crop, max_crop, size, angle, aspect, hue, saturation, exposure, C.byref(it)) != 0:
+        raise Y2Error("y2_aug_draw_classification: " + _check())
+    return {k: getattr(it, k) for k in CLS_DRAWS}
+
+
+def aug_labels(path: str, labels, hierarchy=None):
+    """y2_aug_labels: fill_truth (and fill_hierarchy with a Tree) -> (truth float32 [len(labels)], matching labels)"""
+    names = (C.c_char_p * max(len(labels), 1))(*[l.encode() for l in labels])
+    out = np.zeros(max(len(labels), 1), np.float32)
+    n = lib().y2_aug_labels(path.encode(), names, len(labels), hierarchy, _ptr(out))
+    if n < 0:
+        raise Y2Error("y2_aug_labels: " + _check())
+    return out[:len(labels)], n
+
+
+def aug_cls_rect(item: dict, size: int) -> tuple:
+    """the frame rectangle (x0, y0, rw, rh) the packer sends up for one aug_cls_items dict"""
+    arr, keep = aug_cls_items([item])
+    v = [C.c_int(0) for _ in range(4)]
+    lib().y2_aug_cls_rect(arr, size, *[C.byref(k) for k in v])
+    return tuple(k.value for k in v)
 
 
 def srand(seed: int) -> None:
@@ -860,6 +935,26 @@ class Network:
         if lib().y2_train_load_detection(C.byref(self.net), arr, len(items), int(swap_rb)) != 0:
             raise Y2Error("y2_train_load_detection: " + _check())
 
+    def net_augment_classifier(self) -> dict:
+        """y2_net_augment_classifier: [net] min_crop / max_crop / angle / aspect / hue / saturation / exposure"""
+        i = [C.c_int(0) for _ in range(2)]
+        f = [C.c_float(0) for _ in range(5)]
+        if lib().y2_net_augment_classifier(self.net, *[C.byref(v) for v in i + f]) != 0:
+            raise Y2Error("y2_net_augment_classifier: " + _check())
+        return dict(min_crop=i[0].value, max_crop=i[1].value, angle=f[0].value, aspect=f[1].value, hue=f[2].value,
+                    saturation=f[3].value, exposure=f[4].value)
+
+    def train_load_classification(self, items, truth, swap_rb: bool = False) -> None:
+        """y2_train_load_classification: one batch of aug_cls_items dicts and its truth [batch][truth_floats()] -> the
+        trainer's input and truth, built on the device"""
+        arr, keep = aug_cls_items(items)
+        if truth is not None:
+            truth = np.ascontiguousarray(truth, dtype=np.float32).reshape(-1)
+            if truth.size != self.net.batch * self.truth_floats():
+                raise ValueError("train_load_classification: truth has %d floats" % truth.size)
+        if lib().y2_train_load_classification(C.byref(self.net), arr, _ptr(truth) if truth is not None else None, len(items), int(swap_rb)) != 0:
+            raise Y2Error("y2_train_load_classification: " + _check())
+
     def train_step_loaded(self) -> float:
         loss = C.c_float(0)
         if lib().y2_train_step_loaded(C.byref(self.net), C.byref(loss)) != 0:
@@ -867,9 +962,9 @@ class Network:
         return float(loss.value)
 
     def train_pull_input(self):
-        """the loaded batch as the reference holds it: x [batch][3][h][w], truth [batch][150]"""
+        """the loaded batch as the reference holds it: x [batch][3][h][w], truth [batch][150] (a classifier: [batch][truth_floats()])"""
         x = np.zeros((self.net.batch, self.net.c, self.net.h, self.net.w), np.float32)
-        y = np.zeros((self.net.batch, 150), np.float32)
+        y = np.zeros((self.net.batch, 150 if LAYER_TYPES[self.net.layers[self.net.n - 1].type] == "REGION" else self.truth_floats()), np.float32)
         if lib().y2_train_pull_input(C.byref(self.net), _ptr(x), _ptr(y)) != 0:
             raise Y2Error("y2_train_pull_input: " + _check())
         return x, y

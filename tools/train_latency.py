@@ -20,7 +20,15 @@ A detector's row also names the launches of its head (y2_train_det.hip: region_c
 region_finish): their share of the step is read from one `rocprofv3 --kernel-trace --stats -- python tools/train_latency.py
 --net yolo --no-products --no-reference` run.
 
-With --loader (detectors only) one more row per batch size, the detection loader: `batch` frames of 500x375x3 bytes with
+With --loader one more row per batch size.  For --net darknet19 it is the classifier loader: `batch` frames of 500x375x3
+bytes, the draws made by y2_aug_draw_classification with cfg/tiny.cfg's values (angle=7 aspect=.75 hue=.1 saturation=.75
+exposure=.75 max_crop=320, min_crop = the network's width), one-hot truth rows:
+  kernel    y2h_augment_cls_to_input alone on what y2_aug_cls_pack sends up, already in HBM, twenty launches back to back
+            between two events -> p50 ms per launch, next to its byte floor: the output floats written once plus the
+            packed source bytes read once, at 6.3 TB/s
+  load      host wall time of y2_train_load_classification (p50) and its split as y2_train_load_times reports it
+  step      load + y2_train_step_loaded against y2_train_step fed ready-made host floats, in alternating pairs
+For a detector it is the detection loader: `batch` frames of 500x375x3 bytes with
 three label rows each, the draws made by y2_aug_draw_detection from what y2_net_augment reports:
   kernel    y2h_augment_to_input alone on buffers already in HBM, twenty launches back to back between two events -> p50 ms
             per launch, next to its byte floor: the output
@@ -135,8 +143,69 @@ def products(net, timer, reps, only=None):
 HBM_BYTES_PER_S = 6.3e12          # the achievable rate, not the peak
 
 
+def measure_loader(net, batch, timer, steps, warmup, reps, label, table, pixels, touched, frame_bytes, launch, load):
+    """what both --loader rows measure: `launch(d_desc, d_pix, d_out)` alone on `table` and `pixels` already in HBM, twenty
+    launches between two events; `load(k)` alone with its split; load + y2_train_step_loaded against y2_train_step fed
+    ready-made host floats, in alternating pairs"""
+    L = darknet.lib()
+    w, h = net.net.w, net.net.h
+    d_desc, d_pix, d_out = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    out_bytes = batch * h * w * 3 * 4
+    assert L.y2h_malloc(C.byref(d_desc), table.size) == 0 and L.y2h_malloc(C.byref(d_pix), pixels.size) == 0 and L.y2h_malloc(C.byref(d_out), out_bytes) == 0
+    assert L.y2h_memcpy_h2d(d_desc, table.ctypes.data, table.size, None) == 0 and L.y2h_memcpy_h2d(d_pix, pixels.ctypes.data, pixels.size, None) == 0
+    assert L.y2h_device_sync() == 0
+
+    BACK_TO_BACK = 20                                    # one pair of events around a train of launches: a lone 10 us kernel
+                                                         # would be timed with its launch gap
+
+    def kernel():
+        for _ in range(BACK_TO_BACK):
+            assert launch(d_desc, d_pix, d_out) == 0
+    for _ in range(warmup):
+        kernel()
+    kernel_ms = p50([timer.ms(kernel) for _ in range(max(reps, 5) * 4)]) / BACK_TO_BACK
+    for p_ in (d_desc, d_pix, d_out):
+        L.y2h_free(p_)
+    floor_ms = (out_bytes + touched) / HBM_BYTES_PER_S * 1e3
+    # the load, and load + step against the host-float step, in alternating pairs
+    x = synth.uniform(5, batch * net.net.inputs, 0, 1)
+    y = truth_for(net, batch)
+    loss = C.c_float(0)
+
+    def new_step(k):
+        load(k, y)
+        assert L.y2_train_step_loaded(C.byref(net.net), C.byref(loss)) == 0, darknet._check()
+
+    def old_step(k):
+        assert L.y2_train_step(C.byref(net.net), x.ctypes.data, y.ctypes.data, C.byref(loss)) == 0, darknet._check()
+
+    def wall(fn, *a):
+        t0 = time.perf_counter()
+        fn(*a)
+        return (time.perf_counter() - t0) * 1e3
+    for k in range(warmup):
+        new_step(k)
+        old_step(k)
+    new_ms, old_ms, load_ms, split = [], [], [], []
+    for k in range(steps):
+        new_ms.append(wall(new_step, k))
+        old_ms.append(wall(old_step, k))
+    for k in range(steps):
+        load_ms.append(wall(load, k, y))
+        split.append(net.train_load_times())
+    return {"loader": {"frames": "%d x %s -> %dx%d" % (batch, label, w, h), "kernel_p50_ms": round(kernel_ms, 4), "byte_floor_ms": round(floor_ms, 4),
+                       "kernel_over_floor": round(kernel_ms / floor_ms, 2), "kernel_share_of_step": round(kernel_ms / p50(new_ms), 4),
+                       "output_bytes": out_bytes, "touched_source_bytes": int(touched),
+                       "frame_bytes": int(frame_bytes), "host_float_bytes": int(x.nbytes), "load_wall_p50_ms": round(p50(load_ms), 3),
+                       "load_pack_ms": round(p50([s_[0] for s_ in split]), 3), "load_enqueue_ms": round(p50([s_[1] for s_ in split]), 3),
+                       "load_wait_copy_ms": round(p50([s_[2] for s_ in split]), 3),
+                       "load_plus_step_p50_ms": round(p50(new_ms), 3), "host_float_step_p50_ms": round(p50(old_ms), 3),
+                       "new_over_old": round(p50(new_ms) / p50(old_ms), 3),
+                       "load_plus_step_ms": [round(v, 3) for v in new_ms], "host_float_step_ms": [round(v, 3) for v in old_ms]}}
+
+
 def loader_row(net, batch, timer, steps, warmup, reps):
-    """the --loader row: see the module docstring"""
+    """the --loader row of a detector: see the module docstring"""
     L = darknet.lib()
     aug = net.net_augment()
     w, h = net.net.w, net.net.h
@@ -149,7 +218,7 @@ def loader_row(net, batch, timer, steps, warmup, reps):
     for _ in range(4):                                   # four batches of draws, reused in turn
         items = [dict(darknet.aug_draw_detection(500, 375, aug["jitter"], hue, sat, exp, len(boxes)), frame=f, boxes=boxes) for f in frames]
         sets.append((items,) + darknet.aug_items(items))
-    # kernel alone: whole frames and a table made here, already in HBM
+    # kernel alone: whole frames and a table made here
     items = sets[0][0]
     desc = (darknet.Aug * batch)()
     touched = 0
@@ -162,63 +231,47 @@ def loader_row(net, batch, timer, steps, warmup, reps):
         touched += cols * rows * 3
     pixels = np.concatenate([f.reshape(-1) for f in frames])
     table = np.frombuffer(bytes(desc), np.uint8)
-    d_desc, d_pix, d_out = C.c_void_p(), C.c_void_p(), C.c_void_p()
-    out_bytes = batch * h * w * 3 * 4
-    assert L.y2h_malloc(C.byref(d_desc), table.size) == 0 and L.y2h_malloc(C.byref(d_pix), pixels.size) == 0 and L.y2h_malloc(C.byref(d_out), out_bytes) == 0
-    assert L.y2h_memcpy_h2d(d_desc, table.ctypes.data, table.size, None) == 0 and L.y2h_memcpy_h2d(d_pix, pixels.ctypes.data, pixels.size, None) == 0
-    assert L.y2h_device_sync() == 0
 
-    BACK_TO_BACK = 20                                    # one pair of events around a train of launches: a lone 10 us kernel
-                                                         # would be timed with its launch gap
+    def launch(d_desc, d_pix, d_out):
+        return L.y2h_augment_to_input(d_desc, batch, d_pix, 0, h, w, d_out, timer.stream)
 
-    def kernel():
-        for _ in range(BACK_TO_BACK):
-            assert L.y2h_augment_to_input(d_desc, batch, d_pix, 0, h, w, d_out, timer.stream) == 0
-    for _ in range(warmup):
-        kernel()
-    kernel_ms = p50([timer.ms(kernel) for _ in range(max(reps, 5) * 4)]) / BACK_TO_BACK
-    for p_ in (d_desc, d_pix, d_out):
-        L.y2h_free(p_)
-    floor_ms = (out_bytes + touched) / HBM_BYTES_PER_S * 1e3
-    # the load, and load + step against the host-float step, in alternating pairs
-    x = synth.uniform(5, batch * net.net.inputs, 0, 1)
-    y = truth_for(net, batch)
-    loss = C.c_float(0)
-
-    def load(k):
+    def load(k, _y):
         _, arr, _keep = sets[k % len(sets)]
         assert L.y2_train_load_detection(C.byref(net.net), arr, batch, 0) == 0, darknet._check()
+    return measure_loader(net, batch, timer, steps, warmup, reps, "500x375x3", table, pixels, touched, sum(f.nbytes for f in frames), launch, load)
 
-    def new_step(k):
-        load(k)
-        assert L.y2_train_step_loaded(C.byref(net.net), C.byref(loss)) == 0, darknet._check()
 
-    def old_step(k):
-        assert L.y2_train_step(C.byref(net.net), x.ctypes.data, y.ctypes.data, C.byref(loss)) == 0, darknet._check()
+TINY_CFG = dict(angle=7., aspect=.75, hue=.1, saturation=.75, exposure=.75, max_crop=320)      # cfg/tiny.cfg's [net] values
 
-    def wall(fn, k):
-        t0 = time.perf_counter()
-        fn(k)
-        return (time.perf_counter() - t0) * 1e3
-    for k in range(warmup):
-        new_step(k)
-        old_step(k)
-    new_ms, old_ms, load_ms, split = [], [], [], []
-    for k in range(steps):
-        new_ms.append(wall(new_step, k))
-        old_ms.append(wall(old_step, k))
-    for k in range(steps):
-        load_ms.append(wall(load, k))
-        split.append(net.train_load_times())
-    packed = int(sum(f.nbytes for f in frames))
-    return {"loader": {"frames": "%d x 500x375x3 -> %dx%d" % (batch, w, h), "kernel_p50_ms": round(kernel_ms, 4), "byte_floor_ms": round(floor_ms, 4),
-                       "kernel_over_floor": round(kernel_ms / floor_ms, 2), "output_bytes": out_bytes, "touched_source_bytes": int(touched),
-                       "frame_bytes": packed, "load_wall_p50_ms": round(p50(load_ms), 3),
-                       "load_pack_ms": round(p50([s_[0] for s_ in split]), 3), "load_enqueue_ms": round(p50([s_[1] for s_ in split]), 3),
-                       "load_wait_copy_ms": round(p50([s_[2] for s_ in split]), 3),
-                       "load_plus_step_p50_ms": round(p50(new_ms), 3), "host_float_step_p50_ms": round(p50(old_ms), 3),
-                       "new_over_old": round(p50(new_ms) / p50(old_ms), 3),
-                       "load_plus_step_ms": [round(v, 3) for v in new_ms], "host_float_step_ms": [round(v, 3) for v in old_ms]}}
+
+def cls_loader_row(net, batch, timer, steps, warmup, reps):
+    """the --loader row of a classifier: see the module docstring"""
+    L = darknet.lib()
+    size = net.net.w
+    rng = np.random.default_rng(17)
+    frames = [rng.integers(0, 256, size=(375, 500, 3), dtype=np.uint8) for _ in range(batch)]
+    a = TINY_CFG
+    darknet.srand(1)
+    sets = []
+    for _ in range(4):                                   # four batches of draws, reused in turn
+        items = [dict(darknet.aug_draw_classification(500, 375, size, a["max_crop"], size, a["angle"], a["aspect"], a["hue"], a["saturation"],
+                                                      a["exposure"]), frame=f) for f in frames]
+        sets.append((items,) + darknet.aug_cls_items(items))
+    # kernel alone: the packer's table and rectangles
+    _, arr, _keep = sets[0]
+    touched = int(L.y2_aug_cls_pack_bytes(arr, batch, size))
+    desc = (darknet.AugCls * batch)()
+    pixels = np.zeros(touched, np.uint8)
+    L.y2_aug_cls_pack(arr, batch, size, desc, pixels.ctypes.data)
+    table = np.frombuffer(bytes(desc), np.uint8)
+
+    def launch(d_desc, d_pix, d_out):
+        return L.y2h_augment_cls_to_input(d_desc, batch, d_pix, 0, size, d_out, timer.stream)
+
+    def load(k, y):
+        _, arr, _keep = sets[k % len(sets)]
+        assert L.y2_train_load_classification(C.byref(net.net), arr, y.ctypes.data, batch, 0) == 0, darknet._check()
+    return measure_loader(net, batch, timer, steps, warmup, reps, "500x375x3", table, pixels, touched, sum(f.nbytes for f in frames), launch, load)
 
 
 def reference_step(tmp, wts, name, size, batch, steps=2):
@@ -244,10 +297,8 @@ def main():
     ap.add_argument("--no-products", action="store_true")
     ap.add_argument("--layers", default=None, help="only these layers' products, e.g. 4,18 (with --steps 0 --warmup 0 "
                     "--no-reference: the few launches a counter run wants, `rocprofv3 --pmc ... -- python tools/train_latency.py ...`)")
-    ap.add_argument("--loader", action="store_true", help="add the detection loader's row (detectors only)")
+    ap.add_argument("--loader", action="store_true", help="add the loader's row: the classifier loader for darknet19, the detection loader for a detector")
     a = ap.parse_args()
-    if a.loader and a.net == "darknet19":
-        ap.error("--loader is for the detectors (--net tiny-yolo-voc | yolo)")
     SIZE, batches, ref_batch = NETS[a.net][:3]
     L = darknet.lib()
     tmp = tempfile.mkdtemp()
@@ -281,7 +332,7 @@ def main():
             for k in ("forward", "dinput", "dweight"):
                 res[k + "_sum_ms"] = round(sum(r[k + "_ms"] for r in res["products"]), 3)
         if a.loader:
-            res.update(loader_row(net, batch, timer, max(a.steps, 1), a.warmup, a.reps))
+            res.update((cls_loader_row if a.net == "darknet19" else loader_row)(net, batch, timer, max(a.steps, 1), a.warmup, a.reps))
             print("  " + json.dumps(res["loader"]))
         L.y2h_free(d_x)
         L.y2h_free(d_y)
