@@ -226,6 +226,27 @@ int y2h_conv_wino_forward(const y2h_conv *d, y2h_stream s);
 /* number of such forwards issued by this process so far (tests) */
 unsigned long y2h_wino_launches(void);
 
+/* ---- the split form of the Winograd GEMM: fp32 operands as three bf16 planes (the rule: include/y2_split_rule.h) ---- */
+typedef struct y2h_wino_split {
+    int eligible;                /* the shape is one the split kernels take                                      */
+    int take;                    /* the rule's answer (Y2_WINO_SPLIT=0: never, =1: every eligible layer)          */
+    int bm, bn, bk;              /* tile of the batched GEMM                                                     */
+    long tiles, tiles_pad;       /* 2x2 output patches per component, and padded to a multiple of bm             */
+    size_t u_bytes;              /* split filters U[16][rows_pad(n)][c], three bf16 planes (y2_split_index)      */
+    size_t v_bytes, m_bytes;     /* split input V[16][tiles_pad][c] (6 bytes per element), fp32 M[16][tiles_pad][n] */
+    double present_cost, gemm_cost, split_cost;   /* CU cycles; present: the form the layer has without the split, fp32
+                                                     Winograd or direct (zero when a switch decides, not the rule) */
+} y2h_wino_split;
+/* Host arithmetic only (no GPU).  Leaves what y2h_wino_plan, y2h_winos_plan and the conv queries answer alone. */
+int y2h_wino_split_plan(const y2h_conv *d, y2h_wino_split *out);
+/* bytes of scratch (V at 6 bytes per element, and M) y2h_conv_winox_forward needs in d->ws when the rule takes the descriptor, else 0 */
+size_t y2h_wino_split_workspace_bytes(const y2h_conv *d);
+/* The convolution as split input transform -> split GEMM -> output transform + epilogue.  d->w_packed holds the split U
+ * (y2_split_pack_u), d->ws at least y2h_wino_split_workspace_bytes(d).  Y2H_EINVAL unless y2h_wino_split_plan takes the descriptor. */
+int y2h_conv_winox_forward(const y2h_conv *d, y2h_stream s);
+/* number of split GEMM launches issued by this process so far (tests) */
+unsigned long y2h_wino_split_launches(void);
+
 /* ---- stationary Winograd: F(2x2,3x3) as one fused kernel, filters in registers (the rule: include/y2_winos_rule.h) ---- */
 typedef struct y2h_winos {
     int eligible;                /* the shape is one a form of the kernel takes                              */

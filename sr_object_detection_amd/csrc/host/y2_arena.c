@@ -10,6 +10,7 @@
 #include "y2_internal.h"
 #include "y2_wino_rule.h"
 #include "y2_winos_rule.h"
+#include "y2_split_rule.h"
 
 /* the layer types that own arena space: layout, signature and packing all iterate with this */
 static int owns_arena(const layer *l)
@@ -89,8 +90,9 @@ void y2_arena_layout(network *net)
             d->off_bias = off; off = align_up(off + (size_t)l->outputs * sizeof(float), 64);
             continue;
         }
-        /* a Winograd layer keeps U[16][n][c] = G g G^T in place of its nine packed taps, a stationary one U in register order */
-        d->off_w_packed = off; off = align_up(off + (d->winos ? y2_winos_u_floats(l->n) * sizeof(float) : d->wino ? (size_t)16 * l->n * l->c * sizeof(float) : w_half ? wbytes / 2 : wbytes), 256);
+        /* a Winograd layer keeps U[16][n][c] = G g G^T in place of its nine packed taps, a split one U as three bf16 planes,
+         * a stationary one U in register order */
+        d->off_w_packed = off; off = align_up(off + (d->winos ? y2_winos_u_floats(l->n) * sizeof(float) : d->winox ? y2_split_bytes(y2_split_rows_pad(l->n), l->c) : d->wino ? (size_t)16 * l->n * l->c * sizeof(float) : w_half ? wbytes / 2 : wbytes), 256);
         if (d->has_w_ref) { d->off_w_ref = off; off = align_up(off + wbytes, 256); }
         d->off_bias = off; off = align_up(off + l->n * sizeof(float), 64);
         if (w_half) {
@@ -122,6 +124,7 @@ static uint64_t arena_signature(const network *net)
         SIG_MIX(d->uses_mfma); SIG_MIX(y2_half_weights(net, i));
         SIG_MIX(l->batch_normalize ? d->off_rinv + 1 : 0);
         if (d->wino) SIG_MIX(0x57494e4f);      /* the filter slot holds U, not the packed taps (mixed only where it does) */
+        if (d->winox) SIG_MIX(0x57494e58);     /* ... or the split U: three bf16 planes (y2_split_rule.h) */
         if (d->winos) SIG_MIX(0x57494e53);     /* ... or U in the stationary kernel's register order */
     }
     SIG_MIX(e->strict); SIG_MIX(e->half); SIG_MIX(e->arena_need);
@@ -254,6 +257,7 @@ static void pack_dense(unsigned char *host, const network *net, int i)
     const int K = l->size * l->size * l->c, w_half = y2_half_weights(net, i);
     int co, f, q;
     if (d->winos) pack_winos((float *)(host + d->off_w_packed), l);
+    else if (d->winox) y2_split_pack_u((uint16_t *)(host + d->off_w_packed), l->weights, l->n, l->c);      /* reference layout [n][c][3][3] */
     else if (d->wino) pack_wino((float *)(host + d->off_w_packed), l);
     else pack_filters((float *)(host + d->off_w_packed), net, i, w_half);
     if (w_half) {

@@ -24,6 +24,8 @@ typedef struct y2_ldev {
     int has_w_ref;
     int uses_mfma;
     int wino;                  /* conv: runs as Winograd F(2x2,3x3) (y2_plan.c plan_wino); off_w_packed then holds U[16][n][c] */
+    int winox;                 /* conv: runs as Winograd with the split GEMM (y2_plan.c plan_winox); off_w_packed then holds
+                                  the split U, three bf16 planes (y2_split_rule.h) */
     int winos;                 /* conv: runs as the fused stationary Winograd kernel (y2_plan.c plan_winos); off_w_packed then
                                   holds U in its register order (y2_winos_rule.h) */
     int fused_pool;           /* conv: the following 2x2/2 maxpool runs in this conv's epilogue */

@@ -33,6 +33,7 @@ void y2_free_plan(network *net)
         d->fused_pool = 0; d->fused_into = -1;
         d->out_half = 0;
         d->wino = 0;
+        d->winox = 0;
         d->winos = 0;
         d->tile_bm = d->tile_bn = d->ksplit = 0;
         d->conn_ranges = 0;
@@ -267,7 +268,7 @@ static int plan_workspace(network *net)
         }
         y2_input_view(net, i, &x, &ldx);
         conv_query(net, i, &c, x, ldx);
-        b = ld_of(&net->layers[i])->wino ? y2h_wino_workspace_bytes(&c) : y2h_conv_workspace_bytes(&c);      /* Winograd: V and M */
+        b = ld_of(&net->layers[i])->winox ? y2h_wino_split_workspace_bytes(&c) : ld_of(&net->layers[i])->wino ? y2h_wino_workspace_bytes(&c) : y2h_conv_workspace_bytes(&c);      /* Winograd: V and M */
         if (ld_of(&net->layers[i])->winos) b = 0;                                                             /* stationary Winograd: none */
         if (b > need) need = b;
     }
@@ -298,7 +299,7 @@ static int autotune_layers(network *net)
         y2_ldev *d = ld_of(l);
         y2h_conv c;
         const float *x; int ldx, n, bm[64], bn[64], ks[64];
-        if (l->type != CONVOLUTIONAL || !d->uses_mfma || l->xnor || d->wino || d->winos) continue;      /* (a Winograd layer has no direct tile to measure) */
+        if (l->type != CONVOLUTIONAL || !d->uses_mfma || l->xnor || d->wino || d->winox || d->winos) continue;      /* (a Winograd layer has no direct tile to measure) */
         y2_input_view(net, i, &x, &ldx);
         y2_conv_desc(net, i, &c, x, ldx);
         n = y2h_conv_candidates(&c, bm, bn, ks, 64);
@@ -316,7 +317,7 @@ static int autotune_layers(network *net)
         y2h_conv c;
         const float *x; int ldx, n, hit = 0, bm[64], bn[64], ks[64], best = 0;
         float best_ms = 0.f;
-        if (l->type != CONVOLUTIONAL || !d->uses_mfma || l->xnor || d->wino || d->winos) continue;      /* (a Winograd layer has no direct tile to measure) */
+        if (l->type != CONVOLUTIONAL || !d->uses_mfma || l->xnor || d->wino || d->winox || d->winos) continue;      /* (a Winograd layer has no direct tile to measure) */
         y2_input_view(net, i, &x, &ldx);
         y2_conv_desc(net, i, &c, x, ldx);
         pthread_mutex_lock(&g_tuned_mu);
@@ -930,6 +931,31 @@ static int plan_conv_kernels(network *net)
     return 0;
 }
 
+/* which of them run as Winograd with the split GEMM (the rule: include/y2_split_rule.h, asked through y2h_wino_split_plan).
+ * Such a layer keeps the split U in the arena in place of its packed filters, is named conv_winox_f32_<bm>x<bn>x<bk> and
+ * takes its V / M scratch from the shared workspace.  Runs ahead of plan_wino, which leaves its layers alone. */
+static int plan_winox(network *net)
+{
+    y2_engine *e = y2_engine_of(net);
+    int i;
+    if (e->strict || e->half) return 0;
+    for (i = 0; i < net->n; ++i) {
+        layer *l = &net->layers[i];
+        y2_ldev *d = ld_of(l);
+        y2h_conv c;
+        y2h_wino_split w;
+        const float *x; int ldx;
+        if (l->type != CONVOLUTIONAL || !d->uses_mfma || l->xnor) continue;
+        y2_input_view(net, i, &x, &ldx);
+        conv_query(net, i, &c, x, ldx);
+        if (y2h_wino_split_plan(&c, &w) != 0 || !w.take) continue;
+        d->winox = 1;
+        snprintf(d->kname, sizeof d->kname, "conv_winox_f32_%dx%dx%d%s", w.bm, w.bn, w.bk, d->fused_pool ? "+maxpool2" : "");
+        d->kernel = d->kname;
+    }
+    return 0;
+}
+
 /* which of the fp32 matrix-core 3x3 convolutions run as Winograd F(2x2,3x3) instead (the rule: include/y2_wino_rule.h,
  * asked through y2h_wino_plan).  Such a layer keeps U = G g G^T in the arena in place of its packed filters, is named
  * conv_wino_f32_<bm>x<bn>x32 after its batched GEMM's tile, and takes its V / M scratch from the shared workspace.  Its
@@ -945,7 +971,7 @@ static int plan_wino(network *net)
         y2h_conv c;
         y2h_wino w;
         const float *x; int ldx;
-        if (l->type != CONVOLUTIONAL || !d->uses_mfma || l->xnor) continue;
+        if (l->type != CONVOLUTIONAL || !d->uses_mfma || l->xnor || d->winox) continue;
         y2_input_view(net, i, &x, &ldx);
         conv_query(net, i, &c, x, ldx);
         if (y2h_wino_plan(&c, &w) != 0 || !w.take) continue;
@@ -970,7 +996,7 @@ static int plan_winos(network *net)
         y2h_conv c;
         y2h_winos w;
         const float *x; int ldx;
-        if (l->type != CONVOLUTIONAL || !d->uses_mfma || l->xnor || d->wino) continue;
+        if (l->type != CONVOLUTIONAL || !d->uses_mfma || l->xnor || d->wino || d->winox) continue;
         y2_input_view(net, i, &x, &ldx);
         conv_query(net, i, &c, x, ldx);
         if (y2h_winos_plan(&c, &w) != 0 || !w.take) continue;
@@ -1003,7 +1029,7 @@ int y2_engine_build(network *net)
     y2_free_plan(net);
     if (plan_batches(net) != 0 || plan_routes(net) != 0 || plan_pool_fusion(net) != 0 || plan_half(net) != 0 ||
         plan_activations(net) != 0 || plan_input_copies(net) != 0 || plan_input(net) != 0 || plan_output(net) != 0 ||
-        plan_head_constants(net) != 0 || plan_conv_kernels(net) != 0 || plan_wino(net) != 0 || plan_winos(net) != 0) return -1;
+        plan_head_constants(net) != 0 || plan_conv_kernels(net) != 0 || plan_winox(net) != 0 || plan_wino(net) != 0 || plan_winos(net) != 0) return -1;
     y2_arena_layout(net);
     /* the arena commit: signature, reallocation, the refusal of a replicated rank whose layout changed */
     if (plan_workspace(net) != 0 || y2_arena_commit(net) != 0 || plan_timing_events(net) != 0) return -1;

@@ -59,6 +59,7 @@
 //
 // This file is compiled with -ffp-contract=off: no mul+add below may fuse.
 #include "y2_conv_shared.hpp"
+#include "y2_split_rule.h"
 #include <type_traits>
 
 // ---------------------------------------------------------------------------
@@ -1683,6 +1684,58 @@ extern "C" int y2h_wino_plan(const y2h_conv *d, y2h_wino *out)
     return Y2H_OK;
 }
 
+// The split form of the batched GEMM (include/y2_split_rule.h, y2_wino_split.hip): the rule applies to layers y2h_wino_plan
+// takes and moves a layer when the split cost is below the fp32 Winograd form's by Y2_WINO_MARGIN.  (Layers the Winograd
+// rule leaves direct stay direct: the 76x76 layers of yolo.cfg 608x608 batch 32 measure 25 % faster in the split form, but
+// tests/test_gpu_configs.py requires the benchmark's direct 192x256 tile to run in that network.)  Y2_WINO_SPLIT=0: never;
+// Y2_WINO_SPLIT=1: every eligible layer (tests; Y2_WINO_SPLIT_TILE forces the split GEMM's tile as Y2_CONV_TILE does the
+// fp32 tiles').  A Y2_CONV_TILE names an fp32 tile and keeps the fp32 forms; without Y2_WINO_SPLIT=1 so does a Y2_WINO switch.
+extern "C" int y2h_wino_split_plan(const y2h_conv *d, y2h_wino_split *out)
+{
+    if (!d || !out) return Y2H_EINVAL;
+    memset(out, 0, sizeof *out);
+    int mode = -1;
+    if (const char *f = getenv("Y2_WINO_SPLIT")) mode = atoi(f) != 0 ? 1 : 0;
+    if (!y2_split_shape_ok(d->size, d->stride, d->pad, d->c, d->n, d->h, d->w, d->out_h, d->out_w, d->fuse_maxpool2, d->x_f16, d->y_f16,
+                           d->x_halo, d->x_nchw, d->ldx)) return Y2H_OK;
+    const ConvPlan p = conv_plan(d, 0);
+    if (p.kind != CK_MFMA_F32) return Y2H_OK;
+    const char *wino_env = getenv("Y2_WINO"), *tile_env = getenv("Y2_CONV_TILE");
+    if (const char *f = getenv("Y2_WINO_SPLIT_TILE")) {          // tests: the split GEMM's tile (there is one)
+        int bm = 0, bn = 0;
+        sscanf(f, "%dx%d", &bm, &bn);
+        if (bm != Y2_SPLIT_ROWS || bn != Y2_SPLIT_ROWS) return Y2H_OK;
+    }
+    const long tiles = y2_wino_tiles(d->batch, d->h, d->w), tp = y2_split_rows_pad(tiles);
+    const double vb = (double)y2_split_bytes(tp, d->c), ub = (double)y2_split_bytes(y2_split_rows_pad(d->n), d->c);
+    const double mb = 16.0 * (double)tp * d->n * 4.0;
+    if (vb >= 4294967000.0 || mb >= 4294967000.0 || ub >= 4294967000.0) return Y2H_OK;        // 32-bit buffer offsets
+    out->eligible = 1;
+    out->bm = Y2_SPLIT_ROWS; out->bn = Y2_SPLIT_ROWS; out->bk = Y2_SPLIT_BK;
+    out->tiles = tiles; out->tiles_pad = tp;
+    out->u_bytes = (size_t)ub; out->v_bytes = (size_t)vb; out->m_bytes = (size_t)mb;
+    if (wino_env && atoi(wino_env) == 0) return Y2H_OK;                                       // no Winograd of any form
+    if (tile_env) return Y2H_OK;                                                              // an fp32 tile is asked for
+    if (mode == 1) { out->take = 1; return Y2H_OK; }
+    if (mode == 0 || wino_env) return Y2H_OK;
+    // the fp32 form's answer, with the switches that force it out of the way (none is set here)
+    y2h_wino w;
+    if (y2h_wino_plan(d, &w) != Y2H_OK || !w.eligible) return Y2H_OK;
+    const long blocks = 16 * (tp / Y2_SPLIT_ROWS) * (y2_split_rows_pad(d->n) / Y2_SPLIT_ROWS);
+    out->gemm_cost = y2_split_gemm_cost(blocks, d->c / Y2_SPLIT_BK, vb, ub, mb);
+    out->split_cost = y2_split_cost(out->gemm_cost, y2_split_transform_bytes(d->batch, d->h, d->w, d->c, d->n, d->fuse_maxpool2, tp));
+    out->present_cost = w.take ? w.wino_cost : w.direct_cost;
+    out->take = w.take && y2_wino_wins(out->present_cost, out->split_cost);
+    return Y2H_OK;
+}
+
+extern "C" size_t y2h_wino_split_workspace_bytes(const y2h_conv *d)
+{
+    y2h_wino_split x;
+    if (y2h_wino_split_plan(d, &x) != Y2H_OK || !x.take) return 0;
+    return x.v_bytes + x.m_bytes;
+}
+
 extern "C" size_t y2h_wino_workspace_bytes(const y2h_conv *d)
 {
     y2h_wino w;
@@ -1886,6 +1939,25 @@ extern "C" int y2h_conv_wino_forward(const y2h_conv *d, y2h_stream s)
     if (rc != Y2H_OK) return rc;
     ++g_wino_launches;
     return Y2H_OK;
+}
+
+// The same through the split form: V as three bf16 planes, the batched GEMM on the bf16 matrix cores (y2_wino_split.hip),
+// then the fp32 form's own output pass.  d->w_packed holds the split U (y2_split_pack_u).
+extern "C" int y2h_conv_winox_forward(const y2h_conv *d, y2h_stream s)
+{
+    if (!d || !d->x || !d->y || !d->bias || !d->w_packed) return Y2H_EINVAL;
+    if (d->batch <= 0 || d->h <= 0 || d->w <= 0 || d->c <= 0 || d->n <= 0 || d->ldx < d->c || d->ldy < d->n) return Y2H_EINVAL;
+    if (d->batch_normalize && (!d->mean || !d->rinv || !d->scale)) return Y2H_EINVAL;
+    y2h_wino_split w;
+    if (y2h_wino_split_plan(d, &w) != Y2H_OK || !w.take) return Y2H_EINVAL;
+    if (!d->ws || d->ws_bytes < w.v_bytes + w.m_bytes || ((uintptr_t)d->ws % 16) != 0 || w.v_bytes % 16 != 0) return Y2H_EINVAL;
+    unsigned short *V = (unsigned short *)d->ws;
+    float *M = (float *)((unsigned char *)d->ws + w.v_bytes);
+    int rc = y2_wino_input_split_launch(d, V, w.tiles, w.tiles_pad, s);
+    if (rc != Y2H_OK) return rc;
+    rc = y2_wino_split_gemm_launch(V, (const unsigned short *)d->w_packed, M, w.tiles_pad, d->c, d->n, s);
+    if (rc != Y2H_OK) return rc;
+    return y2_wino_output_launch(d, M, w.tiles, w.tiles_pad, s);
 }
 
 // ---------------------------------------------------------------------------

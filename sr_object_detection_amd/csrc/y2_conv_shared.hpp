@@ -277,6 +277,10 @@ bool y2_f16_first_nchw_ok(const y2h_conv *d);
 // V[16][tiles_pad][c] from the NHWC input of d; the layer's output from M[16][tiles_pad][n] through the shared epilogue.
 int y2_wino_input_launch(const y2h_conv *d, float *V, long tiles, long tiles_pad, y2h_stream s);
 int y2_wino_output_launch(const y2h_conv *d, const float *M, long tiles, long tiles_pad, y2h_stream s);
+// The split form (include/y2_split_rule.h): V as three bf16 planes in the layout of y2_split_index (y2_wino.hip), and the
+// batched GEMM on the bf16 matrix cores, raw fp32 sums to M[16][tiles_pad][n] (y2_wino_split.hip).
+int y2_wino_input_split_launch(const y2h_conv *d, unsigned short *V, long tiles, long tiles_pad, y2h_stream s);
+int y2_wino_split_gemm_launch(const unsigned short *V, const unsigned short *U, float *M, long tiles_pad, int c, int n, y2h_stream s);
 
 // Grid of a kernel that walks its tiles with a grid stride: exactly what is co-resident (256 CUs x the runtime's answer for
 // this kernel), no more -- a surplus block only starts when a resident one has finished ALL its tiles, i.e. runs a second,

@@ -381,6 +381,10 @@ def lib():
     L.y2h_activate_array.argtypes = [C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_int, C.c_void_p]
     L.y2h_activate_copy.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_int, C.c_void_p]
     L.y2h_activate_copy_f16.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_int, C.c_void_p]
+    if hasattr(L, "y2h_wino_split_plan"):          # (an older build under Y2_LIB has no split form)
+        L.y2h_wino_split_plan.argtypes = [C.c_void_p, C.c_void_p]        # (y2h_conv *, y2h_wino_split *): tools/plan_dump.py has the structs
+        L.y2h_wino_split_workspace_bytes.restype = C.c_size_t
+        L.y2h_wino_split_launches.restype = C.c_ulong
     L.y2h_d2h_copies.restype = C.c_ulong
     L.y2h_stream_syncs.restype = C.c_ulong
     L.y2_set_view_block_bytes.argtypes = [C.c_size_t]

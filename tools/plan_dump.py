@@ -6,7 +6,8 @@ check that a change of the cost model leaves the plan of the headline configurat
     tools/plan_dump.py --sweep       every dispatch query for every zoo network, a digest per configuration (tests/golden/conv_plan_table.txt)
     tools/plan_dump.py --sweep-rows  the same queries, one line per conv layer: diff two builds' output (Y2_LIB) to see what moved
     tools/plan_dump.py --wino        the Winograd rule's answer for every 3x3 layer of every zoo network (tests/golden/wino_plan_table.txt)
-    tools/plan_dump.py --winos       the stationary-Winograd rule's answer for the same layers (tests/golden/winos_plan_table.txt)"""
+    tools/plan_dump.py --winos       the stationary-Winograd rule's answer for the same layers (tests/golden/winos_plan_table.txt)
+    tools/plan_dump.py --wino-split  the split rule's answer for the same layers (tests/golden/wino_split_plan_table.txt)"""
 import ctypes as C
 import os
 import sys
@@ -194,6 +195,38 @@ def winos_rows(lib):
                 w.u_bytes, wh.eligible, wh.take)
 
 
+class WinoSplit(C.Structure):     # include/y2_hip.h: y2h_wino_split
+    _fields_ = [("eligible", C.c_int), ("take", C.c_int), ("bm", C.c_int), ("bn", C.c_int), ("bk", C.c_int), ("tiles", C.c_long),
+                ("tiles_pad", C.c_long), ("u_bytes", C.c_size_t), ("v_bytes", C.c_size_t), ("m_bytes", C.c_size_t),
+                ("present_cost", C.c_double), ("gemm_cost", C.c_double), ("split_cost", C.c_double)]
+
+
+def wino_split_plan(lib, f):
+    """y2h_wino_split_plan for one descriptor (a dict of y2h_conv fields)"""
+    d, w = Conv(**f), WinoSplit()
+    assert lib.y2h_wino_split_plan(C.byref(d), C.byref(w)) == 0
+    return w
+
+
+def wino_split_rows(lib):
+    """The split rule's answer (include/y2_split_rule.h through y2h_wino_split_plan) for every 3x3 conv layer of every zoo
+    network: tests/golden/wino_split_plan_table.txt.  Costs in thousands of CU cycles."""
+    for k in [k for k in os.environ if k.startswith("Y2_")]:
+        del os.environ[k]
+    yield "# net size batch layer | h w c n pool | fp32: eligible take tile tiles_pad v_bytes u_bytes present gemm split (kcycles) | fp16: eligible take"
+    for net, size, batch in wino_cases():
+        rows = {}
+        for half in (0, 1):
+            for i, f in _descs(net, size, batch, half, ALIGNED):
+                if f["size"] != 3 or f.get("x_halo") or f.get("x_nchw"):
+                    continue
+                rows.setdefault(i, (f, []))[1].append(wino_split_plan(lib, f))
+        for i, (f, (w, wh)) in sorted(rows.items()):
+            yield "%s %d b%d L%d | %d %d %d %d %d | %d %d %dx%dx%d %d %d %d %.0f %.0f %.0f | %d %d" % (
+                net, size, batch, i, f["h"], f["w"], f["c"], f["n"], f["fuse_maxpool2"], w.eligible, w.take, w.bm, w.bn, w.bk, w.tiles_pad,
+                w.v_bytes, w.u_bytes, w.present_cost / 1e3, w.gemm_cost / 1e3, w.split_cost / 1e3, wh.eligible, wh.take)
+
+
 def main():
     lib = C.CDLL(os.environ.get("Y2_LIB") or os.path.join(ROOT, "sr_object_detection_amd", "libsr_yolo2.so"))
     lib.y2h_conv_variant.restype = C.c_char_p
@@ -206,6 +239,8 @@ def main():
         return print("\n".join(wino_rows(lib)))
     if args == ["--winos"]:
         return print("\n".join(winos_rows(lib)))
+    if args == ["--wino-split"]:
+        return print("\n".join(wino_split_rows(lib)))
     for k in range(0, len(args), 3):
         net, size, batch = args[k], int(args[k + 1]), int(args[k + 2])
         layers = zoo.resolve(net, size)
