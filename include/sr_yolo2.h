@@ -641,7 +641,9 @@ int y2_plane_from_points(const float *p0, const float *p1, const float *p2, floa
 int y2_plane_fit(const double *sums, double *plane);
 /* ------------------------------------------------------------------------- */
 /* Training on the device: the other half of network.c (train_network_datum     */
-/* :225-243 = forward with train = 1, backward_network, update_network), fp32,  */
+/* :225-243 = forward with train = 1, backward_network, update_network), fp32   */
+/* (the convolution products optionally on the bf16 matrix cores, see           */
+/* y2_train_set_precision),                                                     */
 /* for convolutional classifiers and YOLOv2 detectors ([region] loss, [route],  */
 /* [reorg]; the truth of a [region] network is [batch][150], see                */
 /* y2_train_truth_floats).  The trainer owns its buffers (master                */
@@ -675,6 +677,20 @@ int y2_train_prepare(network *net);
 int y2_train_truth_floats(network *net);
 int y2_train_step(network *net, const float *x, const float *y, float *loss);            /* what train_network_datum calls */
 int y2_train_step_device(network *net, const float *d_x, const float *d_y, float *loss); /* the inputs already in HBM */
+/* The precision of the three products of every [convolutional] layer in a step (forward, input gradient, weight gradient).
+ *   Y2_TRAIN_FP32    fp32 operands on the fp32 matrix cores: the default, and what a step always launched
+ *   Y2_TRAIN_BF16X3  every operand value split into three bf16 numbers where it is staged, six bf16 products per fp32 product
+ *                    (include/y2_split_rule.h): fp32 results but for terms below 2^-25 |a b|
+ *   Y2_TRAIN_BF16    mixed precision: every operand value rounded once to bf16 (nearest even), fp32 accumulation
+ * Nothing else of a step changes: batch norm, pooling, the heads, the cost, the update and the master weights stay fp32, no
+ * buffer changes size, and everything the trainer refuses it still refuses (fp16 mode, y2_set_half, among it).  The mode is
+ * the engine's, like the schedule: it may be set before y2_train_prepare or between steps and outlasts set_batch_network,
+ * resize_network, y2_train_free and a new y2_train_prepare.  The environment variable Y2_TRAIN_PRECISION=fp32|bf16x3|bf16 sets
+ * the default of networks parsed afterwards; another word fails parse_network_cfg.  y2_train_set_precision returns -1 (and
+ * y2_last_error names the three modes) for any other value. */
+enum { Y2_TRAIN_FP32 = 0, Y2_TRAIN_BF16X3 = 1, Y2_TRAIN_BF16 = 2 };
+int y2_train_set_precision(network *net, int mode);
+int y2_train_precision(network *net);
 /* After a step the network is dirty: network_predict and every entry built on the forward pass, save_weights[_upto] and
  * y2_weights_arena first bring the masters (weights, biases, scales, rolling statistics) down into the host layer arrays
  * and re-pack the inference arena, so a caller that trains and then predicts or saves sees what it trained -- as with the

@@ -751,6 +751,14 @@ int    y2h_train_conv_dinput(const y2h_train_conv *g, const float *dy, const flo
 int    y2h_train_dweight_splits(const y2h_train_conv *g);
 size_t y2h_train_dweight_ws_bytes(const y2h_train_conv *g);
 int    y2h_train_conv_dweight(const y2h_train_conv *g, const float *x, const float *dy, float *dw, float *ws, y2h_stream s);
+/* The same three products on the bf16 matrix cores (y2_train_bf16.hip), fp32 in and out, fp32 accumulation.  planes = 3: every
+ * operand value is split into three bf16 numbers (include/y2_split_rule.h) and the six products of order <= 2 are summed,
+ * smallest first -- fp32 results but for terms below 2^-25 |a b|.  planes = 1: every operand value is rounded once to bf16,
+ * to nearest even.  Same shapes, same refusals, same workspace and the same reduction ranges and second pass for the weight
+ * gradient as the fp32 entries; any other `planes` is Y2H_EINVAL. */
+int    y2h_train_conv_forward_bf16(const y2h_train_conv *g, const float *x, const float *w, float *y, int planes, y2h_stream s);
+int    y2h_train_conv_dinput_bf16(const y2h_train_conv *g, const float *dy, const float *w, float *dx, int planes, y2h_stream s);
+int    y2h_train_conv_dweight_bf16(const y2h_train_conv *g, const float *x, const float *dy, float *dw, float *ws, int planes, y2h_stream s);
 /* per-channel sums over rows = batch * spatial pixels; `scratch` holds y2h_train_reduce_scratch_bytes(rows, c) bytes.
  *   stats     batchnorm_layer.c:129-137: mean, variance (/(rows-1)), rolling = .9f * rolling + .1f * new  (two sweeps)
  *   bias      backward_bias (+ backward_scale_cpu when x_norm != NULL): bias_updates += sum delta, scale_updates += sum delta*x_norm

@@ -952,10 +952,11 @@ network parse_network_cfg(char *filename)    /* parser.c:585-700 */
     int count = 0;
     y2_lr_schedule lr;
     float hue, saturation, exposure, angle, aspect;
-    int min_crop, max_crop;
+    int min_crop, max_crop, precision = Y2_TRAIN_FP32;
 
     memset(&empty, 0, sizeof empty);
     (void)y2_failed();                        /* a stale failure of an earlier call must not fail this parse */
+    if (y2_train_precision_env(&precision) != 0) return empty;
     sections = read_sections(filename);
     if (!sections) return empty;
     n = sections->front;
@@ -1044,6 +1045,7 @@ network parse_network_cfg(char *filename)    /* parser.c:585-700 */
     net.outputs = net.layers[y2_out_layer(&net)].outputs;
     if (y2_engine_create(&net) != 0) goto fail;
     y2_engine_of(&net)->lr = lr;
+    y2_engine_of(&net)->train_precision = precision;
     y2_engine_of(&net)->aug_hue = hue;
     y2_engine_of(&net)->aug_saturation = saturation;
     y2_engine_of(&net)->aug_exposure = exposure;

@@ -181,6 +181,8 @@ typedef struct y2_engine {
     int n_layers;
     /* training (y2_train.c): the [net] section's learning-rate schedule, and the trainer once y2_train_prepare built it */
     y2_lr_schedule lr;
+    int train_precision;       /* Y2_TRAIN_FP32 / _BF16X3 / _BF16: the kernel of the three convolution products of a step; it lives
+                                  here and not in the trainer, so it outlasts y2_train_free and every new y2_train_prepare */
     struct y2_trainer *trainer;
     float aug_hue, aug_saturation, aug_exposure;   /* [net] hue / saturation / exposure (parser.c:532-534): what y2_net_augment reports */
     int aug_min_crop, aug_max_crop;                /* [net] min_crop / max_crop / angle / aspect (parser.c:527-531): y2_net_augment_classifier */
@@ -279,6 +281,7 @@ void y2_depth_free(y2_engine *e);
 int y2_train_is_dirty(const network *net);     /* steps ran since the masters last reached the host arrays */
 int y2_train_sync_if_dirty(network *net);      /* a trained network's masters reach the host arrays before they are read */
 void y2_lr_parse(list *options, y2_lr_schedule *lr);
+int y2_train_precision_env(int *mode);            /* Y2_TRAIN_PRECISION -> *mode (untouched when unset); -1 and y2_fail for an unknown word */
 
 /* the detection loader's host half (y2_aug.c), device-free */
 int y2_aug_check(const char *who, const y2_aug_item *items, int n);        /* every refusal that reads only the items */

@@ -96,6 +96,62 @@ void y2_lr_parse(list *o, y2_lr_schedule *lr)
     }
 }
 
+/* ------------------------------------------------------------------ */
+/* the precision of the convolution products                           */
+/* ------------------------------------------------------------------ */
+static const char *const precision_names[] = { "fp32", "bf16x3", "bf16" };
+
+int y2_train_precision_env(int *mode)
+{
+    const char *w = getenv("Y2_TRAIN_PRECISION");
+    int k;
+    if (!w || !*w) return 0;
+    for (k = 0; k < 3; ++k)
+        if (!strcmp(w, precision_names[k])) { *mode = k; return 0; }
+    y2_fail("Y2_TRAIN_PRECISION=%s: unknown training precision (fp32, bf16x3, bf16)", w);
+    return -1;
+}
+
+int y2_train_set_precision(network *net, int mode)
+{
+    y2_engine *e = y2_engine_of(net);
+    if (!e) { y2_fail("y2_train_set_precision: network has no engine (was it built by parse_network_cfg?)"); return -1; }
+    if (mode != Y2_TRAIN_FP32 && mode != Y2_TRAIN_BF16X3 && mode != Y2_TRAIN_BF16) {
+        y2_fail("y2_train_set_precision: unknown mode %d (Y2_TRAIN_FP32 = 0 fp32, Y2_TRAIN_BF16X3 = 1 bf16x3, Y2_TRAIN_BF16 = 2 bf16)", mode);
+        return -1;
+    }
+    e->train_precision = mode;
+    return 0;
+}
+
+int y2_train_precision(network *net)
+{
+    const y2_engine *e = y2_engine_of(net);
+    if (!e) { y2_fail("y2_train_precision: network has no engine (was it built by parse_network_cfg?)"); return -1; }
+    return e->train_precision;
+}
+
+/* the three products of a convolution in the engine's precision; fp32 mode launches what it always launched */
+static int planes_of(const y2_engine *e) { return e->train_precision == Y2_TRAIN_BF16X3 ? 3 : 1; }
+
+static int conv_forward(const y2_engine *e, const y2h_train_conv *g, const float *x, const float *w, float *y)
+{
+    if (e->train_precision == Y2_TRAIN_FP32) return y2h_train_conv_forward(g, x, w, y, e->stream);
+    return y2h_train_conv_forward_bf16(g, x, w, y, planes_of(e), e->stream);
+}
+
+static int conv_dinput(const y2_engine *e, const y2h_train_conv *g, const float *dy, const float *w, float *dx)
+{
+    if (e->train_precision == Y2_TRAIN_FP32) return y2h_train_conv_dinput(g, dy, w, dx, e->stream);
+    return y2h_train_conv_dinput_bf16(g, dy, w, dx, planes_of(e), e->stream);
+}
+
+static int conv_dweight(const y2_engine *e, const y2h_train_conv *g, const float *x, const float *dy, float *dw, float *ws)
+{
+    if (e->train_precision == Y2_TRAIN_FP32) return y2h_train_conv_dweight(g, x, dy, dw, ws, e->stream);
+    return y2h_train_conv_dweight_bf16(g, x, dy, dw, ws, planes_of(e), e->stream);
+}
+
 int get_current_batch(network net)
 {
     return (*net.seen) / (net.batch * net.subdivisions);
@@ -428,7 +484,7 @@ static int forward_train(network *net, y2_trainer *t, y2_engine *e)
         switch (l->type) {
         case CONVOLUTIONAL: {
             const long rows = (long)net->batch * l->out_h * l->out_w;
-            HIP_OR_ERR(y2h_train_conv_forward(&L->g, in, L->weights, L->out, e->stream));
+            HIP_OR_ERR(conv_forward(e, &L->g, in, L->weights, L->out));
             if (l->batch_normalize)
                 HIP_OR_ERR(y2h_train_bn_stats(L->out, rows, l->n, L->mean, L->variance, L->rolling_mean, L->rolling_variance, t->scratch, e->stream));
             HIP_OR_ERR(y2h_train_bn_apply(L->out, L->x, L->x_norm, l->batch_normalize ? L->mean : NULL, L->variance, L->scales, L->biases,
@@ -491,8 +547,8 @@ static int backward_train(network *net, y2_trainer *t, y2_engine *e)
                 HIP_OR_ERR(y2h_train_bn_backward(L->delta, L->x, L->scales, L->mean, L->variance, L->mean_delta, L->variance_delta, rows, l->n,
                                                  e->stream));
             }
-            HIP_OR_ERR(y2h_train_conv_dweight(&L->g, in, L->delta, L->weight_updates, t->ws, e->stream));
-            if (din) HIP_OR_ERR(y2h_train_conv_dinput(&L->g, L->delta, L->weights, din, e->stream));
+            HIP_OR_ERR(conv_dweight(e, &L->g, in, L->delta, L->weight_updates, t->ws));
+            if (din) HIP_OR_ERR(conv_dinput(e, &L->g, L->delta, L->weights, din));
         } break;
         case MAXPOOL:
             if (din) HIP_OR_ERR(y2h_train_maxpool_backward(L->delta, L->idx, din, net->batch, l->h, l->w, l->c, l->size, l->stride, l->pad,

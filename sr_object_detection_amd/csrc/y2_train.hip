@@ -10,59 +10,17 @@
 //   DW   i = tap (ky, kx, ci), r = output pixel   A = x    B = dy[r][j]      (split over r, partial tiles, second pass)
 // Edges (rows, columns, the reduction's tail, padding) are guarded in the gathers: every shape takes this kernel.
 // Nothing here uses a floating-point atomic: every reduction is a fixed split followed by a fixed-order second pass.
-#include "y2_common.hpp"
+// The forms, the tile, the gather and the accepted shapes are shared with the bf16 template (y2_train_bf16.hip): y2_train_geo.hpp.
+#include "y2_train_geo.hpp"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
-enum { FWD = 0, DX = 1, DW = 2 };
-constexpr int TB = 64;            // output tile: TB x TB per workgroup of four waves, 32 x 32 per wave
 constexpr int KT = 16;            // reduction depth of one staging step
 constexpr int LDR = KT + 1;       // LDS row pitch of an operand staged [index][r] (its global rows run along r)
 constexpr int LDI = TB + 32;      // LDS row pitch of an operand staged [r][index]: the two k rows a wave reads hit disjoint banks
 constexpr int LDS_FLOATS = (TB * LDR > KT * LDI) ? TB * LDR : KT * LDI;
-
-struct Geo { int B, H, W, C, N, K, P, OH, OW; int I, J, R; };
-struct Pix { int b, y, x; bool ok; };
-struct Tap { int ky, kx, ch; bool ok; };
-
-__device__ __forceinline__ Pix pix_of(int m, int lim, int h, int w)
-{
-    Pix p;
-    p.ok = m < lim;
-    const int mm = p.ok ? m : 0, hw = h * w;
-    p.b = mm / hw;
-    const int r = mm - p.b * hw;
-    p.y = r / w;
-    p.x = r - p.y * w;
-    return p;
-}
-
-__device__ __forceinline__ Tap tap_of(int k, int lim, int ksize, int chans)
-{
-    Tap t;
-    t.ok = k < lim;
-    const int kk = t.ok ? k : 0, q = kk / chans;
-    t.ch = kk - q * chans;
-    t.ky = q / ksize;
-    t.kx = q - t.ky * ksize;
-    return t;
-}
-
-template <int MODE>
-__device__ __forceinline__ float a_val(const float *__restrict__ src, const Geo &g, const Pix &p, const Tap &t)
-{
-    if (!p.ok || !t.ok) return 0.f;
-    if (MODE == DX) {
-        const int oy = p.y + g.P - t.ky, ox = p.x + g.P - t.kx;
-        if ((unsigned)oy >= (unsigned)g.OH || (unsigned)ox >= (unsigned)g.OW) return 0.f;
-        return src[((size_t)(p.b * g.OH + oy) * g.OW + ox) * g.N + t.ch];
-    }
-    const int iy = p.y - g.P + t.ky, ix = p.x - g.P + t.kx;
-    if ((unsigned)iy >= (unsigned)g.H || (unsigned)ix >= (unsigned)g.W) return 0.f;
-    return src[((size_t)(p.b * g.H + iy) * g.W + ix) * g.C + t.ch];
-}
 
 // blockIdx.z = the reduction range; a launch with ranges writes range z's tile to dst + z * I * J
 template <int MODE>
@@ -158,24 +116,6 @@ __global__ void dweight_finish(const float *__restrict__ ws, float *__restrict__
         dw[e] += s;
     }
 }
-
-int geo_of(const y2h_train_conv *c, int mode, Geo *g)
-{
-    if (!c || c->batch <= 0 || c->h <= 0 || c->w <= 0 || c->c <= 0 || c->n <= 0 || c->size <= 0 || c->pad < 0) return Y2H_EINVAL;
-    if (c->out_h != c->h + 2 * c->pad - c->size + 1 || c->out_w != c->w + 2 * c->pad - c->size + 1 || c->out_h <= 0 || c->out_w <= 0)
-        return Y2H_EINVAL;
-    const long mo = (long)c->batch * c->out_h * c->out_w, mi = (long)c->batch * c->h * c->w;
-    const long kc = (long)c->size * c->size * c->c, kn = (long)c->size * c->size * c->n;
-    if (mo * c->n >= 2147483647L || mi * c->c >= 2147483647L || kc * c->n >= 2147483647L) return Y2H_EINVAL;   // int indices
-    g->B = c->batch; g->H = c->h; g->W = c->w; g->C = c->c; g->N = c->n; g->K = c->size; g->P = c->pad;
-    g->OH = c->out_h; g->OW = c->out_w;
-    if (mode == FWD) { g->I = (int)mo; g->J = c->n; g->R = (int)kc; }
-    else if (mode == DX) { g->I = (int)mi; g->J = c->c; g->R = (int)kn; }
-    else { g->I = (int)kc; g->J = c->n; g->R = (int)mo; }
-    return Y2H_OK;
-}
-
-inline dim3 tiles_of(const Geo &g, int z) { return dim3((g.I + TB - 1) / TB, (g.J + TB - 1) / TB, z); }
 
 // ---- per-channel reductions over rows of an NHWC tensor: P row chunks -> part[2][P][c], then one thread per channel ----
 enum { R_SUM = 0, R_VAR = 1, R_BIAS = 2, R_BNDELTA = 3 };
@@ -405,6 +345,13 @@ __global__ void sgd(float *__restrict__ w, float *__restrict__ u, long n, float 
 
 }  // namespace
 
+int y2_train_dweight_finish(const float *ws, float *dw, long n, int splits, y2h_stream s)
+{
+    dweight_finish<<<y2h_grid(n, 256), 256, 0, S(s)>>>(ws, dw, n, splits);
+    Y2H_LAUNCH_CHECK();
+    return Y2H_OK;
+}
+
 extern "C" {
 
 int y2h_train_conv_forward(const y2h_train_conv *c, const float *x, const float *w, float *y, y2h_stream s)
@@ -450,13 +397,9 @@ int y2h_train_conv_dweight(const y2h_train_conv *c, const float *x, const float 
     Geo g;
     if (!x || !dy || !dw || !ws || geo_of(c, DW, &g) != Y2H_OK) return Y2H_EINVAL;
     const int splits = y2h_train_dweight_splits(c);
-    int range = ((g.R + splits - 1) / splits + KT - 1) / KT * KT;
-    const long n = (long)g.I * g.J;
-    train_gemm<DW><<<tiles_of(g, splits), 256, 0, S(s)>>>(x, dy, ws, g, range);
+    train_gemm<DW><<<tiles_of(g, splits), 256, 0, S(s)>>>(x, dy, ws, g, dweight_range(g, splits));
     Y2H_LAUNCH_CHECK();
-    dweight_finish<<<y2h_grid(n, 256), 256, 0, S(s)>>>(ws, dw, n, splits);
-    Y2H_LAUNCH_CHECK();
-    return Y2H_OK;
+    return y2_train_dweight_finish(ws, dw, (long)g.I * g.J, splits, s);
 }
 
 size_t y2h_train_reduce_scratch_bytes(long rows, int c)

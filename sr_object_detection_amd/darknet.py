@@ -145,6 +145,9 @@ class View(C.Structure):     # include/y2_hip.h y2h_view: one view of y2h_views_
 VIEWS_CROP10, VIEWS_MULTI, VIEWS_FULL = 0, 1, 2             # include/sr_yolo2.h Y2_VIEWS_*
 
 
+TRAIN_PRECISIONS = ("fp32", "bf16x3", "bf16")      # include/sr_yolo2.h Y2_TRAIN_FP32 / Y2_TRAIN_BF16X3 / Y2_TRAIN_BF16
+
+
 class TrainConv(C.Structure):  # include/y2_hip.h y2h_train_conv: the shape of one trainable convolution
     _fields_ = [(k, C.c_int) for k in ("batch", "h", "w", "c", "n", "size", "pad", "out_h", "out_w")]
 
@@ -440,6 +443,11 @@ def lib():
     L.y2h_train_dweight_ws_bytes.restype = C.c_size_t
     L.y2h_train_dweight_ws_bytes.argtypes = [C.POINTER(TrainConv)]
     L.y2h_train_conv_dweight.argtypes = [C.POINTER(TrainConv), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.y2h_train_conv_forward_bf16.argtypes = [C.POINTER(TrainConv), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.y2h_train_conv_dinput_bf16.argtypes = [C.POINTER(TrainConv), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.y2h_train_conv_dweight_bf16.argtypes = [C.POINTER(TrainConv), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.y2_train_set_precision.argtypes = [C.POINTER(CNetwork), C.c_int]
+    L.y2_train_precision.argtypes = [C.POINTER(CNetwork)]
     L.y2h_train_reduce_scratch_bytes.restype = C.c_size_t
     L.y2h_train_reduce_scratch_bytes.argtypes = [C.c_long, C.c_int]
     L.y2h_train_bn_stats.argtypes = [C.c_void_p, C.c_long, C.c_int] + [C.c_void_p] * 6
@@ -905,6 +913,21 @@ class Network:
     def train_prepare(self) -> None:
         if lib().y2_train_prepare(C.byref(self.net)) != 0:
             raise Y2Error("y2_train_prepare: " + _check())
+
+    def train_set_precision(self, mode: str) -> None:
+        """y2_train_set_precision: "fp32" (the default), "bf16x3" (3-way bf16 split, fp32 results) or "bf16" (operands
+        rounded to bf16, fp32 accumulation) for the three products of every convolution of a step; before train_prepare
+        or between steps"""
+        if mode not in TRAIN_PRECISIONS:
+            raise Y2Error("train_set_precision: unknown mode %r (%s)" % (mode, ", ".join(TRAIN_PRECISIONS)))
+        if lib().y2_train_set_precision(C.byref(self.net), TRAIN_PRECISIONS.index(mode)) != 0:
+            raise Y2Error("y2_train_set_precision: " + _check())
+
+    def train_precision(self) -> str:
+        mode = lib().y2_train_precision(C.byref(self.net))
+        if mode < 0:
+            raise Y2Error("y2_train_precision: " + _check())
+        return TRAIN_PRECISIONS[mode]
 
     def train_step(self, x: np.ndarray, y: np.ndarray) -> float:
         """one train_network_datum: x [batch][c][h][w]; y [batch][outputs] for a network that ends in [cost],

@@ -38,8 +38,12 @@ three label rows each, the draws made by y2_aug_draw_detection from what y2_net_
   step      host wall time per step of load + y2_train_step_loaded against y2_train_step fed ready-made host floats (no
             augmentation at all, the whole float batch uploaded and transposed), in alternating pairs after a warm-up
 
+With --precision bf16x3 or --precision bf16 the step row and the per-product rows are measured a second time in that mode
+(y2_train_set_precision; the products through y2h_train_conv_*_bf16 with planes 3 or 1), in the same process on the same
+buffers, and reported under "precision": the fp32 rows stay what they are.
+
 usage: train_latency.py [--net darknet19|tiny-yolo-voc|yolo] [--batches 16,64] [--steps 10] [--warmup 3] [--reps 5] [--ref-batch 16] [--no-reference]
-                        [--no-products] [--layers 4,18] [--loader]"""
+                        [--no-products] [--layers 4,18] [--loader] [--precision fp32|bf16x3|bf16]"""
 import argparse
 import ctypes as C
 import json
@@ -107,7 +111,8 @@ def p50(v):
     return float(np.percentile(np.asarray(v), 50))
 
 
-def products(net, timer, reps, only=None):
+def products(net, timer, reps, only=None, planes=0):
+    """planes = 0: the fp32 kernels; 3 / 1: the bf16 kernels, split / rounded operands"""
     L = darknet.lib()
     rows = []
     for i in range(net.n):
@@ -125,6 +130,10 @@ def products(net, timer, reps, only=None):
         calls = {"forward": lambda: L.y2h_train_conv_forward(C.byref(g), x, w, y, timer.stream),
                  "dinput": lambda: L.y2h_train_conv_dinput(C.byref(g), dy, w, dx, timer.stream),
                  "dweight": lambda: L.y2h_train_conv_dweight(C.byref(g), x, dy, dw, ws, timer.stream)}
+        if planes:
+            calls = {"forward": lambda: L.y2h_train_conv_forward_bf16(C.byref(g), x, w, y, planes, timer.stream),
+                     "dinput": lambda: L.y2h_train_conv_dinput_bf16(C.byref(g), dy, w, dx, planes, timer.stream),
+                     "dweight": lambda: L.y2h_train_conv_dweight_bf16(C.byref(g), x, dy, dw, ws, planes, timer.stream)}
         flops = 2.0 * net.batch * l.out_h * l.out_w * l.size * l.size * l.c * l.n
         row = {"layer": i, "shape": "%dx%dx%d -> %d, %dx%d" % (l.w, l.h, l.c, l.n, l.size, l.size), "gflop": round(flops / 1e9, 2),
                "dweight_splits": int(L.y2h_train_dweight_splits(C.byref(g)))}
@@ -297,6 +306,7 @@ def main():
     ap.add_argument("--no-products", action="store_true")
     ap.add_argument("--layers", default=None, help="only these layers' products, e.g. 4,18 (with --steps 0 --warmup 0 "
                     "--no-reference: the few launches a counter run wants, `rocprofv3 --pmc ... -- python tools/train_latency.py ...`)")
+    ap.add_argument("--precision", default="fp32", choices=darknet.TRAIN_PRECISIONS, help="measure the step and the products in this mode as well")
     ap.add_argument("--loader", action="store_true", help="add the loader's row: the classifier loader for darknet19, the detection loader for a detector")
     a = ap.parse_args()
     SIZE, batches, ref_batch = NETS[a.net][:3]
@@ -327,10 +337,27 @@ def main():
         if ms and a.net != "darknet19":
             res["region"] = {k: (None if v != v else v) for k, v in net.train_region_stats().items()}
         print("  " + json.dumps(res))
+        only = None if a.layers is None else {int(v) for v in a.layers.split(",")}
         if not a.no_products:
-            res["products"] = products(net, timer, a.reps, None if a.layers is None else {int(v) for v in a.layers.split(",")})
+            res["products"] = products(net, timer, a.reps, only)
             for k in ("forward", "dinput", "dweight"):
                 res[k + "_sum_ms"] = round(sum(r[k + "_ms"] for r in res["products"]), 3)
+        if a.precision != "fp32":                                    # the same rows once more, in that mode
+            net.train_set_precision(a.precision)
+            mode = {"mode": a.precision}
+            for _ in range(a.warmup):
+                net.train_step_device(d_x.value, d_y.value)
+            ms = [timer.ms(lambda: losses.append(net.train_step_device(d_x.value, d_y.value))) for _ in range(a.steps)]
+            if ms:
+                mode.update(step_p50_ms=round(p50(ms), 3), step_max_ms=round(max(ms), 3), images_per_s=round(batch / (p50(ms) * 1e-3), 1),
+                            last_loss=losses[-1], step_over_fp32=round(p50(ms) / res["step_p50_ms"], 3))
+            print("  " + json.dumps(mode))
+            if not a.no_products:
+                mode["products"] = products(net, timer, a.reps, only, 3 if a.precision == "bf16x3" else 1)
+                for k in ("forward", "dinput", "dweight"):
+                    mode[k + "_sum_ms"] = round(sum(r[k + "_ms"] for r in mode["products"]), 3)
+            res["precision"] = mode
+            net.train_set_precision("fp32")
         if a.loader:
             res.update((cls_loader_row if a.net == "darknet19" else loader_row)(net, batch, timer, max(a.steps, 1), a.warmup, a.reps))
             print("  " + json.dumps(res["loader"]))
