@@ -644,8 +644,10 @@ int y2_plane_fit(const double *sums, double *plane);
 /* :225-243 = forward with train = 1, backward_network, update_network), fp32   */
 /* (the convolution products optionally on the bf16 matrix cores, see           */
 /* y2_train_set_precision),                                                     */
-/* for convolutional classifiers and YOLOv2 detectors ([region] loss, [route],  */
-/* [reorg]; the truth of a [region] network is [batch][150], see                */
+/* for convolutional classifiers, YOLOv2 detectors ([region] loss, [route],     */
+/* [reorg]; the truth of a [region] network is [batch][150]) and YOLOv1          */
+/* detectors ([connected], [dropout], [detection] loss; the truth is            */
+/* [batch][side*side*(1+coords+classes)], the load_data_region layout; see      */
 /* y2_train_truth_floats).  The trainer owns its buffers (master                */
 /* weights, update buffers, per layer output / delta / x / x_norm / mean /      */
 /* variance); the inference plan is untouched, struct network and struct layer  */
@@ -654,7 +656,11 @@ int y2_plane_fit(const double *sums, double *plane);
 /* linear / leaky / logistic / relu), [maxpool], [avgpool], [softmax] (groups   */
 /* 1, no tree), [cost] type=sse; in a network that ends in [region] also        */
 /* [route], [reorg] (reverse=0) and the [region] head (softmax=1, no tree= /    */
-/* map=, classfix=0).  Refused by name before any device allocation,            */
+/* map=, classfix=0); in a network that ends in [detection] also [connected]    */
+/* (batch_normalize 0 / 1, the same four activations; its products are fp32 in  */
+/* every precision mode), [dropout] (its draws are libc rand() in the           */
+/* reference's order: srand() before a step fixes them) and the [detection]     */
+/* head (coords=4, random=0, last layer).  Refused by name before any device allocation,            */
 /* layer number and type in y2_last_error(): every other section type, stride   */
 /* > 1, xnor, another activation, adam=1, policy=random, another cost type, a   */
 /* tree / groups > 1 softmax, fp16 mode, a recurrent network, a batch-normalised */
@@ -672,7 +678,8 @@ float get_network_cost(network net);             /* network.c:183: mean of the [
 /* Builds the trainer from the host weights (load_weights, or whatever the layer arrays hold).  0 / -1. */
 int y2_train_prepare(network *net);
 /* Floats of truth per image of a step: the inputs of a closing [cost]; l.truths = 150 behind a closing [region], 30 rows of
- * x, y, w, h, class in relative units, the list ended by the first x == 0.  -1 (and y2_last_error) for a network the
+ * x, y, w, h, class in relative units, the list ended by the first x == 0; l.truths = side*side*(1+coords+classes) behind a
+ * closing [detection], per cell is-object, the class row, x, y, w, h.  -1 (and y2_last_error) for a network the
  * trainer refuses; touches no device. */
 int y2_train_truth_floats(network *net);
 int y2_train_step(network *net, const float *x, const float *y, float *loss);            /* what train_network_datum calls */
@@ -704,16 +711,26 @@ int y2_train_sync(network *net);
 /* One array of layer `layer` as the reference holds it: activations as [batch][c][h][w], weights as [n][c][size][size]. */
 enum { Y2_TRAIN_OUTPUT = 0, Y2_TRAIN_DELTA, Y2_TRAIN_X, Y2_TRAIN_X_NORM, Y2_TRAIN_MEAN, Y2_TRAIN_VARIANCE, Y2_TRAIN_MEAN_DELTA,
        Y2_TRAIN_VARIANCE_DELTA, Y2_TRAIN_WEIGHT_UPDATES, Y2_TRAIN_BIAS_UPDATES, Y2_TRAIN_SCALE_UPDATES, Y2_TRAIN_WEIGHTS,
-       Y2_TRAIN_BIASES, Y2_TRAIN_SCALES, Y2_TRAIN_ROLLING_MEAN, Y2_TRAIN_ROLLING_VARIANCE };
+       Y2_TRAIN_BIASES, Y2_TRAIN_SCALES, Y2_TRAIN_ROLLING_MEAN, Y2_TRAIN_ROLLING_VARIANCE,
+       Y2_TRAIN_RAND /* [dropout]: the last step's draws, [batch][inputs]; its output and delta are the layer's in front */ };
 int y2_train_pull(network *net, int layer, int what, float *dst, size_t n);
 /* What forward_region_layer prints per call (region_layer.c:320), of the last step: the sums divided as in that printf, so
  * avg_iou, avg_class, avg_obj and recall are NaN when the batch held no truth.  The library prints nothing. */
 typedef struct { float avg_iou, avg_class, avg_obj, avg_noobj, recall; int count, class_count; } y2_region_stats;
 int y2_train_region_stats(network *net, int layer, y2_region_stats *out);
+/* What forward_detection_layer prints per call (detection_layer.c:214), of the last step: Avg IOU, Pos Cat, All Cat, Pos Obj,
+ * Any Obj and count, the sums divided as in that printf (all but avg_anyobj are NaN when no cell held an object). */
+typedef struct { float avg_iou, avg_cat, avg_allcat, avg_obj, avg_anyobj; int count; } y2_detection_stats;
+int y2_train_detection_stats(network *net, int layer, y2_detection_stats *out);
 void y2_train_free(network *net);
 /* The trainer's weight layout, [size][size][c][n], to and from the host's [n][c][size][size]: pure permutations. */
 void y2_train_pack_weights(const float *ref, float *packed, int n, int c, int size);
 void y2_train_unpack_weights(const float *packed, float *ref, int n, int c, int size);
+/* The same for a dense ([connected]) layer's weights (y2h_train_dense_*): [outputs][inputs] on both sides, the K index
+ * ci*h*w + y*w + x of the host (the layer in front is a c x h x w image) against (y*w + x)*c + ci of the dense NHWC activation
+ * the device products read.  h = w = 1: the identity.  Pure permutations, no device. */
+void y2_train_pack_dense_weights(const float *ref, float *packed, int outputs, int c, int h, int w);
+void y2_train_unpack_dense_weights(const float *packed, float *ref, int outputs, int c, int h, int w);
 /* ------------------------------------------------------------------------- */
 /* The detection loader (data.c:664-714 load_data_detection): a training batch  */
 /* is built from 8-bit frames and label rows.  The draws and the truth are made */

@@ -759,6 +759,24 @@ int    y2h_train_conv_dweight(const y2h_train_conv *g, const float *x, const flo
 int    y2h_train_conv_forward_bf16(const y2h_train_conv *g, const float *x, const float *w, float *y, int planes, y2h_stream s);
 int    y2h_train_conv_dinput_bf16(const y2h_train_conv *g, const float *dy, const float *w, float *dx, int planes, y2h_stream s);
 int    y2h_train_conv_dweight_bf16(const y2h_train_conv *g, const float *x, const float *dy, float *dw, float *ws, int planes, y2h_stream s);
+/* The three products of a dense ([connected]) layer (y2_train_dense.hip; connected_layer.c:122-190), fp32 in and out on the
+ * fp32 matrix cores in EVERY training precision: y2_train_set_precision steers the convolutions' products only.
+ * x is [batch][inputs], d and y [batch][outputs], w and dw [outputs][inputs]; any batch, inputs, outputs >= 1 (edges are
+ * guarded, rows beyond 32 run as further passes).
+ *   forward   y[b][o]   = sum_k x[b][k] * w[o][k]     K is cut into ranges of whole 32-steps so that the whole chip streams w once
+ *   dinput    dx[b][k]  = sum_o d[b][o] * w[o][k]     (add != 0: +=); the outputs are cut into ranges of whole 64-steps
+ *   dweight   dw[o][k] += sum_b d[b][o] * x[b][k]     a rank-batch update: every dw element is read and written once, no workspace
+ * With more than one range every range writes raw partial sums to ws[range][batch][outputs | inputs] and a second launch
+ * adds them in ascending range order: no atomics, two runs give the same bytes.  y2h_train_dense_plan (host arithmetic, no
+ * GPU) gives the range count -- a function of the shape alone, unless forced > 0 or Y2_TRAIN_DENSE_KSPLIT=n sets it, clamped
+ * to the steps of the layer (tests) --, the workspace bytes (0 with one range) and, in bounds[0 .. ranges], the ranges'
+ * ends.  The entries take the same `forced`; ws may be NULL when the plan asks for no bytes. */
+typedef struct { int batch, inputs, outputs; } y2h_train_dense;
+enum { Y2H_DENSE_FORWARD = 0, Y2H_DENSE_DINPUT = 1 };
+int y2h_train_dense_plan(const y2h_train_dense *g, int product, int forced, int *ranges, size_t *ws_bytes, int *bounds, int max_bounds);
+int y2h_train_dense_forward(const y2h_train_dense *g, const float *x, const float *w, float *y, float *ws, int forced, y2h_stream s);
+int y2h_train_dense_dinput(const y2h_train_dense *g, const float *d, const float *w, float *dx, int add, float *ws, int forced, y2h_stream s);
+int y2h_train_dense_dweight(const y2h_train_dense *g, const float *x, const float *d, float *dw, y2h_stream s);
 /* per-channel sums over rows = batch * spatial pixels; `scratch` holds y2h_train_reduce_scratch_bytes(rows, c) bytes.
  *   stats     batchnorm_layer.c:129-137: mean, variance (/(rows-1)), rolling = .9f * rolling + .1f * new  (two sweeps)
  *   bias      backward_bias (+ backward_scale_cpu when x_norm != NULL): bias_updates += sum delta, scale_updates += sum delta*x_norm
@@ -767,6 +785,10 @@ int    y2h_train_conv_dweight_bf16(const y2h_train_conv *g, const float *x, cons
 size_t y2h_train_reduce_scratch_bytes(long rows, int c);
 int y2h_train_bn_stats(const float *x, long rows, int c, float *mean, float *variance, float *rolling_mean,
                        float *rolling_variance, float *scratch, y2h_stream s);
+/* the same with the rolling statistics' two constants given: rolling = keep * rolling + take * new (a [connected] layer's
+ * are .95f and .05f, connected_layer.c:138-141; y2h_train_bn_stats is keep = .9f, take = .1f) */
+int y2h_train_bn_stats_rate(const float *x, long rows, int c, float *mean, float *variance, float *rolling_mean,
+                            float *rolling_variance, float keep, float take, float *scratch, y2h_stream s);
 int y2h_train_bias_grad(const float *delta, const float *x_norm, long rows, int c, float *bias_updates, float *scale_updates,
                         float *scratch, y2h_stream s);
 int y2h_train_bn_deltas(const float *delta, const float *x, const float *scales, const float *mean, const float *variance,
@@ -791,6 +813,10 @@ int y2h_train_softmax(const float *x, float *y, int rows, int n, float temperatu
  * error = delta^2 (the layer's output), cost[0] = sum error (fixed tree), delta_prev = scale * delta */
 int y2h_train_cost_sse(const float *pred, const float *truth, float *error, float *delta, float *delta_prev, float scale, long n,
                        float *cost, y2h_stream s);
+/* [dropout] in training mode (dropout_layer.c:38-59), forward on an activation and backward on its delta, in place:
+ * x = rnd < probability ? 0 : x * scale.  x is dense NHWC [batch][hw][c]; rnd holds the layer's draws in the reference's
+ * [batch][c][hw] order (hw = 1: the same order). */
+int y2h_train_dropout(float *x, const float *rnd, float probability, float scale, int batch, int c, int hw, y2h_stream s);
 /* update_convolutional_layer's three statements per array: updates += wd * w (skipped when wd == 0), w += rate * updates,
  * updates *= momentum */
 int y2h_train_sgd(float *w, float *updates, long n, float rate, float wd, float momentum, y2h_stream s);
@@ -809,6 +835,22 @@ typedef struct { float avg_iou, avg_class, avg_obj, avg_noobj, recall; int count
 size_t y2h_train_region_scratch_bytes(const y2h_train_region *g);
 int y2h_train_region_loss(const y2h_train_region *g, const float *in, const float *anchors, const float *truth, int seen, float *out,
                           float *delta, float *delta_prev, float *cost, y2h_train_region_stats *stats, void *scratch, y2h_stream s);
+/* The [detection] head of YOLOv1 with state.train = 1 (detection_layer.c:49-222) and backward_detection_layer, coords = 4.
+ * in / out / delta are [batch][side*side*(5*n + classes)]: per image the cells' class scores, then their n objectness
+ * values, then their n boxes.  truth is [batch][side*side][1 + classes + 4] (load_data_region): is-object (the reference's
+ * int cast), the class row, then x, y, w, h.  out is the input with the optional per-cell class softmax; every delta entry
+ * is written (no memset); delta_prev receives delta (add == 0) or has it added; cost[0] = pow(mag_array(delta), 2) as a
+ * fixed-order two-pass sum; stats are the figures the reference prints, summed in double in a fixed order and divided as in
+ * its printf (NaN when count == 0).  An object cell for which no box wins (every IoU 0 or NaN and every rmse >= 20 or NaN), or
+ * for which forced names box 1 of a one-box head, makes the reference go on with entries that are not the cell's (or not
+ * the array's): here that cell keeps its no-object and class deltas and adds nothing to avg_iou, avg_obj and count.
+ * random=1 (a draw of rand() per object cell) is not implemented: the trainer refuses it.
+ * scratch: y2h_train_detection_scratch_bytes(g) bytes, 8-byte aligned.  No atomics. */
+typedef struct { int batch, side, n, classes, softmax, sqrt, rescore, forced; float coord_scale, object_scale, noobject_scale, class_scale; } y2h_train_detection;
+typedef struct { float avg_iou, avg_cat, avg_allcat, avg_obj, avg_anyobj; int count; } y2h_train_detection_stats;
+size_t y2h_train_detection_scratch_bytes(const y2h_train_detection *g);
+int y2h_train_detection_loss(const y2h_train_detection *g, const float *in, const float *truth, float *out, float *delta,
+                             float *delta_prev, int add, float *cost, y2h_train_detection_stats *stats, void *scratch, y2h_stream s);
 /* [route] on dense NHWC tensors of `pixels` = batch*h*w pixels: forward copies the source's c channels to channels
  * off .. off+c-1 of the route's ldc; backward stores (add == 0) or adds that slice of the route's delta to the source's */
 int y2h_train_route_forward(const float *src, int c, float *dst, int ldc, int off, long pixels, y2h_stream s);

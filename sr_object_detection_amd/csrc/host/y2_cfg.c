@@ -758,6 +758,13 @@ static layer make_detection(list *o, shape p)
     l.softmax = option_find_int(o, "softmax", 0);
     l.sqrt = option_find_int(o, "sqrt", 0);
     l.forced = option_find_int(o, "forced", 0);
+    /* what only the training loss reads (y2_train.c); the defaults are parser.c:298-304's (jitter stays with the caller's loader) */
+    l.coord_scale = option_find_float_quiet(o, "coord_scale", 1);
+    l.object_scale = option_find_float_quiet(o, "object_scale", 1);
+    l.noobject_scale = option_find_float_quiet(o, "noobject_scale", 1);
+    l.class_scale = option_find_float_quiet(o, "class_scale", 1);
+    l.random = option_find_int_quiet(o, "random", 0);
+    l.cost = calloc(1, sizeof(float));
     touch(o, quiet);
     l.batch = p.batch;
     l.inputs = l.outputs = p.inputs;

@@ -2,7 +2,14 @@
  * Training on the device: host-side replacement for the other half of src_yolo2/network.c -- train_network_datum
  * (:225-243), backward_network (:197-215), update_network (:160-171), get_current_rate (:48-79) -- and for the
  * forward(train) / backward / update functions of the convolutional, batch-norm, maxpool, avgpool, softmax, cost, route,
- * reorg and region layers, whose loop nests run as the y2h_train_* kernels (y2_train.hip, y2_train_det.hip).
+ * reorg, region, connected, dropout and detection layers, whose loop nests run as the y2h_train_* kernels (y2_train.hip,
+ * y2_train_det.hip, y2_train_dense.hip).
+ *
+ * A [connected] layer's master is [outputs][inputs] with the K index in the order of the dense NHWC activation it reads
+ * (y2_train_pack_dense_weights); its three products are fp32 in every precision mode.  A [dropout] owns no activation:
+ * its output and delta ARE those of the layer in front (dropout_layer.c scales both in place), so that layer's
+ * gradient_array reads the post-dropout values, as the reference's does; its draws are libc rand() on the host, in the
+ * reference's index order, layer by layer in forward order.
  *
  * The inference plan folds batch norm, fuses pooling and keeps weights in per-kernel layouts, so nothing of it is
  * reused: the trainer owns master parameters, their update buffers and per layer output / delta / x / x_norm / mean /
@@ -41,12 +48,20 @@ typedef struct {
     int *src_add;                       /* [route]: the same per source */
     y2h_train_region rg;                /* [region]; its anchors are `biases`, 2*n floats */
     y2h_train_region_stats *stats;
+    y2h_train_dense dg;                 /* [connected] */
+    int fwd_ranges, dx_ranges;          /* its reduction ranges, fixed when the workspace was sized (Y2_TRAIN_DENSE_KSPLIT is read then) */
+    int src_c, src_h, src_w;            /* [connected], [dropout]: the activation in front as an image (h = w = 1: flat) */
+    float *rnd, *h_rnd;                 /* [dropout]: the step's draws, [batch][inputs] in the reference's order; pinned staging */
+    int alias;                          /* [dropout]: out and delta are the layer's in front, not owned */
+    y2h_train_detection dt;             /* [detection] */
+    y2h_train_detection_stats *dstats;
 } y2_tlayer;
 
 typedef struct y2_trainer {
     int n, batch;
     y2_tlayer *L;
     float *d_x_nchw, *d_x, *d_truth;    /* the step's input as given, as NHWC, and its truth */
+    float *dense_ws;                    /* partial sums of the dense forward / input-gradient ranges */
     float *ws, *scratch, *stage;        /* weight-gradient partial tiles, reduction partials (and the region head's), NCHW staging
                                            of y2_train_pull and landing buffer of a delta's later writers */
     size_t truth_floats;                /* per step: batch * l.truths of a [region] head, batch * inputs of a [cost] */
@@ -221,6 +236,28 @@ void y2_train_unpack_weights(const float *packed, float *ref, int n, int c, int 
                     ref[(((size_t)f * c + ci) * size + ky) * size + kx] = packed[((size_t)(ky * size + kx) * c + ci) * n + f];
 }
 
+/* A dense layer's master is [outputs][inputs] like the host's; behind an image (h * w > 1) the reference's input index is
+ * ci*h*w + y*w + x and the trainer's activation is dense NHWC, so the K index of the master runs (y, x, ci). */
+void y2_train_pack_dense_weights(const float *ref, float *packed, int outputs, int c, int h, int w)
+{
+    const size_t k = (size_t)c * h * w;
+    int o, ci, p;
+    for (o = 0; o < outputs; ++o)
+        for (ci = 0; ci < c; ++ci)
+            for (p = 0; p < h * w; ++p)
+                packed[o * k + (size_t)p * c + ci] = ref[o * k + (size_t)ci * h * w + p];
+}
+
+void y2_train_unpack_dense_weights(const float *packed, float *ref, int outputs, int c, int h, int w)
+{
+    const size_t k = (size_t)c * h * w;
+    int o, ci, p;
+    for (o = 0; o < outputs; ++o)
+        for (ci = 0; ci < c; ++ci)
+            for (p = 0; p < h * w; ++p)
+                ref[o * k + (size_t)ci * h * w + p] = packed[o * k + (size_t)p * c + ci];
+}
+
 /* ------------------------------------------------------------------ */
 /* refusals                                                            */
 /* ------------------------------------------------------------------ */
@@ -228,11 +265,13 @@ static int refuse(const network *net)
 {
     const y2_engine *e = y2_engine_of(net);
     int i, flat = 0;           /* the running activation reads the same as [batch][c][h][w] and as [batch][h][w][c] */
+    int det;                   /* the network ends in [detection]: [connected] and [dropout] train */
     if (!e || !net->layers || net->n <= 0) { y2_fail("y2_train_prepare: network has no engine (was it built by parse_network_cfg?)"); return -1; }
     if (e->half) { y2_fail("training is fp32 only: the network is in fp16 mode (y2_set_half / Y2_FP16)"); return -1; }
     if (e->lr.adam) { y2_fail("training: adam=1 is not implemented (SGD with momentum only)"); return -1; }
     if (e->lr.policy == Y2_LR_RANDOM) { y2_fail("training: policy=random is refused (its rate is a draw of rand(), not a function of the step)"); return -1; }
     if (e->lr.policy == Y2_LR_STEPS && !e->lr.num_steps) { y2_fail("training: STEPS policy must have steps and scales in cfg file"); return -1; }
+    det = net->layers[net->n - 1].type == DETECTION;
     for (i = 0; i < net->n; ++i) {
         const layer *l = &net->layers[i];
         const char *t = get_layer_string(l->type);
@@ -242,11 +281,20 @@ static int refuse(const network *net)
                     "image are ordered by channel in the truth and by pixel on the device", i, t);
             return -1;
         }
+        if (l->type == DETECTION && !flat) {
+            y2_fail("training: layer %d (%s): its input must be one value per channel (put a [connected] in front): the head reads "
+                    "rows ordered by channel, an image is ordered by pixel on the device", i, t);
+            return -1;
+        }
         if (l->type == CONVOLUTIONAL || l->type == MAXPOOL) flat = l->out_h * l->out_w == 1 || l->out_c == 1;
-        if (l->type == AVGPOOL) flat = 1;
+        if (l->type == AVGPOOL || l->type == CONNECTED) flat = 1;
         if (l->type == ROUTE || l->type == REORG || l->type == REGION) flat = 0;
         if ((l->type == ROUTE || l->type == REORG) && net->layers[net->n - 1].type != REGION) {
             y2_fail("training: layer %d (%s) trains only in a network that ends in [region]", i, t);
+            return -1;
+        }
+        if ((l->type == CONNECTED || l->type == DROPOUT) && !det) {
+            y2_fail("training: layer %d (%s) trains only in a network that ends in [detection]", i, t);
             return -1;
         }
         switch (l->type) {
@@ -294,14 +342,44 @@ static int refuse(const network *net)
                 return -1;
             }
             break;
+        case CONNECTED:
+            if (l->activation != LINEAR && l->activation != LEAKY && l->activation != LOGISTIC && l->activation != RELU) {
+                y2_fail("training: layer %d (%s): activation %d is not trainable (linear, leaky, logistic, relu)", i, t, (int)l->activation);
+                return -1;
+            }
+            if (l->batch_normalize && net->batch < 2) {
+                y2_fail("training: layer %d (%s): batch normalisation over batch = %d value divides by zero in the reference", i, t, net->batch);
+                return -1;
+            }
+            break;
+        case DROPOUT:
+            if (i == 0) { y2_fail("training: layer %d (%s): a dropout layer needs a layer in front of it", i, t); return -1; }
+            break;
+        case DETECTION:
+            if (l->random) {
+                y2_fail("training: layer %d (%s): random=1 is refused (it picks the box by a draw of rand() inside the loss while seen < 64000)", i, t);
+                return -1;
+            }
+            if (i != net->n - 1) { y2_fail("training: layer %d (%s): only the last layer may be a detection layer (one truth per step)", i, t); return -1; }
+            if (l->coords != 4) { y2_fail("training: layer %d (%s): coords=%d is not trainable (4 only)", i, t, l->coords); return -1; }
+            /* the parser already refuses a cfg whose count differs (y2_cfg.c make_detection): this guards a network whose
+             * layer fields were set by hand */
+            if (i == 0 || l->side <= 0 || l->n <= 0 || l->classes <= 0 ||
+                net->layers[i - 1].outputs != l->side * l->side * ((1 + l->coords) * l->n + l->classes)) {
+                y2_fail("training: layer %d (%s): the layer in front must give side*side*((1+coords)*num+classes) = %d values", i, t,
+                        l->side * l->side * ((1 + l->coords) * l->n + l->classes));
+                return -1;
+            }
+            break;
         default:
-            y2_fail("training: layer %d (%s) is not trainable (convolutional, maxpool, avgpool, softmax, cost, route, reorg, region)", i, t);
+            y2_fail("training: layer %d (%s) is not trainable (convolutional, maxpool, avgpool, softmax, cost, route, reorg, region; "
+                    "connected, dropout, detection in a network that ends in [detection])", i, t);
             return -1;
         }
     }
     if (net->h <= 0 || net->w <= 0 || net->c <= 0) { y2_fail("training: the network input must be an image (h, w, c > 0)"); return -1; }
-    if (net->layers[net->n - 1].type != COST && net->layers[net->n - 1].type != REGION) {
-        y2_fail("training: layer %d (%s): the last layer must be [cost] or [region]", net->n - 1, get_layer_string(net->layers[net->n - 1].type));
+    if (net->layers[net->n - 1].type != COST && net->layers[net->n - 1].type != REGION && !det) {
+        y2_fail("training: layer %d (%s): the last layer must be [cost], [region] or [detection]", net->n - 1, get_layer_string(net->layers[net->n - 1].type));
         return -1;
     }
     return 0;
@@ -310,7 +388,7 @@ static int refuse(const network *net)
 static int truths_per_image(const network *net)
 {
     const layer *last = &net->layers[net->n - 1];
-    return last->type == REGION ? last->truths : last->inputs;
+    return last->type == REGION || last->type == DETECTION ? last->truths : last->inputs;
 }
 
 int y2_train_truth_floats(network *net)
@@ -336,13 +414,16 @@ void y2_train_free(network *net)
                          L->weight_updates, L->biases, L->bias_updates, L->scales, L->scale_updates, L->rolling_mean,
                          L->rolling_variance, L->cost };
         size_t k;
-        for (k = 0; k < sizeof all / sizeof all[0]; ++k) y2h_free(all[k]);
+        for (k = L->alias ? 2 : 0; k < sizeof all / sizeof all[0]; ++k) y2h_free(all[k]);
         y2h_free(L->idx);
         y2h_free(L->stats);
+        y2h_free(L->dstats);
+        y2h_free(L->rnd);
+        y2h_host_free(L->h_rnd);
         free(L->src_add);
     }
     y2h_free(t->d_x_nchw); y2h_free(t->d_x); y2h_free(t->d_truth);
-    y2h_free(t->ws); y2h_free(t->scratch); y2h_free(t->stage);
+    y2h_free(t->ws); y2h_free(t->scratch); y2h_free(t->stage); y2h_free(t->dense_ws);
     y2h_host_free(t->h_cost); y2h_host_free(t->h_in); y2h_host_free(t->h_pull);
     y2h_host_free(t->h_load); y2h_free(t->d_load);
     if (t->ev_load) y2h_event_destroy(t->ev_load);
@@ -379,6 +460,8 @@ static void plan_deltas(const network *net, y2_trainer *t)
         if (l->type == ROUTE) {
             L->src_add = calloc(l->n, sizeof(int));
             for (k = 0; k < l->n; ++k) { L->src_add[k] = written[l->input_layers[k]]; written[l->input_layers[k]] = 1; }
+        } else if (l->type == DROPOUT) {
+            if (i > 0) written[i - 1] = written[i];                    /* neither stores nor adds: its delta IS the one in front */
         } else if (i > 0) {
             L->din_add = l->type == REORG ? 0 : written[i - 1];        /* reorg_layer.c:92 assigns */
             written[i - 1] = 1;
@@ -392,7 +475,7 @@ int y2_train_prepare(network *net)
     y2_engine *e = y2_engine_of(net);
     y2_trainer *t;
     float *pin, *tmp = NULL;
-    size_t ws = 16, scratch = 16, stage;
+    size_t ws = 16, scratch = 16, dense_ws = 16, stage;
     int i, rc = -1;
     if (refuse(net) != 0) return -1;
     y2_train_free(net);
@@ -408,7 +491,7 @@ int y2_train_prepare(network *net)
     for (i = 0; i < net->n; ++i) {
         const layer *l = &net->layers[i];
         stage = max_z(stage, (size_t)net->batch * l->outputs);
-        if (l->type == CONVOLUTIONAL) stage = max_z(stage, (size_t)l->n * l->c * l->size * l->size);
+        if (l->type == CONVOLUTIONAL || l->type == CONNECTED) stage = max_z(stage, (size_t)l->n * l->c * l->size * l->size);
     }
     t->stage_floats = stage;
     if (y2h_host_alloc((void **)&t->h_pull, stage * sizeof(float)) != 0) { y2_fail("y2_train_prepare: no pinned memory: %s", y2h_last_error()); goto cleanup; }
@@ -422,6 +505,23 @@ int y2_train_prepare(network *net)
         const layer *l = &net->layers[i];
         y2_tlayer *L = &t->L[i];
         const size_t outs = (size_t)net->batch * l->outputs;
+        if (l->type == CONNECTED || l->type == DROPOUT) {       /* the activation in front, seen through any [dropout] */
+            int p = i - 1;
+            while (p >= 0 && net->layers[p].type == DROPOUT) --p;
+            L->src_c = p < 0 ? net->c : net->layers[p].out_c;
+            L->src_h = p < 0 ? net->h : net->layers[p].out_h;
+            L->src_w = p < 0 ? net->w : net->layers[p].out_w;
+            if (L->src_c <= 0 || L->src_h <= 0 || L->src_w <= 0 || (long)L->src_c * L->src_h * L->src_w != l->inputs) {
+                L->src_c = l->inputs; L->src_h = L->src_w = 1;
+            }
+        }
+        if (l->type == DROPOUT) {
+            L->alias = 1;
+            L->out = t->L[i - 1].out; L->delta = t->L[i - 1].delta;
+            if (dev_floats(&L->rnd, outs, e)) goto cleanup;
+            HIP_OR_CLEANUP(y2h_host_alloc((void **)&L->h_rnd, outs * sizeof(float)));
+            continue;
+        }
         if (dev_floats(&L->out, outs, e) || dev_floats(&L->delta, outs, e)) goto cleanup;
         if (l->type == MAXPOOL) HIP_OR_CLEANUP(y2h_malloc((void **)&L->idx, outs * sizeof(int)));
         if (l->type == COST && dev_floats(&L->cost, 1, e)) goto cleanup;
@@ -435,21 +535,42 @@ int y2_train_prepare(network *net)
                 dev_floats((float **)&L->stats, sizeof(y2h_train_region_stats) / sizeof(float), e) ||
                 push(L->biases, l->biases, (size_t)2 * l->n, pin, e)) goto cleanup;
         }
-        if (l->type != CONVOLUTIONAL) continue;
+        if (l->type == DETECTION) {
+            y2h_train_detection dt = { net->batch, l->side, l->n, l->classes, l->softmax, l->sqrt, l->rescore, l->forced, l->coord_scale,
+                                       l->object_scale, l->noobject_scale, l->class_scale };
+            L->dt = dt;
+            if (y2h_train_detection_scratch_bytes(&dt) == 0) { y2_fail("training: layer %d (detection): shape outside what the kernels take", i); goto cleanup; }
+            scratch = max_z(scratch, y2h_train_detection_scratch_bytes(&dt));
+            if (dev_floats(&L->cost, 1, e) || dev_floats((float **)&L->dstats, sizeof(y2h_train_detection_stats) / sizeof(float), e)) goto cleanup;
+        }
+        if (l->type != CONVOLUTIONAL && l->type != CONNECTED) continue;
         {
             const size_t nw = (size_t)l->n * l->c * l->size * l->size;
             const long rows = (long)net->batch * l->out_h * l->out_w;
             y2h_train_conv g = { net->batch, l->h, l->w, l->c, l->n, l->size, l->pad, l->out_h, l->out_w };
-            L->g = g;
-            if (l->out_h != l->h + 2 * l->pad - l->size + 1 || y2h_train_dweight_ws_bytes(&g) == 0) {
-                y2_fail("training: layer %d (convolutional): shape outside what the kernels take", i);
-                goto cleanup;
+            if (l->type == CONNECTED) {         /* l.n = outputs, l.c = inputs, size 1 on a 1 x 1 image (y2_cfg.c) */
+                y2h_train_dense dg = { net->batch, l->inputs, l->outputs };
+                size_t fw = 0, bw = 0;
+                L->dg = dg;
+                if (y2h_train_dense_plan(&dg, Y2H_DENSE_FORWARD, 0, &L->fwd_ranges, &fw, NULL, 0) != 0 ||
+                    y2h_train_dense_plan(&dg, Y2H_DENSE_DINPUT, 0, &L->dx_ranges, &bw, NULL, 0) != 0) {
+                    y2_fail("training: layer %d (connected): shape outside what the kernels take", i);
+                    goto cleanup;
+                }
+                dense_ws = max_z(dense_ws, max_z(fw, bw));
+            } else {
+                L->g = g;
+                if (l->out_h != l->h + 2 * l->pad - l->size + 1 || y2h_train_dweight_ws_bytes(&g) == 0) {
+                    y2_fail("training: layer %d (convolutional): shape outside what the kernels take", i);
+                    goto cleanup;
+                }
+                ws = max_z(ws, y2h_train_dweight_ws_bytes(&g));
             }
-            ws = max_z(ws, y2h_train_dweight_ws_bytes(&g));
             scratch = max_z(scratch, y2h_train_reduce_scratch_bytes(rows, l->n));
             if (dev_floats(&L->weights, nw, e) || dev_floats(&L->weight_updates, nw, e) || dev_floats(&L->biases, l->n, e) ||
                 dev_floats(&L->bias_updates, l->n, e)) goto cleanup;
-            y2_train_pack_weights(l->weights, tmp, l->n, l->c, l->size);
+            if (l->type == CONNECTED) y2_train_pack_dense_weights(l->weights, tmp, l->outputs, L->src_c, L->src_h, L->src_w);
+            else y2_train_pack_weights(l->weights, tmp, l->n, l->c, l->size);
             if (push(L->weights, tmp, nw, pin, e) || push(L->biases, l->biases, l->n, pin, e)) goto cleanup;
             if (!l->batch_normalize) continue;
             if (dev_floats(&L->x, outs, e) || dev_floats(&L->x_norm, outs, e) || dev_floats(&L->mean, l->n, e) ||
@@ -461,6 +582,7 @@ int y2_train_prepare(network *net)
         }
     }
     HIP_OR_CLEANUP(y2h_malloc((void **)&t->ws, ws));
+    HIP_OR_CLEANUP(y2h_malloc((void **)&t->dense_ws, dense_ws));
     HIP_OR_CLEANUP(y2h_malloc((void **)&t->scratch, scratch));
     HIP_OR_CLEANUP(y2h_malloc((void **)&t->stage, stage * sizeof(float)));
     HIP_OR_CLEANUP(y2h_stream_sync(e->stream));
@@ -518,6 +640,26 @@ static int forward_train(network *net, y2_trainer *t, y2_engine *e)
             HIP_OR_ERR(y2h_train_region_loss(&L->rg, in, L->biases, t->d_truth, *net->seen, L->out, L->delta, t->L[i - 1].delta, L->cost,
                                              L->stats, t->scratch, e->stream));
             break;
+        case CONNECTED:     /* connected_layer.c:122-155; the rolling statistics move by .05 here, not by .1 */
+            HIP_OR_ERR(y2h_train_dense_forward(&L->dg, in, L->weights, L->out, t->dense_ws, L->fwd_ranges, e->stream));
+            if (l->batch_normalize)
+                HIP_OR_ERR(y2h_train_bn_stats_rate(L->out, net->batch, l->outputs, L->mean, L->variance, L->rolling_mean, L->rolling_variance,
+                                                   .95f, .05f, t->scratch, e->stream));
+            HIP_OR_ERR(y2h_train_bn_apply(L->out, L->x, L->x_norm, l->batch_normalize ? L->mean : NULL, L->variance, L->scales, L->biases,
+                                          y2_act_code(l->activation), net->batch, l->outputs, e->stream));
+            break;
+        case DROPOUT: {     /* dropout_layer.c:38-48 on the output in front, in place; rand_uniform(0, 1) per element in index order */
+            const size_t n = (size_t)net->batch * l->inputs;
+            size_t k;
+            for (k = 0; k < n; ++k) L->h_rnd[k] = ((float)rand() / RAND_MAX * (1.f - 0.f)) + 0.f;
+            HIP_OR_ERR(y2h_memcpy_h2d(L->rnd, L->h_rnd, n * sizeof(float), e->stream));
+            HIP_OR_ERR(y2h_train_dropout(L->out, L->rnd, l->probability, (float)(1. / (1. - l->probability)), net->batch, L->src_c,
+                                         L->src_h * L->src_w, e->stream));
+        } break;
+        case DETECTION:     /* forward and backward_detection_layer; the last layer, so the first writer of the delta in front */
+            HIP_OR_ERR(y2h_train_detection_loss(&L->dt, in, t->d_truth, L->out, L->delta, t->L[i - 1].delta, 0, L->cost, L->dstats,
+                                                t->scratch, e->stream));
+            break;
         default:
             return -1;
         }
@@ -560,7 +702,26 @@ static int backward_train(network *net, y2_trainer *t, y2_engine *e)
         case SOFTMAX:   /* softmax_layer.c:57-63: state.delta += l.delta */
             if (din) HIP_OR_ERR(y2h_memcpy_d2d(din, L->delta, (size_t)net->batch * l->inputs * sizeof(float), e->stream));
             break;
-        case COST: case REGION:     /* done with its forward */
+        case COST: case REGION: case DETECTION:     /* done with its forward */
+            break;
+        case CONNECTED:     /* connected_layer.c:157-191 */
+            HIP_OR_ERR(y2h_train_act_gradient(L->out, L->delta, y2_act_code(l->activation), (long)net->batch * l->outputs, e->stream));
+            HIP_OR_ERR(y2h_train_bias_grad(L->delta, l->batch_normalize ? L->x_norm : NULL, net->batch, l->outputs, L->bias_updates,
+                                           l->batch_normalize ? L->scale_updates : NULL, t->scratch, e->stream));
+            if (l->batch_normalize) {
+                HIP_OR_ERR(y2h_train_bn_deltas(L->delta, L->x, L->scales, L->mean, L->variance, net->batch, l->outputs, L->mean_delta,
+                                               L->variance_delta, t->scratch, e->stream));
+                HIP_OR_ERR(y2h_train_bn_backward(L->delta, L->x, L->scales, L->mean, L->variance, L->mean_delta, L->variance_delta, net->batch,
+                                                 l->outputs, e->stream));
+            }
+            HIP_OR_ERR(y2h_train_dense_dweight(&L->dg, in, L->delta, L->weight_updates, e->stream));
+            /* always a store: a later writer lands in the staging buffer and is added below, like every other layer, so the
+             * kernel's own add mode is exercised by the product test alone */
+            if (din) HIP_OR_ERR(y2h_train_dense_dinput(&L->dg, L->delta, L->weights, din, 0, t->dense_ws, L->dx_ranges, e->stream));
+            break;
+        case DROPOUT:       /* dropout_layer.c:50-59: the delta in front, in place */
+            if (own) HIP_OR_ERR(y2h_train_dropout(own, L->rnd, l->probability, (float)(1. / (1. - l->probability)), net->batch, L->src_c,
+                                                  L->src_h * L->src_w, e->stream));
             break;
         case ROUTE: {
             int k, off = 0;
@@ -590,7 +751,7 @@ static int update_train(network *net, y2_trainer *t, y2_engine *e)
     for (i = 0; i < net->n; ++i) {
         const layer *l = &net->layers[i];
         y2_tlayer *L = &t->L[i];
-        if (l->type != CONVOLUTIONAL) continue;
+        if (l->type != CONVOLUTIONAL && l->type != CONNECTED) continue;     /* update_connected_layer has the convolution's order */
         HIP_OR_ERR(y2h_train_sgd(L->biases, L->bias_updates, l->n, rate / batch, 0.f, net->momentum, e->stream));
         if (l->batch_normalize) HIP_OR_ERR(y2h_train_sgd(L->scales, L->scale_updates, l->n, rate / batch, 0.f, net->momentum, e->stream));
         HIP_OR_ERR(y2h_train_sgd(L->weights, L->weight_updates, (long)l->n * l->c * l->size * l->size, rate / batch, -net->decay * batch,
@@ -894,7 +1055,9 @@ int y2_train_pull(network *net, int i, int what, float *dst, size_t n)
     case Y2_TRAIN_SCALES: src = L->scales; break;
     case Y2_TRAIN_ROLLING_MEAN: src = L->rolling_mean; break;
     case Y2_TRAIN_ROLLING_VARIANCE: src = L->rolling_variance; break;
+    case Y2_TRAIN_RAND: src = L->rnd; image = 1; break;
     }
+    if (l->type == DROPOUT && what != Y2_TRAIN_RAND) src = NULL;    /* its output and delta are the layer's in front: pull those */
     if (l->type == REGION && !image) src = NULL;             /* its `biases` are the anchors, not a trainable array */
     if (!src) { y2_fail("y2_train_pull: layer %d (%s) has no array %d", i, get_layer_string(l->type), what); return -1; }
     have = image ? (size_t)net->batch * l->outputs : weights ? (size_t)l->n * l->c * l->size * l->size : (size_t)l->n;
@@ -911,7 +1074,8 @@ int y2_train_pull(network *net, int i, int what, float *dst, size_t n)
     if (weights) {
         float *tmp = malloc(n * sizeof(float));
         int rc = pull_flat(e, src, tmp, n);
-        if (rc == 0) y2_train_unpack_weights(tmp, dst, l->n, l->c, l->size);
+        if (rc == 0 && l->type == CONNECTED) y2_train_unpack_dense_weights(tmp, dst, l->outputs, L->src_c, L->src_h, L->src_w);
+        else if (rc == 0) y2_train_unpack_weights(tmp, dst, l->n, l->c, l->size);
         free(tmp);
         return rc;
     }
@@ -945,6 +1109,19 @@ int y2_train_region_stats(network *net, int i, y2_region_stats *out)
     return 0;
 }
 
+int y2_train_detection_stats(network *net, int i, y2_detection_stats *out)
+{
+    y2_engine *e = y2_engine_of(net);
+    y2_trainer *t = e ? e->trainer : NULL;
+    if (!t) { y2_fail("y2_train_detection_stats: no trainer (y2_train_prepare)"); return -1; }
+    if (i < 0 || i >= net->n || !out || !t->L[i].dstats) { y2_fail("y2_train_detection_stats: layer %d of %d is no [detection] layer", i, net->n); return -1; }
+    HIP_OR_ERR(y2h_set_device(e->device));
+    HIP_OR_ERR(y2h_memcpy_d2h(t->h_pull, t->L[i].dstats, sizeof(y2h_train_detection_stats), e->stream));
+    HIP_OR_ERR(y2h_stream_sync(e->stream));
+    memcpy(out, t->h_pull, sizeof *out);     /* y2_detection_stats and y2h_train_detection_stats are one layout */
+    return 0;
+}
+
 int y2_train_is_dirty(const network *net)
 {
     const y2_engine *e = y2_engine_of(net);
@@ -960,7 +1137,7 @@ int y2_train_sync_if_dirty(network *net)
     if (!t || !t->dirty) return 0;
     for (i = 0; i < net->n; ++i) {
         layer *l = &net->layers[i];
-        if (l->type != CONVOLUTIONAL) continue;
+        if (l->type != CONVOLUTIONAL && l->type != CONNECTED) continue;
         if (y2_train_pull(net, i, Y2_TRAIN_WEIGHTS, l->weights, (size_t)l->n * l->c * l->size * l->size) != 0 ||
             y2_train_pull(net, i, Y2_TRAIN_BIASES, l->biases, l->n) != 0) return -1;
         if (l->batch_normalize &&

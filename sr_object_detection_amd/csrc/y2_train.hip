@@ -152,7 +152,7 @@ __global__ __launch_bounds__(256) void col_partial(const float *__restrict__ a, 
     }
 }
 
-struct Finish { float *o0, *o1, *roll0, *roll1; const float *mean, *variance; float scale; };
+struct Finish { float *o0, *o1, *roll0, *roll1; const float *mean, *variance; float scale, keep, take; };
 
 template <int MODE>
 __global__ void col_finish(const float *__restrict__ part, int C, int P, Finish f)
@@ -165,8 +165,8 @@ __global__ void col_finish(const float *__restrict__ part, int C, int P, Finish 
     if (MODE == R_VAR) {                                                             // variance_cpu, then the rolling statistics
         const float var = s0 * f.scale;
         f.o0[c] = var;
-        f.roll0[c] = f.roll0[c] * .9f + .1f * f.mean[c];
-        f.roll1[c] = f.roll1[c] * .9f + .1f * var;
+        f.roll0[c] = f.roll0[c] * f.keep + f.take * f.mean[c];
+        f.roll1[c] = f.roll1[c] * f.keep + f.take * var;
     }
     if (MODE == R_BIAS) { f.o0[c] += s0; if (f.o1) f.o1[c] += s1; }
     if (MODE == R_BNDELTA) {
@@ -332,6 +332,17 @@ __global__ __launch_bounds__(256) void cost_sse(const float *__restrict__ pred, 
     if (threadIdx.x == 0) cost[0] = sh[0];
 }
 
+// dropout_layer.c:38-59 on a dense NHWC tensor; the draws are indexed as the reference's [batch][c][hw]
+__global__ void dropout_apply(float *__restrict__ x, const float *__restrict__ rnd, float probability, float scale, long n, int c, int hw)
+{
+    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
+        const int ci = (int)(e % c);
+        const long q = e / c, b = q / hw;
+        const float r = rnd[(b * c + ci) * hw + (q - b * hw)];
+        x[e] = (r < probability) ? 0.f : x[e] * scale;
+    }
+}
+
 __global__ void sgd(float *__restrict__ w, float *__restrict__ u, long n, float rate, float wd, float momentum)
 {
     for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
@@ -411,12 +422,18 @@ size_t y2h_train_reduce_scratch_bytes(long rows, int c)
 int y2h_train_bn_stats(const float *x, long rows, int c, float *mean, float *variance, float *rolling_mean,
                        float *rolling_variance, float *scratch, y2h_stream s)
 {
+    return y2h_train_bn_stats_rate(x, rows, c, mean, variance, rolling_mean, rolling_variance, .9f, .1f, scratch, s);
+}
+
+int y2h_train_bn_stats_rate(const float *x, long rows, int c, float *mean, float *variance, float *rolling_mean,
+                            float *rolling_variance, float keep, float take, float *scratch, y2h_stream s)
+{
     if (!x || !mean || !variance || !rolling_mean || !rolling_variance || !scratch || rows < 2 || c <= 0) return Y2H_EINVAL;
     Finish f = {};
     f.o0 = mean; f.scale = (float)(1. / (double)rows);
     int rc = col_reduce<R_SUM>(x, nullptr, nullptr, nullptr, rows, c, scratch, f, s);
     if (rc != Y2H_OK) return rc;
-    f.o0 = variance; f.scale = (float)(1. / (double)(rows - 1)); f.mean = mean; f.roll0 = rolling_mean; f.roll1 = rolling_variance;
+    f.o0 = variance; f.scale = (float)(1. / (double)(rows - 1)); f.mean = mean; f.roll0 = rolling_mean; f.roll1 = rolling_variance; f.keep = keep; f.take = take;
     return col_reduce<R_VAR>(x, nullptr, nullptr, mean, rows, c, scratch, f, s);
 }
 
@@ -520,6 +537,15 @@ int y2h_train_cost_sse(const float *pred, const float *truth, float *error, floa
 {
     if (!pred || !truth || !error || !delta || !delta_prev || !cost || n <= 0) return Y2H_EINVAL;
     cost_sse<<<1, 256, 0, S(s)>>>(pred, truth, error, delta, delta_prev, scale, n, cost);
+    Y2H_LAUNCH_CHECK();
+    return Y2H_OK;
+}
+
+int y2h_train_dropout(float *x, const float *rnd, float probability, float scale, int batch, int c, int hw, y2h_stream s)
+{
+    if (!x || !rnd || batch <= 0 || c <= 0 || hw <= 0 || (long)batch * c * hw >= 2147483647L) return Y2H_EINVAL;
+    const long n = (long)batch * c * hw;
+    dropout_apply<<<y2h_grid(n, 256), 256, 0, S(s)>>>(x, rnd, probability, scale, n, c, hw);
     Y2H_LAUNCH_CHECK();
     return Y2H_OK;
 }

@@ -1,7 +1,8 @@
 // Training kernels of the detector's tail (gfx950): the [region] head in training mode after src_yolo2/region_layer.c:144-321
 // (CPU branch, DOABS 1, flat softmax) with backward_region_layer (:323-326), the two directions of [route]
 // (route_layer.c:73-101) on dense NHWC tensors, the backward of a non-reverse [reorg] (reorg_layer.c:87-94) and the plain
-// add a delta with more than one writer needs.
+// add a delta with more than one writer needs.  The [detection] head of YOLOv1 (detection_layer.c:49-222) is below the region head:
+// detection_cells (one thread per image and cell), the region head's region_sumsq, detection_finish.
 //
 // The region head is four launches on one stream:
 //   region_cells    one thread per (image, cell, anchor): activation, predicted box, best IoU over the image's truths,
@@ -192,6 +193,7 @@ __global__ __launch_bounds__(64) void region_truths(y2h_train_region g, const fl
     }
 }
 
+template <bool ADD>
 __global__ __launch_bounds__(SUM_BLOCK) void region_sumsq(const float *__restrict__ delta, float *__restrict__ delta_prev, long n,
                                                           float *__restrict__ part)
 {
@@ -200,7 +202,8 @@ __global__ __launch_bounds__(SUM_BLOCK) void region_sumsq(const float *__restric
     float s = 0.f;
     for (long e = e0 + threadIdx.x; e < e1; e += SUM_BLOCK) {
         const float d = delta[e];
-        delta_prev[e] = d;                 // axpy_cpu(.., 1, l.delta, 1, state.delta, 1) into the zeroed delta
+        if (ADD) delta_prev[e] += d;       // axpy_cpu(.., 1, l.delta, 1, state.delta, 1): a later writer adds,
+        else delta_prev[e] = d;            // the first one finds the zeroed delta
         s += d * d;
     }
     sh[threadIdx.x] = s;
@@ -233,6 +236,127 @@ __global__ void region_finish(y2h_train_region g, const float *__restrict__ part
     stats->recall = (float)st[3] / count;
     stats->count = count;
     stats->class_count = class_count;
+}
+
+// ---- the [detection] head (YOLOv1) in training mode, detection_layer.c:49-222 ----
+// An image's row is [cells][classes] class scores | [cells][n] objectness | [cells][n][4] boxes.  A cell writes only its
+// own entries of out and delta, all of them (zeros included), so one thread per (image, cell) needs no memset and no order.
+constexpr int DET_BLOCK = 64;
+
+// box.c:99-105: the four squares, their sum and the root in double
+__device__ __forceinline__ float box_rmse(const Box &a, const Box &b)
+{
+    return (float)sqrt(pow((double)(a.x - b.x), 2.) + pow((double)(a.y - b.y), 2.) + pow((double)(a.w - b.w), 2.) +
+                       pow((double)(a.h - b.h), 2.));
+}
+
+__device__ __forceinline__ Box det_box(const float *o, int side, int sq)
+{
+    Box b = { o[0] / side, o[1] / side, o[2], o[3] };
+    if (sq) { b.w = b.w * b.w; b.h = b.h * b.h; }
+    return b;
+}
+
+// per workgroup: sums of iou, positive class, all classes, chosen objectness, every objectness, and the object count
+__global__ __launch_bounds__(DET_BLOCK) void detection_cells(y2h_train_detection g, const float *__restrict__ in,
+                                                             const float *__restrict__ truth, float *__restrict__ out,
+                                                             float *__restrict__ delta, double *__restrict__ stat_part)
+{
+    __shared__ double sh[6][DET_BLOCK];
+    const int cells = g.side * g.side, per = (1 + 4) * g.n + g.classes, tper = 1 + 4 + g.classes;
+    const long idx = (long)blockIdx.x * DET_BLOCK + threadIdx.x;
+    double st[6] = { 0., 0., 0., 0., 0., 0. };
+    if (idx < (long)g.batch * cells) {
+        const int b = (int)(idx / cells), i = (int)(idx % cells);
+        const size_t image = (size_t)b * cells * per;
+        const float *t = truth + (size_t)idx * tper;
+        const size_t cls = image + (size_t)i * g.classes, obj = image + (size_t)cells * g.classes + (size_t)i * g.n;
+        const size_t box = image + (size_t)cells * (g.classes + g.n) + (size_t)i * g.n * 4;
+        if (g.softmax) softmax_seq(in + cls, g.classes, 1.f, out + cls);
+        else for (int j = 0; j < g.classes; ++j) out[cls + j] = in[cls + j];
+        for (int j = 0; j < g.n; ++j) {
+            const float p = in[obj + j];
+            out[obj + j] = p;
+            delta[obj + j] = g.noobject_scale * (0 - p);
+            st[4] += p;
+        }
+        for (int j = 0; j < 4 * g.n; ++j) { out[box + j] = in[box + j]; delta[box + j] = 0.f; }
+        const int is_obj = (int)t[0];
+        if (!is_obj) {
+            for (int j = 0; j < g.classes; ++j) delta[cls + j] = 0.f;
+        } else {
+            for (int j = 0; j < g.classes; ++j) {
+                const float p = out[cls + j];
+                delta[cls + j] = g.class_scale * (t[1 + j] - p);
+                if (t[1 + j]) st[1] += p;
+                st[2] += p;
+            }
+            const float *tb = t + 1 + g.classes;
+            const Box tr = { tb[0] / g.side, tb[1] / g.side, tb[2], tb[3] };
+            int best = -1;
+            float best_iou = 0, best_rmse = 20;
+            for (int j = 0; j < g.n; ++j) {
+                const Box o = det_box(out + box + 4 * j, g.side, g.sqrt);
+                const float iou = box_iou(o, tr), rmse = box_rmse(o, tr);
+                if (best_iou > 0 || iou > 0) {
+                    if (iou > best_iou) { best_iou = iou; best = j; }
+                } else if (rmse < best_rmse) {
+                    best_rmse = rmse;
+                    best = j;
+                }
+            }
+            if (g.forced) best = (tr.w * tr.h < .1) ? 1 : 0;
+            // no box won (every IoU 0 or NaN and every rmse >= 20 or NaN), or forced names box 1 of a one-box head: the
+            // reference goes on with entries that are not this cell's; here the cell keeps its no-object and class deltas
+            if (best >= 0 && best < g.n) {
+                const float *o = out + box + 4 * best;
+                const float iou = box_iou(det_box(o, g.side, g.sqrt), tr), p = out[obj + best];
+                st[3] += p;
+                delta[obj + best] = g.rescore ? g.object_scale * (iou - p) : (float)((double)g.object_scale * (1. - (double)p));
+                float *d = delta + box + 4 * best;
+                d[0] = g.coord_scale * (tb[0] - o[0]);
+                d[1] = g.coord_scale * (tb[1] - o[1]);
+                if (g.sqrt) {
+                    d[2] = (float)((double)g.coord_scale * (sqrt((double)tb[2]) - (double)o[2]));
+                    d[3] = (float)((double)g.coord_scale * (sqrt((double)tb[3]) - (double)o[3]));
+                } else {
+                    d[2] = g.coord_scale * (tb[2] - o[2]);
+                    d[3] = g.coord_scale * (tb[3] - o[3]);
+                }
+                st[0] += iou;
+                st[5] += 1.;
+            }
+        }
+    }
+    for (int k = 0; k < 6; ++k) sh[k][threadIdx.x] = st[k];
+    __syncthreads();
+    for (int s = DET_BLOCK / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s)
+            for (int k = 0; k < 6; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x < 6) stat_part[(size_t)blockIdx.x * 6 + threadIdx.x] = sh[threadIdx.x][0];
+}
+
+__global__ void detection_finish(y2h_train_detection g, const float *__restrict__ part, int parts,
+                                 const double *__restrict__ stat_part, int stat_parts, float *__restrict__ cost,
+                                 y2h_train_detection_stats *__restrict__ stats)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    float sum = 0.f;
+    for (int p = 0; p < parts; ++p) sum += part[p];
+    const float mag = sqrtf(sum);                                   // mag_array
+    cost[0] = (float)pow((double)mag, 2.);
+    double st[6] = { 0., 0., 0., 0., 0., 0. };
+    for (int p = 0; p < stat_parts; ++p)
+        for (int k = 0; k < 6; ++k) st[k] += stat_part[(size_t)p * 6 + k];
+    const int count = (int)st[5];
+    stats->avg_iou = (float)st[0] / count;                          // the printf of :214: float / int, NaN when count == 0
+    stats->avg_cat = (float)st[1] / count;
+    stats->avg_allcat = (float)st[2] / (count * g.classes);
+    stats->avg_obj = (float)st[3] / count;
+    stats->avg_anyobj = (float)st[4] / (g.batch * g.side * g.side * g.n);
+    stats->count = count;
 }
 
 __global__ void route_fwd(const float *__restrict__ src, int c, float *__restrict__ dst, int ldc, int off, long n)
@@ -289,6 +413,16 @@ inline bool region_ok(const y2h_train_region *g)
            (long)g->h * g->w * g->n * (5 + g->classes) < 2147483647L && region_floats(g) < 2147483647L;
 }
 
+inline long detection_floats(const y2h_train_detection *g) { return (long)g->batch * g->side * g->side * (5 * g->n + g->classes); }
+inline int detection_blocks(const y2h_train_detection *g) { return (int)(((long)g->batch * g->side * g->side + DET_BLOCK - 1) / DET_BLOCK); }
+inline int detection_parts(const y2h_train_detection *g) { return (int)((detection_floats(g) + SUM_CHUNK - 1) / SUM_CHUNK); }
+
+inline bool detection_ok(const y2h_train_detection *g)
+{
+    return g && g->batch > 0 && g->side > 0 && g->side <= 4096 && g->n > 0 && g->classes > 0 &&
+           (long)g->side * g->side * (5L * g->n + g->classes) < 2147483647L && detection_floats(g) < 2147483647L;
+}
+
 }  // namespace
 
 extern "C" {
@@ -310,9 +444,32 @@ int y2h_train_region_loss(const y2h_train_region *g, const float *in, const floa
     Y2H_LAUNCH_CHECK();
     region_truths<<<g->batch, 64, 0, S(s)>>>(*g, anchors, truth, out, delta, image_stats);
     Y2H_LAUNCH_CHECK();
-    region_sumsq<<<parts, SUM_BLOCK, 0, S(s)>>>(delta, delta_prev, region_floats(g), part);
+    region_sumsq<false><<<parts, SUM_BLOCK, 0, S(s)>>>(delta, delta_prev, region_floats(g), part);
     Y2H_LAUNCH_CHECK();
     region_finish<<<1, 64, 0, S(s)>>>(*g, part, parts, any_part, g->batch * cb, image_stats, cost, stats);
+    Y2H_LAUNCH_CHECK();
+    return Y2H_OK;
+}
+
+size_t y2h_train_detection_scratch_bytes(const y2h_train_detection *g)
+{
+    if (!detection_ok(g)) return 0;
+    return (size_t)detection_blocks(g) * 6 * sizeof(double) + (size_t)detection_parts(g) * sizeof(float);
+}
+
+int y2h_train_detection_loss(const y2h_train_detection *g, const float *in, const float *truth, float *out, float *delta,
+                             float *delta_prev, int add, float *cost, y2h_train_detection_stats *stats, void *scratch, y2h_stream s)
+{
+    if (!detection_ok(g) || !in || !truth || !out || !delta || !delta_prev || !cost || !stats || !scratch) return Y2H_EINVAL;
+    const int blocks = detection_blocks(g), parts = detection_parts(g);
+    double *stat_part = (double *)scratch;
+    float *part = (float *)(stat_part + (size_t)blocks * 6);
+    detection_cells<<<blocks, DET_BLOCK, 0, S(s)>>>(*g, in, truth, out, delta, stat_part);
+    Y2H_LAUNCH_CHECK();
+    if (add) region_sumsq<true><<<parts, SUM_BLOCK, 0, S(s)>>>(delta, delta_prev, detection_floats(g), part);
+    else region_sumsq<false><<<parts, SUM_BLOCK, 0, S(s)>>>(delta, delta_prev, detection_floats(g), part);
+    Y2H_LAUNCH_CHECK();
+    detection_finish<<<1, 64, 0, S(s)>>>(*g, part, parts, stat_part, blocks, cost, stats);
     Y2H_LAUNCH_CHECK();
     return Y2H_OK;
 }

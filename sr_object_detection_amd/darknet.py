@@ -152,9 +152,22 @@ class TrainConv(C.Structure):  # include/y2_hip.h y2h_train_conv: the shape of o
     _fields_ = [(k, C.c_int) for k in ("batch", "h", "w", "c", "n", "size", "pad", "out_h", "out_w")]
 
 
+class TrainDense(C.Structure):  # include/y2_hip.h y2h_train_dense: the shape of one trainable [connected] layer
+    _fields_ = [(k, C.c_int) for k in ("batch", "inputs", "outputs")]
+
+
 class TrainRegion(C.Structure):  # include/y2_hip.h y2h_train_region: one [region] head in training mode
     _fields_ = [(k, C.c_int) for k in ("batch", "h", "w", "n", "classes", "bias_match", "rescore")] + \
                [(k, C.c_float) for k in ("thresh", "coord_scale", "object_scale", "noobject_scale", "class_scale")]
+
+
+class TrainDetection(C.Structure):  # include/y2_hip.h y2h_train_detection: one [detection] head in training mode (coords = 4)
+    _fields_ = [(k, C.c_int) for k in ("batch", "side", "n", "classes", "softmax", "sqrt", "rescore", "forced")] + \
+               [(k, C.c_float) for k in ("coord_scale", "object_scale", "noobject_scale", "class_scale")]
+
+
+class DetectionStats(C.Structure):  # include/sr_yolo2.h y2_detection_stats == include/y2_hip.h y2h_train_detection_stats
+    _fields_ = [(k, C.c_float) for k in ("avg_iou", "avg_cat", "avg_allcat", "avg_obj", "avg_anyobj")] + [("count", C.c_int)]
 
 
 class RegionStats(C.Structure):  # include/sr_yolo2.h y2_region_stats == include/y2_hip.h y2h_train_region_stats
@@ -437,6 +450,15 @@ def lib():
     L.y2_train_pack_weights.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
     L.y2_train_unpack_weights.restype = None
     L.y2_train_unpack_weights.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
+    for f in (L.y2_train_pack_dense_weights, L.y2_train_unpack_dense_weights):
+        f.restype = None
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.y2h_train_dense_plan.argtypes = [C.POINTER(TrainDense), C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_size_t),
+                                       C.c_void_p, C.c_int]
+    L.y2h_train_dense_forward.argtypes = [C.POINTER(TrainDense), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.y2h_train_dense_dinput.argtypes = [C.POINTER(TrainDense), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                         C.c_void_p]
+    L.y2h_train_dense_dweight.argtypes = [C.POINTER(TrainDense), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.y2h_train_conv_forward.argtypes = [C.POINTER(TrainConv), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.y2h_train_conv_dinput.argtypes = [C.POINTER(TrainConv), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.y2h_train_dweight_splits.argtypes = [C.POINTER(TrainConv)]
@@ -451,6 +473,8 @@ def lib():
     L.y2h_train_reduce_scratch_bytes.restype = C.c_size_t
     L.y2h_train_reduce_scratch_bytes.argtypes = [C.c_long, C.c_int]
     L.y2h_train_bn_stats.argtypes = [C.c_void_p, C.c_long, C.c_int] + [C.c_void_p] * 6
+    L.y2h_train_bn_stats_rate.argtypes = [C.c_void_p, C.c_long, C.c_int] + [C.c_void_p] * 4 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p]
+    L.y2h_train_dropout.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p]
     L.y2h_train_bias_grad.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int] + [C.c_void_p] * 4
     L.y2h_train_bn_deltas.argtypes = [C.c_void_p] * 5 + [C.c_long, C.c_int] + [C.c_void_p] * 4
     L.y2h_train_bn_backward.argtypes = [C.c_void_p] * 7 + [C.c_long, C.c_int, C.c_void_p]
@@ -465,6 +489,10 @@ def lib():
     L.y2h_train_sgd.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_float, C.c_float, C.c_float, C.c_void_p]
     L.y2_train_region_stats.argtypes = [C.POINTER(CNetwork), C.c_int, C.POINTER(RegionStats)]
     L.y2_train_truth_floats.argtypes = [C.POINTER(CNetwork)]
+    L.y2_train_detection_stats.argtypes = [C.POINTER(CNetwork), C.c_int, C.POINTER(DetectionStats)]
+    L.y2h_train_detection_scratch_bytes.restype = C.c_size_t
+    L.y2h_train_detection_scratch_bytes.argtypes = [C.POINTER(TrainDetection)]
+    L.y2h_train_detection_loss.argtypes = [C.POINTER(TrainDetection)] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 4
     L.y2h_train_region_scratch_bytes.restype = C.c_size_t
     L.y2h_train_region_scratch_bytes.argtypes = [C.POINTER(TrainRegion)]
     L.y2h_train_region_loss.argtypes = [C.POINTER(TrainRegion), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7
@@ -693,6 +721,21 @@ def plane_samples(depth, far_m: float, iters: int, seed: int) -> np.ndarray:
     return out[:iters]
 
 
+DENSE_FORWARD, DENSE_DINPUT = 0, 1     # include/y2_hip.h Y2H_DENSE_FORWARD / Y2H_DENSE_DINPUT
+
+
+def train_dense_plan(batch: int, inputs: int, outputs: int, product: int = DENSE_FORWARD, forced: int = 0):
+    """y2h_train_dense_plan: how the trainer cuts the reduction of a dense layer's forward (over inputs) or input-gradient
+    (over outputs) product, on the host (no GPU) -> (ranges, workspace bytes, bounds[ranges + 1])"""
+    g = TrainDense(batch, inputs, outputs)
+    n, ws = C.c_int(0), C.c_size_t(0)
+    if lib().y2h_train_dense_plan(C.byref(g), product, forced, C.byref(n), C.byref(ws), None, 0) != 0:
+        raise Y2Error("y2h_train_dense_plan: bad arguments")
+    bounds = np.zeros(n.value + 1, np.int32)
+    lib().y2h_train_dense_plan(C.byref(g), product, forced, C.byref(n), C.byref(ws), _ptr(bounds), bounds.size)
+    return n.value, ws.value, bounds
+
+
 def connected_f16_plan(rows: int, inputs: int, outputs: int, forced: int = 0):
     """y2h_connected_f16_plan: how fp16 mode cuts a dense layer of `inputs` x `outputs` along K, on the host (no GPU) ->
     (K ranges, bytes of partial-sum workspace, int32 [ranges + 1] range bounds); forced > 0 sets the number of ranges"""
@@ -908,7 +951,7 @@ class Network:
 
     # --- training (include/sr_yolo2.h: train_network_datum and the y2_train_* calls it is written on) ---
     TRAIN_ARRAYS = ("output", "delta", "x", "x_norm", "mean", "variance", "mean_delta", "variance_delta", "weight_updates",
-                    "bias_updates", "scale_updates", "weights", "biases", "scales", "rolling_mean", "rolling_variance")
+                    "bias_updates", "scale_updates", "weights", "biases", "scales", "rolling_mean", "rolling_variance", "rand")
 
     def train_prepare(self) -> None:
         if lib().y2_train_prepare(C.byref(self.net)) != 0:
@@ -1008,10 +1051,11 @@ class Network:
             raise Y2Error("y2_train_sync: " + _check())
 
     def train_pull(self, layer: int, what: str) -> np.ndarray:
-        """one array of the trainer in the reference's order: activations [batch][c][h][w], weights [n][c][size][size]"""
+        """one array of the trainer in the reference's order: activations [batch][c][h][w], weights [n][c][size][size] (a
+        [connected] layer's [outputs][inputs]); "rand" is a [dropout] layer's draws of the last step, [batch][inputs]"""
         l = self.net.layers[layer]
         code = self.TRAIN_ARRAYS.index(what)
-        if code < 4:
+        if code < 4 or what == "rand":
             n = self.net.batch * l.outputs
         elif what in ("weights", "weight_updates"):
             n = l.n * l.c * l.size * l.size
@@ -1023,7 +1067,8 @@ class Network:
         return out[:n]
 
     def truth_floats(self) -> int:
-        """floats of truth per image of a training step: l.truths (150) behind a [region] head, the inputs of a [cost]"""
+        """floats of truth per image of a training step: l.truths behind a [region] head (150) or a [detection] head
+        (side*side*(1+coords+classes)), the inputs of a [cost]"""
         n = lib().y2_train_truth_floats(C.byref(self.net))
         if n < 0:
             raise Y2Error("y2_train_truth_floats: " + _check())       # a network the trainer refuses says so first
@@ -1035,6 +1080,13 @@ class Network:
         if lib().y2_train_region_stats(C.byref(self.net), layer if layer >= 0 else self.net.n - 1, C.byref(st)) != 0:
             raise Y2Error("y2_train_region_stats: " + _check())
         return {k: getattr(st, k) for k, _ in RegionStats._fields_}
+
+    def train_detection_stats(self, layer: int = -1) -> dict:
+        """what the reference prints per forward_detection_layer call, of the last step (NaN averages when count == 0)"""
+        st = DetectionStats()
+        if lib().y2_train_detection_stats(C.byref(self.net), layer if layer >= 0 else self.net.n - 1, C.byref(st)) != 0:
+            raise Y2Error("y2_train_detection_stats: " + _check())
+        return {k: getattr(st, k) for k, _ in DetectionStats._fields_}
 
     def train_free(self) -> None:
         lib().y2_train_free(C.byref(self.net))

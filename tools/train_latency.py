@@ -42,7 +42,7 @@ With --precision bf16x3 or --precision bf16 the step row and the per-product row
 (y2_train_set_precision; the products through y2h_train_conv_*_bf16 with planes 3 or 1), in the same process on the same
 buffers, and reported under "precision": the fp32 rows stay what they are.
 
-usage: train_latency.py [--net darknet19|tiny-yolo-voc|yolo] [--batches 16,64] [--steps 10] [--warmup 3] [--reps 5] [--ref-batch 16] [--no-reference]
+usage: train_latency.py [--net darknet19|tiny-yolo-voc|yolo|tiny-yolo-v1] [--dense 32x12544x1470,...] [--batches 16,64] [--steps 10] [--warmup 3] [--reps 5] [--ref-batch 16] [--no-reference]
                         [--no-products] [--layers 4,18] [--loader] [--precision fp32|bf16x3|bf16]"""
 import argparse
 import ctypes as C
@@ -60,12 +60,19 @@ sys.path.insert(0, ROOT)
 from sr_object_detection_amd import darknet, synth, zoo  # noqa: E402
 
 # name: (size, default batches, default reference batch, reference driver)
-NETS = {"darknet19": (224, "16,64", 16, "train_ref"), "tiny-yolo-voc": (416, "16", 16, "train_det_ref"), "yolo": (416, "8", 8, "train_det_ref")}
+NETS = {"darknet19": (224, "16,64", 16, "train_ref"), "tiny-yolo-voc": (416, "16", 16, "train_det_ref"), "yolo": (416, "8", 8, "train_det_ref"),
+        "tiny-yolo-v1": (448, "32", 32, None)}            # no reference row: tests/native/train_v1_ref.c has no `time` command          # cfg/yolov1/tiny-yolo.cfg: batch=64 subdivisions=2
 # what cfg/yolo.cfg sets for training behind softmax=1
 REGION_TRAINING = "softmax=1\nbias_match=1\nrescore=1\nobject_scale=5\nnoobject_scale=1\nclass_scale=1\ncoord_scale=1\nthresh=.6\njitter=.3"
 
 
+# what cfg/yolov1/tiny-yolo.cfg sets for training
+DETECTION_TRAINING = "object_scale=1\nnoobject_scale=.5\nclass_scale=1\ncoord_scale=5\njitter=.2"
+
+
 def cfg_for(name, size, batch):
+    if name == "tiny-yolo-v1":
+        return zoo.cfg_text(name, size, size, batch).replace("jitter=.2", DETECTION_TRAINING)
     return zoo.cfg_text(name, size, size, batch).replace("softmax=1", REGION_TRAINING)
 
 
@@ -78,6 +85,14 @@ def truth_for(net, batch):
         for i in range(batch):
             for t in range(3):
                 y[i, 5 * t:5 * t + 5] = (.2 + .3 * t, .7 - .2 * t, .1 + .15 * t, .4 - .1 * t, (i + t) % last.classes)
+    elif last.type == darknet.LAYER_TYPES.index("DETECTION"):            # three object cells per image: is-object, class row, box
+        row = 1 + last.classes + 4
+        for i in range(batch):
+            for t in range(3):
+                c0 = ((7 * i + 11 * t) % (last.side * last.side)) * row
+                y[i, c0] = 1
+                y[i, c0 + 1 + (i + t) % last.classes] = 1
+                y[i, c0 + 1 + last.classes:c0 + row] = (.2 + .3 * t, .7 - .2 * t, .1 + .15 * t, .4 - .1 * t)
     else:
         y[np.arange(batch), np.arange(batch) % per] = 1
     return y
@@ -150,6 +165,84 @@ def products(net, timer, reps, only=None, planes=0):
 
 
 HBM_BYTES_PER_S = 6.3e12          # the achievable rate, not the peak
+
+
+COLD_BYTES = 640 << 20           # --cold: rotate over this many bytes of weights, 2.5 times the 256 MB last-level cache
+
+
+def dense_products(batch, inputs, outputs, timer, reps, label="", cold=False):
+    """the three products of one [connected] layer: the dense kernels (y2_train_dense.hip), the byte floor of each (the
+    weight bytes it must move at HBM_BYTES_PER_S: w once for forward and dinput, dw read and written for dweight) and the
+    baseline, the convolution template called at the 1x1 geometry (h = w = size = 1), which a step would otherwise run.
+    cold: every launch takes the next of ceil(COLD_BYTES / weight bytes) copies of w and dw, so that no launch finds its
+    weights in the last-level cache -- as in a step, where the convolutions' tensors pass through it in between"""
+    L = darknet.lib()
+    g = darknet.TrainDense(batch, inputs, outputs)
+    c = darknet.TrainConv(batch, 1, 1, inputs, outputs, 1, 0, 1, 1)
+    nx, ny, nw = batch * inputs, batch * outputs, inputs * outputs
+    copies = -(-COLD_BYTES // (nw * 4)) if cold else 1
+    x = dev_floats(L, nx, synth.uniform(7, nx, -1, 1))
+    dy = dev_floats(L, ny, synth.uniform(70, ny, -1, 1))
+    w0 = synth.uniform(700, nw, -.1, .1)
+    ws_, dws = [dev_floats(L, nw, w0) for _ in range(copies)], [dev_floats(L, nw) for _ in range(copies)]
+    for p in dws:
+        assert L.y2h_memset(p, 0, C.c_size_t(nw * 4), None) == 0
+    assert L.y2h_device_sync() == 0
+    y, dx = dev_floats(L, ny), dev_floats(L, nx)
+    plans = [darknet.train_dense_plan(batch, inputs, outputs, p) for p in (darknet.DENSE_FORWARD, darknet.DENSE_DINPUT)]
+    ws, cws = C.c_void_p(), C.c_void_p()
+    assert L.y2h_malloc(C.byref(ws), max(16, plans[0][1], plans[1][1])) == 0
+    assert L.y2h_malloc(C.byref(cws), L.y2h_train_dweight_ws_bytes(C.byref(c))) == 0
+    turn = [0]
+
+    def nxt(bufs):
+        turn[0] += 1
+        return bufs[turn[0] % copies]
+    calls = {"forward": (lambda: L.y2h_train_dense_forward(C.byref(g), x, nxt(ws_), y, ws, 0, timer.stream),
+                         lambda: L.y2h_train_conv_forward(C.byref(c), x, nxt(ws_), y, timer.stream), nw * 4),
+             "dinput": (lambda: L.y2h_train_dense_dinput(C.byref(g), dy, nxt(ws_), dx, 0, ws, 0, timer.stream),
+                        lambda: L.y2h_train_conv_dinput(C.byref(c), dy, nxt(ws_), dx, timer.stream), nw * 4),
+             "dweight": (lambda: L.y2h_train_dense_dweight(C.byref(g), x, dy, nxt(dws), timer.stream),
+                         lambda: L.y2h_train_conv_dweight(C.byref(c), x, dy, nxt(dws), cws, timer.stream), 2 * nw * 4)}
+    row = {"dense": "%s%d x %d x %d" % (label, batch, inputs, outputs), "weights": "cold, %d copies in turn" % copies if cold else "warm, one copy",
+           "forward_ranges": plans[0][0], "dinput_ranges": plans[1][0], "ws_bytes": int(max(plans[0][1], plans[1][1]))}
+    for name, (new, old, nbytes) in calls.items():
+        times = {"new": [], "old": []}
+        for fn in (new, old):
+            assert fn() == 0, L.y2h_last_error()
+        for _ in range(reps):                              # alternating: both see the same clocks and the same cache state
+            times["new"].append(timer.ms(new))
+            times["old"].append(timer.ms(old))
+        row[name] = {"ms": round(p50(times["new"]), 4), "min_max_ms": [round(min(times["new"]), 4), round(max(times["new"]), 4)],
+                     "byte_floor_ms": round(nbytes / HBM_BYTES_PER_S * 1e3, 4),
+                     "conv_template_1x1_ms": round(p50(times["old"]), 4),
+                     "conv_template_min_max_ms": [round(min(times["old"]), 4), round(max(times["old"]), 4)]}
+    for p in [x, dy, y, dx, ws, cws] + ws_ + dws:
+        L.y2h_free(p)
+    print("    " + json.dumps(row))
+    return row
+
+
+def detection_head_ms(net, timer, reps):
+    """the [detection] head alone (forward, delta, cost, statistics) at the network's shape"""
+    L = darknet.lib()
+    l = net.layer(net.n - 1)
+    g = darknet.TrainDetection(net.batch, l.side, l.n, l.classes, l.softmax, l.sqrt, l.rescore, l.forced, l.coord_scale, l.object_scale,
+                               l.noobject_scale, l.class_scale)
+    n = net.batch * l.outputs
+    x = dev_floats(L, n, synth.uniform(3, n, .1, .9))
+    t = dev_floats(L, net.batch * l.truths, truth_for(net, net.batch))
+    bufs = [dev_floats(L, n) for _ in range(3)] + [dev_floats(L, 16), dev_floats(L, 16)]
+    sc = C.c_void_p()
+    assert L.y2h_malloc(C.byref(sc), L.y2h_train_detection_scratch_bytes(C.byref(g))) == 0
+
+    def fn():
+        return L.y2h_train_detection_loss(C.byref(g), x, t, bufs[0], bufs[1], bufs[2], 0, bufs[3], bufs[4], sc, timer.stream)
+    assert fn() == 0, L.y2h_last_error()
+    ms = p50([timer.ms(fn) for _ in range(reps)])
+    for p in [x, t, sc] + bufs:
+        L.y2h_free(p)
+    return round(ms, 4)
 
 
 def measure_loader(net, batch, timer, steps, warmup, reps, label, table, pixels, touched, frame_bytes, launch, load):
@@ -284,8 +377,8 @@ def cls_loader_row(net, batch, timer, steps, warmup, reps):
 
 
 def reference_step(tmp, wts, name, size, batch, steps=2):
-    driver = os.path.join(ROOT, "oracle", "_ref", NETS[name][3])
-    if not os.path.exists(driver):
+    driver = NETS[name][3] and os.path.join(ROOT, "oracle", "_ref", NETS[name][3])
+    if not driver or not os.path.exists(driver):
         return None
     cfg = os.path.join(tmp, "ref_b%d.cfg" % batch)
     open(cfg, "w").write(cfg_for(name, size, batch))
@@ -307,10 +400,20 @@ def main():
     ap.add_argument("--layers", default=None, help="only these layers' products, e.g. 4,18 (with --steps 0 --warmup 0 "
                     "--no-reference: the few launches a counter run wants, `rocprofv3 --pmc ... -- python tools/train_latency.py ...`)")
     ap.add_argument("--precision", default="fp32", choices=darknet.TRAIN_PRECISIONS, help="measure the step and the products in this mode as well")
+    ap.add_argument("--dense", default=None, help="only the three dense products at these shapes, batch x inputs x outputs, "
+                    "e.g. 32x12544x1470,64x4096x1470: the dense kernels, their byte floors and the convolution template at 1x1")
+    ap.add_argument("--cold", action="store_true", help="with --dense: rotate over copies of the weights so that no launch finds them in the last-level cache")
     ap.add_argument("--loader", action="store_true", help="add the loader's row: the classifier loader for darknet19, the detection loader for a detector")
     a = ap.parse_args()
     SIZE, batches, ref_batch = NETS[a.net][:3]
     L = darknet.lib()
+    if a.dense:
+        stream = C.c_void_p()
+        assert L.y2h_stream_create(C.byref(stream)) == 0
+        print("dense products, device %s" % darknet.device_name())
+        print(json.dumps({"dense": [dense_products(*[int(v) for v in shape.split("x")], Timer(stream), max(a.reps, 11), "", a.cold)
+                                    for shape in a.dense.split(",")]}))
+        return
     tmp = tempfile.mkdtemp()
     wts = os.path.join(tmp, "net.weights")
     synth.write_weights(wts, zoo.resolve(a.net, SIZE), 41, 1.0)
@@ -334,7 +437,16 @@ def main():
         if ms:
             res.update(step_p50_ms=round(p50(ms), 3), step_max_ms=round(max(ms), 3),
                        images_per_s=round(batch / (p50(ms) * 1e-3), 1), first_loss=losses[0], last_loss=losses[-1])
-        if ms and a.net != "darknet19":
+        if ms and a.net == "tiny-yolo-v1":
+            res["detection"] = {k: (None if v != v else v) for k, v in net.train_detection_stats().items()}
+            res["head_ms"] = detection_head_ms(net, timer, max(a.reps, 11))
+            res["head_share_of_step"] = round(res["head_ms"] / res["step_p50_ms"], 4)
+            if not a.no_products:
+                dense = [dense_products(batch, net.layer(i).inputs, net.layer(i).outputs, timer, max(a.reps, 11), "layer %d: " % i)
+                         for i in range(net.n) if net.layer(i).type == darknet.LAYER_TYPES.index("CONNECTED")]
+                res["dense"] = dense
+                res["dense_share_of_step"] = round(sum(d[k]["ms"] for d in dense for k in ("forward", "dinput", "dweight")) / res["step_p50_ms"], 4)
+        elif ms and a.net != "darknet19":
             res["region"] = {k: (None if v != v else v) for k, v in net.train_region_stats().items()}
         print("  " + json.dumps(res))
         only = None if a.layers is None else {int(v) for v in a.layers.split(",")}
