@@ -82,6 +82,7 @@ void y2_arena_layout(network *net)
         y2_ldev *d = ld_of(l);
         const size_t wbytes = (size_t)l->n * l->size * l->size * l->c * sizeof(float);
         const int w_half = y2_half_weights(net, i);
+        const y2_conv_form *form;
         if (!owns_arena(l)) continue;
         if (l->type == BATCHNORM) { y2_bn_slots(&off, l->c, &d->off_mean, &d->off_scale, &d->off_rinv); continue; }
         if (is_recurrent(l)) { off = y2_rec_layout(d, l, off); continue; }
@@ -90,9 +91,9 @@ void y2_arena_layout(network *net)
             d->off_bias = off; off = align_up(off + (size_t)l->outputs * sizeof(float), 64);
             continue;
         }
-        /* a Winograd layer keeps U[16][n][c] = G g G^T in place of its nine packed taps, a split one U as three bf16 planes,
-         * a stationary one U in register order */
-        d->off_w_packed = off; off = align_up(off + (d->winos ? y2_winos_u_floats(l->n) * sizeof(float) : d->winox ? y2_split_bytes(y2_split_rows_pad(l->n), l->c) : d->wino ? (size_t)16 * l->n * l->c * sizeof(float) : w_half ? wbytes / 2 : wbytes), 256);
+        /* a Winograd layer keeps its form's U in place of its nine packed taps (y2_conv_forms) */
+        form = &y2_conv_forms[d->form];
+        d->off_w_packed = off; off = align_up(off + (form->slot_bytes ? form->slot_bytes(l) : w_half ? wbytes / 2 : wbytes), 256);
         if (d->has_w_ref) { d->off_w_ref = off; off = align_up(off + wbytes, 256); }
         d->off_bias = off; off = align_up(off + l->n * sizeof(float), 64);
         if (w_half) {
@@ -115,6 +116,7 @@ static uint64_t arena_signature(const network *net)
     for (i = 0; i < net->n; ++i) {
         const layer *l = &net->layers[i];
         const y2_ldev *d = ld_of(l);
+        uint64_t sig_form;
         if (!owns_arena(l)) continue;
         if (is_recurrent(l)) {
             for (k = 0; k < 3; ++k) { SIG_MIX(i); SIG_MIX(d->rd[k].off_w); SIG_MIX(d->rd[k].off_bias); SIG_MIX(d->rd[k].bn ? d->rd[k].off_rinv + 1 : 0); }
@@ -123,9 +125,8 @@ static uint64_t arena_signature(const network *net)
         SIG_MIX(i); SIG_MIX(d->off_w_packed); SIG_MIX(d->has_w_ref ? d->off_w_ref + 1 : 0); SIG_MIX(d->off_bias);
         SIG_MIX(d->uses_mfma); SIG_MIX(y2_half_weights(net, i));
         SIG_MIX(l->batch_normalize ? d->off_rinv + 1 : 0);
-        if (d->wino) SIG_MIX(0x57494e4f);      /* the filter slot holds U, not the packed taps (mixed only where it does) */
-        if (d->winox) SIG_MIX(0x57494e58);     /* ... or the split U: three bf16 planes (y2_split_rule.h) */
-        if (d->winos) SIG_MIX(0x57494e53);     /* ... or U in the stationary kernel's register order */
+        sig_form = y2_conv_forms[d->form].sig;
+        if (sig_form) SIG_MIX(sig_form);       /* the filter slot holds a form's U, not the packed taps (mixed only where it does) */
     }
     SIG_MIX(e->strict); SIG_MIX(e->half); SIG_MIX(e->arena_need);
 #undef SIG_MIX
@@ -222,9 +223,10 @@ static void pack_filters(float *wp, const network *net, int i, int w_half)
 /* the filters of a Winograd layer: U[g][n][c] = component g of G g G^T of filter n, channel c (y2_wino_filter: evaluated
  * in double, rounded once), each component in the [n][c] layout the 1x1 matrix-core tiles read.  Reference layout
  * [n][c][3][3] (im2col.c:24-27). */
-static void pack_wino(float *up, const layer *l)
+static void pack_wino(void *slot, const layer *l)
 {
     const size_t comp = (size_t)l->n * l->c;
+    float *up = slot;
     int co, ci, g;
     for (co = 0; co < l->n; ++co)
         for (ci = 0; ci < l->c; ++ci) {
@@ -237,8 +239,9 @@ static void pack_wino(float *up, const layer *l)
 /* the filters of a stationary-Winograd layer: the same U = G g G^T (y2_wino_filter), each value where the kernel's wave
  * (filter tile, component row) and lane load it as part of one 16-byte register (y2_winos_u_index); filters past n in the
  * last 32-filter tile are zero */
-static void pack_winos(float *up, const layer *l)
+static void pack_winos(void *slot, const layer *l)
 {
+    float *up = slot;
     int co, ci, g;
     memset(up, 0, y2_winos_u_floats(l->n) * sizeof(float));
     for (co = 0; co < l->n; ++co)
@@ -249,16 +252,30 @@ static void pack_winos(float *up, const layer *l)
         }
 }
 
+/* the filters of a split-Winograd layer: U as three bf16 planes (y2_split_rule.h), from the reference layout [n][c][3][3] */
+static void pack_winox(void *slot, const layer *l) { y2_split_pack_u(slot, l->weights, l->n, l->c); }
+
+static size_t wino_slot_bytes(const layer *l) { return (size_t)16 * l->n * l->c * sizeof(float); }
+static size_t winox_slot_bytes(const layer *l) { return y2_split_bytes(y2_split_rows_pad(l->n), l->c); }
+static size_t winos_slot_bytes(const layer *l) { return y2_winos_u_floats(l->n) * sizeof(float); }
+
+/* the signature constants are part of the signature's format (arena_signature) */
+const y2_conv_form y2_conv_forms[Y2_FORM_COUNT] = {
+    [Y2_FORM_DIRECT] = { 0, NULL, NULL, y2h_conv_workspace_bytes, NULL },
+    [Y2_FORM_WINO] = { 0x57494e4f, wino_slot_bytes, pack_wino, y2h_wino_workspace_bytes, y2h_conv_wino_forward },          /* V and M */
+    [Y2_FORM_WINOX] = { 0x57494e58, winox_slot_bytes, pack_winox, y2h_wino_split_workspace_bytes, y2h_conv_winox_forward },
+    [Y2_FORM_WINOS] = { 0x57494e53, winos_slot_bytes, pack_winos, NULL, y2h_conv_winos_forward },
+};
+
 /* a [convolutional] or [connected] layer: filters, the reference-layout copy where the layer needs one, constants */
 static void pack_dense(unsigned char *host, const network *net, int i)
 {
     const layer *l = &net->layers[i];
     const y2_ldev *d = ld_of(l);
+    const y2_conv_form *form = &y2_conv_forms[d->form];
     const int K = l->size * l->size * l->c, w_half = y2_half_weights(net, i);
     int co, f, q;
-    if (d->winos) pack_winos((float *)(host + d->off_w_packed), l);
-    else if (d->winox) y2_split_pack_u((uint16_t *)(host + d->off_w_packed), l->weights, l->n, l->c);      /* reference layout [n][c][3][3] */
-    else if (d->wino) pack_wino((float *)(host + d->off_w_packed), l);
+    if (form->pack) form->pack(host + d->off_w_packed, l);
     else pack_filters((float *)(host + d->off_w_packed), net, i, w_half);
     if (w_half) {
         /* folded batch-norm for the fp16 kernels: y = act(acc*alpha + beta), constants evaluated in double */

@@ -261,6 +261,7 @@ static int forward_convolutional(network *net, int i, const float *x, int ldx)
     y2_engine *e = y2_engine_of(net);
     const layer *l = &net->layers[i];
     const y2_ldev *d = ld_of(l);
+    const y2_conv_form *form = &y2_conv_forms[d->form];
     y2h_conv c;
     if (l->xnor) {
         /* the input view already points at d_bin: binarize the producer's activations into it first */
@@ -270,9 +271,7 @@ static int forward_convolutional(network *net, int i, const float *x, int ldx)
         HIP_OR_ERR(y2h_binarize(px, pld, d->d_bin, (long)l->batch * l->h * l->w, l->c, e->stream));
     }
     y2_conv_desc(net, i, &c, x, ldx);
-    if (d->winos) HIP_OR_ERR(y2h_conv_winos_forward(&c, e->stream));     /* w_packed holds U in register order (plan_winos) */
-    else if (d->winox) HIP_OR_ERR(y2h_conv_winox_forward(&c, e->stream)); /* w_packed holds the split U (plan_winox, y2_arena.c) */
-    else if (d->wino) HIP_OR_ERR(y2h_conv_wino_forward(&c, e->stream));  /* w_packed holds U (plan_wino, y2_arena.c) */
+    if (form->forward) HIP_OR_ERR(form->forward(&c, e->stream));       /* w_packed holds the form's U (y2_arena.c) */
     else HIP_OR_ERR(y2h_conv_forward(&c, e->strict, e->stream));
     return y2_activate_after(e, l->activation, d->out, d->out_ld, (long)l->batch * l->out_h * l->out_w, l->out_c);
 }

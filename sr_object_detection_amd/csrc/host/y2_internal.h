@@ -23,11 +23,8 @@ typedef struct y2_ldev {
     size_t off_w_packed, off_w_ref, off_bias, off_mean, off_scale, off_rinv;
     int has_w_ref;
     int uses_mfma;
-    int wino;                  /* conv: runs as Winograd F(2x2,3x3) (y2_plan.c plan_wino); off_w_packed then holds U[16][n][c] */
-    int winox;                 /* conv: runs as Winograd with the split GEMM (y2_plan.c plan_winox); off_w_packed then holds
-                                  the split U, three bf16 planes (y2_split_rule.h) */
-    int winos;                 /* conv: runs as the fused stationary Winograd kernel (y2_plan.c plan_winos); off_w_packed then
-                                  holds U in its register order (y2_winos_rule.h) */
+    int form;                  /* conv: the Y2_FORM_* it runs in (y2_plan.c plan_conv_forms); what off_w_packed holds, the scratch and
+                                  the entry point that go with a form are its row of y2_conv_forms */
     int fused_pool;           /* conv: the following 2x2/2 maxpool runs in this conv's epilogue */
     int fused_into;            /* maxpool: index of the conv that computes it, or -1 */
     int out_half;              /* this layer's activations are IEEE half (fp16 mode), out_ld counts halves */
@@ -66,6 +63,22 @@ typedef struct y2_ldev {
     float *d_zf;               /* gru: z and f of the current step, [2][B][outputs] */
     float *d_tmp;              /* matrix-core step form: the step's dense values, [B][2*outputs] */
 } y2_ldev;
+
+/* How a convolution runs (y2_ldev.form, decided by y2_conv_form_of): the direct kernels of y2h_conv_forward, Winograd
+ * F(2x2,3x3) as three launches with U[16][n][c] in the filter slot, the same with the GEMM split into three bf16 planes
+ * (y2_split_rule.h), or the fused stationary Winograd kernel with U in its register order (y2_winos_rule.h). */
+enum { Y2_FORM_DIRECT = 0, Y2_FORM_WINO, Y2_FORM_WINOX, Y2_FORM_WINOS, Y2_FORM_COUNT };
+/* What depends on the form, one row per form (y2_arena.c).  The direct row holds its workspace query alone: its filter
+ * slot depends on the storage mode, its packer on the network and its entry point on the strict flag, so the sites that
+ * find a NULL there spell those out. */
+typedef struct y2_conv_form {
+    uint64_t sig;                                        /* mixed into the arena signature; 0: nothing is mixed */
+    size_t (*slot_bytes)(const layer *l);                /* what the form keeps at off_w_packed ... */
+    void (*pack)(void *slot, const layer *l);            /* ... and how the host weights get there */
+    size_t (*workspace_bytes)(const y2h_conv *c);        /* scratch in the shared workspace; NULL: none */
+    int (*forward)(const y2h_conv *c, y2h_stream s);
+} y2_conv_form;
+extern const y2_conv_form y2_conv_forms[Y2_FORM_COUNT];
 
 /* how a recurrent layer's dense products run (y2_rec.c rec_form) */
 enum { Y2_REC_REF = 0, Y2_REC_SKINNY = 1, Y2_REC_MFMA = 2 };
@@ -246,6 +259,7 @@ int y2_half_weights(const network *net, int i);
 void y2_input_form(const network *net, y2_in_form *f);
 void y2_input_view(const network *net, int i, const float **x, int *ldx);
 void y2_conv_desc(const network *net, int i, y2h_conv *c, const float *x, int ldx);
+int y2_conv_form_of(const y2h_conv *c, int fused_pool, char *name, size_t name_len);   /* host arithmetic only */
 
 /* weight arena (y2_arena.c) */
 void y2_bn_slots(size_t *off, int n, size_t *mean, size_t *scale, size_t *rinv);

@@ -32,9 +32,7 @@ void y2_free_plan(network *net)
         d->placed_in = -1; d->alias_of = -1; d->copy_mask = 0;
         d->fused_pool = 0; d->fused_into = -1;
         d->out_half = 0;
-        d->wino = 0;
-        d->winox = 0;
-        d->winos = 0;
+        d->form = Y2_FORM_DIRECT;
         d->tile_bm = d->tile_bn = d->ksplit = 0;
         d->conn_ranges = 0;
     }
@@ -258,6 +256,7 @@ static int plan_workspace(network *net)
     int i;
     for (i = 0; i < net->n; ++i) {
         y2h_conv c;
+        const y2_conv_form *f;
         const float *x; int ldx;
         size_t b;
         if ((net->layers[i].type != CONVOLUTIONAL && net->layers[i].type != CONNECTED) || e->strict) continue;
@@ -268,8 +267,8 @@ static int plan_workspace(network *net)
         }
         y2_input_view(net, i, &x, &ldx);
         conv_query(net, i, &c, x, ldx);
-        b = ld_of(&net->layers[i])->winox ? y2h_wino_split_workspace_bytes(&c) : ld_of(&net->layers[i])->wino ? y2h_wino_workspace_bytes(&c) : y2h_conv_workspace_bytes(&c);      /* Winograd: V and M */
-        if (ld_of(&net->layers[i])->winos) b = 0;                                                             /* stationary Winograd: none */
+        f = &y2_conv_forms[ld_of(&net->layers[i])->form];
+        b = f->workspace_bytes ? f->workspace_bytes(&c) : 0;
         if (b > need) need = b;
     }
     return grow_workspace(e, need);
@@ -285,6 +284,12 @@ static tune_entry g_tuned[256];
 static int g_ntuned = 0;
 static pthread_mutex_t g_tuned_mu = PTHREAD_MUTEX_INITIALIZER;    /* networks / Detectors may be built from several threads */
 
+/* the layers autotuning looks at: the direct matrix-core convolutions (a Winograd layer has no direct tile to measure) */
+static int has_tile_to_measure(const layer *l)
+{
+    return l->type == CONVOLUTIONAL && ld_of(l)->uses_mfma && !l->xnor && ld_of(l)->form == Y2_FORM_DIRECT;
+}
+
 /* Candidates are timed INSIDE whole forward passes (per-layer HIP events, as y2_layer_times_ms reads them): timed in
  * isolation, back to back, a layer finds its own weights in the Infinity Cache and small tiles look better than they are
  * in the real sequence, where the 204 MB of yolo.cfg weights stream from HBM once per forward. */
@@ -296,10 +301,9 @@ static int autotune_layers(network *net)
     size_t need = 0;
     for (i = 0; i < net->n; ++i) {          /* scratch for the largest K-split any candidate may ask for */
         const layer *l = &net->layers[i];
-        y2_ldev *d = ld_of(l);
         y2h_conv c;
         const float *x; int ldx, n, bm[64], bn[64], ks[64];
-        if (l->type != CONVOLUTIONAL || !d->uses_mfma || l->xnor || d->wino || d->winox || d->winos) continue;      /* (a Winograd layer has no direct tile to measure) */
+        if (!has_tile_to_measure(l)) continue;
         y2_input_view(net, i, &x, &ldx);
         y2_conv_desc(net, i, &c, x, ldx);
         n = y2h_conv_candidates(&c, bm, bn, ks, 64);
@@ -317,7 +321,7 @@ static int autotune_layers(network *net)
         y2h_conv c;
         const float *x; int ldx, n, hit = 0, bm[64], bn[64], ks[64], best = 0;
         float best_ms = 0.f;
-        if (l->type != CONVOLUTIONAL || !d->uses_mfma || l->xnor || d->wino || d->winox || d->winos) continue;      /* (a Winograd layer has no direct tile to measure) */
+        if (!has_tile_to_measure(l)) continue;
         y2_input_view(net, i, &x, &ldx);
         y2_conv_desc(net, i, &c, x, ldx);
         pthread_mutex_lock(&g_tuned_mu);
@@ -931,10 +935,27 @@ static int plan_conv_kernels(network *net)
     return 0;
 }
 
-/* which of them run as Winograd with the split GEMM (the rule: include/y2_split_rule.h, asked through y2h_wino_split_plan).
- * Such a layer keeps the split U in the arena in place of its packed filters, is named conv_winox_f32_<bm>x<bn>x<bk> and
- * takes its V / M scratch from the shared workspace.  Runs ahead of plan_wino, which leaves its layers alone. */
-static int plan_winox(network *net)
+/* The form a convolution runs in, and for a Winograd form the name of its kernel.  The precedence is stated here and
+ * nowhere else: the split GEMM (the rule: include/y2_split_rule.h, asked through y2h_wino_split_plan) beats fp32 Winograd
+ * (y2_wino_rule.h, y2h_wino_plan), which beats the fused stationary kernel (y2_winos_rule.h, y2h_winos_plan); the first
+ * whose rule takes the descriptor has it, and a descriptor none takes stays direct, its name untouched.  Host arithmetic
+ * only. */
+int y2_conv_form_of(const y2h_conv *c, int fused_pool, char *name, size_t name_len)
+{
+    const char *pool = fused_pool ? "+maxpool2" : "";
+    y2h_wino_split x;
+    y2h_wino w;
+    y2h_winos s;
+    if (y2h_wino_split_plan(c, &x) == 0 && x.take) { snprintf(name, name_len, "conv_winox_f32_%dx%dx%d%s", x.bm, x.bn, x.bk, pool); return Y2_FORM_WINOX; }
+    if (y2h_wino_plan(c, &w) == 0 && w.take) { snprintf(name, name_len, "conv_wino_f32_%dx%dx32%s", w.bm, w.bn, pool); return Y2_FORM_WINO; }
+    if (y2h_winos_plan(c, &s) == 0 && s.take) { snprintf(name, name_len, "conv_winos_f32_c%d%s", s.form, pool); return Y2_FORM_WINOS; }
+    return Y2_FORM_DIRECT;
+}
+
+/* which of the fp32 matrix-core convolutions run as a Winograd form instead (y2_conv_form_of).  Such a layer keeps its
+ * form's U in the arena in place of its packed filters and is named after the form; its launches sit between the layer's
+ * two timing events like any layer's.  Never in strict or half mode. */
+static int plan_conv_forms(network *net)
 {
     y2_engine *e = y2_engine_of(net);
     int i;
@@ -943,66 +964,12 @@ static int plan_winox(network *net)
         layer *l = &net->layers[i];
         y2_ldev *d = ld_of(l);
         y2h_conv c;
-        y2h_wino_split w;
         const float *x; int ldx;
         if (l->type != CONVOLUTIONAL || !d->uses_mfma || l->xnor) continue;
         y2_input_view(net, i, &x, &ldx);
         conv_query(net, i, &c, x, ldx);
-        if (y2h_wino_split_plan(&c, &w) != 0 || !w.take) continue;
-        d->winox = 1;
-        snprintf(d->kname, sizeof d->kname, "conv_winox_f32_%dx%dx%d%s", w.bm, w.bn, w.bk, d->fused_pool ? "+maxpool2" : "");
-        d->kernel = d->kname;
-    }
-    return 0;
-}
-
-/* which of the fp32 matrix-core 3x3 convolutions run as Winograd F(2x2,3x3) instead (the rule: include/y2_wino_rule.h,
- * asked through y2h_wino_plan).  Such a layer keeps U = G g G^T in the arena in place of its packed filters, is named
- * conv_wino_f32_<bm>x<bn>x32 after its batched GEMM's tile, and takes its V / M scratch from the shared workspace.  Its
- * three launches sit between the layer's two timing events like any layer's. */
-static int plan_wino(network *net)
-{
-    y2_engine *e = y2_engine_of(net);
-    int i;
-    if (e->strict || e->half) return 0;
-    for (i = 0; i < net->n; ++i) {
-        layer *l = &net->layers[i];
-        y2_ldev *d = ld_of(l);
-        y2h_conv c;
-        y2h_wino w;
-        const float *x; int ldx;
-        if (l->type != CONVOLUTIONAL || !d->uses_mfma || l->xnor || d->winox) continue;
-        y2_input_view(net, i, &x, &ldx);
-        conv_query(net, i, &c, x, ldx);
-        if (y2h_wino_plan(&c, &w) != 0 || !w.take) continue;
-        d->wino = 1;
-        snprintf(d->kname, sizeof d->kname, "conv_wino_f32_%dx%dx32%s", w.bm, w.bn, d->fused_pool ? "+maxpool2" : "");
-        d->kernel = d->kname;
-    }
-    return 0;
-}
-
-/* which of the shallow fp32 3x3 convolutions run as the fused stationary Winograd kernel (the rule: include/y2_winos_rule.h,
- * asked through y2h_winos_plan).  Such a layer keeps U in the kernel's register order in the arena in place of its packed
- * filters, is named conv_winos_f32_c<channels> and needs no workspace.  Gated like plan_wino, whose layers it leaves alone. */
-static int plan_winos(network *net)
-{
-    y2_engine *e = y2_engine_of(net);
-    int i;
-    if (e->strict || e->half) return 0;
-    for (i = 0; i < net->n; ++i) {
-        layer *l = &net->layers[i];
-        y2_ldev *d = ld_of(l);
-        y2h_conv c;
-        y2h_winos w;
-        const float *x; int ldx;
-        if (l->type != CONVOLUTIONAL || !d->uses_mfma || l->xnor || d->wino || d->winox) continue;
-        y2_input_view(net, i, &x, &ldx);
-        conv_query(net, i, &c, x, ldx);
-        if (y2h_winos_plan(&c, &w) != 0 || !w.take) continue;
-        d->winos = 1;
-        snprintf(d->kname, sizeof d->kname, "conv_winos_f32_c%d%s", w.form, d->fused_pool ? "+maxpool2" : "");
-        d->kernel = d->kname;
+        d->form = y2_conv_form_of(&c, d->fused_pool, d->kname, sizeof d->kname);
+        if (d->form != Y2_FORM_DIRECT) d->kernel = d->kname;
     }
     return 0;
 }
@@ -1021,7 +988,9 @@ static int plan_timing_events(network *net)
 }
 
 /* Pass order is part of the plan: fusion must see placement, the buffers must see fusion and fp16 storage, the kernel
- * choice reads the buffers' alignment, and the arena layout must see the kernel choice. */
+ * choice reads the buffers' alignment.  plan_conv_forms follows plan_conv_kernels because it chooses among the layers that
+ * pass put on the matrix cores, with the fused pool as that pass left it, and overwrites the name it gave; it precedes
+ * y2_arena_layout because the form decides what the filter slot holds.  The arena layout must see both. */
 int y2_engine_build(network *net)
 {
     y2_engine *e = y2_engine_of(net);
@@ -1029,7 +998,7 @@ int y2_engine_build(network *net)
     y2_free_plan(net);
     if (plan_batches(net) != 0 || plan_routes(net) != 0 || plan_pool_fusion(net) != 0 || plan_half(net) != 0 ||
         plan_activations(net) != 0 || plan_input_copies(net) != 0 || plan_input(net) != 0 || plan_output(net) != 0 ||
-        plan_head_constants(net) != 0 || plan_conv_kernels(net) != 0 || plan_winox(net) != 0 || plan_wino(net) != 0 || plan_winos(net) != 0) return -1;
+        plan_head_constants(net) != 0 || plan_conv_kernels(net) != 0 || plan_conv_forms(net) != 0) return -1;
     y2_arena_layout(net);
     /* the arena commit: signature, reallocation, the refusal of a replicated rank whose layout changed */
     if (plan_workspace(net) != 0 || y2_arena_commit(net) != 0 || plan_timing_events(net) != 0) return -1;

@@ -1191,33 +1191,24 @@ struct Variant {
     void (*fn_wg)(ConvK);  // the same tile as the batched GEMM of the Winograd path (1x1 tiles the rule may pick)
 };
 
-#define VAR(BM, BN, BK, KS, WM, WN)                                                             \
+// One tile: its name, its plain kernel, its LDS and threads, then -- where instantiated -- fn_xo, fn_sk and fn_wg in that order
+// (members left out are nullptr).  The entries' order matters: pick_variant breaks ties by walk order.
+#define VAR(BM, BN, BK, KS, WM, WN, ...)                                                        \
     { "conv_mfma_f32_" #BM "x" #BN "x" #BK "_k" #KS, BM, BN, BK, KS, conv_mfma_kernel<BM, BN, BK, KS, WM, WN>, \
-      (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float) + (WM * WN == 8 ? (size_t)8 * 16 * 36 * sizeof(float) : 0), WM * WN * 64, nullptr, nullptr }
-#define VARSK(BM, BN, BK, KS, WM, WN)                                                           \
-    { "conv_mfma_f32_" #BM "x" #BN "x" #BK "_k" #KS, BM, BN, BK, KS, conv_mfma_kernel<BM, BN, BK, KS, WM, WN>, \
-      (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float) + (WM * WN == 8 ? (size_t)8 * 16 * 36 * sizeof(float) : 0), WM * WN * 64, \
-      nullptr, conv_mfma_kernel<BM, BN, BK, KS, WM, WN, false, true> }
-#define VARXO(BM, BN, BK, KS, WM, WN)                                                           \
-    { "conv_mfma_f32_" #BM "x" #BN "x" #BK "_k" #KS, BM, BN, BK, KS, conv_mfma_kernel<BM, BN, BK, KS, WM, WN>, \
-      (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float) + (WM * WN == 8 ? (size_t)8 * 16 * 36 * sizeof(float) : 0), WM * WN * 64, \
-      conv_mfma_kernel<BM, BN, BK, KS, WM, WN, true>, nullptr }
-
-#define VARWG(BM, BN, BK, KS, WM, WN)                                                           \
-    { "conv_mfma_f32_" #BM "x" #BN "x" #BK "_k" #KS, BM, BN, BK, KS, conv_mfma_kernel<BM, BN, BK, KS, WM, WN>, \
-      (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float) + (WM * WN == 8 ? (size_t)8 * 16 * 36 * sizeof(float) : 0), WM * WN * 64, \
-      conv_mfma_kernel<BM, BN, BK, KS, WM, WN, true>, nullptr, conv_mfma_kernel<BM, BN, BK, KS, WM, WN, false, false, true> }
+      (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float) + (WM * WN == 8 ? (size_t)8 * 16 * 36 * sizeof(float) : 0), WM * WN * 64, __VA_ARGS__ }
 
 static Variant g_variants[] = {
     // 8 waves (2 per SIMD), ONE workgroup per CU: the co-resident partner wave that hides LDS/barrier
     // stalls comes from the same workgroup, so a CU never ends up with a lone half-speed pair in the tail
-    VARSK(192, 256, 32, 3, 2, 4), VARWG(192, 256, 32, 1, 2, 4),
+    VAR(192, 256, 32, 3, 2, 4, nullptr, conv_mfma_kernel<192, 256, 32, 3, 2, 4, false, true>),
+    VAR(192, 256, 32, 1, 2, 4, conv_mfma_kernel<192, 256, 32, 1, 2, 4, true>, nullptr, conv_mfma_kernel<192, 256, 32, 1, 2, 4, false, false, true>),
     VAR(256, 128, 32, 3, 4, 2), VAR(256, 128, 32, 1, 4, 2),
     VAR(256, 64, 32, 3, 8, 1),  VAR(256, 64, 32, 1, 8, 1),
     // 4 waves, two workgroups per CU
-    VARSK(128, 128, 32, 3, 2, 2), VARWG(128, 128, 32, 1, 2, 2),
+    VAR(128, 128, 32, 3, 2, 2, nullptr, conv_mfma_kernel<128, 128, 32, 3, 2, 2, false, true>),
+    VAR(128, 128, 32, 1, 2, 2, conv_mfma_kernel<128, 128, 32, 1, 2, 2, true>, nullptr, conv_mfma_kernel<128, 128, 32, 1, 2, 2, false, false, true>),
     VAR(128, 64, 32, 3, 2, 2),  VAR(128, 64, 32, 1, 2, 2),
-    VAR(64, 64, 32, 3, 2, 2),   VARXO(64, 64, 32, 1, 2, 2),
+    VAR(64, 64, 32, 3, 2, 2),   VAR(64, 64, 32, 1, 2, 2, conv_mfma_kernel<64, 64, 32, 1, 2, 2, true>),
     VAR(128, 32, 32, 3, 4, 1),  VAR(128, 32, 32, 1, 4, 1),
     VAR(128, 128, 16, 3, 2, 2), VAR(128, 128, 16, 1, 2, 2),
     VAR(128, 64, 16, 3, 2, 2),  VAR(128, 64, 16, 1, 2, 2),
@@ -1227,6 +1218,7 @@ static Variant g_variants[] = {
     VAR(128, 128, 32, 5, 2, 2), VAR(64, 64, 32, 5, 2, 2),
     VAR(128, 128, 16, 5, 2, 2), VAR(64, 64, 16, 5, 2, 2),
 };
+#undef VAR
 
 static unsigned long g_xcd_order_launches = 0;
 extern "C" unsigned long y2h_xcd_order_launches(void) { return g_xcd_order_launches; }
@@ -1860,9 +1852,7 @@ static int direct_launch(const y2h_conv *d, ConvK &a, y2h_stream s)
 
 extern "C" int y2h_conv_forward(const y2h_conv *d, int strict, y2h_stream s)
 {
-    if (!d || !d->x || !d->y || !d->bias) return Y2H_EINVAL;
-    if (d->batch <= 0 || d->h <= 0 || d->w <= 0 || d->c <= 0 || d->n <= 0 || d->ldx < d->c || d->ldy < d->n) return Y2H_EINVAL;
-    if (d->batch_normalize && (!d->mean || !d->rinv || !d->scale)) return Y2H_EINVAL;
+    if (!conv_args_ok(d)) return Y2H_EINVAL;
     if (d->out_h != (d->h + 2 * d->pad - d->size) / d->stride + 1) return Y2H_EINVAL;
     if (d->out_w != (d->w + 2 * d->pad - d->size) / d->stride + 1) return Y2H_EINVAL;
 
@@ -1902,9 +1892,7 @@ extern "C" unsigned long y2h_wino_launches(void) { return g_wino_launches; }
 
 extern "C" int y2h_conv_wino_forward(const y2h_conv *d, y2h_stream s)
 {
-    if (!d || !d->x || !d->y || !d->bias || !d->w_packed) return Y2H_EINVAL;
-    if (d->batch <= 0 || d->h <= 0 || d->w <= 0 || d->c <= 0 || d->n <= 0 || d->ldx < d->c || d->ldy < d->n) return Y2H_EINVAL;
-    if (d->batch_normalize && (!d->mean || !d->rinv || !d->scale)) return Y2H_EINVAL;
+    if (!conv_args_ok(d) || !d->w_packed) return Y2H_EINVAL;
     y2h_wino w;
     if (y2h_wino_plan(d, &w) != Y2H_OK || !w.take) return Y2H_EINVAL;
     if (!d->ws || d->ws_bytes < w.v_bytes + w.m_bytes || ((uintptr_t)d->ws % 16) != 0) return Y2H_EINVAL;
@@ -1945,9 +1933,7 @@ extern "C" int y2h_conv_wino_forward(const y2h_conv *d, y2h_stream s)
 // then the fp32 form's own output pass.  d->w_packed holds the split U (y2_split_pack_u).
 extern "C" int y2h_conv_winox_forward(const y2h_conv *d, y2h_stream s)
 {
-    if (!d || !d->x || !d->y || !d->bias || !d->w_packed) return Y2H_EINVAL;
-    if (d->batch <= 0 || d->h <= 0 || d->w <= 0 || d->c <= 0 || d->n <= 0 || d->ldx < d->c || d->ldy < d->n) return Y2H_EINVAL;
-    if (d->batch_normalize && (!d->mean || !d->rinv || !d->scale)) return Y2H_EINVAL;
+    if (!conv_args_ok(d) || !d->w_packed) return Y2H_EINVAL;
     y2h_wino_split w;
     if (y2h_wino_split_plan(d, &w) != Y2H_OK || !w.take) return Y2H_EINVAL;
     if (!d->ws || d->ws_bytes < w.v_bytes + w.m_bytes || ((uintptr_t)d->ws % 16) != 0 || w.v_bytes % 16 != 0) return Y2H_EINVAL;

@@ -273,6 +273,16 @@ int y2_f16_launch(const ConvPlan &p, const y2h_conv *d, ConvK &a, y2h_stream s);
 bool y2_f16_first_ok(const y2h_conv *d);
 bool y2_f16_first_nchw_ok(const y2h_conv *d);
 
+// What every forward entry point (y2h_conv_forward and the three Winograd forms) asks of a descriptor before it plans: the
+// pointers every kernel reads, sane dimensions and strides, the batch-norm constants where the layer normalizes.  Each adds
+// its own conditions (w_packed, the output size, workspace size and alignment).
+static inline bool conv_args_ok(const y2h_conv *d)
+{
+    if (!d || !d->x || !d->y || !d->bias) return false;
+    if (d->batch <= 0 || d->h <= 0 || d->w <= 0 || d->c <= 0 || d->n <= 0 || d->ldx < d->c || d->ldy < d->n) return false;
+    return !d->batch_normalize || (d->mean && d->rinv && d->scale);
+}
+
 // Winograd F(2x2,3x3) transforms (y2_wino.hip), the passes in front of and behind the batched GEMM of y2h_conv_wino_forward:
 // V[16][tiles_pad][c] from the NHWC input of d; the layer's output from M[16][tiles_pad][n] through the shared epilogue.
 int y2_wino_input_launch(const y2h_conv *d, float *V, long tiles, long tiles_pad, y2h_stream s);

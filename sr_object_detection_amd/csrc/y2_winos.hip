@@ -258,8 +258,7 @@ extern "C" unsigned long y2h_winos_launches(void) { return g_winos_launches; }
 
 extern "C" int y2h_conv_winos_forward(const y2h_conv *d, y2h_stream s)
 {
-    if (!d || !d->x || !d->y || !d->bias || !d->w_packed) return Y2H_EINVAL;
-    if (d->batch_normalize && (!d->mean || !d->rinv || !d->scale)) return Y2H_EINVAL;
+    if (!conv_args_ok(d) || !d->w_packed) return Y2H_EINVAL;
     y2h_winos w;
     if (y2h_winos_plan(d, &w) != Y2H_OK || !w.take || w.form != 32) return Y2H_EINVAL;
     ConvK a;

@@ -150,6 +150,28 @@ def test_winos_switches(workdir, monkeypatch):
     assert np.array_equal(out, plain)              # integer data: exact either way
 
 
+def test_one_form_per_layer_split_beats_wino_beats_stationary(workdir, monkeypatch):
+    """The layer of test_winos_switches is one all three Winograd rules find eligible (tests/test_conv_form_cpu.py).  With every
+    switch on it runs as the split form, without Y2_WINO_SPLIT as fp32 Winograd, with Y2_WINOS alone as the stationary kernel:
+    the name says so, exactly that form's launch counter moves, and on integer data every form gives the direct kernel's bits."""
+    spec = [("conv", 32, 3, 0, "linear"), ("conv", 64, 3, 1, "leaky")]
+    cfg, wts, x = _small_int_conv_case(workdir, spec, 32, 2, 46000)
+    lib = darknet.lib()
+    counters = (lib.y2h_wino_split_launches, lib.y2h_wino_launches, lib.y2h_winos_launches)
+    _env(monkeypatch, None, None)
+    direct, direct_name = _predict(cfg, wts, x)
+    assert direct_name.startswith("conv_mfma_f32_"), direct_name
+    rows = [(dict(Y2_WINO=1, Y2_WINO_SPLIT=1), "conv_winox_f32_"), (dict(Y2_WINO=1), "conv_wino_f32_"), (dict(), "conv_winos_f32_c32")]
+    for k, (more, prefix) in enumerate(rows):
+        _env(monkeypatch, 1, None, **more)
+        before = [c() for c in counters]
+        out, name = _predict(cfg, wts, x)
+        moved = [c() - b for c, b in zip(counters, before)]
+        assert name.startswith(prefix), (more, name)
+        assert [m > 0 for m in moved] == [j == k for j in range(3)], (more, name, moved)
+        assert np.array_equal(out, direct), (more, name)
+
+
 def test_winos_real_valued_layer_is_within_tolerance(oracle, workdir, monkeypatch):
     """real-valued data, 3 -> 32 -> 64 channels, 32x32, batch 2: within 1e-4 * max(1, |layer max|) of the oracle (whose own
     distance from the truth is its sequential fp32 k-sum); the direct kernel's error for the same case is printed beside it"""

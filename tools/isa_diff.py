@@ -31,7 +31,7 @@ def demangle(names):
 
 def short(d):
     """`void f<1, 2>(ConvK)` -> `f<1, 2>`; the integral-constant spellings of clang shortened"""
-    d = re.sub(r"^void ", "", d.strip())
+    d = re.sub(r"^void ", "", d.strip()).replace("(anonymous namespace)::", "")      # (its bracket is not the argument list's)
     depth = 0
     for i, c in enumerate(d):
         depth += c == "<"

@@ -7,7 +7,8 @@ check that a change of the cost model leaves the plan of the headline configurat
     tools/plan_dump.py --sweep-rows  the same queries, one line per conv layer: diff two builds' output (Y2_LIB) to see what moved
     tools/plan_dump.py --wino        the Winograd rule's answer for every 3x3 layer of every zoo network (tests/golden/wino_plan_table.txt)
     tools/plan_dump.py --winos       the stationary-Winograd rule's answer for the same layers (tests/golden/winos_plan_table.txt)
-    tools/plan_dump.py --wino-split  the split rule's answer for the same layers (tests/golden/wino_split_plan_table.txt)"""
+    tools/plan_dump.py --wino-split  the split rule's answer for the same layers (tests/golden/wino_split_plan_table.txt)
+    tools/plan_dump.py --forms       the form the three rules together give each of those layers, and its kernel name (y2_conv_form_of)"""
 import ctypes as C
 import os
 import sys
@@ -227,6 +228,35 @@ def wino_split_rows(lib):
                 w.v_bytes, w.u_bytes, w.present_cost / 1e3, w.gemm_cost / 1e3, w.split_cost / 1e3, wh.eligible, wh.take)
 
 
+FORM_NAMES = ("direct", "wino", "winox", "winos")          # csrc/host/y2_internal.h: Y2_FORM_*
+
+
+def conv_form(lib, f):
+    """y2_conv_form_of (y2_plan.c) for one descriptor (a dict of y2h_conv fields): the form and, unless it is direct, the name"""
+    d, name = Conv(**f), C.create_string_buffer(80)
+    lib.y2_conv_form_of.argtypes = [C.POINTER(Conv), C.c_int, C.c_char_p, C.c_size_t]
+    form = lib.y2_conv_form_of(C.byref(d), f.get("fuse_maxpool2", 0), name, len(name))
+    return form, name.value.decode()
+
+
+def form_rows(lib):
+    """The form every 3x3 conv layer of every zoo network runs in, the three rules combined (y2_conv_form_of).  For people:
+    tests/test_conv_form_cpu.py derives what it expects from the three rule tables, not from this dump."""
+    for k in [k for k in os.environ if k.startswith("Y2_")]:
+        del os.environ[k]
+    yield "# net size batch layer | h w c n pool | fp32: form name | fp16: form name"
+    for net, size, batch in wino_cases():
+        rows = {}
+        for half in (0, 1):
+            for i, f in _descs(net, size, batch, half, ALIGNED):
+                if f["size"] != 3 or f.get("x_halo") or f.get("x_nchw"):
+                    continue
+                rows.setdefault(i, (f, []))[1].append(conv_form(lib, f))
+        for i, (f, forms) in sorted(rows.items()):
+            yield "%s %d b%d L%d | %d %d %d %d %d | %s" % (net, size, batch, i, f["h"], f["w"], f["c"], f["n"], f["fuse_maxpool2"],
+                                                           " | ".join("%s %s" % (FORM_NAMES[k], n or "-") for k, n in forms))
+
+
 def main():
     lib = C.CDLL(os.environ.get("Y2_LIB") or os.path.join(ROOT, "sr_object_detection_amd", "libsr_yolo2.so"))
     lib.y2h_conv_variant.restype = C.c_char_p
@@ -241,6 +271,8 @@ def main():
         return print("\n".join(winos_rows(lib)))
     if args == ["--wino-split"]:
         return print("\n".join(wino_split_rows(lib)))
+    if args == ["--forms"]:
+        return print("\n".join(form_rows(lib)))
     for k in range(0, len(args), 3):
         net, size, batch = args[k], int(args[k + 1]), int(args[k + 2])
         layers = zoo.resolve(net, size)
