@@ -835,6 +835,61 @@ int y2_train_pull_input(network *net, float *x_nchw, float *truth);
 /* Host wall time of the last y2_train_load_detection / y2_train_load_classification in ms: ms[0] pack (pixels, table,
  * truth), ms[1] enqueueing the copy, the kernel and the truth copy, ms[2] waiting for the copy to leave the staging buffer. */
 int y2_train_load_times(network *net, float *ms);
+
+/* ------------------------------------------------------------------------ */
+/* Dreaming: nightmare.c's optimize_picture / run_nightmare (y2_dream.c).      */
+/* The gradient of a layer's activations with respect to the input picture,  */
+/* climbed on a picture that stays in HBM.  A context is opened on a loaded  */
+/* batch-1 network and a picture ([c][h][w] floats, c as the network's); the */
+/* picture is uploaded once, every step reads and writes it there, the host  */
+/* sees it on y2_dream_fetch.  The context packs the weights of the layers   */
+/* it needs once (again after load_weights, y2_denormalize_network or        */
+/* training steps changed them) and keeps per input size the activations,    */
+/* deltas and maxpool winners of the truncated network, at most eight sizes, */
+/* least recently used dropped.  It NEVER resizes or truncates the caller's  */
+/* network (the reference leaves net->n, w, h changed; here network_predict  */
+/* gives the bytes it gave before).  Accepted: [convolutional] without       */
+/* batch_normalize, stride 1, linear / leaky / logistic / relu, and          */
+/* [maxpool]; everything else is refused by name before any allocation.      */
+/* Weight and bias gradients are not computed: the reference accumulates     */
+/* them and never applies them.  -reconstruct is out of scope.               */
+/* ------------------------------------------------------------------------ */
+typedef struct y2_dream y2_dream;
+typedef struct { int layer_offset, octave, dx, dy, flip; } y2_dream_draws;
+/* selected: values of the last layer the last step kept (0: the gradient was all zero, and with norm the picture is NaN now,
+ * as in the reference); bytes copied since open; device allocations since open; steps since open */
+typedef struct { int selected; unsigned long long h2d_bytes, d2h_bytes; unsigned long allocations, steps; } y2_dream_counters;
+/* the five rand() calls of one run_nightmare iteration in its order: rand()%range - range/2 (add max_layer), rand()%octaves,
+ * rand()%16 - 8, rand()%16 - 8, rand()%2 */
+void y2_dream_draw(int range, int octaves, y2_dream_draws *out);
+float y2_dream_scale(int octave);                                        /* 1/pow(1.33333333, octave), as a float argument */
+void y2_dream_size(int w, int h, float scale, int *ow, int *oh);         /* (int)(w*scale), (int)(h*scale) */
+/* Every refusal of a step at (max_layer, scale) on a c x h x w picture, by name ("dream: layer %d (%s): ..."), without a
+ * device call: what y2_dream_step, optimize_picture and y2_nightmare ask before they allocate.  0, or -1 after y2_fail. */
+int y2_dream_check(network *net, int max_layer, int c, int h, int w, float scale);
+y2_dream *y2_dream_open(network *net, const float *picture, int c, int h, int w);
+int y2_dream_step(y2_dream *d, int max_layer, float scale, float rate, float thresh, int norm, int dx, int dy, int flip);
+/* run_nightmare's round end: rotate_image when rotate != 0, crop_image by zoom with its float-to-int truncations, resize back */
+int y2_dream_round_end(y2_dream *d, float rotate, float zoom);
+int y2_dream_fetch(y2_dream *d, float *picture);
+int y2_dream_stats(y2_dream *d, y2_dream_counters *out);
+/* For tests and callers that look, of the last step: Y2_DREAM_OUTPUT / Y2_DREAM_DELTA of layer `layer` as [c][h][w];
+ * Y2_DREAM_INPUT (the network input the step built) and Y2_DREAM_GRADIENT (the image gradient) as [c][h][w] at the step's
+ * size; Y2_DREAM_UPDATE, the picture-sized update before normalisation.  n must be the array's size. */
+enum { Y2_DREAM_OUTPUT = 0, Y2_DREAM_DELTA, Y2_DREAM_INPUT, Y2_DREAM_GRADIENT, Y2_DREAM_UPDATE };
+int y2_dream_pull(y2_dream *d, int layer, int what, float *dst, size_t n);
+void y2_dream_close(y2_dream *d);
+/* The reference's entry point with its own three rand() draws: uploads orig, steps, fetches into orig.data.  The context is
+ * cached on the network (reopened when the picture's size changes) and freed by free_network. */
+void optimize_picture(network *net, image orig, int max_layer, float scale, float rate, float thresh, int norm);
+/* Seeding: the draws are libc's rand().  The HIP runtime draws from the same generator while it starts up at the first device
+ * work of a process, so call srand() after that (after a y2_dream_open, a network_predict, ...), not before it, when the
+ * sequence matters. */
+/* run_nightmare's loop without file I/O and without srand: rounds x iters steps with its draws, one fetch per round into
+ * im.data, then per_round(round, im, user) if given, then the round end.  Returns 0, or -1 after y2_fail. */
+int y2_nightmare(network *net, image im, int max_layer, int range, int norm, int rounds, int iters, int octaves, float zoom,
+                 float rate, float thresh, float rotate, void (*per_round)(int round, image im, void *user), void *user);
+
 /* Copy layer i's activations to host as NCHW [batch][out_c][out_h][out_w] (or [batch][outputs]). */
 int y2_pull_layer_output(network net, int i, float *dst);
 /* Per-layer device time of the last forward in ms (needs y2_set_timing(net,1)); returns layers written. */

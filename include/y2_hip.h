@@ -860,6 +860,36 @@ int y2h_train_add(float *dst, const float *src, long n, y2h_stream s);          
  * an assignment.  dy is dense NHWC [h/stride][w/stride][c*stride*stride], dx dense NHWC [h][w][c]. */
 int y2h_train_reorg_backward(const float *dy, float *dx, int batch, int h, int w, int c, int stride, y2h_stream s);
 
+/* ---- dreaming (y2_dream.hip): the picture side of nightmare.c's optimize_picture / run_nightmare ----
+ * One resample is crop_image(src, cx, cy, cw, ch) -> resize_image(., ow, oh) -> crop_image(., px, py, ow, oh), both crops
+ * repeating edge pixels (constrain_int), with flip_image on the source (src_flip) or on the result (dst_flip) and either
+ * layout ([c][h][w] or [h][w][c]) on either end.  Two launches; tmp holds y2h_dream_resample_tmp_floats(r) floats.  The
+ * values are formed by the fp32 expressions of y2h_resize_chw in its order, nothing contracted. */
+typedef struct {
+    int c;
+    int sh, sw, src_nhwc, src_flip;      /* the source */
+    int cx, cy, ch, cw;                  /* the crop in front of the resize */
+    int oh, ow;                          /* the resize */
+    int px, py;                          /* the crop behind it */
+    int dst_nhwc, dst_flip;              /* the result */
+} y2h_dream_resample;
+size_t y2h_dream_resample_tmp_floats(const y2h_dream_resample *r);
+int y2h_dream_resample_run(const y2h_dream_resample *r, const float *src, float *tmp, float *dst, y2h_stream s);
+/* Deterministic moments: block b sums chunk b of Y2H_DREAM_CHUNK values (16 per thread in index order, then a fixed tree),
+ * the chunk sums are added in chunk order by the same tree; the variance is a second pass about the mean.  `partials`
+ * holds 2 * y2h_dream_chunks(n) floats; stat[0] = mean, stat[1] = variance (/n).  No floating-point atomics.
+ *   loss    nightmare.c:23-32 calculate_loss: delta[i] = output[i] where (double)output[i] > mean + thresh*sqrt(var), else 0;
+ *           *selected = how many were kept (output and delta may be any layout: the rule is per element)
+ *   apply   norm: out = (out - mean) / (float)sqrt(var) (utils.c:482, no epsilon: 0/0 stays NaN); then
+ *           picture = constrain(picture + rate * out) with constrain_image's two tests, which a NaN passes */
+#define Y2H_DREAM_CHUNK 4096
+int y2h_dream_chunks(long n);
+int y2h_dream_loss(const float *output, float *delta, long n, float thresh, float *partials, float *stat, int *selected, y2h_stream s);
+int y2h_dream_apply(float *picture, const float *out, long n, float rate, int norm, float *partials, float *stat, y2h_stream s);
+/* image.c:1481 rotate_image about (w/2., h/2.) with bilinear_interpolate; cos(rad) and sin(rad) come from the host's libm as
+ * doubles, the coordinates are formed in double and rounded to float as the C expression does.  src != dst. */
+int y2h_dream_rotate(const float *src, float *dst, int c, int h, int w, double cos_rad, double sin_rad, y2h_stream s);
+
 #ifdef __cplusplus
 }
 #endif

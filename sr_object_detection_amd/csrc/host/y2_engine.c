@@ -107,6 +107,7 @@ void y2_engine_destroy(network *net)
     int i;
     if (!e) return;
     if (e->stream || e->arena || e->built) y2h_set_device(e->device);
+    y2_dream_free_cached(e);
     y2_train_free(net);
     free(e->lr.steps); free(e->lr.scales);
     y2_free_plan(net);

@@ -125,6 +125,8 @@ typedef struct y2_engine {
     int built_batch, built_w, built_h, built_strict;
     int weights_dirty;         /* host weights changed since the last upload */
     int weights_external;      /* arena filled from outside (broadcast) */
+    unsigned long weights_gen; /* counts the changes of the host weights (load_weights, denormalize, a trainer's sync): what a
+                                  holder of packed copies of its own (y2_dream.c) compares against */
     /* weight arena */
     unsigned char *arena;
     size_t arena_bytes;
@@ -198,6 +200,7 @@ typedef struct y2_engine {
                                   here and not in the trainer, so it outlasts y2_train_free and every new y2_train_prepare */
     struct y2_trainer *trainer;
     float aug_hue, aug_saturation, aug_exposure;   /* [net] hue / saturation / exposure (parser.c:532-534): what y2_net_augment reports */
+    struct y2_dream *dream;    /* optimize_picture's cached context (y2_dream.c), NULL until its first call */
     int aug_min_crop, aug_max_crop;                /* [net] min_crop / max_crop / angle / aspect (parser.c:527-531): y2_net_augment_classifier */
     float aug_angle, aug_aspect;
 } y2_engine;
@@ -296,6 +299,9 @@ int y2_train_is_dirty(const network *net);     /* steps ran since the masters la
 int y2_train_sync_if_dirty(network *net);      /* a trained network's masters reach the host arrays before they are read */
 void y2_lr_parse(list *options, y2_lr_schedule *lr);
 int y2_train_precision_env(int *mode);            /* Y2_TRAIN_PRECISION -> *mode (untouched when unset); -1 and y2_fail for an unknown word */
+
+/* dreaming (y2_dream.c) */
+void y2_dream_free_cached(y2_engine *e);
 
 /* the detection loader's host half (y2_aug.c), device-free */
 int y2_aug_check(const char *who, const y2_aug_item *items, int n);        /* every refusal that reads only the items */

@@ -1146,6 +1146,7 @@ int y2_train_sync_if_dirty(network *net)
     }
     t->dirty = 0;
     e->weights_dirty = 1;
+    e->weights_gen++;
     e->weights_external = 0;
     return 0;
 }

@@ -150,6 +150,7 @@ void load_weights_upto(network *net, char *filename, int cutoff)
     fprintf(stderr, "Done!\n");
     if (y2_engine_of(net)) {
         y2_engine_of(net)->weights_dirty = 1;
+        y2_engine_of(net)->weights_gen++;
         y2_engine_of(net)->weights_external = 0;
     }
 }
@@ -230,7 +231,10 @@ void denormalize_convolutional_layer(layer l)
         l.rolling_mean[i] = 0;
         l.rolling_variance[i] = 1;
     }
-    if (l.dev && ((y2_ldev *)l.dev)->eng) ((y2_ldev *)l.dev)->eng->weights_dirty = 1;   /* re-pack at the next forward */
+    if (l.dev && ((y2_ldev *)l.dev)->eng) {
+        ((y2_ldev *)l.dev)->eng->weights_dirty = 1;                 /* re-pack at the next forward */
+        ((y2_ldev *)l.dev)->eng->weights_gen++;
+    }
 }
 
 /* darknet.c:309-345 denormalize_net for the layer types this engine has */

@@ -175,6 +175,20 @@ class RegionStats(C.Structure):  # include/sr_yolo2.h y2_region_stats == include
                [("count", C.c_int), ("class_count", C.c_int)]
 
 
+class DreamDraws(C.Structure):    # include/sr_yolo2.h y2_dream_draws: the five rand() calls of one run_nightmare iteration
+    _fields_ = [("layer_offset", C.c_int), ("octave", C.c_int), ("dx", C.c_int), ("dy", C.c_int), ("flip", C.c_int)]
+
+
+class DreamCounters(C.Structure):  # include/sr_yolo2.h y2_dream_counters
+    _fields_ = [("selected", C.c_int), ("h2d_bytes", C.c_ulonglong), ("d2h_bytes", C.c_ulonglong), ("allocations", C.c_ulong),
+                ("steps", C.c_ulong)]
+
+
+class DreamResample(C.Structure):  # include/y2_hip.h y2h_dream_resample: crop -> resize -> crop with flips and layouts
+    _fields_ = [(k, C.c_int) for k in ("c", "sh", "sw", "src_nhwc", "src_flip", "cx", "cy", "ch", "cw", "oh", "ow", "px", "py",
+                                       "dst_nhwc", "dst_flip")]
+
+
 class AugItem(C.Structure):  # include/sr_yolo2.h y2_aug_item: one image of y2_train_load_detection
     _fields_ = [("data", C.c_void_p), ("h", C.c_int), ("w", C.c_int), ("c", C.c_int), ("step", C.c_int),
                 ("pleft", C.c_int), ("ptop", C.c_int), ("swidth", C.c_int), ("sheight", C.c_int), ("flip", C.c_int),
@@ -522,6 +536,33 @@ def lib():
     L.y2_aug_cls_pack.restype = None
     L.y2_aug_cls_pack.argtypes = [C.POINTER(AugClsItem), C.c_int, C.c_int, C.POINTER(AugCls), C.c_void_p]
     L.y2h_augment_cls_to_input.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.y2_dream_draw.restype = None
+    L.y2_dream_draw.argtypes = [C.c_int, C.c_int, C.POINTER(DreamDraws)]
+    L.y2_dream_scale.restype = C.c_float
+    L.y2_dream_scale.argtypes = [C.c_int]
+    L.y2_dream_size.restype = None
+    L.y2_dream_size.argtypes = [C.c_int, C.c_int, C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.y2_dream_check.argtypes = [C.POINTER(CNetwork), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float]
+    L.y2_dream_open.restype = C.c_void_p
+    L.y2_dream_open.argtypes = [C.POINTER(CNetwork), C.c_void_p, C.c_int, C.c_int, C.c_int]
+    L.y2_dream_step.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.y2_dream_round_end.argtypes = [C.c_void_p, C.c_float, C.c_float]
+    L.y2_dream_fetch.argtypes = [C.c_void_p, C.c_void_p]
+    L.y2_dream_stats.argtypes = [C.c_void_p, C.POINTER(DreamCounters)]
+    L.y2_dream_pull.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+    L.y2_dream_close.restype = None
+    L.y2_dream_close.argtypes = [C.c_void_p]
+    L.optimize_picture.restype = None
+    L.optimize_picture.argtypes = [C.POINTER(CNetwork), Image, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int]
+    L.y2_nightmare.argtypes = [C.POINTER(CNetwork), Image, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                               C.c_float, C.c_float, C.c_void_p, C.c_void_p]
+    L.y2h_dream_resample_tmp_floats.restype = C.c_size_t
+    L.y2h_dream_resample_tmp_floats.argtypes = [C.POINTER(DreamResample)]
+    L.y2h_dream_resample_run.argtypes = [C.POINTER(DreamResample), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.y2h_dream_chunks.argtypes = [C.c_long]
+    L.y2h_dream_loss.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.y2h_dream_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.y2h_dream_rotate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]
     L.y2h_stream_k_launches.restype = C.c_ulong
     L.y2h_tail_launches.restype = C.c_ulong
     L.y2h_xcd_order_launches.restype = C.c_ulong
@@ -1091,6 +1132,40 @@ class Network:
     def train_free(self) -> None:
         lib().y2_train_free(C.byref(self.net))
 
+    # --- dreaming (nightmare.c) ---
+    def dream_check(self, max_layer: int, c: int, h: int, w: int, scale: float = 1.0) -> None:
+        """every refusal of a dream step, by name, without a device call"""
+        if lib().y2_dream_check(C.byref(self.net), max_layer, c, h, w, scale) != 0:
+            raise Y2Error("y2_dream_check: " + _check())
+
+    def dream_open(self, picture: np.ndarray) -> "Dream":
+        """a dream context on this batch-1 network: picture float32 [c][h][w], uploaded once and kept in HBM"""
+        return Dream(self, picture)
+
+    def optimize_picture(self, picture: np.ndarray, max_layer: int, scale: float, rate: float, thresh: float, norm: int) -> np.ndarray:
+        """nightmare.c:34 with its own three rand() draws (libc's: seed with darknet.srand); returns the new picture"""
+        p = np.array(picture, dtype=np.float32, order="C", copy=True)
+        c, h, w = p.shape
+        L = lib()
+        L.optimize_picture(C.byref(self.net), Image(h, w, c, p.ctypes.data_as(C.POINTER(C.c_float))), max_layer, scale, rate, thresh, norm)
+        if L.y2_failed_and_clear():
+            raise Y2Error("optimize_picture: " + _check())
+        return p
+
+    def nightmare(self, picture: np.ndarray, max_layer: int, range_: int = 1, norm: int = 1, rounds: int = 1, iters: int = 10,
+                  octaves: int = 4, zoom: float = 1.0, rate: float = .04, thresh: float = 1.0, rotate: float = 0.0, per_round=None) -> np.ndarray:
+        """run_nightmare's loop (nightmare.c:258-306) with its defaults and libc's rand(); per_round(round, picture [c][h][w]) sees
+        each round's picture, fetched once per round; returns the last round's"""
+        p = np.array(picture, dtype=np.float32, order="C", copy=True)
+        c, h, w = p.shape
+        cb_t = C.CFUNCTYPE(None, C.c_int, Image, C.c_void_p)
+        cb = cb_t(lambda r, im, user: per_round(r, np.ctypeslib.as_array(im.data, shape=(c, h, w)).copy())) if per_round else None
+        rc = lib().y2_nightmare(C.byref(self.net), Image(h, w, c, p.ctypes.data_as(C.POINTER(C.c_float))), max_layer, range_, norm, rounds,
+                                iters, octaves, zoom, rate, thresh, rotate, C.cast(cb, C.c_void_p) if cb else None, None)
+        if rc != 0:
+            raise Y2Error("y2_nightmare: " + _check())
+        return p
+
     def get_current_rate(self) -> float:
         return float(lib().get_current_rate(self.net))
 
@@ -1606,6 +1681,85 @@ class Network:
             self.free()
         except Exception:
             pass
+
+
+class Dream:
+    """A dream context (include/sr_yolo2.h y2_dream): the picture in HBM, the packed weights, the buffers per input size.
+    Close it before the network is freed."""
+    ARRAYS = ("output", "delta", "input", "gradient", "update")
+
+    def __init__(self, net: Network, picture: np.ndarray):
+        p = np.ascontiguousarray(picture, dtype=np.float32)
+        if p.ndim != 3:
+            raise ValueError("picture must be [c][h][w]")
+        self.net, self.shape = net, p.shape
+        self.h = lib().y2_dream_open(C.byref(net.net), _ptr(p), p.shape[0], p.shape[1], p.shape[2])
+        if not self.h:
+            raise Y2Error("y2_dream_open: " + _check())
+
+    def step(self, max_layer: int, scale: float = 1.0, rate: float = .04, thresh: float = 1.0, norm: int = 1, dx: int = 0, dy: int = 0,
+             flip: int = 0) -> None:
+        if lib().y2_dream_step(self.h, max_layer, scale, rate, thresh, norm, dx, dy, flip) != 0:
+            raise Y2Error("y2_dream_step: " + _check())
+
+    def round_end(self, rotate: float = 0.0, zoom: float = 1.0) -> None:
+        if lib().y2_dream_round_end(self.h, rotate, zoom) != 0:
+            raise Y2Error("y2_dream_round_end: " + _check())
+
+    def fetch(self) -> np.ndarray:
+        out = np.zeros(self.shape, np.float32)
+        if lib().y2_dream_fetch(self.h, _ptr(out)) != 0:
+            raise Y2Error("y2_dream_fetch: " + _check())
+        return out
+
+    def stats(self) -> dict:
+        st = DreamCounters()
+        if lib().y2_dream_stats(self.h, C.byref(st)) != 0:
+            raise Y2Error("y2_dream_stats: " + _check())
+        return {k: int(getattr(st, k)) for k, _ in DreamCounters._fields_}
+
+    def pull(self, what: str, layer: int = 0, shape=None) -> np.ndarray:
+        """of the last step: "output" / "delta" of a layer, the "input" it built and the image "gradient" ([c][h][w] at the
+        step's size), the picture-sized "update" before normalisation; shape = (c, h, w) of the array"""
+        shape = tuple(shape) if shape is not None else self.shape
+        out = np.zeros(shape, np.float32)
+        if lib().y2_dream_pull(self.h, layer, self.ARRAYS.index(what), _ptr(out), out.size) != 0:
+            raise Y2Error("y2_dream_pull: " + _check())
+        return out
+
+    def close(self) -> None:
+        if self.h:
+            lib().y2_dream_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            if not self.net._freed:
+                self.close()
+        except Exception:
+            pass
+
+
+def srand(seed: int) -> None:
+    """libc's srand: the generator y2_dream_draw, optimize_picture and y2_nightmare draw from"""
+    C.CDLL(None).srand(C.c_uint(seed))
+
+
+def dream_draw(range_: int = 1, octaves: int = 4) -> dict:
+    """the five rand() calls of one run_nightmare iteration in its order"""
+    d = DreamDraws()
+    lib().y2_dream_draw(range_, octaves, C.byref(d))
+    return {k: int(getattr(d, k)) for k, _ in DreamDraws._fields_}
+
+
+def dream_scale(octave: int) -> float:
+    return float(lib().y2_dream_scale(octave))
+
+
+def dream_size(w: int, h: int, scale: float) -> tuple:
+    ow, oh = C.c_int(), C.c_int()
+    lib().y2_dream_size(w, h, scale, C.byref(ow), C.byref(oh))
+    return ow.value, oh.value
 
 
 def do_nms_sort(boxes: np.ndarray, probs: np.ndarray, thresh: float, classes: int | None = None) -> np.ndarray:
