@@ -712,7 +712,12 @@ int y2_train_sync(network *net);
 enum { Y2_TRAIN_OUTPUT = 0, Y2_TRAIN_DELTA, Y2_TRAIN_X, Y2_TRAIN_X_NORM, Y2_TRAIN_MEAN, Y2_TRAIN_VARIANCE, Y2_TRAIN_MEAN_DELTA,
        Y2_TRAIN_VARIANCE_DELTA, Y2_TRAIN_WEIGHT_UPDATES, Y2_TRAIN_BIAS_UPDATES, Y2_TRAIN_SCALE_UPDATES, Y2_TRAIN_WEIGHTS,
        Y2_TRAIN_BIASES, Y2_TRAIN_SCALES, Y2_TRAIN_ROLLING_MEAN, Y2_TRAIN_ROLLING_VARIANCE,
-       Y2_TRAIN_RAND /* [dropout]: the last step's draws, [batch][inputs]; its output and delta are the layer's in front */ };
+       Y2_TRAIN_RAND /* [dropout]: the last step's draws, [batch][inputs]; its output and delta are the layer's in front */,
+       Y2_TRAIN_STATE /* [rnn]: the state history, [time_steps + 1][B][hidden]; step t read slot t and wrote slot t + 1 */ };
+/* An [rnn] layer's sub-layers, k = 0 input, 1 self, 2 output: Y2_TRAIN_SUB(k, what) names array `what` of sub-layer k.  Their
+ * activations are [time_steps][B][outputs] (rows step-major); mean and variance are the last time step's, as in the reference
+ * after a step.  The layer's own Y2_TRAIN_OUTPUT / Y2_TRAIN_DELTA are the output sub-layer's. */
+#define Y2_TRAIN_SUB(k, what) ((((k) + 1) << 8) | (what))
 int y2_train_pull(network *net, int layer, int what, float *dst, size_t n);
 /* What forward_region_layer prints per call (region_layer.c:320), of the last step: the sums divided as in that printf, so
  * avg_iou, avg_class, avg_obj and recall are NaN when the batch held no truth.  The library prints nothing. */
@@ -826,6 +831,17 @@ int y2_net_augment_classifier(network net, int *min_crop, int *max_crop, float *
  * that the trainer refuses, NULL truth or data, c < 3, step < w * c, a frame without pixels, a scale or aspect that is
  * not finite and positive, a rad, dx or dy that is not finite.  A refused load leaves nothing loaded. */
 int y2_train_load_classification(network *net, const y2_aug_cls_item *items, const float *truth, int n, int swap_rb);
+/* get_rnn_data (rnn.c:86-114): x and y are [steps*batch][characters], zeroed here; row j*batch + i holds the one-hot of the
+ * byte stream i reads at its step j (x) and of the byte behind it (y); offsets[i] advances by one per step, modulo len.
+ * Where the reference calls error("Bad char") half-way -- a zero byte -- this returns -1 with that message (y2_last_error)
+ * BEFORE anything is written or any offset moves; a byte >= characters, which the reference would write out of bounds, is
+ * refused the same way. */
+int y2_get_rnn_data(const unsigned char *text, size_t *offsets, int characters, size_t len, int batch, int steps, float *x, float *y);
+/* The same on the device, into the trainer's input and truth: the B x (time_steps + 1) bytes the B = net.batch / time_steps
+ * streams read go up (not 2 x net.batch x inputs floats), one kernel writes both one-hot tensors, offsets advance as
+ * get_rnn_data's.  For a network whose first layer is an [rnn] and whose [cost] has as many values as the network reads.
+ * Refused by name, nothing loaded and no offset moved: a network the trainer refuses, a zero byte or one >= inputs. */
+int y2_train_load_rnn_data(network *net, const unsigned char *text, size_t len, size_t *offsets);
 /* step_on_device on what y2_train_load_detection or y2_train_load_classification loaded; a second step on the same load is
  * allowed.  Refused with nothing loaded, and after set_batch_network / resize_network dropped the trainer (load again). */
 int y2_train_step_loaded(network *net, float *loss);

@@ -813,6 +813,11 @@ int y2h_train_softmax(const float *x, float *y, int rows, int n, float temperatu
  * error = delta^2 (the layer's output), cost[0] = sum error (fixed tree), delta_prev = scale * delta */
 int y2h_train_cost_sse(const float *pred, const float *truth, float *error, float *delta, float *delta_prev, float scale, long n,
                        float *cost, y2h_stream s);
+/* the same over Y2H_COST_CHUNKS contiguous chunks, one workgroup each with the tree above, their sums added in chunk order by
+ * a second launch: for a cost over millions of values (a char-rnn's [T*B][inputs]).  scratch: Y2H_COST_CHUNKS floats. */
+enum { Y2H_COST_CHUNKS = 256 };
+int y2h_train_cost_sse_chunked(const float *pred, const float *truth, float *error, float *delta, float *delta_prev, float scale,
+                               long n, float *cost, float *scratch, y2h_stream s);
 /* [dropout] in training mode (dropout_layer.c:38-59), forward on an activation and backward on its delta, in place:
  * x = rnd < probability ? 0 : x * scale.  x is dense NHWC [batch][hw][c]; rnd holds the layer's draws in the reference's
  * [batch][c][hw] order (hw = 1: the same order). */
@@ -859,6 +864,51 @@ int y2h_train_add(float *dst, const float *src, long n, y2h_stream s);          
 /* backward of a non-reverse [reorg] whose input is h x w x c (reorg_layer.c:92): the exact inverse of y2h_reorg(reverse = 0),
  * an assignment.  dy is dense NHWC [h/stride][w/stride][c*stride*stride], dx dense NHWC [h][w][c]. */
 int y2h_train_reorg_backward(const float *dy, float *dx, int batch, int h, int w, int c, int stride, y2h_stream s);
+
+/* ---- training, [rnn] (y2_train_rnn.hip): the per-step parts of back-propagation through time ----
+ * Tensors are [T][B][C], rows step-major; a group is one step's B rows.  Every sum has one fixed order; no atomics.
+ *   bn_stats   mean / variance [T][C], each over its own group (variance / (B-1), B >= 2), then the rolling statistics
+ *              rolling = keep * rolling + take * new once per step in step order
+ *   bn_apply   y2h_train_bn_apply with the group's own mean / variance
+ *   delta      backward_connected_layer up to its products, group by group, in place on delta: gradient_array on `out`, the
+ *              group's bias sum -> bias_steps[T][C] (and sum delta * x_norm -> scale_steps), then with mean != NULL scale_bias,
+ *              mean_delta, variance_delta and normalize_delta over the group's B rows.  mean / variance are ONE row [C] used
+ *              for every group (the reference's backward reads the last step's); mean_delta / variance_delta [C] receive
+ *              group 0's, which is what the reference's arrays hold after its loop.
+ *   sum_steps  dst[c] += steps[T-1][c] + ... + steps[0][c], added one by one in that order
+ *   combine    dst = (0 + a) + b */
+int y2h_train_rnn_bn_stats(const float *x, int T, int B, int C, float *mean, float *variance, float *rolling_mean,
+                           float *rolling_variance, float keep, float take, y2h_stream s);
+int y2h_train_rnn_bn_apply(float *y, float *x, float *x_norm, const float *mean, const float *variance, const float *scales,
+                           const float *biases, int act, int T, int B, int C, y2h_stream s);
+/* one step of the self sub-layer behind its product y [B][C], one launch: bn_stats (T = 1), bn_apply and
+ * next = (0 + proj) + y; mean == NULL: y = act(y + bias) only (x, x_norm, variance, the rolling pair and scales unused) */
+int y2h_train_rnn_step_finish(float *y, float *x, float *x_norm, float *mean, float *variance, float *rolling_mean,
+                              float *rolling_variance, float keep, float take, const float *scales, const float *biases, int act,
+                              int B, int C, const float *proj, float *next, y2h_stream s);
+/* The fused step kernels of the self sub-layer.  fits: the rule -- B <= 128 rows (four 32-row tiles of one matrix-core
+ * accumulator each in a 16-wave workgroup that owns 32 columns and all rows), the LDS tiles within a CU's 160 KB, the backward
+ * partials (ws_bytes = ceil(hidden / 32) * B * hidden floats) within 256 MiB.  Host arithmetic, no GPU.
+ * forward: y = state x w^T on the fp32 matrix cores and everything y2h_train_rnn_step_finish does, ONE launch.
+ * backward: everything y2h_train_rnn_delta does for one group (T = 1), and with dprev != NULL  dprev += delta x w: each
+ * workgroup's 32 outputs give a partial in ws, a second launch adds the partials in range order.  Two launches. */
+int y2h_train_rnn_fused_fits(int B, int hidden);
+size_t y2h_train_rnn_fused_ws_bytes(int B, int hidden);
+int y2h_train_rnn_fused_forward(const float *state, const float *w, float *y, float *x, float *x_norm, float *mean, float *variance,
+                                float *rolling_mean, float *rolling_variance, float keep, float take, const float *scales,
+                                const float *biases, int act, int B, int H, const float *proj, float *next, y2h_stream s);
+int y2h_train_rnn_fused_backward(const float *out, float *delta, const float *x, const float *x_norm, const float *scales,
+                                 const float *mean, const float *variance, int act, int B, int H, const float *w, float *bias_step,
+                                 float *scale_step, float *mean_delta, float *variance_delta, float *dprev, float *ws, y2h_stream s);
+int y2h_train_rnn_delta(const float *out, float *delta, const float *x, const float *x_norm, const float *scales, const float *mean,
+                        const float *variance, int act, int T, int B, int C, float *bias_steps, float *scale_steps,
+                        float *mean_delta, float *variance_delta, y2h_stream s);
+int y2h_train_rnn_sum_steps(const float *steps, int T, int C, float *dst, y2h_stream s);
+int y2h_train_rnn_combine(const float *a, const float *b, float *dst, long n, y2h_stream s);
+int y2h_train_rnn_add_transposed(float *dst, const float *src, int outputs, int inputs, y2h_stream s);   /* dst[o][k] += src[k][o] */
+/* get_rnn_data (rnn.c:86-114) on the device: tok is [B][T + 1] bytes in HBM, every one below C (the caller checked); x and y
+ * are [T][B][C]: x[t*B + b] is the one-hot of tok[b][t], y[t*B + b] of tok[b][t + 1].  Every element is written. */
+int y2h_train_rnn_onehot(const unsigned char *tok, int T, int B, int C, float *x, float *y, y2h_stream s);
 
 /* ---- dreaming (y2_dream.hip): the picture side of nightmare.c's optimize_picture / run_nightmare ----
  * One resample is crop_image(src, cx, cy, cw, ch) -> resize_image(., ow, oh) -> crop_image(., px, py, ow, oh), both crops

@@ -28,6 +28,10 @@
  * in place; the draws, the truth and the packer are the device-free y2_aug.c.  The classifier loader (data.c:870-879
  * load_data_augment) is y2_train_load_classification, staged the same way: rotate_crop_image, flip and distortion are the
  * second kernel of y2_augment.hip, the draws and the label row come from y2_aug.c.
+ *
+ * An [rnn] trains by back-propagation through time (rnn_layer.c:83-172, CPU branch) in the composed form: the
+ * products that do not depend on the step before run once over all T*B rows, the self sub-layer's forward and its delta chain
+ * run step by step, the per-step batch-norm work runs as the grouped kernels of y2_train_rnn.hip.
  */
 #include <math.h>
 #include <stdio.h>
@@ -36,7 +40,7 @@
 #include <time.h>
 #include "y2_internal.h"
 
-typedef struct {
+typedef struct y2_tlayer {
     float *out, *delta;                 /* [batch][out_h][out_w][out_c] */
     float *x, *x_norm;                  /* batch-normalised convolutions */
     float *mean, *variance, *mean_delta, *variance_delta;
@@ -55,6 +59,16 @@ typedef struct {
     int alias;                          /* [dropout]: out and delta are the layer's in front, not owned */
     y2h_train_detection dt;             /* [detection] */
     y2h_train_detection_stats *dstats;
+    /* [rnn]: its three [connected] sub-layers input / self / output, each with out, delta, x, x_norm over all T*B rows
+     * (step-major), mean and variance [T][outputs] and dg the product over all rows; the T+1 state slots of [B][hidden];
+     * the per-step bias and scale sums.  out and delta of the [rnn] ARE the output sub-layer's (rnn_layer.c:58-59). */
+    struct y2_tlayer *sub;
+    float *state, *bias_steps, *scale_steps;
+    y2h_train_dense dg_step;            /* the self sub-layer: one step's B rows */
+    y2h_train_conv cg;                  /* a sub-layer whose hoisted weight gradient runs as the convolution template at size 1 */
+    int dw_conv;
+    int step_fwd_ranges, step_dx_ranges;
+    int fused;                          /* the self sub-layer's steps run as the fused kernels (rnn_step_form) */
 } y2_tlayer;
 
 typedef struct y2_trainer {
@@ -62,6 +76,10 @@ typedef struct y2_trainer {
     y2_tlayer *L;
     float *d_x_nchw, *d_x, *d_truth;    /* the step's input as given, as NHWC, and its truth */
     float *dense_ws;                    /* partial sums of the dense forward / input-gradient ranges */
+    float *step_ws;                     /* the fused backward step's partials (y2h_train_rnn_fused_ws_bytes) */
+    size_t step_ws_bytes;
+    float *dw_tmp;                      /* [inputs][outputs] landing buffer of an [rnn] sub-layer's weight gradient (rnn_dweight) */
+    size_t dw_tmp_floats;
     float *ws, *scratch, *stage;        /* weight-gradient partial tiles, reduction partials (and the region head's), NCHW staging
                                            of y2_train_pull and landing buffer of a delta's later writers */
     size_t truth_floats;                /* per step: batch * l.truths of a [region] head, batch * inputs of a [cost] */
@@ -261,21 +279,63 @@ void y2_train_unpack_dense_weights(const float *packed, float *ref, int outputs,
 /* ------------------------------------------------------------------ */
 /* refusals                                                            */
 /* ------------------------------------------------------------------ */
+/* an [rnn]: what backward_rnn_layer's CPU branch can be followed through */
+static int refuse_rnn(const network *net, int i)
+{
+    const layer *l = &net->layers[i];
+    const layer *subs[3] = { l->input_layer, l->self_layer, l->output_layer };
+    int k;
+    if (i + 1 >= net->n || (net->layers[i + 1].type != RNN && net->layers[i + 1].type != CONNECTED)) {
+        y2_fail("training: layer %d (rnn): a recurrent layer must feed an [rnn] or a [connected] layer", i);
+        return -1;
+    }
+    /* the parser already refuses an [rnn] behind an image (y2_cfg.c flat_before): this guards a network whose layer fields were
+     * set by hand.  The input sub-layer's weights are in the reference's column order, an image is ordered by pixel here. */
+    if (i == 0 ? (net->h > 0 && net->w > 0 && net->c > 1 && net->h * net->w > 1)
+               : (net->layers[i - 1].out_h * net->layers[i - 1].out_w > 1 && net->layers[i - 1].out_c > 1)) {
+        y2_fail("training: layer %d (rnn): a recurrent layer needs a flat input (inputs= in the [net], or a dense layer in front), not an image", i);
+        return -1;
+    }
+    if (l->shortcut) {
+        y2_fail("training: layer %d (rnn): shortcut=1 is not trainable (the reference's backward reads a state its forward did not produce)", i);
+        return -1;
+    }
+    if (l->self_layer->activation == LOGGY) { y2_fail("training: layer %d (rnn): logistic=2 (loggy) is not trainable", i); return -1; }
+    for (k = 0; k < 3; ++k) {
+        const ACTIVATION a = subs[k]->activation;
+        if (a != LINEAR && a != LEAKY && a != LOGISTIC && a != RELU) {
+            y2_fail("training: layer %d (rnn): activation %d is not trainable (linear, leaky, logistic, relu)", i, (int)a);
+            return -1;
+        }
+    }
+    if (l->batch_normalize && l->batch < 2) {
+        y2_fail("training: layer %d (rnn): batch normalisation over batch / time_steps = %d value divides by zero in the reference", i, l->batch);
+        return -1;
+    }
+    return 0;
+}
+
 static int refuse(const network *net)
 {
     const y2_engine *e = y2_engine_of(net);
     int i, flat = 0;           /* the running activation reads the same as [batch][c][h][w] and as [batch][h][w][c] */
     int det;                   /* the network ends in [detection]: [connected] and [dropout] train */
+    int rnn = 0;               /* the network holds an [rnn]: [connected] trains */
     if (!e || !net->layers || net->n <= 0) { y2_fail("y2_train_prepare: network has no engine (was it built by parse_network_cfg?)"); return -1; }
     if (e->half) { y2_fail("training is fp32 only: the network is in fp16 mode (y2_set_half / Y2_FP16)"); return -1; }
     if (e->lr.adam) { y2_fail("training: adam=1 is not implemented (SGD with momentum only)"); return -1; }
     if (e->lr.policy == Y2_LR_RANDOM) { y2_fail("training: policy=random is refused (its rate is a draw of rand(), not a function of the step)"); return -1; }
     if (e->lr.policy == Y2_LR_STEPS && !e->lr.num_steps) { y2_fail("training: STEPS policy must have steps and scales in cfg file"); return -1; }
     det = net->layers[net->n - 1].type == DETECTION;
+    for (i = 0; i < net->n; ++i) rnn |= net->layers[i].type == RNN;
     for (i = 0; i < net->n; ++i) {
         const layer *l = &net->layers[i];
         const char *t = get_layer_string(l->type);
-        if (is_recurrent(l)) { y2_fail("training: layer %d (%s): a recurrent network cannot be trained", i, t); return -1; }
+        if (l->type == GRU) {
+            y2_fail("training: layer %d (%s): a [gru] layer cannot be trained (the reference's backward_gru_layer is empty: there is no gradient to follow)", i, t);
+            return -1;
+        }
+        if (l->type == RNN && refuse_rnn(net, i) != 0) return -1;
         if ((l->type == SOFTMAX || l->type == COST) && !flat) {
             y2_fail("training: layer %d (%s): its input must be one value per channel (put an [avgpool] in front): rows of an "
                     "image are ordered by channel in the truth and by pixel on the device", i, t);
@@ -287,13 +347,13 @@ static int refuse(const network *net)
             return -1;
         }
         if (l->type == CONVOLUTIONAL || l->type == MAXPOOL) flat = l->out_h * l->out_w == 1 || l->out_c == 1;
-        if (l->type == AVGPOOL || l->type == CONNECTED) flat = 1;
+        if (l->type == AVGPOOL || l->type == CONNECTED || l->type == RNN) flat = 1;
         if (l->type == ROUTE || l->type == REORG || l->type == REGION) flat = 0;
         if ((l->type == ROUTE || l->type == REORG) && net->layers[net->n - 1].type != REGION) {
             y2_fail("training: layer %d (%s) trains only in a network that ends in [region]", i, t);
             return -1;
         }
-        if ((l->type == CONNECTED || l->type == DROPOUT) && !det) {
+        if ((l->type == CONNECTED || l->type == DROPOUT) && !det && !(rnn && l->type == CONNECTED)) {
             y2_fail("training: layer %d (%s) trains only in a network that ends in [detection]", i, t);
             return -1;
         }
@@ -355,6 +415,8 @@ static int refuse(const network *net)
         case DROPOUT:
             if (i == 0) { y2_fail("training: layer %d (%s): a dropout layer needs a layer in front of it", i, t); return -1; }
             break;
+        case RNN:           /* refuse_rnn above */
+            break;
         case DETECTION:
             if (l->random) {
                 y2_fail("training: layer %d (%s): random=1 is refused (it picks the box by a draw of rand() inside the loss while seen < 64000)", i, t);
@@ -373,11 +435,11 @@ static int refuse(const network *net)
             break;
         default:
             y2_fail("training: layer %d (%s) is not trainable (convolutional, maxpool, avgpool, softmax, cost, route, reorg, region; "
-                    "connected, dropout, detection in a network that ends in [detection])", i, t);
+                    "connected, dropout, detection in a network that ends in [detection]; rnn, and connected behind it)", i, t);
             return -1;
         }
     }
-    if (net->h <= 0 || net->w <= 0 || net->c <= 0) { y2_fail("training: the network input must be an image (h, w, c > 0)"); return -1; }
+    if ((net->h <= 0 || net->w <= 0 || net->c <= 0) && !(net->layers[0].type == RNN && net->inputs > 0)) { y2_fail("training: the network input must be an image (h, w, c > 0)"); return -1; }
     if (net->layers[net->n - 1].type != COST && net->layers[net->n - 1].type != REGION && !det) {
         y2_fail("training: layer %d (%s): the last layer must be [cost], [region] or [detection]", net->n - 1, get_layer_string(net->layers[net->n - 1].type));
         return -1;
@@ -414,7 +476,17 @@ void y2_train_free(network *net)
                          L->weight_updates, L->biases, L->bias_updates, L->scales, L->scale_updates, L->rolling_mean,
                          L->rolling_variance, L->cost };
         size_t k;
-        for (k = L->alias ? 2 : 0; k < sizeof all / sizeof all[0]; ++k) y2h_free(all[k]);
+        int m;
+        for (m = 0; L->sub && m < 3; ++m) {
+            y2_tlayer *S = &L->sub[m];
+            float *mine[] = { S->out, S->delta, S->x, S->x_norm, S->mean, S->variance, S->mean_delta, S->variance_delta, S->weights,
+                              S->weight_updates, S->biases, S->bias_updates, S->scales, S->scale_updates, S->rolling_mean,
+                              S->rolling_variance };
+            for (k = 0; k < sizeof mine / sizeof mine[0]; ++k) y2h_free(mine[k]);
+        }
+        y2h_free(L->state); y2h_free(L->bias_steps); y2h_free(L->scale_steps);
+        for (k = L->alias || L->sub ? 2 : 0; k < sizeof all / sizeof all[0]; ++k) y2h_free(all[k]);
+        free(L->sub);
         y2h_free(L->idx);
         y2h_free(L->stats);
         y2h_free(L->dstats);
@@ -423,6 +495,7 @@ void y2_train_free(network *net)
         free(L->src_add);
     }
     y2h_free(t->d_x_nchw); y2h_free(t->d_x); y2h_free(t->d_truth);
+    y2h_free(t->dw_tmp); y2h_free(t->step_ws);
     y2h_free(t->ws); y2h_free(t->scratch); y2h_free(t->stage); y2h_free(t->dense_ws);
     y2h_host_free(t->h_cost); y2h_host_free(t->h_in); y2h_host_free(t->h_pull);
     y2h_host_free(t->h_load); y2h_free(t->d_load);
@@ -447,6 +520,10 @@ static int push(float *dst, const float *src, size_t n, float *pinned, y2_engine
     return 0;
 }
 
+/* a [cost] over this many values or more sums in chunks (y2h_train_cost_sse_chunked); every network below it -- a classifier's
+ * batch x classes -- launches what it launched */
+#define COST_CHUNKED_FROM (1L << 20)
+
 static size_t max_z(size_t a, size_t b) { return a > b ? a : b; }
 
 /* the reference's backward order (network.c:204-223), walked once: who finds a delta already written */
@@ -470,12 +547,259 @@ static void plan_deltas(const network *net, y2_trainer *t)
     free(written);
 }
 
+/* ------------------------------------------------------------------ */
+/* [rnn]: back-propagation through time (rnn_layer.c:83-172) */
+/* ------------------------------------------------------------------ */
+static const layer *rnn_sub(const layer *l, int k) { return k == 0 ? l->input_layer : k == 1 ? l->self_layer : l->output_layer; }
+
+/* the bytes prepare_rnn is about to ask for, summed before the first of them is.  The sum decides nothing: the runtime layer
+ * has no query for free memory, so an allocation that fails is what stops y2_train_prepare, and the figure (a double: no
+ * overflow at any shape) is there for its message, which names the layer and the figure and so tells the caller what to
+ * shrink. */
+static double rnn_device_bytes(const network *net)
+{
+    double floats = 0;
+    int i, k;
+    for (i = 0; i < net->n; ++i) {
+        const layer *l = &net->layers[i];
+        const double rows = (double)l->steps * l->batch;
+        if (l->type != RNN) continue;
+        floats += (rows + l->batch) * l->hidden + 2. * l->steps * (l->hidden > l->outputs ? l->hidden : l->outputs);
+        for (k = 0; k < 3; ++k) {
+            const layer *s = rnn_sub(l, k);
+            floats += rows * s->outputs * (s->batch_normalize ? 4 : 2) + 2. * s->outputs * s->inputs + 2. * s->outputs;
+            if (s->batch_normalize) floats += (2. * l->steps + 6) * s->outputs;
+        }
+    }
+    return floats * sizeof(float);
+}
+
+/* Which kernels make a hoisted weight gradient over `rows` = T*B rows.  y2h_train_dense_dweight is laid out around few rows
+ * and walks all of them in one wave per 32 x 32 tile of the gradient; the convolution template at size 1 splits the rows.
+ * Measured: at 73 728 rows the template takes 3.01 ms against 4.87 (1024 inputs) and 0.81 against 4.71 (256), at
+ * 128 rows 0.021 against 0.015.  The crossing was not looked for: the template from 8192 rows on.  The template writes
+ * [inputs][outputs], so its result lands in a buffer of its own and is added transposed.
+ * Y2_RNN_TRAIN_DWEIGHT=dense|conv forces one at prepare time (tests). */
+#define RNN_DWEIGHT_CONV_FROM 8192
+/* Measured in alternating processes: the fused form LOSES, 251.3 ms a step against 164.0 at 128 x 576 and 11.0
+ * against 8.2 at 16 x 64 -- its hidden / 32 workgroups leave 224 of 256 CUs idle while the dense product spreads a step over
+ * K ranges -- so the rule chooses the composed form everywhere and the fused one runs only when forced. */
+#define RNN_STEP_DEFAULT_FUSED 0
+
+static int rnn_dweight_by_conv(long rows, int *by_conv)
+{
+    const char *f = getenv("Y2_RNN_TRAIN_DWEIGHT");
+    *by_conv = rows >= RNN_DWEIGHT_CONV_FROM;
+    if (!f || !*f) return 0;
+    if (!strcmp(f, "dense")) *by_conv = 0;
+    else if (!strcmp(f, "conv")) *by_conv = 1;
+    else { y2_fail("Y2_RNN_TRAIN_DWEIGHT=%s: unknown form (dense, conv)", f); return -1; }
+    return 0;
+}
+
+/* The form of the self sub-layer's steps.  The rule is y2h_train_rnn_fused_fits (B <= 128 rows, LDS, the partials' bytes);
+ * what fits takes RNN_STEP_DEFAULT_FUSED's form, everything else the composed one.  Y2_RNN_TRAIN_STEP=composed|fused forces a
+ * form at prepare time (tests); a forced fused form that does not fit is refused. */
+static int rnn_step_form(int i, int B, int hidden, int *fused)
+{
+    const char *f = getenv("Y2_RNN_TRAIN_STEP");
+    const int fits = y2h_train_rnn_fused_fits(B, hidden);
+    *fused = fits && RNN_STEP_DEFAULT_FUSED;
+    if (!f || !*f) return 0;
+    if (!strcmp(f, "composed")) *fused = 0;
+    else if (!strcmp(f, "fused")) {
+        if (!fits) {
+            y2_fail("training: layer %d (rnn): Y2_RNN_TRAIN_STEP=fused, but %d sequences of %d values do not fit the fused step kernels "
+                    "(at most 128 rows; partial sums within 256 MiB)", i, B, hidden);
+            return -1;
+        }
+        *fused = 1;
+    } else { y2_fail("Y2_RNN_TRAIN_STEP=%s: unknown form (composed, fused)", f); return -1; }
+    return 0;
+}
+
+static int rnn_dweight(y2_tlayer *S, const float *x, y2_trainer *t, y2_engine *e)
+{
+    const size_t nw = (size_t)S->dg.inputs * S->dg.outputs;
+    if (!S->dw_conv) { HIP_OR_ERR(y2h_train_dense_dweight(&S->dg, x, S->delta, S->weight_updates, e->stream)); return 0; }
+    HIP_OR_ERR(y2h_memset(t->dw_tmp, 0, nw * sizeof(float), e->stream));
+    HIP_OR_ERR(y2h_train_conv_dweight(&S->cg, x, S->delta, t->dw_tmp, t->ws, e->stream));
+    HIP_OR_ERR(y2h_train_rnn_add_transposed(S->weight_updates, t->dw_tmp, S->dg.outputs, S->dg.inputs, e->stream));
+    return 0;
+}
+
+static int prepare_rnn(network *net, int i, y2_trainer *t, y2_engine *e, float *pin, size_t *dense_ws, size_t *ws)
+{
+    const layer *l = &net->layers[i];
+    y2_tlayer *L = &t->L[i];
+    const int T = l->steps, B = l->batch, wide = l->hidden > l->outputs ? l->hidden : l->outputs;
+    int k;
+    if (!(L->sub = calloc(3, sizeof *L->sub))) { y2_fail("out of memory"); return -1; }
+    if (rnn_step_form(i, B, l->hidden, &L->fused) != 0) return -1;
+    if (L->fused) t->step_ws_bytes = max_z(t->step_ws_bytes, y2h_train_rnn_fused_ws_bytes(B, l->hidden));
+    if (dev_floats(&L->state, (size_t)(T + 1) * B * l->hidden, e) || dev_floats(&L->bias_steps, (size_t)T * wide, e) ||
+        dev_floats(&L->scale_steps, (size_t)T * wide, e)) return -1;
+    for (k = 0; k < 3; ++k) {
+        const layer *s = rnn_sub(l, k);
+        y2_tlayer *S = &L->sub[k];
+        const size_t outs = (size_t)T * B * s->outputs, nw = (size_t)s->outputs * s->inputs, n = s->outputs;
+        y2h_train_dense dg = { T * B, s->inputs, s->outputs }, step = { B, s->inputs, s->outputs };
+        size_t fw = 0, bw = 0, sfw = 0, sbw = 0;
+        S->dg = dg;
+        if (y2h_train_dense_plan(&dg, Y2H_DENSE_FORWARD, 0, &S->fwd_ranges, &fw, NULL, 0) != 0 ||
+            y2h_train_dense_plan(&dg, Y2H_DENSE_DINPUT, 0, &S->dx_ranges, &bw, NULL, 0) != 0 ||
+            (k == 1 && (y2h_train_dense_plan(&step, Y2H_DENSE_FORWARD, 0, &L->step_fwd_ranges, &sfw, NULL, 0) != 0 ||
+                        y2h_train_dense_plan(&step, Y2H_DENSE_DINPUT, 0, &L->step_dx_ranges, &sbw, NULL, 0) != 0))) {
+            y2_fail("training: layer %d (rnn): shape outside what the kernels take", i);
+            return -1;
+        }
+        if (k == 1) L->dg_step = step;
+        if (rnn_dweight_by_conv((long)T * B, &S->dw_conv) != 0) return -1;
+        if (S->dw_conv) {
+            y2h_train_conv cg = { T * B, 1, 1, s->inputs, s->outputs, 1, 0, 1, 1 };
+            S->cg = cg;
+            if (y2h_train_dweight_ws_bytes(&cg) == 0) { y2_fail("training: layer %d (rnn): shape outside what the kernels take", i); return -1; }
+            *ws = max_z(*ws, y2h_train_dweight_ws_bytes(&cg));
+            t->dw_tmp_floats = max_z(t->dw_tmp_floats, nw);
+        }
+        *dense_ws = max_z(*dense_ws, max_z(max_z(fw, bw), max_z(sfw, sbw)));
+        if (dev_floats(&S->out, outs, e) || dev_floats(&S->delta, outs, e) || dev_floats(&S->weights, nw, e) ||
+            dev_floats(&S->weight_updates, nw, e) || dev_floats(&S->biases, n, e) || dev_floats(&S->bias_updates, n, e) ||
+            push(S->weights, s->weights, nw, pin, e) || push(S->biases, s->biases, n, pin, e)) return -1;
+        if (!s->batch_normalize) continue;
+        if (dev_floats(&S->x, outs, e) || dev_floats(&S->x_norm, outs, e) || dev_floats(&S->mean, (size_t)T * n, e) ||
+            dev_floats(&S->variance, (size_t)T * n, e) || dev_floats(&S->mean_delta, n, e) || dev_floats(&S->variance_delta, n, e) ||
+            dev_floats(&S->scales, n, e) || dev_floats(&S->scale_updates, n, e) || dev_floats(&S->rolling_mean, n, e) ||
+            dev_floats(&S->rolling_variance, n, e) || push(S->scales, s->scales, n, pin, e) ||
+            push(S->rolling_mean, s->rolling_mean, n, pin, e) || push(S->rolling_variance, s->rolling_variance, n, pin, e)) return -1;
+    }
+    L->out = L->sub[2].out;             /* rnn_layer.c:58-59 */
+    L->delta = L->sub[2].delta;
+    return 0;
+}
+
+/* forward_connected_layer behind its product, on `groups` steps of B rows from step t0: each step normalises over its own
+ * rows and moves the rolling statistics once, in step order */
+static int rnn_sub_forward(const layer *s, y2_tlayer *S, int t0, int groups, int B, y2_engine *e)
+{
+    const size_t n = s->outputs, off = (size_t)t0 * B * n;
+    if (!s->batch_normalize)
+        return y2h_train_bn_apply(S->out + off, NULL, NULL, NULL, NULL, NULL, S->biases, y2_act_code(s->activation), (long)groups * B, s->outputs, e->stream);
+    HIP_OR_ERR(y2h_train_rnn_bn_stats(S->out + off, groups, B, s->outputs, S->mean + t0 * n, S->variance + t0 * n, S->rolling_mean,
+                                      S->rolling_variance, .95f, .05f, e->stream));
+    HIP_OR_ERR(y2h_train_rnn_bn_apply(S->out + off, S->x + off, S->x_norm + off, S->mean + t0 * n, S->variance + t0 * n, S->scales, S->biases,
+                                      y2_act_code(s->activation), groups, B, s->outputs, e->stream));
+    return 0;
+}
+
+/* backward_connected_layer in front of its products, on `groups` steps from step t0, the steps' bias and scale sums into
+ * slots t0.. of the layer's [T][n] buffers.  increment_layer does not advance mean and variance: every step's backward
+ * reads the LAST step's statistics with its own x and x_norm, as the compiled reference does. */
+static int rnn_sub_delta(const layer *s, y2_tlayer *S, y2_tlayer *L, int t0, int groups, int T, int B, y2_engine *e)
+{
+    const size_t n = s->outputs, off = (size_t)t0 * B * n, last = (size_t)(T - 1) * n;
+    const int bn = s->batch_normalize;
+    HIP_OR_ERR(y2h_train_rnn_delta(S->out + off, S->delta + off, bn ? S->x + off : NULL, bn ? S->x_norm + off : NULL, S->scales,
+                                   bn ? S->mean + last : NULL, bn ? S->variance + last : NULL, y2_act_code(s->activation), groups, B,
+                                   s->outputs, L->bias_steps + t0 * n, L->scale_steps + t0 * n, S->mean_delta, S->variance_delta, e->stream));
+    return 0;
+}
+
+/* the T per-step sums, added to the update buffers last step first: the order in which the reference's loop meets them */
+static int rnn_sub_sums(const layer *s, y2_tlayer *S, y2_tlayer *L, int T, y2_engine *e)
+{
+    HIP_OR_ERR(y2h_train_rnn_sum_steps(L->bias_steps, T, s->outputs, S->bias_updates, e->stream));
+    if (s->batch_normalize) HIP_OR_ERR(y2h_train_rnn_sum_steps(L->scale_steps, T, s->outputs, S->scale_updates, e->stream));
+    return 0;
+}
+
+/* THE COPY POINT (rnn_layer.c:161): input.delta[t] is self.delta[t] as the self sub-layer's backward LEFT it, its activation
+ * gradient and batch-norm backward applied in place -- the compiled CPU path, the project's parity.  The reference's GPU twin
+ * copies before that backward (rnn_layer.c:258), which is the true gradient; the two differ whenever the self sub-layer is
+ * not a plain linear one.  Every self.delta[t] is final once the chain has passed t, so all T copies are one. */
+static int rnn_copy_point(const layer *l, y2_tlayer *L, y2_engine *e)
+{
+    HIP_OR_ERR(y2h_memcpy_d2d(L->sub[0].delta, L->sub[1].delta, (size_t)l->steps * l->batch * l->hidden * sizeof(float), e->stream));
+    return 0;
+}
+
+static int forward_rnn(const layer *l, y2_tlayer *L, const float *in, y2_trainer *t, y2_engine *e)
+{
+    const int T = l->steps, B = l->batch;
+    const size_t bh = (size_t)B * l->hidden;
+    y2_tlayer *S0 = &L->sub[0], *S1 = &L->sub[1], *S2 = &L->sub[2];
+    int k;
+    /* state.train: slot 0 is zero at every step.  No delta is zeroed: each of the three has a first writer that stores */
+    HIP_OR_ERR(y2h_memset(L->state, 0, bh * sizeof(float), e->stream));
+    HIP_OR_ERR(y2h_train_dense_forward(&S0->dg, in, S0->weights, S0->out, t->dense_ws, S0->fwd_ranges, e->stream));
+    if (rnn_sub_forward(l->input_layer, S0, 0, T, B, e) != 0) return -1;
+    for (k = 0; k < T; ++k) {           /* step k reads slot k and writes slot k + 1 */
+        const int bn = l->self_layer->batch_normalize;
+        const size_t h = l->hidden;
+        if (L->fused) {         /* the product on the matrix cores and all of the below: one launch */
+            HIP_OR_ERR(y2h_train_rnn_fused_forward(L->state + k * bh, S1->weights, S1->out + k * bh, bn ? S1->x + k * bh : NULL,
+                                                   bn ? S1->x_norm + k * bh : NULL, bn ? S1->mean + k * h : NULL,
+                                                   bn ? S1->variance + k * h : NULL, S1->rolling_mean, S1->rolling_variance, .95f, .05f,
+                                                   S1->scales, S1->biases, y2_act_code(l->self_layer->activation), B, l->hidden,
+                                                   S0->out + k * bh, L->state + (k + 1) * bh, e->stream));
+            continue;
+        }
+        HIP_OR_ERR(y2h_train_dense_forward(&L->dg_step, L->state + k * bh, S1->weights, S1->out + k * bh, t->dense_ws, L->step_fwd_ranges, e->stream));
+        /* statistics over the step's own rows, the rolling update, apply and the combine into slot k + 1: one launch */
+        HIP_OR_ERR(y2h_train_rnn_step_finish(S1->out + k * bh, bn ? S1->x + k * bh : NULL, bn ? S1->x_norm + k * bh : NULL,
+                                             bn ? S1->mean + k * h : NULL, bn ? S1->variance + k * h : NULL, S1->rolling_mean,
+                                             S1->rolling_variance, .95f, .05f, S1->scales, S1->biases, y2_act_code(l->self_layer->activation),
+                                             B, l->hidden, S0->out + k * bh, L->state + (k + 1) * bh, e->stream));
+    }
+    HIP_OR_ERR(y2h_train_dense_forward(&S2->dg, L->state + bh, S2->weights, S2->out, t->dense_ws, S2->fwd_ranges, e->stream));
+    return rnn_sub_forward(l->output_layer, S2, 0, T, B, e);
+}
+
+/* in: the layer's input rows; din: where its input gradient is stored (NULL: layer 0) */
+static int backward_rnn(const layer *l, y2_tlayer *L, const float *in, float *din, y2_trainer *t, y2_engine *e)
+{
+    const int T = l->steps, B = l->batch;
+    const size_t bh = (size_t)B * l->hidden;
+    y2_tlayer *S0 = &L->sub[0], *S1 = &L->sub[1], *S2 = &L->sub[2];
+    int k;
+    /* the output sub-layer, all steps at once; its input is slots 1..T, its input gradient the first writer of self.delta */
+    if (rnn_sub_delta(l->output_layer, S2, L, 0, T, T, B, e) != 0 || rnn_sub_sums(l->output_layer, S2, L, T, e) != 0) return -1;
+    if (rnn_dweight(S2, L->state + bh, t, e) != 0) return -1;
+    HIP_OR_ERR(y2h_train_dense_dinput(&S2->dg, S2->delta, S2->weights, S1->delta, 0, t->dense_ws, S2->dx_ranges, e->stream));
+    /* the self sub-layer's delta chain, last step first; step 0 has no input gradient */
+    for (k = T - 1; k >= 0; --k) {
+        if (L->fused) {         /* the delta work and the partial products in one launch, the range-order sum in a second */
+            const layer *s = l->self_layer;
+            const size_t n = l->hidden, last = (size_t)(T - 1) * n;
+            const int bn = s->batch_normalize;
+            HIP_OR_ERR(y2h_train_rnn_fused_backward(S1->out + k * bh, S1->delta + k * bh, bn ? S1->x + k * bh : NULL,
+                                                    bn ? S1->x_norm + k * bh : NULL, S1->scales, bn ? S1->mean + last : NULL,
+                                                    bn ? S1->variance + last : NULL, y2_act_code(s->activation), B, l->hidden, S1->weights,
+                                                    L->bias_steps + k * n, L->scale_steps + k * n, S1->mean_delta, S1->variance_delta,
+                                                    k > 0 ? S1->delta + (k - 1) * bh : NULL, t->step_ws, e->stream));
+            continue;
+        }
+        if (rnn_sub_delta(l->self_layer, S1, L, k, 1, T, B, e) != 0) return -1;
+        if (k > 0) HIP_OR_ERR(y2h_train_dense_dinput(&L->dg_step, S1->delta + k * bh, S1->weights, S1->delta + (k - 1) * bh, 1, t->dense_ws,
+                                                     L->step_dx_ranges, e->stream));
+    }
+    if (rnn_sub_sums(l->self_layer, S1, L, T, e) != 0) return -1;
+    if (rnn_dweight(S1, L->state, t, e) != 0) return -1;        /* its input is slots 0..T-1 */
+    if (rnn_copy_point(l, L, e) != 0) return -1;
+    /* the input sub-layer, all steps at once */
+    if (rnn_sub_delta(l->input_layer, S0, L, 0, T, T, B, e) != 0 || rnn_sub_sums(l->input_layer, S0, L, T, e) != 0) return -1;
+    if (rnn_dweight(S0, in, t, e) != 0) return -1;
+    if (din) HIP_OR_ERR(y2h_train_dense_dinput(&S0->dg, S0->delta, S0->weights, din, 0, t->dense_ws, S0->dx_ranges, e->stream));
+    return 0;
+}
+
 int y2_train_prepare(network *net)
 {
     y2_engine *e = y2_engine_of(net);
     y2_trainer *t;
     float *pin, *tmp = NULL;
     size_t ws = 16, scratch = 16, dense_ws = 16, stage;
+    double rnn_bytes;
     int i, rc = -1;
     if (refuse(net) != 0) return -1;
     y2_train_free(net);
@@ -491,9 +815,15 @@ int y2_train_prepare(network *net)
     for (i = 0; i < net->n; ++i) {
         const layer *l = &net->layers[i];
         stage = max_z(stage, (size_t)net->batch * l->outputs);
+        if (l->type == RNN) {       /* a sub-layer's rows, its weights, the state history */
+            stage = max_z(stage, (size_t)(net->batch + l->batch) * l->hidden);
+            stage = max_z(stage, (size_t)l->hidden * (size_t)(l->hidden > l->inputs ? l->hidden : l->inputs));
+            stage = max_z(stage, (size_t)l->hidden * l->outputs);
+        }
         if (l->type == CONVOLUTIONAL || l->type == CONNECTED) stage = max_z(stage, (size_t)l->n * l->c * l->size * l->size);
     }
     t->stage_floats = stage;
+    rnn_bytes = rnn_device_bytes(net);
     if (y2h_host_alloc((void **)&t->h_pull, stage * sizeof(float)) != 0) { y2_fail("y2_train_prepare: no pinned memory: %s", y2h_last_error()); goto cleanup; }
     pin = t->h_pull;
     tmp = malloc(stage * sizeof(float));
@@ -522,9 +852,20 @@ int y2_train_prepare(network *net)
             HIP_OR_CLEANUP(y2h_host_alloc((void **)&L->h_rnd, outs * sizeof(float)));
             continue;
         }
+        if (l->type == RNN) {
+            if (prepare_rnn(net, i, t, e, pin, &dense_ws, &ws) != 0) {
+                char why[256];
+                snprintf(why, sizeof why, "%s", y2_last_error());
+                y2_fail("y2_train_prepare: layer %d (rnn): its training buffers (%.1f MB for the network's recurrent layers) could not be made: %s",
+                        i, rnn_bytes / 1048576., why);
+                goto cleanup;
+            }
+            continue;
+        }
         if (dev_floats(&L->out, outs, e) || dev_floats(&L->delta, outs, e)) goto cleanup;
         if (l->type == MAXPOOL) HIP_OR_CLEANUP(y2h_malloc((void **)&L->idx, outs * sizeof(int)));
         if (l->type == COST && dev_floats(&L->cost, 1, e)) goto cleanup;
+        if (l->type == COST) scratch = max_z(scratch, Y2H_COST_CHUNKS * sizeof(float));
         if (l->type == REGION) {
             y2h_train_region rg = { net->batch, l->h, l->w, l->n, l->classes, l->bias_match, l->rescore, l->thresh, l->coord_scale,
                                     l->object_scale, l->noobject_scale, l->class_scale };
@@ -581,6 +922,8 @@ int y2_train_prepare(network *net)
                 push(L->rolling_variance, l->rolling_variance, l->n, pin, e)) goto cleanup;
         }
     }
+    if (t->dw_tmp_floats && dev_floats(&t->dw_tmp, t->dw_tmp_floats, e)) goto cleanup;
+    if (t->step_ws_bytes) HIP_OR_CLEANUP(y2h_malloc((void **)&t->step_ws, t->step_ws_bytes));
     HIP_OR_CLEANUP(y2h_malloc((void **)&t->ws, ws));
     HIP_OR_CLEANUP(y2h_malloc((void **)&t->dense_ws, dense_ws));
     HIP_OR_CLEANUP(y2h_malloc((void **)&t->scratch, scratch));
@@ -621,8 +964,12 @@ static int forward_train(network *net, y2_trainer *t, y2_engine *e)
         case SOFTMAX:
             HIP_OR_ERR(y2h_train_softmax(in, L->out, net->batch, l->inputs, l->temperature, e->stream));
             break;
-        case COST:      /* forward and backward_cost_layer in one launch */
-            HIP_OR_ERR(y2h_train_cost_sse(in, t->d_truth, L->out, L->delta, t->L[i - 1].delta, l->scale, (long)net->batch * l->inputs, L->cost, e->stream));
+        case COST:      /* forward and backward_cost_layer in one launch; over COST_CHUNKED_FROM values (a char-rnn's rows) in chunks */
+            if ((long)net->batch * l->inputs >= COST_CHUNKED_FROM)
+                HIP_OR_ERR(y2h_train_cost_sse_chunked(in, t->d_truth, L->out, L->delta, t->L[i - 1].delta, l->scale, (long)net->batch * l->inputs,
+                                                      L->cost, t->scratch, e->stream));
+            else
+                HIP_OR_ERR(y2h_train_cost_sse(in, t->d_truth, L->out, L->delta, t->L[i - 1].delta, l->scale, (long)net->batch * l->inputs, L->cost, e->stream));
             break;
         case ROUTE: {
             int k, off = 0;
@@ -659,6 +1006,9 @@ static int forward_train(network *net, y2_trainer *t, y2_engine *e)
         case DETECTION:     /* forward and backward_detection_layer; the last layer, so the first writer of the delta in front */
             HIP_OR_ERR(y2h_train_detection_loss(&L->dt, in, t->d_truth, L->out, L->delta, t->L[i - 1].delta, 0, L->cost, L->dstats,
                                                 t->scratch, e->stream));
+            break;
+        case RNN:
+            if (forward_rnn(l, L, in, t, e) != 0) return -1;
             break;
         default:
             return -1;
@@ -719,6 +1069,9 @@ static int backward_train(network *net, y2_trainer *t, y2_engine *e)
              * kernel's own add mode is exercised by the product test alone */
             if (din) HIP_OR_ERR(y2h_train_dense_dinput(&L->dg, L->delta, L->weights, din, 0, t->dense_ws, L->dx_ranges, e->stream));
             break;
+        case RNN:
+            if (backward_rnn(l, L, in, din, t, e) != 0) return -1;
+            break;
         case DROPOUT:       /* dropout_layer.c:50-59: the delta in front, in place */
             if (own) HIP_OR_ERR(y2h_train_dropout(own, L->rnd, l->probability, (float)(1. / (1. - l->probability)), net->batch, L->src_c,
                                                   L->src_h * L->src_w, e->stream));
@@ -751,6 +1104,18 @@ static int update_train(network *net, y2_trainer *t, y2_engine *e)
     for (i = 0; i < net->n; ++i) {
         const layer *l = &net->layers[i];
         y2_tlayer *L = &t->L[i];
+        if (l->type == RNN) {           /* update_rnn_layer: three update_connected_layer calls */
+            int k;
+            for (k = 0; k < 3; ++k) {
+                const layer *s = rnn_sub(l, k);
+                y2_tlayer *S = &L->sub[k];
+                HIP_OR_ERR(y2h_train_sgd(S->biases, S->bias_updates, s->outputs, rate / batch, 0.f, net->momentum, e->stream));
+                if (s->batch_normalize) HIP_OR_ERR(y2h_train_sgd(S->scales, S->scale_updates, s->outputs, rate / batch, 0.f, net->momentum, e->stream));
+                HIP_OR_ERR(y2h_train_sgd(S->weights, S->weight_updates, (long)s->outputs * s->inputs, rate / batch, -net->decay * batch,
+                                         net->momentum, e->stream));
+            }
+            continue;
+        }
         if (l->type != CONVOLUTIONAL && l->type != CONNECTED) continue;     /* update_connected_layer has the convolution's order */
         HIP_OR_ERR(y2h_train_sgd(L->biases, L->bias_updates, l->n, rate / batch, 0.f, net->momentum, e->stream));
         if (l->batch_normalize) HIP_OR_ERR(y2h_train_sgd(L->scales, L->scale_updates, l->n, rate / batch, 0.f, net->momentum, e->stream));
@@ -770,7 +1135,10 @@ static int step_enqueue(network *net, const float *d_x_nchw, const float *d_y, f
     float sum = 0;
     if (d_x_nchw) {
         t->loaded = 0;
-        HIP_OR_ERR(y2h_nchw_to_nhwc(d_x_nchw, t->d_x, net->batch, net->c, net->h, net->w, net->c, e->stream));
+        if (net->h > 0 && net->w > 0 && net->c > 0)
+            HIP_OR_ERR(y2h_nchw_to_nhwc(d_x_nchw, t->d_x, net->batch, net->c, net->h, net->w, net->c, e->stream));
+        else            /* a flat input (inputs= in front of an [rnn]): rows as given */
+            HIP_OR_ERR(y2h_memcpy_d2d(t->d_x, d_x_nchw, (size_t)net->batch * net->inputs * sizeof(float), e->stream));
     }
     if (d_y != t->d_truth)
         HIP_OR_ERR(y2h_memcpy_d2d(t->d_truth, d_y, t->truth_floats * sizeof(float), e->stream));
@@ -991,12 +1359,78 @@ int y2_train_load_classification(network *net, const y2_aug_cls_item *items, con
     return 0;
 }
 
+/* ------------------------------------------------------------------ */
+/* the char-rnn loader (rnn.c:86-114 get_rnn_data)                      */
+/* ------------------------------------------------------------------ */
+int y2_get_rnn_data(const unsigned char *text, size_t *offsets, int characters, size_t len, int batch, int steps, float *x, float *y)
+{
+    int i, j;
+    if (!text || !offsets || !x || !y || characters <= 0 || len == 0 || batch <= 0 || steps <= 0) { y2_fail("get_rnn_data: bad arguments"); return -1; }
+    for (i = 0; i < batch; ++i) {           /* checked before anything is written or moved: the reference exits half-way */
+        size_t o = offsets[i];
+        for (j = 0; j <= steps; ++j, ++o) {
+            const unsigned char ch = text[o % len];
+            if (ch == 0 || ch >= characters) { y2_fail("get_rnn_data: Bad char (byte %d at offset %zu; the network reads %d characters)", (int)ch, o % len, characters); return -1; }
+        }
+    }
+    memset(x, 0, (size_t)batch * steps * characters * sizeof(float));
+    memset(y, 0, (size_t)batch * steps * characters * sizeof(float));
+    for (i = 0; i < batch; ++i)
+        for (j = 0; j < steps; ++j) {
+            const unsigned char curr = text[offsets[i] % len], next = text[(offsets[i] + 1) % len];
+            x[((size_t)j * batch + i) * characters + curr] = 1;
+            y[((size_t)j * batch + i) * characters + next] = 1;
+            offsets[i] = (offsets[i] + 1) % len;
+        }
+    return 0;
+}
+
+int y2_train_load_rnn_data(network *net, const unsigned char *text, size_t len, size_t *offsets)
+{
+    static const char who[] = "y2_train_load_rnn_data";
+    y2_engine *e;
+    y2_trainer *t;
+    unsigned char *tok;
+    int T, B, i, j;
+    if (!net || !net->layers || net->n <= 0) { y2_fail("%s: no network", who); return -1; }
+    e = y2_engine_of(net);
+    if (e && e->trainer) e->trainer->loaded = 0;         /* a refused load leaves nothing to step on */
+    if (!text || !len || !offsets) { y2_fail("%s: NULL text or offsets", who); return -1; }
+    /* a trainer of this batch exists only for a network y2_train_prepare accepted: the loop's calls skip the walk */
+    if (!(e && e->trainer && e->trainer->batch == net->batch) && refuse(net) != 0) return -1;
+    if (net->layers[0].type != RNN || truths_per_image(net) != net->inputs) {
+        y2_fail("%s: the network must start with an [rnn] and end in a [cost] over as many values as it reads (one-hot in, one-hot truth)", who);
+        return -1;
+    }
+    T = net->time_steps; B = net->batch / T;
+    for (i = 0; i < B; ++i)
+        for (j = 0; j <= T; ++j) {
+            const unsigned char ch = text[(offsets[i] + j) % len];
+            if (ch == 0 || ch >= net->inputs) { y2_fail("%s: Bad char (byte %d at offset %zu; the network reads %d characters)", who, (int)ch, (offsets[i] + j) % len, net->inputs); return -1; }
+        }
+    if (!(t = trainer_for_step(net))) return -1;
+    e = y2_engine_of(net);
+    t->loaded = 0;
+    if (grow_load(t, (size_t)B * (T + 1)) != 0) return -1;   /* free: the last load waited for its copy before it returned */
+    tok = t->h_load;
+    for (i = 0; i < B; ++i) {
+        for (j = 0; j <= T; ++j) tok[(size_t)i * (T + 1) + j] = text[(offsets[i] + j) % len];
+        offsets[i] = (offsets[i] + T) % len;            /* T times (o + 1) % len */
+    }
+    HIP_OR_ERR(y2h_memcpy_h2d(t->d_load, t->h_load, (size_t)B * (T + 1), e->stream));
+    HIP_OR_ERR(y2h_event_record(t->ev_load, e->stream));
+    HIP_OR_ERR(y2h_train_rnn_onehot(t->d_load, T, B, net->inputs, t->d_x, t->d_truth, e->stream));
+    HIP_OR_ERR(y2h_event_sync(t->ev_load));         /* recorded behind the copy, in front of the kernel: the pinned bytes are free again */
+    t->loaded = 1;
+    return 0;
+}
+
 int y2_train_step_loaded(network *net, float *loss)
 {
     y2_engine *e = net ? y2_engine_of(net) : NULL;
     y2_trainer *t = e ? e->trainer : NULL;
     if (!t || !t->loaded || t->batch != net->batch) {
-        y2_fail("y2_train_step_loaded: nothing is loaded (y2_train_load_detection / y2_train_load_classification; set_batch_network and resize_network drop a load)");
+        y2_fail("y2_train_step_loaded: nothing is loaded (y2_train_load_detection / y2_train_load_classification / y2_train_load_rnn_data; set_batch_network and resize_network drop a load)");
         return -1;
     }
     HIP_OR_ERR(y2h_set_device(e->device));
@@ -1025,6 +1459,40 @@ static int pull_flat(y2_engine *e, const float *src, float *dst, size_t n)
     return 0;
 }
 
+/* one array of sub-layer k of an [rnn]: activations over all T*B rows, step-major; mean and variance as the reference's
+ * arrays hold them after a step, the LAST time step's */
+static int pull_rnn(network *net, int i, int k, int what, float *dst, size_t n)
+{
+    y2_engine *e = y2_engine_of(net);
+    const layer *l = &net->layers[i], *s = rnn_sub(l, k);
+    const y2_tlayer *S = &e->trainer->L[i].sub[k];
+    const size_t rows = (size_t)l->steps * l->batch, last = (size_t)(l->steps - 1) * s->outputs;
+    const float *src = NULL;
+    size_t have = s->outputs;
+    switch (what) {
+    case Y2_TRAIN_OUTPUT: src = S->out; have *= rows; break;
+    case Y2_TRAIN_DELTA: src = S->delta; have *= rows; break;
+    case Y2_TRAIN_X: src = S->x; have *= rows; break;
+    case Y2_TRAIN_X_NORM: src = S->x_norm; have *= rows; break;
+    case Y2_TRAIN_MEAN: src = S->mean ? S->mean + last : NULL; break;
+    case Y2_TRAIN_VARIANCE: src = S->variance ? S->variance + last : NULL; break;
+    case Y2_TRAIN_MEAN_DELTA: src = S->mean_delta; break;
+    case Y2_TRAIN_VARIANCE_DELTA: src = S->variance_delta; break;
+    case Y2_TRAIN_WEIGHT_UPDATES: src = S->weight_updates; have *= s->inputs; break;
+    case Y2_TRAIN_WEIGHTS: src = S->weights; have *= s->inputs; break;
+    case Y2_TRAIN_BIAS_UPDATES: src = S->bias_updates; break;
+    case Y2_TRAIN_BIASES: src = S->biases; break;
+    case Y2_TRAIN_SCALE_UPDATES: src = S->scale_updates; break;
+    case Y2_TRAIN_SCALES: src = S->scales; break;
+    case Y2_TRAIN_ROLLING_MEAN: src = S->rolling_mean; break;
+    case Y2_TRAIN_ROLLING_VARIANCE: src = S->rolling_variance; break;
+    }
+    if (!src) { y2_fail("y2_train_pull: layer %d (rnn) sub-layer %d has no array %d", i, k, what); return -1; }
+    if (n != have) { y2_fail("y2_train_pull: layer %d sub-layer %d array %d holds %zu floats, not %zu", i, k, what, have, n); return -1; }
+    HIP_OR_ERR(y2h_set_device(e->device));
+    return pull_flat(e, src, dst, n);
+}
+
 int y2_train_pull(network *net, int i, int what, float *dst, size_t n)
 {
     y2_engine *e = y2_engine_of(net);
@@ -1038,6 +1506,17 @@ int y2_train_pull(network *net, int i, int what, float *dst, size_t n)
     if (i < 0 || i >= net->n || !dst) { y2_fail("y2_train_pull: layer %d of %d", i, net->n); return -1; }
     l = &net->layers[i];
     L = &t->L[i];
+    if (what >> 8) {                                        /* Y2_TRAIN_SUB(k, what) */
+        if (l->type != RNN || (what >> 8) > 3) { y2_fail("y2_train_pull: layer %d (%s) has no sub-layer %d", i, get_layer_string(l->type), (what >> 8) - 1); return -1; }
+        return pull_rnn(net, i, (what >> 8) - 1, what & 255, dst, n);
+    }
+    if (what == Y2_TRAIN_STATE) {
+        const size_t have = l->type == RNN ? (size_t)(l->steps + 1) * l->batch * l->hidden : 0;
+        if (!have) { y2_fail("y2_train_pull: layer %d (%s) has no state", i, get_layer_string(l->type)); return -1; }
+        if (n != have) { y2_fail("y2_train_pull: layer %d state holds %zu floats, not %zu", i, have, n); return -1; }
+        HIP_OR_ERR(y2h_set_device(e->device));
+        return pull_flat(e, L->state, dst, n);
+    }
     switch (what) {
     case Y2_TRAIN_OUTPUT: src = L->out; image = 1; break;
     case Y2_TRAIN_DELTA: src = L->delta; image = 1; break;
@@ -1088,7 +1567,9 @@ int y2_train_pull_input(network *net, float *x_nchw, float *truth)
     y2_trainer *t = e ? e->trainer : NULL;
     if (!t || !t->loaded) { y2_fail("y2_train_pull_input: nothing is loaded (y2_train_load_detection / y2_train_load_classification)"); return -1; }
     HIP_OR_ERR(y2h_set_device(e->device));
-    if (x_nchw) {
+    if (x_nchw && !(net->h > 0 && net->w > 0 && net->c > 0)) {        /* a flat input: rows as they are */
+        if (pull_flat(e, t->d_x, x_nchw, (size_t)net->batch * net->inputs) != 0) return -1;
+    } else if (x_nchw) {
         HIP_OR_ERR(y2h_nhwc_to_nchw(t->d_x, net->c, t->stage, net->batch, net->c, net->h, net->w, e->stream));
         if (pull_flat(e, t->stage, x_nchw, (size_t)net->batch * net->inputs) != 0) return -1;
     }
@@ -1137,6 +1618,19 @@ int y2_train_sync_if_dirty(network *net)
     if (!t || !t->dirty) return 0;
     for (i = 0; i < net->n; ++i) {
         layer *l = &net->layers[i];
+        if (l->type == RNN) {           /* the three sub-layers' weights, biases, scales and rolling statistics */
+            int k;
+            for (k = 0; k < 3; ++k) {
+                const layer *s = rnn_sub(l, k);
+                if (y2_train_pull(net, i, Y2_TRAIN_SUB(k, Y2_TRAIN_WEIGHTS), s->weights, (size_t)s->outputs * s->inputs) != 0 ||
+                    y2_train_pull(net, i, Y2_TRAIN_SUB(k, Y2_TRAIN_BIASES), s->biases, s->outputs) != 0) return -1;
+                if (s->batch_normalize &&
+                    (y2_train_pull(net, i, Y2_TRAIN_SUB(k, Y2_TRAIN_SCALES), s->scales, s->outputs) != 0 ||
+                     y2_train_pull(net, i, Y2_TRAIN_SUB(k, Y2_TRAIN_ROLLING_MEAN), s->rolling_mean, s->outputs) != 0 ||
+                     y2_train_pull(net, i, Y2_TRAIN_SUB(k, Y2_TRAIN_ROLLING_VARIANCE), s->rolling_variance, s->outputs) != 0)) return -1;
+            }
+            continue;
+        }
         if (l->type != CONVOLUTIONAL && l->type != CONNECTED) continue;
         if (y2_train_pull(net, i, Y2_TRAIN_WEIGHTS, l->weights, (size_t)l->n * l->c * l->size * l->size) != 0 ||
             y2_train_pull(net, i, Y2_TRAIN_BIASES, l->biases, l->n) != 0) return -1;

@@ -332,6 +332,38 @@ __global__ __launch_bounds__(256) void cost_sse(const float *__restrict__ pred, 
     if (threadIdx.x == 0) cost[0] = sh[0];
 }
 
+// chunk b of gridDim.x: the same lane sums and tree over its contiguous part -> part[b]
+__global__ __launch_bounds__(256) void cost_sse_chunk(const float *__restrict__ pred, const float *__restrict__ truth,
+                                                      float *__restrict__ error, float *__restrict__ delta,
+                                                      float *__restrict__ delta_prev, float scale, long n, float *__restrict__ part)
+{
+    __shared__ float sh[256];
+    const long chunk = (n + gridDim.x - 1) / gridDim.x, e0 = blockIdx.x * chunk, e1 = e0 + chunk < n ? e0 + chunk : n;
+    float s = 0.f;
+    for (long e = e0 + threadIdx.x; e < e1; e += 256) {
+        const float d = truth[e] - pred[e];
+        const float sq = d * d;
+        error[e] = sq;
+        delta[e] = d;
+        delta_prev[e] = scale * d;
+        s += sq;
+    }
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[blockIdx.x] = sh[0];
+}
+
+__global__ void cost_sse_sum(const float *__restrict__ part, int chunks, float *__restrict__ cost)
+{
+    float s = 0.f;
+    for (int b = 0; b < chunks; ++b) s += part[b];
+    cost[0] = s;
+}
+
 // dropout_layer.c:38-59 on a dense NHWC tensor; the draws are indexed as the reference's [batch][c][hw]
 __global__ void dropout_apply(float *__restrict__ x, const float *__restrict__ rnd, float probability, float scale, long n, int c, int hw)
 {
@@ -537,6 +569,17 @@ int y2h_train_cost_sse(const float *pred, const float *truth, float *error, floa
 {
     if (!pred || !truth || !error || !delta || !delta_prev || !cost || n <= 0) return Y2H_EINVAL;
     cost_sse<<<1, 256, 0, S(s)>>>(pred, truth, error, delta, delta_prev, scale, n, cost);
+    Y2H_LAUNCH_CHECK();
+    return Y2H_OK;
+}
+
+int y2h_train_cost_sse_chunked(const float *pred, const float *truth, float *error, float *delta, float *delta_prev, float scale,
+                               long n, float *cost, float *scratch, y2h_stream s)
+{
+    if (!pred || !truth || !error || !delta || !delta_prev || !cost || !scratch || n <= 0) return Y2H_EINVAL;
+    cost_sse_chunk<<<Y2H_COST_CHUNKS, 256, 0, S(s)>>>(pred, truth, error, delta, delta_prev, scale, n, scratch);
+    Y2H_LAUNCH_CHECK();
+    cost_sse_sum<<<1, 1, 0, S(s)>>>(scratch, Y2H_COST_CHUNKS, cost);
     Y2H_LAUNCH_CHECK();
     return Y2H_OK;
 }

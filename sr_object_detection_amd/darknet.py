@@ -501,6 +501,21 @@ def lib():
     L.y2h_train_softmax.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]
     L.y2h_train_cost_sse.argtypes = [C.c_void_p] * 5 + [C.c_float, C.c_long, C.c_void_p, C.c_void_p]
     L.y2h_train_sgd.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_float, C.c_float, C.c_float, C.c_void_p]
+    # y2_train_rnn.hip: tensors [T][B][C]
+    L.y2h_train_rnn_bn_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_float, C.c_float, C.c_void_p]
+    L.y2h_train_rnn_bn_apply.argtypes = [C.c_void_p] * 7 + [C.c_int] * 4 + [C.c_void_p]
+    L.y2h_train_rnn_step_finish.argtypes = [C.c_void_p] * 7 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 3
+    L.y2h_train_cost_sse_chunked.argtypes = [C.c_void_p] * 5 + [C.c_float, C.c_long] + [C.c_void_p] * 3
+    L.y2h_train_rnn_fused_fits.argtypes = [C.c_int, C.c_int]
+    L.y2h_train_rnn_fused_ws_bytes.argtypes = [C.c_int, C.c_int]
+    L.y2h_train_rnn_fused_ws_bytes.restype = C.c_size_t
+    L.y2h_train_rnn_fused_forward.argtypes = [C.c_void_p] * 9 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 3
+    L.y2h_train_rnn_fused_backward.argtypes = [C.c_void_p] * 7 + [C.c_int] * 3 + [C.c_void_p] * 8
+    L.y2h_train_rnn_delta.argtypes = [C.c_void_p] * 7 + [C.c_int] * 4 + [C.c_void_p] * 5
+    L.y2h_train_rnn_sum_steps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.y2h_train_rnn_combine.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]
+    L.y2h_train_rnn_add_transposed.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.y2h_train_rnn_onehot.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.y2_train_region_stats.argtypes = [C.POINTER(CNetwork), C.c_int, C.POINTER(RegionStats)]
     L.y2_train_truth_floats.argtypes = [C.POINTER(CNetwork)]
     L.y2_train_detection_stats.argtypes = [C.POINTER(CNetwork), C.c_int, C.POINTER(DetectionStats)]
@@ -522,6 +537,8 @@ def lib():
     L.y2_net_augment.argtypes = [CNetwork] + [C.POINTER(C.c_float)] * 4 + [C.POINTER(C.c_int)]
     L.y2_train_load_detection.argtypes = [C.POINTER(CNetwork), C.POINTER(AugItem), C.c_int, C.c_int]
     L.y2_train_step_loaded.argtypes = [C.POINTER(CNetwork), C.POINTER(C.c_float)]
+    L.y2_get_rnn_data.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.y2_train_load_rnn_data.argtypes = [C.POINTER(CNetwork), C.c_char_p, C.c_size_t, C.c_void_p]
     L.y2_train_pull_input.argtypes = [C.POINTER(CNetwork), C.c_void_p, C.c_void_p]
     L.y2_train_load_times.argtypes = [C.POINTER(CNetwork), C.c_void_p]
     L.y2h_augment_to_input.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
@@ -765,6 +782,17 @@ def plane_samples(depth, far_m: float, iters: int, seed: int) -> np.ndarray:
 DENSE_FORWARD, DENSE_DINPUT = 0, 1     # include/y2_hip.h Y2H_DENSE_FORWARD / Y2H_DENSE_DINPUT
 
 
+def get_rnn_data(text: bytes, offsets: np.ndarray, characters: int, batch: int, steps: int):
+    """rnn.c:86-114 through the library: (x, y) float32 [steps*batch][characters]; `offsets` (uint64 [batch]) advances in place"""
+    if offsets.dtype != np.uint64 or not offsets.flags.c_contiguous or offsets.size != batch:
+        raise ValueError("get_rnn_data: offsets must be a contiguous uint64 array of `batch` values")
+    x = np.empty((steps * batch, characters), np.float32)
+    y = np.empty((steps * batch, characters), np.float32)
+    if lib().y2_get_rnn_data(text, _ptr(offsets), characters, len(text), batch, steps, _ptr(x), _ptr(y)) != 0:
+        raise Y2Error("get_rnn_data: " + _check())
+    return x, y
+
+
 def train_dense_plan(batch: int, inputs: int, outputs: int, product: int = DENSE_FORWARD, forced: int = 0):
     """y2h_train_dense_plan: how the trainer cuts the reduction of a dense layer's forward (over inputs) or input-gradient
     (over outputs) product, on the host (no GPU) -> (ranges, workspace bytes, bounds[ranges + 1])"""
@@ -993,6 +1021,7 @@ class Network:
     # --- training (include/sr_yolo2.h: train_network_datum and the y2_train_* calls it is written on) ---
     TRAIN_ARRAYS = ("output", "delta", "x", "x_norm", "mean", "variance", "mean_delta", "variance_delta", "weight_updates",
                     "bias_updates", "scale_updates", "weights", "biases", "scales", "rolling_mean", "rolling_variance", "rand")
+    RNN_SUBS = ("input", "self", "output")
 
     def train_prepare(self) -> None:
         if lib().y2_train_prepare(C.byref(self.net)) != 0:
@@ -1066,6 +1095,14 @@ class Network:
         if lib().y2_train_load_classification(C.byref(self.net), arr, _ptr(truth) if truth is not None else None, len(items), int(swap_rb)) != 0:
             raise Y2Error("y2_train_load_classification: " + _check())
 
+    def train_load_chars(self, text: bytes, offsets: np.ndarray) -> None:
+        """y2_train_load_rnn_data: the next time_steps characters of each of the B = batch / time_steps streams -> the
+        trainer's one-hot input and truth, written on the device; `offsets` (uint64 [B]) advances in place as get_rnn_data's"""
+        if offsets.dtype != np.uint64 or not offsets.flags.c_contiguous or offsets.size != self.net.batch // max(self.net.time_steps, 1):
+            raise ValueError("train_load_chars: offsets must be a contiguous uint64 array of batch / time_steps values")
+        if lib().y2_train_load_rnn_data(C.byref(self.net), text, len(text), _ptr(offsets)) != 0:
+            raise Y2Error("y2_train_load_rnn_data: " + _check())
+
     def train_step_loaded(self) -> float:
         loss = C.c_float(0)
         if lib().y2_train_step_loaded(C.byref(self.net), C.byref(loss)) != 0:
@@ -1074,7 +1111,8 @@ class Network:
 
     def train_pull_input(self):
         """the loaded batch as the reference holds it: x [batch][3][h][w], truth [batch][150] (a classifier: [batch][truth_floats()])"""
-        x = np.zeros((self.net.batch, self.net.c, self.net.h, self.net.w), np.float32)
+        flat = not (self.net.h > 0 and self.net.w > 0 and self.net.c > 0)       # inputs= in front of an [rnn]: rows as given
+        x = np.zeros((self.net.batch, self.net.inputs) if flat else (self.net.batch, self.net.c, self.net.h, self.net.w), np.float32)
         y = np.zeros((self.net.batch, 150 if LAYER_TYPES[self.net.layers[self.net.n - 1].type] == "REGION" else self.truth_floats()), np.float32)
         if lib().y2_train_pull_input(C.byref(self.net), _ptr(x), _ptr(y)) != 0:
             raise Y2Error("y2_train_pull_input: " + _check())
@@ -1095,6 +1133,26 @@ class Network:
         """one array of the trainer in the reference's order: activations [batch][c][h][w], weights [n][c][size][size] (a
         [connected] layer's [outputs][inputs]); "rand" is a [dropout] layer's draws of the last step, [batch][inputs]"""
         l = self.net.layers[layer]
+        if what == "state" or "." in what:
+            # an [rnn]: "state" is [time_steps + 1][B][hidden]; "input.weights", "self.delta", "output.x_norm" ... name an
+            # array of a sub-layer: activations [time_steps * B][outputs] (rows step-major), mean / variance the last step's
+            if LAYER_TYPES[l.type] != "RNN":
+                raise Y2Error("train_pull: layer %d is no [rnn] layer: it has no %r" % (layer, what))
+            if what == "state":
+                code, n = len(self.TRAIN_ARRAYS), (l.steps + 1) * l.batch * l.hidden
+            else:
+                sub, name = what.split(".", 1)
+                if sub not in self.RNN_SUBS or name not in self.TRAIN_ARRAYS[:-1]:
+                    raise Y2Error("train_pull: unknown array %r (input. / self. / output. and one of %s)" % (what, ", ".join(self.TRAIN_ARRAYS[:-1])))
+                k = self.RNN_SUBS.index(sub)
+                ins, outs = ((l.inputs, l.hidden), (l.hidden, l.hidden), (l.hidden, l.outputs))[k]
+                base = self.TRAIN_ARRAYS.index(name)
+                code = ((k + 1) << 8) | base
+                n = self.net.batch * outs if base < 4 else (ins * outs if name in ("weights", "weight_updates") else outs)
+            out = np.zeros(max(n, 1), np.float32)
+            if lib().y2_train_pull(C.byref(self.net), layer, code, _ptr(out), n) != 0:
+                raise Y2Error("y2_train_pull: " + _check())
+            return out[:n]
         code = self.TRAIN_ARRAYS.index(what)
         if code < 4 or what == "rand":
             n = self.net.batch * l.outputs

@@ -42,7 +42,11 @@ With --precision bf16x3 or --precision bf16 the step row and the per-product row
 (y2_train_set_precision; the products through y2h_train_conv_*_bf16 with planes 3 or 1), in the same process on the same
 buffers, and reported under "precision": the fp32 rows stay what they are.
 
-usage: train_latency.py [--net darknet19|tiny-yolo-voc|yolo|tiny-yolo-v1] [--dense 32x12544x1470,...] [--batches 16,64] [--steps 10] [--warmup 3] [--reps 5] [--ref-batch 16] [--no-reference]
+With --net rnn the rows are char-rnn training steps (the layers of cfg/rnn.train.cfg: three batch-normalised [rnn] of 1024,
+[connected] 256) at `--batches BxT,...` (default 128x576, the cfg's own, and 16x64): ms per step and characters per second;
+--loader adds the wall time of train_load_chars + train_step_loaded.
+
+usage: train_latency.py [--net darknet19|tiny-yolo-voc|yolo|tiny-yolo-v1|rnn] [--dense 32x12544x1470,...] [--batches 16,64] [--steps 10] [--warmup 3] [--reps 5] [--ref-batch 16] [--no-reference]
                         [--no-products] [--layers 4,18] [--loader] [--precision fp32|bf16x3|bf16]"""
 import argparse
 import ctypes as C
@@ -387,9 +391,56 @@ def reference_step(tmp, wts, name, size, batch, steps=2):
     return {"batch": batch, "threads": os.environ.get("OMP_NUM_THREADS", "unset"), "seconds_per_step": secs}
 
 
+def rnn_rows(a):
+    """--net rnn: char-rnn training (cfg/rnn.train.cfg's layers) at B sequences x T steps, `--batches BxT,...`: ms per step and
+    characters per second through train_step_device, with --loader through train_load_chars + train_step_loaded as well.
+    The split of a step is read from a kernel trace of this run with --steps 1."""
+    L = darknet.lib()
+    out = []
+    print("rnn, device %s" % darknet.device_name())
+    tmp = tempfile.mkdtemp()
+    text = bytes(1 + (i * 7 + i // 13) % 250 for i in range(1 << 16))
+    for shape in (a.batches or "128x576,16x64").split(","):
+        B, T = [int(v) for v in shape.split("x")]
+        cfg = os.path.join(tmp, "rnn_%dx%d.cfg" % (B, T))
+        open(cfg, "w").write(zoo.recurrent_cfg_text("rnn", B, T).replace("[net]", "[net]\nlearning_rate=0.1\nmomentum=0.9\ndecay=0.001", 1))
+        net = darknet.Network.parse_network_cfg(cfg)
+        t0 = time.time()
+        net.train_prepare()
+        rows, inputs = B * T, net.net.inputs
+        off = np.arange(B, dtype=np.uint64) * 101
+        x, y = darknet.get_rnn_data(text, off, inputs, B, T)
+        d_x, d_y = dev_floats(L, x.size, x), dev_floats(L, y.size, y)
+        timer = Timer(net.stream())
+        losses = [net.train_step_device(d_x.value, d_y.value) for _ in range(a.warmup)]
+        ms = [timer.ms(lambda: losses.append(net.train_step_device(d_x.value, d_y.value))) for _ in range(a.steps)]
+        res = {"sequences": B, "time_steps": T, "prepare_s": round(time.time() - t0, 2)}
+        if ms:
+            res.update(step_p50_ms=round(p50(ms), 3), step_max_ms=round(max(ms), 3), chars_per_s=round(rows / (p50(ms) * 1e-3), 1),
+                       first_loss=losses[0], last_loss=losses[-1])
+        if a.loader:
+            def loaded():
+                net.train_load_chars(text, off)
+                losses.append(net.train_step_loaded())
+            for _ in range(a.warmup):
+                loaded()
+            wall = []
+            for _ in range(max(a.steps, 1)):
+                w0 = time.perf_counter()
+                loaded()
+                wall.append((time.perf_counter() - w0) * 1e3)
+            res["loader"] = {"load_and_step_wall_p50_ms": round(p50(wall), 3), "chars_per_s": round(rows / (p50(wall) * 1e-3), 1)}
+        print("  " + json.dumps(res))
+        L.y2h_free(d_x)
+        L.y2h_free(d_y)
+        net.free()
+        out.append(res)
+    print(json.dumps({"tool": "train_latency", "device": darknet.device_name(), "net": "rnn", "rows": out}))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--net", default="darknet19", choices=sorted(NETS))
+    ap.add_argument("--net", default="darknet19", choices=sorted(NETS) + ["rnn"])
     ap.add_argument("--batches", default=None)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
@@ -405,6 +456,8 @@ def main():
     ap.add_argument("--cold", action="store_true", help="with --dense: rotate over copies of the weights so that no launch finds them in the last-level cache")
     ap.add_argument("--loader", action="store_true", help="add the loader's row: the classifier loader for darknet19, the detection loader for a detector")
     a = ap.parse_args()
+    if a.net == "rnn":
+        return rnn_rows(a)
     SIZE, batches, ref_batch = NETS[a.net][:3]
     L = darknet.lib()
     if a.dense:
