@@ -640,6 +640,56 @@ int y2_plane_samples(const uint16_t *depth, int dh, int dw, float far_m, int ite
 int y2_plane_from_points(const float *p0, const float *p1, const float *p2, float *plane);
 int y2_plane_fit(const double *sums, double *plane);
 /* ------------------------------------------------------------------------- */
+/* The KCF trackers of the Kinect loop, on the device, all objects in one      */
+/* batch (KinectUtil_with_cam.cpp:764-803 InitialTracker / test_tracker_img    */
+/* over kcf.cpp, complexmat.hpp, piotr_fhog/), with the fork's parameters      */
+/* (kcf.h:51-57: padding 3.0, kernel sigma 0.5, lambda 1e-4, interpolation     */
+/* 0.02, output sigma factor 0.1, cell 4).  No scale adaptation, as in the     */
+/* reference.  OpenCV's cvtColor, resize and dft are not linked; this library  */
+/* DEFINES: grey = (1868*B + 9617*G + 4899*R + 8192) >> 14 of an 8-bit BGR /   */
+/* BGRA pixel (a 1-channel frame is taken as is); the halving of a frame as    */
+/* round-half-even(0.5*cols) x round-half-even(0.5*rows) pixels with taps      */
+/* (-3, 19, 19, -3)/32 at source columns 2d-1 .. 2d+2 clamped to the image,    */
+/* horizontal pass first, then vertical, in fp32; the DFT as a dense product   */
+/* with twiddles of (j*k) mod n.  Parity with OpenCV is unpinned.              */
+/* ------------------------------------------------------------------------- */
+#define Y2_KCF_MAX_TRACKERS 32
+/* A feature map has at most 256 cells per side: a window of 1024 px, a box of 256 px per side in the tracker's own scale.
+ * A box with w*h > 10000 is tracked at half resolution, so that is a box of roughly 512 px on a side in the frame. */
+#define Y2_KCF_MAX_CELLS 256
+typedef struct { double cx, cy, w, h; } y2_kcf_box;            /* BBox_c, pixels of the frame */
+typedef struct { int resized, win_w, win_h, cells_w, cells_h; double cx, cy, w, h, output_sigma; } y2_kcf_geometry;
+/* init's arithmetic (kcf.cpp:7-27), device-free: the halving rule (w*h > 100.*100. strictly), the pose in the tracker's
+ * scale, the window floor(w * 4) x floor(h * 4), its cells (window / 4) and p_output_sigma.  Refused (-1): a box that is
+ * not finite or has w <= 0 or h <= 0, a feature map above Y2_KCF_MAX_CELLS per side or below 2 x 2 cells. */
+int  y2_kcf_plan(const y2_kcf_box *b, y2_kcf_geometry *g);
+/* KCF_Tracker::init of n trackers on one frame (h x w x c bytes, c = 1, 3: BGR, 4: BGRA, rows `step` bytes apart); the
+ * trackers of an earlier init are dropped.  Only the frame rows the windows touch are uploaded, in one copy.  Refused by
+ * name before any device work: n < 1 or n > Y2_KCF_MAX_TRACKERS, a NULL frame or box list, c other than 1, 3, 4,
+ * step < w*c, and what y2_kcf_plan refuses. */
+int  y2_kcf_init(network net, const unsigned char *frame, int h, int w, int c, int step, const y2_kcf_box *boxes, int n);
+/* KCF_Tracker::track of every tracker on a new frame -> out[i] = getBBox(), peak[i] = the response maximum (either may be
+ * NULL).  update = 0: what the application's copy-and-drop call gives (the stored model and pose stay as they are, the
+ * retraining half is skipped); update != 0: the stored tracker is retrained and moves.  Refused before any device work:
+ * no trackers (y2_kcf_init first), a frame whose size or channel count differs from the init frame's, a NULL frame,
+ * step < w*c. */
+int  y2_kcf_track(network net, const unsigned char *frame, int h, int w, int c, int step, int update, y2_kcf_box *out, float *peak);
+int  y2_kcf_count(network net);
+/* The tests' window: tensor `what` of tracker i as of the last call.  PATCH: win_h x win_w grey; FEATURES: 31 x R x C
+ * (no window); XF: the model, 31 x 2 x R x C (real plane, imaginary plane); ALPHAF: 2 x R x C; RESPONSE: R x C of the
+ * last track.  `floats` must be the tensor's size. */
+enum { Y2_KCF_PATCH = 0, Y2_KCF_FEATURES = 1, Y2_KCF_XF = 2, Y2_KCF_ALPHAF = 3, Y2_KCF_RESPONSE = 4 };
+int  y2_kcf_fetch(network net, int i, int what, float *dst, size_t floats);
+/* The DFT kernels alone: forward, src real rows x cols -> dst 2 x rows x cols; inverse, src 2 x rows x cols -> dst the
+ * real part, rows x cols, scaled by 1/(rows*cols).  2 <= rows, cols <= Y2_KCF_MAX_CELLS.  Leaves the trackers alone. */
+int  y2_kcf_dft(network net, const float *src, int rows, int cols, int inverse, float *dst);
+void y2_kcf_free(network net);
+/* the application's two calls, objects relative to the frame as it holds them (KinectUtil_with_cam.cpp:764-803):
+ * InitialTracker (bb = x*W, y*H, w*W, h*H in fp32; the objects are kept as tracking_objects) and test_tracker_img
+ * (update = 0; objs[i] = tracking_objects[i] with x, y, w, h = cx/W, cy/H, w/W, h/H; *n = the tracker count). */
+void y2_kcf_init_objects(network net, const unsigned char *frame, int h, int w, int c, int step, const object *objs, int n);
+void y2_kcf_track_objects(network net, const unsigned char *frame, int h, int w, int c, int step, object *objs, int *n);
+/* ------------------------------------------------------------------------- */
 /* Training on the device: the other half of network.c (train_network_datum     */
 /* :225-243 = forward with train = 1, backward_network, update_network), fp32   */
 /* (the convolution products optionally on the bf16 matrix cores, see           */

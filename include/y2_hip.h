@@ -654,6 +654,55 @@ int y2h_plane_remove(const y2h_plane_job *j, int stages, y2h_stream s);
 int y2h_plane_register(const unsigned short *grasp_depth, const short *dxy, int H, int W, int dw, unsigned short *grasp16,
                        y2h_stream s);
 
+/* ---- KCF tracker of the Kinect loop (y2_kcf.hip; kcf.cpp, complexmat.hpp, piotr_fhog/) ---- */
+#define Y2H_KCF_CHANNELS 31         /* fHOG channels kept of 32 */
+#define Y2H_KCF_CHUNKS 32           /* partial sums of sqr_norm per tracker, added in chunk order */
+#define Y2H_KCF_MAX_TRACKERS 32
+#define Y2H_KCF_MAX_CELLS 256       /* feature map side; the window is 4x that in pixels */
+/* One tracker: its window (pixels of the possibly halved image), its feature map (R = cells_h rows, C = cells_w columns,
+ * P = R*C) and where its buffers start, as float offsets into the arena every kernel takes.  Complex tensors are two
+ * planes, [re][R][C] then [im][R][C], per channel.
+ *   patch win_h*win_w | mag, bin the same (bin holds ints) | hist 18*P | ssum P | feat 31*P | x 31*P (feat times the window)
+ *   y, xf, model_xf 31*2*P | z, t, gy, kf, p, model_alphaf, yf 2*P | xy, g, resp, lab P | win R + C (row then column
+ *   factors of the Hann window) | cc, nsc C*C: cos and -sin of 2*pi*((j*k) mod C)/C | cr, sr, nsr R*R: cos, sin, -sin of
+ *   2*pi*((j*k) mod R)/R | part 2*Y2H_KCF_CHUNKS */
+typedef struct y2h_kcf_desc {
+    int resized, win_w, win_h, cells_w, cells_h, pad_;
+    long long patch, mag, bin, hist, ssum, feat, x, y, xf, z, t, xy, g, gy, kf, p, resp, model_xf, model_alphaf, yf, lab, win,
+              cc, nsc, cr, sr, nsr, part;
+} y2h_kcf_desc;
+/* what the arg-max leaves per tracker: the tracked centre in the tracker's own scale, the response maximum, its wrapped cell */
+typedef struct y2h_kcf_rec { double cx, cy; float peak; int mx, my, pad_; } y2h_kcf_rec;
+/* rows [row_lo, row_hi) of an h x w x c 8-bit frame (c = 1, 3: BGR, 4: BGRA), packed at w*c bytes per row */
+typedef struct y2h_kcf_frame { const unsigned char *bytes; int h, w, c, row_lo, row_hi; } y2h_kcf_frame;
+/* Every call serves the n trackers of the device table `desc` in one launch per kernel, on stream s, without
+ * synchronisation.  max_pixels / max_cells / max_side: the largest win_w*win_h, cells_w*cells_h and cell side of the table
+ * (they size the launch; a tracker's own sizes bound what is touched).
+ * patch: grey ((1868*B + 9617*G + 4899*R + 8192) >> 14; one channel as is), for a resized tracker the half-resolution
+ *   pixel formed on the fly (taps (-3, 19, 19, -3)/32 at 2d-1 .. 2d+2 clamped, horizontal then vertical, left to right),
+ *   and get_subwindow (kcf.cpp:277-325) about (centres[t*stride], centres[t*stride + 1]) truncated to int. */
+int y2h_kcf_patch(const y2h_kcf_desc *desc, int n, float *arena, const y2h_kcf_frame *f, const double *centres, int stride,
+                  long max_pixels, y2h_stream s);
+/* FHoG::extract(patch, 2, 4, 9) -> feat, and x = feat * window: gradient / orientation bin, the histogram gather, the
+ * norm sums, the channels (four launches). */
+int y2h_kcf_fhog(const y2h_kcf_desc *desc, int n, float *arena, long max_pixels, long max_cells, y2h_stream s);
+/* Dense DFTs on the fp32 matrix cores, two launches each: x -> xf (31 channels), g -> kf, lab -> yf forward; z -> xy and
+ * p -> resp inverse, real part only, scaled by 1/(R*C). */
+enum { Y2H_KCF_DFT_X = 0, Y2H_KCF_DFT_G = 1, Y2H_KCF_DFT_LAB = 2, Y2H_KCF_IDFT_Z = 3, Y2H_KCF_IDFT_P = 4 };
+int y2h_kcf_dft(const y2h_kcf_desc *desc, int n, float *arena, int which, int max_side, y2h_stream s);
+/* z = sum over the channels of xf * conj(model_xf) (autocorrelation: |xf|^2) and the partial sums of both sqr_norms */
+int y2h_kcf_cross(const y2h_kcf_desc *desc, int n, float *arena, int autocorrelation, y2h_stream s);
+/* g = exp(-1/sigma^2 * max((xx + yy - 2*xy) / (P*31), 0)), sigma = 0.5 */
+int y2h_kcf_gauss(const y2h_kcf_desc *desc, int n, float *arena, long max_cells, y2h_stream s);
+/* alphaf = yf / (kf + 1e-4).  update == 0: model = (xf, alphaf).  Otherwise model = model * 0.98 + new * 0.02 and
+ * pose[t] = (rec[t].cx, rec[t].cy). */
+int y2h_kcf_train(const y2h_kcf_desc *desc, int n, float *arena, int update, double *pose, const y2h_kcf_rec *rec, long max_cells,
+                  y2h_stream s);
+/* p = model_alphaf * kf */
+int y2h_kcf_apply(const y2h_kcf_desc *desc, int n, float *arena, long max_cells, y2h_stream s);
+/* the first maximum of resp in row-major order, wrapped (> R/2, > C/2 with integer halves); rec = pose + 4 * cell */
+int y2h_kcf_argmax(const y2h_kcf_desc *desc, int n, const float *arena, const double *pose, y2h_kcf_rec *rec, y2h_stream s);
+
 /* ---- classifier views (classifier.c:336-593 valid10 / validmulti / validfull) ---- */
 /* One view of y2h_views_to_input: a w x h window of a CHW fp32 source image that becomes batch slot b of the network
  * input.  The window's top-left corner sits at (dx, dy) of the source; both may be negative or reach past the source. */

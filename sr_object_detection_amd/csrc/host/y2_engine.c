@@ -124,6 +124,7 @@ void y2_engine_destroy(network *net)
     y2h_free(e->arena);
     y2_chargen_free(e);
     y2_depth_free(e);
+    y2_kcf_free_engine(e);
     y2h_host_free(e->h_out_stage);
     y2h_host_free(e->h_reg_stage);
     y2h_host_free(e->h_tta); y2h_free(e->d_tta);

@@ -190,6 +190,7 @@ typedef struct y2_engine {
     unsigned char *h_tta, *d_tta;
     size_t h_tta_cap, d_tta_cap;
     struct y2_depth_state *depth;      /* the depth stage's planes and scratch (y2_depth.c), NULL until the first upload */
+    struct y2_kcf_state *kcf;          /* the KCF trackers (y2_kcf.c), NULL until the first y2_kcf_init */
     /* timing */
     y2h_event *ev;             /* n+1 events */
     int n_ev;
@@ -293,6 +294,7 @@ int y2_depth_filter_check(const char *who, network net, const y2_region *items, 
 const unsigned char *y2_depth_plane8(const y2_engine *e, int *W);
 const unsigned short *y2_depth_plane_grasp(const y2_engine *e);
 void y2_depth_free(y2_engine *e);
+void y2_kcf_free_engine(y2_engine *e);            /* the KCF trackers (y2_kcf.c) */
 
 /* training (y2_train.c) */
 int y2_train_is_dirty(const network *net);     /* steps ran since the masters last reached the host arrays */

@@ -52,6 +52,39 @@ class Object(C.Structure):   # utils.h:14-28
                 ("flagBelong2Person", C.c_ubyte), ("boxRGB", C.c_float * 3), ("bodyId", C.c_int)]
 
 
+class KcfBox(C.Structure):          # include/sr_yolo2.h y2_kcf_box
+    _fields_ = [("cx", C.c_double), ("cy", C.c_double), ("w", C.c_double), ("h", C.c_double)]
+
+
+class KcfGeometry(C.Structure):     # include/sr_yolo2.h y2_kcf_geometry
+    _fields_ = [("resized", C.c_int), ("win_w", C.c_int), ("win_h", C.c_int), ("cells_w", C.c_int), ("cells_h", C.c_int),
+                ("cx", C.c_double), ("cy", C.c_double), ("w", C.c_double), ("h", C.c_double), ("output_sigma", C.c_double)]
+
+
+KCF_PATCH, KCF_FEATURES, KCF_XF, KCF_ALPHAF, KCF_RESPONSE = range(5)
+KCF_MAX_TRACKERS, KCF_MAX_CELLS, KCF_CHANNELS = 32, 256, 31
+
+
+def kcf_plan(box) -> dict:
+    """y2_kcf_plan: init's arithmetic of one (cx, cy, w, h) box in pixels -> dict of y2_kcf_geometry's fields"""
+    b, g = KcfBox(*[float(v) for v in box]), KcfGeometry()
+    if lib().y2_kcf_plan(C.byref(b), C.byref(g)) != 0:
+        raise Y2Error(_check())
+    return {k: getattr(g, k) for k, _ in KcfGeometry._fields_}
+
+
+def _kcf_frame(frame):
+    """uint8 [h][w] or [h][w][c]; a view with padded rows is passed with its step -> (array kept alive, h, w, c, step)"""
+    f = np.asarray(frame)
+    if f.dtype != np.uint8 or f.ndim not in (2, 3):
+        raise ValueError("a frame is uint8 [h][w] or [h][w][c]")
+    c = 1 if f.ndim == 2 else f.shape[2]
+    inner_ok = f.strides[-1] == 1 and (f.ndim == 2 or f.strides[1] == c)
+    if not inner_ok or f.strides[0] < f.shape[1] * c:
+        f = np.ascontiguousarray(f)
+    return f, f.shape[0], f.shape[1], c, f.strides[0]
+
+
 class Layer(C.Structure):    # include/sr_yolo2.h struct layer
     pass
 
@@ -584,6 +617,18 @@ def lib():
     L.y2h_tail_launches.restype = C.c_ulong
     L.y2h_xcd_order_launches.restype = C.c_ulong
     L.y2h_f32_stream_k_launches.restype = C.c_ulong
+    L.y2_kcf_plan.argtypes = [C.POINTER(KcfBox), C.POINTER(KcfGeometry)]
+    L.y2_kcf_init.argtypes = [CNetwork, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    L.y2_kcf_track.argtypes = [CNetwork, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.y2_kcf_count.argtypes = [CNetwork]
+    L.y2_kcf_fetch.argtypes = [CNetwork, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+    L.y2_kcf_dft.argtypes = [CNetwork, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.y2_kcf_free.argtypes = [CNetwork]
+    L.y2_kcf_free.restype = None
+    L.y2_kcf_init_objects.argtypes = [CNetwork, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Object), C.c_int]
+    L.y2_kcf_init_objects.restype = None
+    L.y2_kcf_track_objects.argtypes = [CNetwork, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Object), C.POINTER(C.c_int)]
+    L.y2_kcf_track_objects.restype = None
     _lib = L
     return L
 
@@ -1445,6 +1490,74 @@ class Network:
                                    cap) != 0:
             raise Y2Error(_check())
         return [dets[i, :min(int(counts[i]), cap)].copy() for i in range(n)], counts[:n]
+
+    # --- the KCF trackers of the Kinect loop (include/sr_yolo2.h y2_kcf_*) ---
+    def kcf_init(self, frame, boxes) -> None:
+        """y2_kcf_init: frame uint8 [h][w] / [h][w][3] BGR / [h][w][4] BGRA, boxes [n][4] = (cx, cy, w, h) in pixels"""
+        f, h, w, c, step = _kcf_frame(frame)
+        b = np.ascontiguousarray(boxes, dtype=np.float64).reshape(-1, 4)
+        if lib().y2_kcf_init(self.net, f.ctypes.data_as(C.c_void_p), h, w, c, step, _ptr(b), len(b)) != 0:
+            raise Y2Error(_check())
+        self._kcf_geo = [kcf_plan(row) for row in b]
+
+    def kcf_track(self, frame, update: bool = False):
+        """y2_kcf_track -> (boxes float64 [n][4], peaks float32 [n]); update=False is the application's copy-and-drop call"""
+        f, h, w, c, step = _kcf_frame(frame)
+        n = lib().y2_kcf_count(self.net)
+        boxes, peaks = np.zeros((max(n, 1), 4), np.float64), np.zeros(max(n, 1), np.float32)
+        if lib().y2_kcf_track(self.net, f.ctypes.data_as(C.c_void_p), h, w, c, step, int(bool(update)), _ptr(boxes), _ptr(peaks)) != 0:
+            raise Y2Error(_check())
+        return boxes[:n], peaks[:n]
+
+    def kcf_count(self) -> int:
+        return int(lib().y2_kcf_count(self.net))
+
+    def kcf_fetch(self, i: int, what: int) -> np.ndarray:
+        """y2_kcf_fetch: PATCH [win_h][win_w], FEATURES [31][R][C], XF [31][2][R][C], ALPHAF [2][R][C], RESPONSE [R][C]"""
+        geo = getattr(self, "_kcf_geo", [])
+        if not 0 <= i < len(geo):
+            raise Y2Error("kcf_fetch: tracker %d of %d (kcf_init first)" % (i, len(geo)))
+        g = geo[i]
+        R, Cc = g["cells_h"], g["cells_w"]
+        shape = {KCF_PATCH: (g["win_h"], g["win_w"]), KCF_FEATURES: (KCF_CHANNELS, R, Cc), KCF_XF: (KCF_CHANNELS, 2, R, Cc),
+                 KCF_ALPHAF: (2, R, Cc), KCF_RESPONSE: (R, Cc)}.get(what)
+        if shape is None:
+            raise Y2Error("kcf_fetch: unknown tensor %d" % what)
+        out = np.zeros(shape, np.float32)
+        if lib().y2_kcf_fetch(self.net, i, what, _ptr(out), out.size) != 0:
+            raise Y2Error(_check())
+        return out
+
+    def kcf_dft(self, a, inverse: bool = False) -> np.ndarray:
+        """y2_kcf_dft: forward float32 [R][C] -> [2][R][C]; inverse [2][R][C] -> the real part [R][C] / (R*C)"""
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        R, Cc = a.shape[-2:]
+        out = np.zeros((R, Cc) if inverse else (2, R, Cc), np.float32)
+        if lib().y2_kcf_dft(self.net, _ptr(a), R, Cc, int(bool(inverse)), _ptr(out)) != 0:
+            raise Y2Error(_check())
+        return out
+
+    def kcf_init_objects(self, frame, objs) -> None:
+        """y2_kcf_init_objects: objs is a ctypes array of Object, boxes relative to the frame"""
+        f, h, w, c, step = _kcf_frame(frame)
+        lib().y2_kcf_init_objects(self.net, f.ctypes.data_as(C.c_void_p), h, w, c, step, objs, len(objs))
+        if lib().y2_failed_and_clear():
+            raise Y2Error(_check())
+        self._kcf_geo = [kcf_plan((float(np.float32(o.x) * np.float32(w)), float(np.float32(o.y) * np.float32(h)),
+                                   float(np.float32(o.w) * np.float32(w)), float(np.float32(o.h) * np.float32(h)))) for o in objs]
+
+    def kcf_track_objects(self, frame, objs) -> int:
+        """y2_kcf_track_objects: fills objs (a ctypes array of Object with room for every tracker) -> the tracker count"""
+        f, h, w, c, step = _kcf_frame(frame)
+        n = C.c_int(0)
+        lib().y2_kcf_track_objects(self.net, f.ctypes.data_as(C.c_void_p), h, w, c, step, objs, C.byref(n))
+        if lib().y2_failed_and_clear():
+            raise Y2Error(_check())
+        return n.value
+
+    def kcf_free(self) -> None:
+        lib().y2_kcf_free(self.net)
+        self._kcf_geo = []
 
     # --- the depth stage of the Kinect loop (include/sr_yolo2.h y2_depth_*) ---
     def depth_upload(self, depth, body=None, map_=None, color_hw=None) -> None:
