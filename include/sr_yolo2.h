@@ -956,6 +956,75 @@ void optimize_picture(network *net, image orig, int max_layer, float scale, floa
 int y2_nightmare(network *net, image im, int max_layer, int range, int norm, int rounds, int iters, int octaves, float zoom,
                  float rate, float thresh, float rotate, void (*per_round)(int round, image im, void *user), void *user);
 
+/* ------------------------------------------------------------------------ */
+/* Go: go.c's entry points and the batched calls under them (y2_go.c).        */
+/* ------------------------------------------------------------------------ */
+/* A board is 361 floats holding exactly 0, 1 or -1, row-major (board[row*19+col]); a packed board or ko string is 91 bytes
+ * (four points per byte, bit 2j = 1, bit 2j+1 = -1); a record is 93 bytes: row, column, the packed board seen by the mover.
+ * Device-free, under the reference's names and signatures: */
+typedef struct { char **data; int n; } moves;                    /* go.c:16-19 */
+void string_to_board(char *s, float *board);                     /* go.c:56 */
+void board_to_string(char *s, float *board);                     /* go.c:75 */
+void flip_board(float *board);                                   /* go.c:254 */
+int *calculate_liberties(float *board);                          /* go.c:188: calloc'ed, the caller frees */
+void move_go(float *b, int p, int r, int c);                     /* go.c:304 */
+int suicide_go(float *b, int p, int r, int c);                   /* go.c:326 */
+int legal_go(float *b, char *ko, int p, int r, int c);           /* go.c:338: does NOT reject suicide */
+void print_board(float *board, int swap, int *indexes);          /* go.c:208: to stderr; indexes NULL or five points */
+/* go.c:34: a file of 94-byte lines (the 93-byte record and the newline self_go prints behind it); data[i] holds line i.  The
+ * count is not printed.  A file that cannot be opened is an error (y2_last_error), n = 0. */
+moves load_go_moves(char *filename);
+void y2_go_free_moves(moves m);
+/* random_go_moves' draws (go.c:97-105) for one batch, in its order: rand() % n_records, rand() % 2, rand() % 4 per item. */
+int y2_go_draw_moves(int n_records, int batch, int *pick, int *flip, int *rot);
+/* The reference's two device entries.  predict_move (go.c:262): the network on the board and, with multi, on its seven
+ * other dihedral views, summed in the reference's order and scaled by 1/8, occupied points zeroed.  generate_move (go.c:351)
+ * writes temp on every layer, draws its one uniform with libc rand() exactly as rand_uniform(0, 1) does -- on every call
+ * that is not refused, also when it returns -1 -- and returns the point, or -1 when the best point is suicide.  The board
+ * comes back unchanged.  A refused call also returns -1 (y2_last_error). */
+void predict_move(network net, float *board, float *move, int multi);
+int generate_move(network net, int player, float *board, int multi, float thresh, float temp, char *ko, int print);
+/* The batched entries.  All of them refuse, by the argument's name in y2_last_error() and before any device work: a network
+ * that does not read 19 x 19 x 1 or does not give 361 values, fp16 mode, n <= 0, a board value other than 0 / 1 / -1, a
+ * player other than 1 / -1.  Any n is taken: rows beyond net.batch are forwarded net.batch rows at a time (the network is
+ * never re-planned; set_batch_network(&net, 8 * n) first makes a multi move one forward).
+ *   y2_go_predict   moves[n][361] = predict_move of each board as seen by players[i] (a -1 negates it first)
+ *   y2_go_rules     liberties[n][361] ints, legal[n][361] and suicide[n][361] bytes (any may be NULL) of the positions
+ *                   (boards as they are, ko[n][91], players); the network only supplies the device and stream
+ *   y2_go_generate  generate_move for n positions in one chain -- views, forward, merge, rules, pick -- and one sync:
+ *                   index[n]; kept (or NULL) receives the thresholded arrays [n][361] the samples were drawn from.
+ *                   Position i uses uniforms[i]; temp is written on every layer.
+ *   y2_go_valid     valid_go's loop (go.c:421-431): predicted[i] = max_index(predict_move(board of record i)); records is
+ *                   [n][93].  The caller compares with records[i][0] * 19 + records[i][1].
+ *   y2_go_selfplay  self_go's loop (go.c:775-823) for `games` games in lockstep from empty boards and zeroed ko strings (the
+ *                   reference keeps its two strings from one game into the next; here every call starts clean).  Per ply:
+ *                   one forward over all games, the rules, the pick, the move.  first = 0: net moves first, 1: net2 does;
+ *                   all games share it, so a ply uses one network (net2 may be the same network).  Game g's ply t uses
+ *                   uniforms[g*max_moves+t].  records[games][max_moves][93] holds, per move made, the reference's record
+ *                   (row, column, the board packed from the mover's side, before the move); counts[g] how many.  A game
+ *                   ends at -1 or at max_moves (the reference's cap is 300); an ended game's records and board no longer
+ *                   change.  final_boards[games][361] or NULL.  With two different networks every ply ends in a host
+ *                   wait; with one network the call waits once at its end and once every 16 plies, where it asks whether a
+ *                   game is still alive and returns when none is (y2_go_set_poll(net, every) changes the interval, 0:
+ *                   never asked).  The results do not depend on it. */
+int y2_go_predict(network net, const float *boards, const int *players, int n, int multi, float *moves);
+int y2_go_rules(network net, const float *boards, const char *ko, const int *players, int n, int *liberties, unsigned char *legal,
+                unsigned char *suicide);
+int y2_go_generate(network net, const float *boards, const char *ko, const int *players, int n, int multi, float thresh, float temp,
+                   const float *uniforms, int *index, float *kept);
+int y2_go_valid(network net, const unsigned char *records, int n, int multi, int *predicted);
+int y2_go_selfplay(network net, network net2, int games, int first, int max_moves, int multi, float thresh, float temp,
+                   const float *uniforms, unsigned char *records, int *counts, float *final_boards);
+int y2_go_set_poll(network net, int every);
+/* train_go's input (random_go_moves, go.c:92-115) built in the trainer on the device, staged like the other loaders: the
+ * net.batch picked records and the draws go up in one copy, one kernel writes input and truth.  Per item: decode record
+ * pick[i], the one-hot label at (row, col), the board cleared at that point, flip_image on both when flip[i], then
+ * rotate_image_cw(rot[i]) on both -- flip first, the opposite of predict_move's views.  records is [n_records][93].
+ * Refused by name with nothing loaded: a network that is not 19 x 19 x 1 with a 361-value [cost], one the trainer refuses,
+ * a pick outside the records, a flip other than 0 / 1, a rot outside 0..3, a picked record whose row or column is outside
+ * 0..18.  y2_train_step_loaded steps on it. */
+int y2_train_load_go(network *net, const unsigned char *records, int n_records, const int *pick, const int *flip, const int *rot);
+
 /* Copy layer i's activations to host as NCHW [batch][out_c][out_h][out_w] (or [batch][outputs]). */
 int y2_pull_layer_output(network net, int i, float *dst);
 /* Per-layer device time of the last forward in ms (needs y2_set_timing(net,1)); returns layers written. */

@@ -989,6 +989,45 @@ int y2h_dream_apply(float *picture, const float *out, long n, float rate, int no
  * doubles, the coordinates are formed in double and rounded to float as the C expression does.  src != dst. */
 int y2h_dream_rotate(const float *src, float *dst, int c, int h, int w, double cos_rad, double sin_rad, y2h_stream s);
 
+/* ---- Go (y2_go.hip): go.c's predict_move views, rules and generate_move's decision, batched ----
+ * Boards are [n][361] floats holding exactly 0, 1 or -1, row-major (board[row*19+col]); players are +1 / -1; a ko string
+ * is board_to_string's 91 bytes (go.c:75-90); legal / suicide maps are bytes, liberties ints.
+ * y2h_go_views   x[(b*V+v)][361], V = multi ? 8 : 1: view v of board b is rotate_image_cw(board, v) -- one turn is
+ *                new[r][c] = old[c][18-r] (image.c:1035-1054) -- then flip_image (columns) when v >= 4; players[b] < 0
+ *                negates the board first (flip_board).
+ * y2h_go_merge   move[b] = row 0, += rows 1..7 un-flipped (v >= 4) and turned by -v, in that order in fp32, x 0.125
+ *                (go.c:265-284); with multi = 0 row 0 alone; then 0 wherever boards[b] is non-zero.  rows are V*n rows of
+ *                ld floats.
+ * y2h_go_rules   per position: liberties as calculate_liberties (go.c:188), legal as legal_go(board, ko, player, r, c)
+ *                (go.c:338: occupied points and a move whose packed result equals ko are illegal, suicide is not), suicide
+ *                as suicide_go (go.c:326).  ko may be NULL (all strings zero); any output may be NULL.  One workgroup per
+ *                position, integers in LDS, no global atomics: the same bytes on every run.
+ * y2h_go_apply   move_go(board, player, move / 19, move % 19) in place where 0 <= moves[b] < 361, then board_to_string into
+ *                strings[b] (or NULL).
+ * y2h_go_play    one ply of self_go (go.c:801-822) for the games with alive[b]: index[b] < 0 clears alive[b]; otherwise the
+ *                record (row, column, the board packed from the mover's side) lands at records[b][counts[b]++] ([n][max_moves]
+ *                [93]), the move is made and the new board is packed into ko[b] ([n][91]).
+ * y2h_go_pick    generate_move from go.c:362 on: illegal points zeroed, top_k's insertion rule for the five best, the
+ *                threshold (go.c:370), max_index, sample_array with u[b] as its one uniform; index[b] = -1 when the arg-max
+ *                is suicide, else the sample, or the arg-max when the sample is suicide.  kept (or NULL) receives the
+ *                thresholded array, before sample_array scales it.
+ * y2h_go_argmax  max_index per row (the first maximum).
+ * y2h_go_decode  item i from record pick[i] (NULL: i) of 93-byte records: string_to_board of bytes 2..92.  With labels (the
+ *                training loader, random_go_moves go.c:92-115): the one-hot label at (row, col), the board cleared there,
+ *                flip_image when flip[i], then rotate_image_cw(rot[i]), on both.  Rows and columns must lie in 0..18. */
+int y2h_go_views(const float *boards, const int *players, int n, int multi, float *x, y2h_stream s);
+int y2h_go_merge(const float *rows, int ld, const float *boards, int n, int multi, float *move, y2h_stream s);
+int y2h_go_rules(const float *boards, const unsigned char *ko, const int *players, int n, int *liberties, unsigned char *legal,
+                 unsigned char *suicide, y2h_stream s);
+int y2h_go_apply(float *boards, const int *players, const int *moves, int n, unsigned char *strings, y2h_stream s);
+int y2h_go_play(float *boards, unsigned char *ko, int player, const int *index, int *alive, unsigned char *records,
+                int *counts, int max_moves, int n, y2h_stream s);
+int y2h_go_pick(const float *move, int ld, const unsigned char *legal, const unsigned char *suicide, int n, float thresh,
+                const float *u, int *index, float *kept, y2h_stream s);
+int y2h_go_argmax(const float *move, int ld, int n, int *index, y2h_stream s);
+int y2h_go_decode(const unsigned char *records, const int *pick, const int *flip, const int *rot, int n, float *boards,
+                  float *labels, y2h_stream s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -125,6 +125,7 @@ void y2_engine_destroy(network *net)
     y2_chargen_free(e);
     y2_depth_free(e);
     y2_kcf_free_engine(e);
+    y2_go_free_engine(e);
     y2h_host_free(e->h_out_stage);
     y2h_host_free(e->h_reg_stage);
     y2h_host_free(e->h_tta); y2h_free(e->d_tta);
@@ -409,7 +410,10 @@ int y2_enqueue_forward(network *net, const float *d_input_nchw)
             /* the input of a softmax layer is a flat [batch][inputs] vector; an image-like producer
              * (1x1 spatial, as after avgpool) is contiguous when its stride equals its channel count */
             layer *pl = &net->layers[i - 1];
-            if (i == 0 || (pl->out_h * pl->out_w > 1 && pl->type != AVGPOOL && pl->type != SOFTMAX)) {
+            /* a one-channel fp32 image at pixel stride 1 reads the same as NHWC and as the reference's NCHW row (go.test.cfg:
+             * a 1x1 convolution to one channel in front of the softmax over the 361 points) */
+            const int one_channel = i > 0 && pl->out_c == 1 && ldx == 1 && !ld_of(pl)->out_half;
+            if (i == 0 || (pl->out_h * pl->out_w > 1 && pl->type != AVGPOOL && pl->type != SOFTMAX && !one_channel)) {
                 y2_fail("softmax layer %d: input must be a flat vector (e.g. after avgpool)", i);
                 return -1;
             }

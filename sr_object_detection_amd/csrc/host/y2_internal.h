@@ -191,6 +191,7 @@ typedef struct y2_engine {
     size_t h_tta_cap, d_tta_cap;
     struct y2_depth_state *depth;      /* the depth stage's planes and scratch (y2_depth.c), NULL until the first upload */
     struct y2_kcf_state *kcf;          /* the KCF trackers (y2_kcf.c), NULL until the first y2_kcf_init */
+    struct y2_go_state *go;            /* the Go entries' HBM and pinned blocks (y2_go.c), NULL until the first call */
     /* timing */
     y2h_event *ev;             /* n+1 events */
     int n_ev;
@@ -295,6 +296,7 @@ const unsigned char *y2_depth_plane8(const y2_engine *e, int *W);
 const unsigned short *y2_depth_plane_grasp(const y2_engine *e);
 void y2_depth_free(y2_engine *e);
 void y2_kcf_free_engine(y2_engine *e);            /* the KCF trackers (y2_kcf.c) */
+void y2_go_free_engine(y2_engine *e);             /* the Go entries' blocks (y2_go.c) */
 
 /* training (y2_train.c) */
 int y2_train_is_dirty(const network *net);     /* steps ran since the masters last reached the host arrays */

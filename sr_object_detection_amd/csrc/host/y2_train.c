@@ -1425,6 +1425,64 @@ int y2_train_load_rnn_data(network *net, const unsigned char *text, size_t len, 
     return 0;
 }
 
+/* ------------------------------------------------------------------ */
+/* the Go loader (go.c:92-115 random_go_moves)                          */
+/* ------------------------------------------------------------------ */
+int y2_train_load_go(network *net, const unsigned char *records, int n_records, const int *pick, const int *flip, const int *rot)
+{
+    static const char who[] = "y2_train_load_go";
+    enum { P = 361, REC = 93 };
+    y2_engine *e;
+    y2_trainer *t;
+    size_t rec_bytes, draw_bytes;
+    int i, B, *draws;
+    if (!net || !net->layers || net->n <= 0) { y2_fail("%s: no network", who); return -1; }
+    e = y2_engine_of(net);
+    if (e && e->trainer) e->trainer->loaded = 0;         /* a refused load leaves nothing to step on */
+    if (net->w != 19 || net->h != 19 || net->c != 1) {
+        y2_fail("%s: net: the network reads %d x %d x %d, a Go network reads 19 x 19 x 1", who, net->w, net->h, net->c);
+        return -1;
+    }
+    if (!(e && e->trainer && e->trainer->batch == net->batch) && refuse(net) != 0) return -1;
+    if (net->layers[net->n - 1].type != COST || truths_per_image(net) != P) {
+        y2_fail("%s: net: the network must end in a [cost] over 361 values (one per point)", who);
+        return -1;
+    }
+    if (!records || n_records <= 0) { y2_fail("%s: n_records = %d (or NULL records)", who, n_records); return -1; }
+    if (!pick || !flip || !rot) { y2_fail("%s: pick, flip or rot is NULL", who); return -1; }
+    B = net->batch;
+    for (i = 0; i < B; ++i) {
+        const signed char *r;
+        if (pick[i] < 0 || pick[i] >= n_records) { y2_fail("%s: pick: item %d picks record %d of %d", who, i, pick[i], n_records); return -1; }
+        if (flip[i] != 0 && flip[i] != 1) { y2_fail("%s: flip: item %d has flip %d (0 or 1)", who, i, flip[i]); return -1; }
+        if (rot[i] < 0 || rot[i] > 3) { y2_fail("%s: rot: item %d has rot %d (0..3)", who, i, rot[i]); return -1; }
+        r = (const signed char *)records + (size_t)pick[i] * REC;
+        if (r[0] < 0 || r[0] > 18 || r[1] < 0 || r[1] > 18) {
+            y2_fail("%s: records: record %d moves at row %d, column %d (0..18)", who, pick[i], r[0], r[1]);
+            return -1;
+        }
+    }
+    if (!(t = trainer_for_step(net))) return -1;
+    e = y2_engine_of(net);
+    t->loaded = 0;
+    rec_bytes = align_up((size_t)B * REC, 64);
+    draw_bytes = (size_t)2 * B * sizeof(int);
+    if (grow_load(t, rec_bytes + draw_bytes) != 0) return -1;        /* free: the last load waited for its copy before it returned */
+    draws = (int *)(t->h_load + rec_bytes);
+    for (i = 0; i < B; ++i) {                           /* only the picked records go up, in batch order */
+        memcpy(t->h_load + (size_t)i * REC, records + (size_t)pick[i] * REC, REC);
+        draws[i] = flip[i];
+        draws[B + i] = rot[i];
+    }
+    HIP_OR_ERR(y2h_memcpy_h2d(t->d_load, t->h_load, rec_bytes + draw_bytes, e->stream));
+    HIP_OR_ERR(y2h_event_record(t->ev_load, e->stream));
+    HIP_OR_ERR(y2h_go_decode(t->d_load, NULL, (const int *)(t->d_load + rec_bytes), (const int *)(t->d_load + rec_bytes) + B, B, t->d_x,
+                             t->d_truth, e->stream));
+    HIP_OR_ERR(y2h_event_sync(t->ev_load));
+    t->loaded = 1;
+    return 0;
+}
+
 int y2_train_step_loaded(network *net, float *loss)
 {
     y2_engine *e = net ? y2_engine_of(net) : NULL;

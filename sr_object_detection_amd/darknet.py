@@ -629,6 +629,41 @@ def lib():
     L.y2_kcf_init_objects.restype = None
     L.y2_kcf_track_objects.argtypes = [CNetwork, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Object), C.POINTER(C.c_int)]
     L.y2_kcf_track_objects.restype = None
+    # Go (go.c; include/sr_yolo2.h, include/y2_hip.h y2h_go_*)
+    for f in (L.string_to_board, L.board_to_string, L.flip_board, L.move_go, L.print_board, L.predict_move, L.y2_go_free_moves):
+        f.restype = None
+    L.string_to_board.argtypes = [C.c_void_p, C.c_void_p]
+    L.board_to_string.argtypes = [C.c_void_p, C.c_void_p]
+    L.flip_board.argtypes = [C.c_void_p]
+    L.calculate_liberties.restype = C.POINTER(C.c_int)
+    L.calculate_liberties.argtypes = [C.c_void_p]
+    L.move_go.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    L.suicide_go.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    L.legal_go.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
+    L.print_board.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.load_go_moves.restype = GoMoves
+    L.load_go_moves.argtypes = [C.c_char_p]
+    L.y2_go_free_moves.argtypes = [GoMoves]
+    L.y2_go_draw_moves.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.predict_move.argtypes = [CNetwork, C.c_void_p, C.c_void_p, C.c_int]
+    L.generate_move.argtypes = [CNetwork, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_int]
+    L.y2_go_predict.argtypes = [CNetwork, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.y2_go_rules.argtypes = [CNetwork, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.y2_go_generate.argtypes = [CNetwork, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p,
+                                 C.c_void_p, C.c_void_p]
+    L.y2_go_valid.argtypes = [CNetwork, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.y2_go_selfplay.argtypes = [CNetwork, CNetwork, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p]
+    L.y2_go_set_poll.argtypes = [CNetwork, C.c_int]
+    L.y2_train_load_go.argtypes = [C.POINTER(CNetwork), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.y2h_go_views.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.y2h_go_merge.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.y2h_go_rules.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.y2h_go_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.y2h_go_play.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.y2h_go_pick.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.y2h_go_argmax.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.y2h_go_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -1836,6 +1871,96 @@ class Network:
             raise Y2Error("y2_rnn_perplexity: " + _check())
         return a.value, b.value
 
+    # --- Go (go.c; include/sr_yolo2.h y2_go_*) ---
+    def predict_move(self, board, multi: bool = False) -> np.ndarray:
+        """go.c:262 on one board [361] as the mover sees it -> move [361]"""
+        b = _go_boards(board, 1).copy()
+        move = np.zeros(GO_POINTS, np.float32)
+        lib().predict_move(self.net, _ptr(b), _ptr(move), int(multi))
+        if lib().y2_failed_and_clear():
+            raise Y2Error("predict_move: " + _check())
+        return move
+
+    def generate_move(self, player: int, board, multi: bool, thresh: float, temp: float, ko: bytes) -> int:
+        """go.c:351: one libc rand() draw, then the point or -1"""
+        b = _go_boards(board, 1).copy()
+        k = np.frombuffer(_go_ko(ko, 1), np.uint8).copy()
+        r = lib().generate_move(self.net, int(player), _ptr(b), int(multi), thresh, temp, _ptr(k), 0)
+        if r < 0 and lib().y2_failed_and_clear():
+            raise Y2Error("generate_move: " + _check())
+        return int(r)
+
+    def go_predict(self, boards, players, multi: bool = False) -> np.ndarray:
+        """y2_go_predict: boards [n][361] (absolute), players [n] -> moves [n][361]"""
+        p = np.ascontiguousarray(players, dtype=np.int32).reshape(-1)
+        b = _go_boards(boards, p.size)
+        out = np.zeros((p.size, GO_POINTS), np.float32)
+        if lib().y2_go_predict(self.net, _ptr(b), _ptr(p), p.size, int(multi), _ptr(out)) != 0:
+            raise Y2Error("y2_go_predict: " + _check())
+        return out
+
+    def go_rules(self, boards, ko, players):
+        """y2_go_rules -> (liberties int32 [n][361], legal uint8 [n][361], suicide uint8 [n][361])"""
+        p = np.ascontiguousarray(players, dtype=np.int32).reshape(-1)
+        n = p.size
+        b = _go_boards(boards, n)
+        k = np.frombuffer(_go_ko(ko, n), np.uint8)
+        lib_, legal, sui = np.zeros((n, GO_POINTS), np.int32), np.zeros((n, GO_POINTS), np.uint8), np.zeros((n, GO_POINTS), np.uint8)
+        if lib().y2_go_rules(self.net, _ptr(b), _ptr(k), _ptr(p), n, _ptr(lib_), _ptr(legal), _ptr(sui)) != 0:
+            raise Y2Error("y2_go_rules: " + _check())
+        return lib_, legal, sui
+
+    def go_generate(self, boards, ko, players, multi: bool, thresh: float, temp: float, uniforms, kept: bool = False):
+        """y2_go_generate: one chain and one sync for n positions -> index int32 [n] (and the thresholded arrays)"""
+        p = np.ascontiguousarray(players, dtype=np.int32).reshape(-1)
+        n = p.size
+        b = _go_boards(boards, n)
+        k = np.frombuffer(_go_ko(ko, n), np.uint8)
+        u = np.ascontiguousarray(uniforms, dtype=np.float32).reshape(-1)
+        if u.size != n:
+            raise ValueError("go_generate: %d uniforms for %d positions" % (u.size, n))
+        index = np.zeros(n, np.int32)
+        rows = np.zeros((n, GO_POINTS), np.float32) if kept else None
+        if lib().y2_go_generate(self.net, _ptr(b), _ptr(k), _ptr(p), n, int(multi), thresh, temp, _ptr(u), _ptr(index),
+                                _ptr(rows) if kept else None) != 0:
+            raise Y2Error("y2_go_generate: " + _check())
+        return (index, rows) if kept else index
+
+    def go_valid(self, records, multi: bool = False) -> np.ndarray:
+        """y2_go_valid: records uint8 [n][93] -> predicted point per record"""
+        r = np.ascontiguousarray(records, dtype=np.uint8).reshape(-1, GO_RECORD)
+        out = np.zeros(r.shape[0], np.int32)
+        if lib().y2_go_valid(self.net, _ptr(r), r.shape[0], int(multi), _ptr(out)) != 0:
+            raise Y2Error("y2_go_valid: " + _check())
+        return out
+
+    def go_selfplay(self, games: int, max_moves: int, uniforms, multi: bool = False, thresh: float = .1, temp: float = .7,
+                    other: "Network | None" = None, first: int = 0):
+        """y2_go_selfplay -> (records uint8 [games][max_moves][93], counts int32 [games], final boards [games][361])"""
+        u = np.ascontiguousarray(uniforms, dtype=np.float32).reshape(-1)
+        if u.size != max(games, 0) * max(max_moves, 0):
+            raise ValueError("go_selfplay: %d uniforms for %d games x %d moves" % (u.size, games, max_moves))
+        rec = np.zeros((max(games, 1), max(max_moves, 1), GO_RECORD), np.uint8)
+        counts = np.zeros(max(games, 1), np.int32)
+        boards = np.zeros((max(games, 1), GO_POINTS), np.float32)
+        if lib().y2_go_selfplay(self.net, (other or self).net, games, first, max_moves, int(multi), thresh, temp, _ptr(u), _ptr(rec),
+                                _ptr(counts), _ptr(boards)) != 0:
+            raise Y2Error("y2_go_selfplay: " + _check())
+        return rec, counts, boards
+
+    def go_set_poll(self, every: int) -> None:
+        if lib().y2_go_set_poll(self.net, int(every)) != 0:
+            raise Y2Error("y2_go_set_poll: " + _check())
+
+    def train_load_go(self, records, pick, flip, rot) -> None:
+        """y2_train_load_go: records uint8 [n][93] and the draws of go_draw_moves -> the trainer's input and truth"""
+        r = np.ascontiguousarray(records, dtype=np.uint8).reshape(-1, GO_RECORD)
+        d = [np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (pick, flip, rot)]
+        if any(a.size != self.net.batch for a in d):
+            raise ValueError("train_load_go: pick, flip and rot need net.batch = %d values each" % self.net.batch)
+        if lib().y2_train_load_go(C.byref(self.net), _ptr(r), r.shape[0], _ptr(d[0]), _ptr(d[1]), _ptr(d[2])) != 0:
+            raise Y2Error("y2_train_load_go: " + _check())
+
     def sync(self) -> None:
         lib().y2_sync(self.net)
 
@@ -1914,6 +2039,90 @@ class Dream:
 def srand(seed: int) -> None:
     """libc's srand: the generator y2_dream_draw, optimize_picture and y2_nightmare draw from"""
     C.CDLL(None).srand(C.c_uint(seed))
+
+
+# --- Go: the device-free half of go.c ---
+GO_POINTS, GO_KO, GO_RECORD, GO_LINE = 361, 91, 93, 94
+
+
+class GoMoves(C.Structure):
+    _fields_ = [("data", C.POINTER(C.c_void_p)), ("n", C.c_int)]
+
+
+def _go_boards(boards, n: int) -> np.ndarray:
+    b = np.ascontiguousarray(boards, dtype=np.float32).reshape(-1)
+    if b.size != n * GO_POINTS:
+        raise ValueError("%d board values for %d positions" % (b.size, n))
+    return b
+
+
+def _go_ko(ko, n: int) -> bytes:
+    k = bytes(n * GO_KO) if ko is None else (ko if isinstance(ko, (bytes, bytearray)) else np.ascontiguousarray(ko, dtype=np.uint8).tobytes())
+    if len(k) != n * GO_KO:
+        raise ValueError("%d ko bytes for %d positions" % (len(k), n))
+    return bytes(k)
+
+
+def string_to_board(s) -> np.ndarray:
+    k = np.frombuffer(_go_ko(s, 1), np.uint8).copy()
+    board = np.zeros(GO_POINTS, np.float32)
+    lib().string_to_board(_ptr(k), _ptr(board))
+    return board
+
+
+def board_to_string(board) -> bytes:
+    b = _go_boards(board, 1)
+    s = np.zeros(GO_KO, np.uint8)
+    lib().board_to_string(_ptr(s), _ptr(b))
+    return s.tobytes()
+
+
+def calculate_liberties(board) -> np.ndarray:
+    b = _go_boards(board, 1)
+    L = lib()
+    p = L.calculate_liberties(_ptr(b))
+    out = np.ctypeslib.as_array(p, shape=(GO_POINTS,)).astype(np.int32)
+    C.CDLL(None).free(C.cast(p, C.c_void_p))
+    return out
+
+
+def move_go(board, player: int, row: int, col: int) -> np.ndarray:
+    """the board after the move (the argument is not changed)"""
+    b = _go_boards(board, 1).copy()
+    lib().move_go(_ptr(b), int(player), int(row), int(col))
+    return b
+
+
+def suicide_go(board, player: int, row: int, col: int) -> int:
+    b = _go_boards(board, 1).copy()
+    return int(lib().suicide_go(_ptr(b), int(player), int(row), int(col)))
+
+
+def legal_go(board, ko, player: int, row: int, col: int) -> int:
+    b = _go_boards(board, 1).copy()
+    k = np.frombuffer(_go_ko(ko, 1), np.uint8).copy()
+    return int(lib().legal_go(_ptr(b), _ptr(k), int(player), int(row), int(col)))
+
+
+def load_go_moves(path: str) -> np.ndarray:
+    """go.c:34 -> records uint8 [n][93] (the lines without their newline)"""
+    L = lib()
+    m = L.load_go_moves(path.encode())
+    if L.y2_failed_and_clear():
+        raise Y2Error("load_go_moves: " + _check())
+    out = np.zeros((m.n, GO_RECORD), np.uint8)
+    for i in range(m.n):
+        out[i] = np.frombuffer(C.string_at(m.data[i], GO_RECORD), np.uint8)
+    L.y2_go_free_moves(m)
+    return out
+
+
+def go_draw_moves(n_records: int, batch: int):
+    """random_go_moves' draws for one batch, on libc rand: (pick, flip, rot), int32 [batch] each"""
+    d = [np.zeros(max(batch, 1), np.int32) for _ in range(3)]
+    if lib().y2_go_draw_moves(n_records, batch, _ptr(d[0]), _ptr(d[1]), _ptr(d[2])) != 0:
+        raise Y2Error("y2_go_draw_moves: " + _check())
+    return tuple(a[:batch] for a in d)
 
 
 def dream_draw(range_: int = 1, octaves: int = 4) -> dict:

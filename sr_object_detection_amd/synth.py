@@ -193,3 +193,16 @@ def char_rows(seed: int, batch: int, steps: int, inputs: int, onehot: bool) -> n
         x[np.arange(steps * batch), chars] = 1
         return x
     return uniform01(seed, steps * batch * inputs).reshape(steps * batch, inputs)
+
+
+def write_go_weights(path: str, name: str, seed: int) -> int:
+    """.weights of a zoo.GO network by write_weights' recipe (head_gain 1: there is no region head)"""
+    from sr_object_detection_amd import zoo
+    return write_weights(path, zoo.go_resolve(name), seed, head_gain=1.0)
+
+
+def go_boards(seed: int, n: int, fill: float = 0.4) -> np.ndarray:
+    """[n][361] float32 boards of 0 / 1 / -1: each point holds a stone with probability `fill`, either colour alike.  Not
+    positions of a game (no captures are resolved): inputs for kernels and forwards."""
+    u = uniform01(seed, n * 361 * 2).reshape(2, n, 361)
+    return np.where(u[0] < fill, np.where(u[1] < .5, 1, -1), 0).astype(np.float32)

@@ -490,3 +490,23 @@ def lrn_resolve(name: str, width: int | None = None, height: int | None = None, 
     """the layer table (resolve) of an LRN entry"""
     w, h, _, own = LRN[name]
     return resolve(own if spec is None else spec, width or w, height or h)
+
+
+# Go networks: a 19 x 19 x 1 board in, a softmax over the 361 points out.  Kept apart from SPECS, like LRN.
+# "go" is the topology of cfg/go.test.cfg (thirteen 3x3/192 convolutions with batch-norm and relu, a 1x1 convolution to
+# one channel, softmax, cost); "go-mini" is its shape at test size.
+GO = {
+    "go": [("conv", 192, 3, 1, "relu")] * 13 + [("conv", 1, 1, 0, "linear"), ("softmax",), ("cost",)],
+    "go-mini": [("conv", 8, 3, 1, "relu"), ("conv", 8, 3, 1, "relu"), ("conv", 1, 1, 0, "linear"), ("softmax",), ("cost",)],
+}
+
+
+def go_cfg_text(name: str, batch: int = 1) -> str:
+    """cfg text of a GO entry: cfg_text's, with the one-channel 19 x 19 input and a rate a test's training step can take"""
+    text = cfg_text(name, 19, 19, batch, spec=GO[name])
+    return text.replace("channels=3", "channels=1\nlearning_rate=0.1\nmomentum=0.9\ndecay=0.0005", 1)
+
+
+def go_resolve(name: str):
+    """the layer table (resolve) of a GO entry"""
+    return resolve(GO[name], 19, 19, channels=1)
