@@ -1164,7 +1164,12 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(ConvK a)
                         const size_t xi = ((size_t)(n * a.H + iy) * a.W + ix) * a.ldx + c;
                         xv = XH ? (float)((const _Float16 *)a.x)[xi] : a.x[xi];
                     }
-                    const float prod = wrow[(c * a.size + kh) * a.size + kw] * xv;
+                    // a layer with a half input holds half weights (y2_half_weights): the direct kernel reads the fp32
+                    // reference-layout copy and rounds as the pack of the matrix-core kernels does, so a half layer gives
+                    // act(sum of half(w) * half(x)) whichever kernel takes it
+                    float wv = wrow[(c * a.size + kh) * a.size + kw];
+                    if (XH) wv = (float)(_Float16)wv;
+                    const float prod = wv * xv;
                     sum = sum + prod;
                 }
             }
