@@ -263,6 +263,24 @@ int y2h_conv_winos_forward(const y2h_conv *d, y2h_stream s);
 /* number of such forwards issued by this process so far (tests) */
 unsigned long y2h_winos_launches(void);
 
+/* ---- direct 3x3 convolution on the bf16 matrix cores by 3-way split (the rule: include/y2_splitd_rule.h) ---- */
+typedef struct y2h_splitd {
+    int eligible;                /* the shape is one the kernel takes and the direct plan is the fp32 matrix-core kernel */
+    int take;                    /* the rule's answer (Y2_SPLITD=0: never, Y2_SPLITD=1: every eligible layer)             */
+    int bm, bn, bk;              /* tile: positions x filters, K-tile                                                    */
+    long tiles;                  /* tiles the persistent grid walks (position tiles x filter tiles)                      */
+    size_t u_bytes;              /* split filters, three bf16 planes (y2_splitd_u_index)                                 */
+    size_t lds_bytes;            /* LDS of the launch                                                                    */
+    double direct_cost, matrix_cost, byte_cost, splitd_cost;   /* CU cycles; the larger of matrix and byte is the cost   */
+} y2h_splitd;
+/* Host arithmetic only (no GPU).  Leaves what every other query answers alone; needs no workspace. */
+int y2h_conv_splitd_plan(const y2h_conv *d, y2h_splitd *out);
+/* The convolution as one launch.  d->w_packed holds the split filters (y2_splitd_pack_u with y2_splitd_bn(n, pool)).  Y2H_EINVAL
+ * unless y2h_conv_splitd_plan takes the descriptor. */
+int y2h_conv_splitd_forward(const y2h_conv *d, y2h_stream s);
+/* number of such forwards issued by this process so far (tests) */
+unsigned long y2h_conv_splitd_launches(void);
+
 /* ---- other layers (NHWC) ---- */
 int y2h_maxpool(const float *x, int ldx, float *y, int ldy, int batch, int h, int w, int c,
                 int size, int stride, int pad, int out_h, int out_w, y2h_stream s);

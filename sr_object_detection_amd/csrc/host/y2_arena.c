@@ -10,6 +10,7 @@
 #include "y2_internal.h"
 #include "y2_wino_rule.h"
 #include "y2_winos_rule.h"
+#include "y2_splitd_rule.h"
 #include "y2_split_rule.h"
 
 /* the layer types that own arena space: layout, signature and packing all iterate with this */
@@ -255,9 +256,14 @@ static void pack_winos(void *slot, const layer *l)
 /* the filters of a split-Winograd layer: U as three bf16 planes (y2_split_rule.h), from the reference layout [n][c][3][3] */
 static void pack_winox(void *slot, const layer *l) { y2_split_pack_u(slot, l->weights, l->n, l->c); }
 
+/* the filters of a direct split layer: three bf16 planes of the reference-layout weights themselves, one run per (filter
+ * tile, K-tile, tap) (y2_splitd_rule.h) */
+static void pack_splitd(void *slot, const layer *l) { y2_splitd_pack_u(slot, l->weights, l->n, l->c, y2_splitd_bn(l->n, ld_of(l)->fused_pool)); }
+
 static size_t wino_slot_bytes(const layer *l) { return (size_t)16 * l->n * l->c * sizeof(float); }
 static size_t winox_slot_bytes(const layer *l) { return y2_split_bytes(y2_split_rows_pad(l->n), l->c); }
 static size_t winos_slot_bytes(const layer *l) { return y2_winos_u_floats(l->n) * sizeof(float); }
+static size_t splitd_slot_bytes(const layer *l) { return y2_splitd_u_elems(l->n, l->c, y2_splitd_bn(l->n, ld_of(l)->fused_pool)) * 2; }
 
 /* the signature constants are part of the signature's format (arena_signature) */
 const y2_conv_form y2_conv_forms[Y2_FORM_COUNT] = {
@@ -265,6 +271,7 @@ const y2_conv_form y2_conv_forms[Y2_FORM_COUNT] = {
     [Y2_FORM_WINO] = { 0x57494e4f, wino_slot_bytes, pack_wino, y2h_wino_workspace_bytes, y2h_conv_wino_forward },          /* V and M */
     [Y2_FORM_WINOX] = { 0x57494e58, winox_slot_bytes, pack_winox, y2h_wino_split_workspace_bytes, y2h_conv_winox_forward },
     [Y2_FORM_WINOS] = { 0x57494e53, winos_slot_bytes, pack_winos, NULL, y2h_conv_winos_forward },
+    [Y2_FORM_SPLITD] = { 0x53504c44, splitd_slot_bytes, pack_splitd, NULL, y2h_conv_splitd_forward },
 };
 
 /* a [convolutional] or [connected] layer: filters, the reference-layout copy where the layer needs one, constants */

@@ -64,10 +64,11 @@ typedef struct y2_ldev {
     float *d_tmp;              /* matrix-core step form: the step's dense values, [B][2*outputs] */
 } y2_ldev;
 
-/* How a convolution runs (y2_ldev.form, decided by y2_conv_form_of): the direct kernels of y2h_conv_forward, Winograd
+/* How a convolution runs (y2_ldev.form, decided by y2_conv_layer_form): the direct kernels of y2h_conv_forward, Winograd
  * F(2x2,3x3) as three launches with U[16][n][c] in the filter slot, the same with the GEMM split into three bf16 planes
- * (y2_split_rule.h), or the fused stationary Winograd kernel with U in its register order (y2_winos_rule.h). */
-enum { Y2_FORM_DIRECT = 0, Y2_FORM_WINO, Y2_FORM_WINOX, Y2_FORM_WINOS, Y2_FORM_COUNT };
+ * (y2_split_rule.h), the fused stationary Winograd kernel with U in its register order (y2_winos_rule.h), or the direct
+ * kernel on the bf16 matrix cores with the split filters in its streaming order (y2_splitd_rule.h). */
+enum { Y2_FORM_DIRECT = 0, Y2_FORM_WINO, Y2_FORM_WINOX, Y2_FORM_WINOS, Y2_FORM_SPLITD, Y2_FORM_COUNT };
 /* What depends on the form, one row per form (y2_arena.c).  The direct row holds its workspace query alone: its filter
  * slot depends on the storage mode, its packer on the network and its entry point on the strict flag, so the sites that
  * find a NULL there spell those out. */
@@ -264,6 +265,7 @@ int y2_half_weights(const network *net, int i);
 void y2_input_form(const network *net, y2_in_form *f);
 void y2_input_view(const network *net, int i, const float **x, int *ldx);
 void y2_conv_desc(const network *net, int i, y2h_conv *c, const float *x, int ldx);
+int y2_conv_layer_form(const y2h_conv *c, int fused_pool, char *name, size_t name_len);   /* y2_conv_form_of, then the direct split rule */
 int y2_conv_form_of(const y2h_conv *c, int fused_pool, char *name, size_t name_len);   /* host arithmetic only */
 
 /* weight arena (y2_arena.c) */

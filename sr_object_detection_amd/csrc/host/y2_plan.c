@@ -935,7 +935,7 @@ static int plan_conv_kernels(network *net)
     return 0;
 }
 
-/* The form a convolution runs in, and for a Winograd form the name of its kernel.  The precedence is stated here and
+/* The Winograd form a convolution runs in, and the name of its kernel.  The precedence is stated here and
  * nowhere else: the split GEMM (the rule: include/y2_split_rule.h, asked through y2h_wino_split_plan) beats fp32 Winograd
  * (y2_wino_rule.h, y2h_wino_plan), which beats the fused stationary kernel (y2_winos_rule.h, y2h_winos_plan); the first
  * whose rule takes the descriptor has it, and a descriptor none takes stays direct, its name untouched.  Host arithmetic
@@ -952,7 +952,22 @@ int y2_conv_form_of(const y2h_conv *c, int fused_pool, char *name, size_t name_l
     return Y2_FORM_DIRECT;
 }
 
-/* which of the fp32 matrix-core convolutions run as a Winograd form instead (y2_conv_form_of).  Such a layer keeps its
+/* The form of a layer: a Winograd form where y2_conv_form_of gives one -- nothing that runs in a Winograd form moves -- and
+ * among the layers it leaves direct the direct split kernel where its rule takes the descriptor (y2_splitd_rule.h,
+ * y2h_conv_splitd_plan).  Host arithmetic only. */
+int y2_conv_layer_form(const y2h_conv *c, int fused_pool, char *name, size_t name_len)
+{
+    const int form = y2_conv_form_of(c, fused_pool, name, name_len);
+    y2h_splitd sd;
+    if (form != Y2_FORM_DIRECT) return form;
+    if (y2h_conv_splitd_plan(c, &sd) == 0 && sd.take) {
+        snprintf(name, name_len, "conv_splitd_f32_%dx%dx%d%s", sd.bm, sd.bn, sd.bk, fused_pool ? "+maxpool2" : "");
+        return Y2_FORM_SPLITD;
+    }
+    return Y2_FORM_DIRECT;
+}
+
+/* which of the fp32 matrix-core convolutions run as a Winograd form or as the direct split kernel instead (y2_conv_layer_form).  Such a layer keeps its
  * form's U in the arena in place of its packed filters and is named after the form; its launches sit between the layer's
  * two timing events like any layer's.  Never in strict or half mode. */
 static int plan_conv_forms(network *net)
@@ -968,7 +983,7 @@ static int plan_conv_forms(network *net)
         if (l->type != CONVOLUTIONAL || !d->uses_mfma || l->xnor) continue;
         y2_input_view(net, i, &x, &ldx);
         conv_query(net, i, &c, x, ldx);
-        d->form = y2_conv_form_of(&c, d->fused_pool, d->kname, sizeof d->kname);
+        d->form = y2_conv_layer_form(&c, d->fused_pool, d->kname, sizeof d->kname);
         if (d->form != Y2_FORM_DIRECT) d->kernel = d->kname;
     }
     return 0;

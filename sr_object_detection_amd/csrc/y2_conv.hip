@@ -60,6 +60,7 @@
 // This file is compiled with -ffp-contract=off: no mul+add below may fuse.
 #include "y2_conv_shared.hpp"
 #include "y2_split_rule.h"
+#include "y2_splitd_rule.h"
 #include <type_traits>
 
 // ---------------------------------------------------------------------------
@@ -1731,6 +1732,50 @@ extern "C" size_t y2h_wino_split_workspace_bytes(const y2h_conv *d)
     y2h_wino_split x;
     if (y2h_wino_split_plan(d, &x) != Y2H_OK || !x.take) return 0;
     return x.v_bytes + x.m_bytes;
+}
+
+// The direct split form (include/y2_splitd_rule.h, y2_conv_split.hip): asked for the layers the three Winograd rules leave direct (y2_conv_layer_form),
+// for layers whose direct plan is the fp32 matrix-core kernel.  Y2_SPLITD=0: never; Y2_SPLITD=1: every eligible descriptor
+// (tests; Y2_SPLITD_TILE forces the filter tile); otherwise the rule: the cost below the direct plan's by the margin, one
+// 128-wide filter tile (layers with more filters stay direct: the rule's header says why), at least one round of tiles, and
+// a direct plan that walks whole tiles (as y2h_wino_plan asks, for the same reason).  A measured or forced fp32 tile keeps
+// the layer on the tile it names.
+extern "C" int y2h_conv_splitd_plan(const y2h_conv *d, y2h_splitd *out)
+{
+    if (!d || !out) return Y2H_EINVAL;
+    memset(out, 0, sizeof *out);
+    int mode = -1;
+    if (const char *f = getenv("Y2_SPLITD")) mode = atoi(f) != 0 ? 1 : 0;
+    const int pool = d->fuse_maxpool2 ? 1 : 0;
+    if (!y2_splitd_shape_ok(d->size, d->stride, d->pad, d->c, d->n, d->h, d->w, d->out_h, d->out_w, pool, d->x_f16, d->y_f16,
+                            d->x_halo, d->x_nchw, d->ldx)) return Y2H_OK;
+    if (d->ldy < d->n || d->tile_bm || d->ksplit > 1 || getenv("Y2_CONV_TILE")) return Y2H_OK;
+    if (((uintptr_t)d->x | (uintptr_t)d->w_packed) % 16 != 0 || !d->w_packed) return Y2H_OK;
+    const ConvPlan p = conv_plan(d, 0);
+    if (p.kind != CK_MFMA_F32) return Y2H_OK;
+    const int bn = y2_splitd_bn(d->n, pool);
+    const double xbytes = (double)d->batch * d->h * d->w * d->ldx * 4.0;
+    const double ybytes = (double)d->batch * d->h * d->w * (pool ? 0.25 : 1.0) * d->ldy * 4.0;
+    const double ubytes = (double)y2_splitd_u_elems(d->n, d->c, bn) * 2.0;
+    if (xbytes >= 4294967000.0 || ybytes >= 4294967000.0 || ubytes >= 4294967000.0) return Y2H_OK;       // 32-bit buffer offsets
+    if ((double)d->batch * (d->h + 1) * (d->w + 2) >= 1073741824.0) return Y2H_OK;
+    const size_t lds = y2_splitd_lds_bytes(d->w, pool, bn);
+    if (lds > Y2_SPLITD_LDS_BYTES || 2 * y2_splitd_patch_positions(d->w, pool) > (bn == 256 ? 2 : 3) * 512) return Y2H_OK;  // the staging passes
+    const long tiles_n = (d->n + bn - 1) / bn, tiles = y2_splitd_tiles_m(d->batch, d->h, d->w, pool) * tiles_n;
+    if (tiles >= 0x7fffffffL / 256) return Y2H_OK;
+    out->eligible = 1;
+    out->bm = Y2_SPLITD_BM; out->bn = bn; out->bk = Y2_SPLIT_BK;
+    out->tiles = tiles;
+    out->u_bytes = (size_t)ubytes;
+    out->lds_bytes = lds;
+    out->direct_cost = p.cost;
+    out->matrix_cost = y2_splitd_matrix_cost(tiles, d->c / Y2_SPLIT_BK, bn);
+    out->byte_cost = y2_splitd_byte_cost((double)d->batch * d->h * d->w * d->c * 4.0, y2_splitd_halo(d->w, pool), ubytes,
+                                         (double)d->batch * d->h * d->w * (pool ? 0.25 : 1.0) * d->n * 4.0);
+    out->splitd_cost = out->matrix_cost > out->byte_cost ? out->matrix_cost : out->byte_cost;
+    if (mode >= 0) out->take = mode;
+    else out->take = tiles_n == 1 && bn == 128 && tiles >= 256 && p.sk_wgs == 0 && p.tile_ksplit == 1 && y2_wino_wins(p.cost, out->splitd_cost);
+    return Y2H_OK;
 }
 
 extern "C" size_t y2h_wino_workspace_bytes(const y2h_conv *d)

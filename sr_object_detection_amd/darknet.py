@@ -448,6 +448,9 @@ def lib():
         L.y2h_wino_split_plan.argtypes = [C.c_void_p, C.c_void_p]        # (y2h_conv *, y2h_wino_split *): tools/plan_dump.py has the structs
         L.y2h_wino_split_workspace_bytes.restype = C.c_size_t
         L.y2h_wino_split_launches.restype = C.c_ulong
+    if hasattr(L, "y2h_conv_splitd_plan"):         # (an older build under Y2_LIB has no direct split form)
+        L.y2h_conv_splitd_plan.argtypes = [C.c_void_p, C.c_void_p]       # (y2h_conv *, y2h_splitd *)
+        L.y2h_conv_splitd_launches.restype = C.c_ulong
     L.y2h_d2h_copies.restype = C.c_ulong
     L.y2h_stream_syncs.restype = C.c_ulong
     L.y2_set_view_block_bytes.argtypes = [C.c_size_t]

@@ -8,7 +8,8 @@ check that a change of the cost model leaves the plan of the headline configurat
     tools/plan_dump.py --wino        the Winograd rule's answer for every 3x3 layer of every zoo network (tests/golden/wino_plan_table.txt)
     tools/plan_dump.py --winos       the stationary-Winograd rule's answer for the same layers (tests/golden/winos_plan_table.txt)
     tools/plan_dump.py --wino-split  the split rule's answer for the same layers (tests/golden/wino_split_plan_table.txt)
-    tools/plan_dump.py --forms       the form the three rules together give each of those layers, and its kernel name (y2_conv_form_of)"""
+    tools/plan_dump.py --splitd      the direct split rule's answer for the same layers (tests/golden/splitd_plan_table.txt)
+    tools/plan_dump.py --forms       the form the four rules together give each of those layers, and its kernel name (y2_conv_layer_form)"""
 import ctypes as C
 import os
 import sys
@@ -228,7 +229,40 @@ def wino_split_rows(lib):
                 w.v_bytes, w.u_bytes, w.present_cost / 1e3, w.gemm_cost / 1e3, w.split_cost / 1e3, wh.eligible, wh.take)
 
 
-FORM_NAMES = ("direct", "wino", "winox", "winos")          # csrc/host/y2_internal.h: Y2_FORM_*
+class SplitD(C.Structure):        # include/y2_hip.h: y2h_splitd
+    _fields_ = [("eligible", C.c_int), ("take", C.c_int), ("bm", C.c_int), ("bn", C.c_int), ("bk", C.c_int), ("tiles", C.c_long),
+                ("u_bytes", C.c_size_t), ("lds_bytes", C.c_size_t),
+                ("direct_cost", C.c_double), ("matrix_cost", C.c_double), ("byte_cost", C.c_double), ("splitd_cost", C.c_double)]
+
+
+def splitd_plan(lib, f):
+    """y2h_conv_splitd_plan for one descriptor (a dict of y2h_conv fields)"""
+    d, w = Conv(**f), SplitD()
+    assert lib.y2h_conv_splitd_plan(C.byref(d), C.byref(w)) == 0
+    return w
+
+
+def splitd_rows(lib):
+    """The direct split rule's answer (include/y2_splitd_rule.h through y2h_conv_splitd_plan) for every 3x3 conv layer of every
+    zoo network: tests/golden/splitd_plan_table.txt.  Costs in thousands of CU cycles.  The rule is asked after the three
+    Winograd rules (y2_conv_layer_form): a layer one of them takes keeps that form whatever this table says."""
+    for k in [k for k in os.environ if k.startswith("Y2_")]:
+        del os.environ[k]
+    yield "# net size batch layer | h w c n pool | fp32: eligible take tile tiles lds u_bytes direct matrix bytes (kcycles) | fp16: eligible take"
+    for net, size, batch in wino_cases():
+        rows = {}
+        for half in (0, 1):
+            for i, f in _descs(net, size, batch, half, ALIGNED):
+                if f["size"] != 3 or f.get("x_halo") or f.get("x_nchw"):
+                    continue
+                rows.setdefault(i, (f, []))[1].append(splitd_plan(lib, f))
+        for i, (f, (w, wh)) in sorted(rows.items()):
+            yield "%s %d b%d L%d | %d %d %d %d %d | %d %d %dx%dx%d %d %d %d %.0f %.0f %.0f | %d %d" % (
+                net, size, batch, i, f["h"], f["w"], f["c"], f["n"], f["fuse_maxpool2"], w.eligible, w.take, w.bm, w.bn, w.bk, w.tiles,
+                w.lds_bytes, w.u_bytes, w.direct_cost / 1e3, w.matrix_cost / 1e3, w.byte_cost / 1e3, wh.eligible, wh.take)
+
+
+FORM_NAMES = ("direct", "wino", "winox", "winos", "splitd")          # csrc/host/y2_internal.h: Y2_FORM_*
 
 
 def conv_form(lib, f):
@@ -239,8 +273,16 @@ def conv_form(lib, f):
     return form, name.value.decode()
 
 
+def layer_form(lib, f):
+    """y2_conv_layer_form (y2_plan.c) for one descriptor: y2_conv_form_of, then the direct split rule among what it leaves direct"""
+    d, name = Conv(**f), C.create_string_buffer(80)
+    lib.y2_conv_layer_form.argtypes = [C.POINTER(Conv), C.c_int, C.c_char_p, C.c_size_t]
+    form = lib.y2_conv_layer_form(C.byref(d), f.get("fuse_maxpool2", 0), name, len(name))
+    return form, name.value.decode()
+
+
 def form_rows(lib):
-    """The form every 3x3 conv layer of every zoo network runs in, the three rules combined (y2_conv_form_of).  For people:
+    """The form every 3x3 conv layer of every zoo network runs in, the four rules combined (y2_conv_layer_form).  For people:
     tests/test_conv_form_cpu.py derives what it expects from the three rule tables, not from this dump."""
     for k in [k for k in os.environ if k.startswith("Y2_")]:
         del os.environ[k]
@@ -251,7 +293,7 @@ def form_rows(lib):
             for i, f in _descs(net, size, batch, half, ALIGNED):
                 if f["size"] != 3 or f.get("x_halo") or f.get("x_nchw"):
                     continue
-                rows.setdefault(i, (f, []))[1].append(conv_form(lib, f))
+                rows.setdefault(i, (f, []))[1].append(layer_form(lib, f))
         for i, (f, forms) in sorted(rows.items()):
             yield "%s %d b%d L%d | %d %d %d %d %d | %s" % (net, size, batch, i, f["h"], f["w"], f["c"], f["n"], f["fuse_maxpool2"],
                                                            " | ".join("%s %s" % (FORM_NAMES[k], n or "-") for k, n in forms))
@@ -271,6 +313,8 @@ def main():
         return print("\n".join(winos_rows(lib)))
     if args == ["--wino-split"]:
         return print("\n".join(wino_split_rows(lib)))
+    if args == ["--splitd"]:
+        return print("\n".join(splitd_rows(lib)))
     if args == ["--forms"]:
         return print("\n".join(form_rows(lib)))
     for k in range(0, len(args), 3):
